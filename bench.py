@@ -1,6 +1,6 @@
 """Headline benchmark: PPO rollout-collect + learner-update on synthetic HalfCheetah shapes.
 
-    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong]
+    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--dump-outputs DIR]
 
 One "step" = one full pass of the hot path over one Segment of synthetic input, THROUGH the
 drop-in API with the host in the loop: T=4096 environment steps x W workers per GPU, each one
@@ -635,11 +635,12 @@ class HostLoop:
                     steps=environment_steps, transport=getattr(agent, 'transport_in_effect', agent.transport))
 
 
-def parallel_workers_loop(agent, groups=8, per_group=32, steps=512):
+def parallel_workers_loop(agent, groups=4, per_group=64, steps=512):
     """The trainer's loop body with the worker-PROCESS transport of the reference's `Parallel`
-    (tonic/environments/distributed.py:136-155): distribute(builder, 8, 32) = 8 forked groups of 32
+    (tonic/environments/distributed.py:136-155): distribute(builder, 4, 64) = 4 forked groups of 64
     Python environments writing into the shared block the GPU reads in place, two futex words per
-    step.  us per environment step of 256 workers (the simulators are 256 Python objects here, so
+    step (4 groups, not 8: a forked group inherits this process's open device files, and the benchmark
+    keeps at most 6 processes holding the GPU).  us per environment step of 256 workers (the simulators are 256 Python objects here, so
     this is mostly their cost: 32 sequential `Synthetic.step` calls per group)."""
     from tonic_amd import environments
     env = environments.distribute(lambda: environments.Synthetic(O, A, max_episode_steps=1000),
@@ -730,13 +731,49 @@ def timed_steps(run_one, steps, warmup, world, finish=None):
     return elapsed
 
 
-def measure_job(workers, rank, world, steps, warmup, capture, device_too=True):
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory, arrays):
+    """`--dump-outputs DIR`: writes each array as DIR/<name>.npy (float64 stays float64, everything else
+    becomes float32), refusing more than 64 MB in all, so two builds can be compared output for output."""
+    import torch
+    out = {}
+    for name, value in arrays.items():
+        if isinstance(value, torch.Tensor):
+            value = value.detach().cpu().numpy()
+        value = np.array(value)
+        out[name] = value.astype(np.float64 if value.dtype == np.float64 else np.float32)
+    total = sum(v.nbytes for v in out.values())
+    assert total <= DUMP_LIMIT_BYTES, f'--dump-outputs: {total} bytes exceed the 64 MB limit'
+    os.makedirs(directory, exist_ok=True)
+    for name, value in out.items():
+        np.save(os.path.join(directory, name + '.npy'), value)
+
+
+def ppo_outputs(agent, loop):
+    """What a caller of the timed path holds after its last step: that step's actions (agent.step) and
+    next observations (environment.step), the learner update's statistics (actor and critic rows) and the
+    parameters and normaliser it left.  (The last step issues nothing ahead: the block still holds its
+    actions; its input observations are overwritten in place by the next ones.)"""
+    actor_infos, critic_infos = agent.last_infos
+    arrays = dict(actions=agent.last_actions, next_observations=loop.observations,
+                  actor_infos=actor_infos, critic_infos=critic_infos)
+    for key, value in agent.model.state_dict().items():
+        arrays['param.' + key] = value
+    return arrays
+
+
+def measure_job(workers, rank, world, steps, warmup, capture, device_too=True, dump=None):
     """Builds one agent with `workers` workers on this rank and times (a) the host-in-the-loop
-    path and (b) the device-resident path; returns (agent, loop, rollout, results)."""
+    path and (b) the device-resident path; returns (agent, loop, rollout, results).  `dump`: a
+    directory that receives the host-in-the-loop path's outputs of its last timed step (rank 0)."""
     from tonic_amd.rollout import DeviceRollout
     agent = build_agent(seed=0)                      # same seed: replicated parameters
     loop = HostLoop(agent, workers, seed=1 + rank)
     elapsed = timed_steps(lambda: loop.run(T), steps, warmup, world, finish=agent.settle)
+    if dump is not None and rank == 0:
+        dump_outputs(dump, ppo_outputs(agent, loop))
     out = dict(elapsed=elapsed, ms_per_step=elapsed / steps * 1e3,
                value=world * T * workers * steps / elapsed,
                actor_iterations=int((agent.last_infos[0][:, 6] > 0).sum()),
@@ -850,11 +887,19 @@ def cfg4_main(args, rank, world):
         agent, replay = build_offpolicy(kind, o_dim, a_dim, batch, workers, iterations,
                                         fill_seed=rank)
 
+        last = {}
+
         def run_one():
             indices = replay.sample_indices()              # the GLOBAL stream, same on every rank
             eps = agent._draw_noise(iterations)
-            agent.enqueue_update(indices, eps).cpu()       # one read-back per update call
+            last['infos'] = agent.enqueue_update(indices, eps).cpu()     # one read-back per update call
         elapsed = timed_steps(run_one, args.steps, max(args.warmup, 2), world)
+        if batch == 100 and args.dump_outputs is not None and rank == 0:
+            # the headline run's last update call: its statistics rows and the parameters it left
+            arrays = dict(infos=last['infos'])
+            for key, value in agent.model.state_dict().items():
+                arrays['param.' + key] = value
+            dump_outputs(args.dump_outputs, arrays)
         results[batch] = dict(elapsed=elapsed, ms_per_step=elapsed / args.steps * 1e3,
                               value=iterations * args.steps / elapsed)
     main_run = results[100]
@@ -956,6 +1001,9 @@ def main():
     #  next rollout — 23 ms that a steady-state job pays once, not once per three steps)
     parser.add_argument('--steps', type=int, default=8)
     parser.add_argument('--warmup', type=int, default=1)
+    parser.add_argument('--dump-outputs', metavar='DIR', default=None,
+                        help="write what the timed path computed in its last timed step to DIR/<name>.npy "
+                             "(rank 0; float32 / float64, at most 64 MB)")
     parser.add_argument('--no-graph', action='store_true', help='eager launches, no hipGraph')
     parser.add_argument('--quick-extras', action='store_true',
                         help='only the phase split and the host-loop breakdown')
@@ -971,6 +1019,8 @@ def main():
                              'cfg4: TD3 humanoid-walk shapes, 512 workers sharded over the ranks, '
                              'learner updates/s (BASELINE config 4)')
     args = parser.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        parser.error('--steps must be at least 1 and --warmup at least 0')
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         return spawn_ranks(args.gpus)                 # no launcher: start the ranks ourselves
     global O, A, W
@@ -1002,7 +1052,7 @@ def main():
     # (the device-resident leg replays a hipGraph: single-process only — a capture next to
     #  RCCL's watchdog threads is not worth risking the multi-GPU line for)
     agent, loop, rollout, main_run = measure_job(workers, rank, world, args.steps, args.warmup,
-                                                 capture, device_too=world == 1)
+                                                 capture, device_too=world == 1, dump=args.dump_outputs)
     name = 'HalfCheetah-v3' if args.workload == 'cfg2' else 'AntBulletEnv-v0'
     result = {
         'metric': f'env steps/sec (+ learner updates/sec), PPO {name.split("-")[0]} '
@@ -1025,7 +1075,7 @@ def main():
                    # what `environment.step` is here: the vectorised synthetic simulator of this
                    # package, whose whole step (observations ~ N(0,1) from a pool, reward, episode
                    # lengths, resets) is ONE C entry point of the product library writing into the
-                   # shared block; with the reference's transport — 8 forked groups of 32 Python
+                   # shared block; with the reference's transport — 4 forked groups of 64 Python
                    # environments — the same loop is bound by the simulators (`parallel_workers`)
                    'simulator': 'SyntheticBatch: library C step (tonic_collector_synthetic_step)',
                    # one GPU, full-batch iterations: the critic's 80 iterations of an update run on a

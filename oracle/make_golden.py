@@ -509,6 +509,42 @@ def run_offpolicy(tonic, name, kind, obs_dim=11, act_dim=3, workers=4, hidden=32
                       'replays/buffers.py:28-91', **out)
 
 
+AGENTS = ('PPO', 'A2C', 'TRPO', 'SAC', 'TD3', 'DDPG', 'D4PG', 'MPO')
+
+
+def golden_reference_dropin(tonic):
+    """What tests/test_reference_dropin.py holds this package against: the key set and shapes of each
+    reference agent's state_dict (O=11, A=3: what its strict load_state_dict demands of a checkpoint),
+    DistributionalValueHead / CategoricalWithSupport on seeded logits and returns (support,
+    probabilities, mean, projection), and the action streams of tests/reference_streams.py."""
+    sys.path.insert(0, os.path.join(os.path.dirname(HERE), 'tests'))
+    import reference_streams
+    out = {}
+    observation_space, action_space = rl._Box(-np.inf, np.inf, (11,)), rl._Box(-1, 1, (3,))
+    for name in AGENTS:
+        agent = getattr(tonic.torch.agents, name)()
+        agent.initialize(observation_space, action_space, seed=0)
+        for key, value in agent.model.state_dict().items():
+            out[f'state/{name}/{key}'] = np.array(value.shape, np.int64)
+    torch.manual_seed(3)
+    head = tonic.torch.models.DistributionalValueHead(-7.5, 4.0, 23)
+    logits = torch.randn(40, 23) * 2
+    returns = torch.randn(40, 23) * 6
+    returns[0] = head.values                         # exactly on the atoms
+    returns[1] = -100.0
+    returns[2] = 100.0
+    categorical = tonic.torch.models.critics.CategoricalWithSupport(head.values, logits)
+    out.update({'categorical/logits': logits.numpy(), 'categorical/returns': returns.numpy(),
+                'categorical/values': head.values.numpy(),
+                'categorical/probabilities': categorical.probabilities.numpy(),
+                'categorical/mean': categorical.mean().numpy(),
+                'categorical/project': categorical.project(returns).numpy()})
+    for key, value in reference_streams.records(tonic, action_space).items():
+        out['streams/' + key] = value
+    save('reference_dropin', source='tonic/torch/agents/*.py initialize; torch/models/critics.py:23-66; '
+                                    'explorations/noisy.py; agents/basic.py', **out)
+
+
 def main():
     torch.set_num_threads(1)
     tonic = rl.load_reference()
@@ -563,6 +599,7 @@ def main():
     golden_buffer(tonic)
     golden_segment_minibatches(tonic)
     golden_sequential(tonic)
+    golden_reference_dropin(tonic)
     # cfg-2 shapes (HalfCheetah O=17, A=6) at N = 32*8 = 256, two consecutive updates.
     run_ppo(tonic, 'ppo_halfcheetah_small', 17, 6, workers=8, steps=32, seed=0, updates=2)
     # cfg-1 shapes (Pendulum O=3, A=1), W=1.

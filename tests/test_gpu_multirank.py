@@ -148,7 +148,9 @@ def test_two_ranks_keep_the_critic_under_the_next_rollout(tmp_path, exchange):
 ALLREDUCE_WORKER = os.path.join(ROOT, 'tests', 'mp_allreduce_worker.py')
 
 
-@pytest.mark.parametrize('world', [2, 4, 8])
+# (at most 4 ranks sharing the device: with the test process itself, 5 processes hold the GPU; the suite
+#  keeps every test at no more than 6)
+@pytest.mark.parametrize('world', [2, 4])
 def test_one_shot_allreduce_is_the_rank_ordered_sum(tmp_path, world):
     """tonic_allreduce_f32 between `world` processes (sharing this box's GPU; windows exchanged as
     IPC handles): every rank ends with the float32 sum of the contributions taken in rank order —
@@ -184,8 +186,8 @@ def test_one_shot_allreduce_between_peer_devices(tmp_path):
     import torch
     devices = torch.cuda.device_count()
     if devices < 2:
-        pytest.skip('one GPU on this box: peer windows need two')
-    world = min(devices, 8)
+        pytest.skip(f'needs 2 GPUs, found {devices}: peer windows need two devices')
+    world = min(devices, 4)                 # (with the test process: at most 5 processes on the GPUs)
     out = str(tmp_path / 'peer')
     launch(world, out, 29720 + world, command=(ALLREDUCE_WORKER,),
            extra_env={'TONIC_AMD_BACKEND': 'nccl'})
