@@ -54,10 +54,11 @@ const char* tonic_last_error(void);
  * tonic_value_regression_grad, 7 = tonic_stream_gate, 8 = the tonic_*_torso entries, tonic_mlp_hidden, `min_log_dual` of the MPO entries,  tonic_q_iteration_t.phase,
  * 9 = collector transport 3 + tonic_collector_transport, 10 = tonic_q_iteration_t.refresh_images (fp16x2 weight
  * images of the off-policy passes in the workspaces: tonic_offpolicy_workspace_bytes / tonic_q_iteration_workspace_bytes
- * grow), tonic_mlp_hidden packs with bit 30 set (plain widths of any size pass as they are), tonic_collector_q_act)
+ * grow), tonic_mlp_hidden packs with bit 30 set (plain widths of any size pass as they are), tonic_collector_q_act,
+ * 12 = the *_ranged critic entries (Return normaliser's value head) + tonic_reward_range)
  * and the gfx target the kernels were built for.  TONIC_ABI_VERSION is what a binding was compiled against:
  * tonic_amd/_fastcall (csrc/fastcall.c) and tonic_amd/_lib.py compare it with the loaded library's answer. */
-#define TONIC_ABI_VERSION 11
+#define TONIC_ABI_VERSION 12
 int32_t tonic_abi_version(void);
 const char* tonic_target_arch(void);
 
@@ -213,6 +214,59 @@ int tonic_value_regression_grad_torso(int32_t layers, const int32_t* sizes, int3
                                       const float* d_observations, const float* d_returns,
                                       float* d_grad_sums, int64_t n, int32_t O, void* d_workspace,
                                       int64_t workspace_bytes, void* stream);
+
+/* ---- the Return normaliser (on-policy critics: A2C, PPO, TRPO) ------------------------------
+ * The *_ranged entries replace the same reference code as the entry they are named after, for a model
+ *   built with ActorCritic(..., return_normalizer=tonic.torch.normalizers.Return(discount_factor)): the value
+ *   head then squashes its output, tonic/torch/models/critics.py:17-19 + normalizers/returns.py:21-23,
+ *     v = low + sigmoid(z) * (high - low),   z = w_v . h + b_v,
+ *   formed as torch forms it (s = 1 / (1 + exp(-z)), t = high - low, m = s * t, v = low + m, separate
+ *   float32 operations), and the regression's loss, gradient and statistics are those of the squashed v
+ *   (dz = 2 (v - ret) * t * (1 - s) * s, torch's sigmoid_backward order).
+ * d_value_low / d_value_high: float32 scalars on the device, the normaliser's `_low` / `_high` parameters
+ *   (read by the kernels: graph-safe, no host sync).  Both NULL = the plain head, the same bits as the entry
+ *   without the suffix; exactly one NULL = TONIC_ERR_INVALID_ARGUMENT.  The squashed head is served by the
+ *   shipped grad chain only (grad_variant 4, tonic_hip_dev.h).  Off-policy critics (Q heads) have no
+ *   squashed form.
+ */
+int tonic_value_forward_ranged(const float* d_critic_params, const float* d_norm_mean,
+                               const float* d_norm_std, double norm_clip, const float* d_observations,
+                               float* d_values, int64_t n, int32_t O, const float* d_value_low,
+                               const float* d_value_high, void* stream);
+int tonic_value_forward_wide_ranged(const float* d_critic_params, const float* d_norm_mean,
+                                    const float* d_norm_std, double norm_clip,
+                                    const float* d_observations, float* d_values, int64_t n, int32_t O,
+                                    void* d_workspace, int64_t workspace_bytes, const float* d_value_low,
+                                    const float* d_value_high, void* stream);
+int tonic_value_forward_torso_ranged(int32_t layers, const int32_t* sizes, int32_t activation,
+                                     const float* d_critic_params, const float* d_norm_mean,
+                                     const float* d_norm_std, double norm_clip,
+                                     const float* d_observations, float* d_values, int64_t n, int32_t O,
+                                     void* d_workspace, int64_t workspace_bytes, const float* d_value_low,
+                                     const float* d_value_high, void* stream);
+int tonic_value_regression_grad_ranged(const float* d_critic_params, const float* d_norm_mean,
+                                       const float* d_norm_std, double norm_clip,
+                                       const float* d_observations, const float* d_returns,
+                                       float* d_grad_sums, int64_t n, int32_t O, int32_t max_workgroups,
+                                       void* d_workspace, int64_t workspace_bytes,
+                                       const float* d_value_low, const float* d_value_high, void* stream);
+int tonic_value_regression_grad_torso_ranged(int32_t layers, const int32_t* sizes, int32_t activation,
+                                             const float* d_critic_params, const float* d_norm_mean,
+                                             const float* d_norm_std, double norm_clip,
+                                             const float* d_observations, const float* d_returns,
+                                             float* d_grad_sums, int64_t n, int32_t O, void* d_workspace,
+                                             int64_t workspace_bytes, const float* d_value_low,
+                                             const float* d_value_high, void* stream);
+
+/* tonic_reward_range replaces: tonic/torch/agents/a2c.py:68-69 / trpo.py:48-49
+ *   (`return_normalizer.record(rewards)` at every step) for a whole rollout: d_range2[2] = {min, max} of the
+ *   n floats at d_rewards (the Segment's rewards [T, W]).  Return.record (normalizers/returns.py:25-30) only
+ *   keeps a running min / max, so record([min, max]) does what recording every reward does.  NaN is skipped
+ *   (the reference's `<` / `>` are false for it), +-inf is kept; no non-NaN value (or n = 0) gives
+ *   {+inf, -inf}, min > max, the empty pair.  Exact: the same bits for any launch width and order.
+ *   Stream-ordered (a memset + two launches), no host sync.
+ */
+int tonic_reward_range(const float* d_rewards, int64_t n, float* d_range2, void* stream);
 
 /* ---- optimizer ---------------------------------------------------------------------------
  * replaces: torch.optim.Adam single-tensor path (torch/optim/adam.py:395-547) as

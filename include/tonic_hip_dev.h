@@ -28,6 +28,7 @@ extern "C" {
  *   "chain_fault" = 1      the NEXT chained critic step loses its first workgroup (test hook);
  *   "q_chain" = 0 | 1      off-policy iteration as chained launches (1, default) or one launch per pass;
  *   "gae_stream" = 0..4    which bit-exact GAE kernel serves small W (developer probe);
+ *   "range_blocks" = 0..256  workgroups of the reward-range reduction: at most this many (0, default: by n); same bits;
  *   "policy_tail" = 0 | 1  off-policy actors: sampling / target noise / dense copy in the tail of
  *                          the forward launch (1, default) or in their own launches (0); same bits. */
 int tonic_set_tuning(const char* key, int32_t value);

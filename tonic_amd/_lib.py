@@ -80,6 +80,17 @@ SIGNATURES = {
                                    [c_i64, c_i32, c_i32, c_f64, c_f64, c_vp, c_vp, c_i64, c_vp]),
     'tonic_value_regression_grad_torso': (ctypes.c_int, [c_i32, c_vp, c_i32] + [c_vp] * 3 + [c_f64] +
                                           [c_vp] * 3 + [c_i64, c_i32, c_vp, c_i64, c_vp]),
+    'tonic_value_forward_ranged': (ctypes.c_int, [c_vp] * 3 + [c_f64] + [c_vp] * 2 + [c_i64, c_i32] +
+                                   [c_vp] * 3),
+    'tonic_value_forward_wide_ranged': (ctypes.c_int, [c_vp] * 3 + [c_f64] + [c_vp] * 2 +
+                                        [c_i64, c_i32, c_vp, c_i64] + [c_vp] * 3),
+    'tonic_value_forward_torso_ranged': (ctypes.c_int, [c_i32, c_vp, c_i32] + [c_vp] * 3 + [c_f64] +
+                                         [c_vp] * 2 + [c_i64, c_i32, c_vp, c_i64] + [c_vp] * 3),
+    'tonic_value_regression_grad_ranged': (ctypes.c_int, [c_vp] * 3 + [c_f64] + [c_vp] * 3 +
+                                           [c_i64, c_i32, c_i32, c_vp, c_i64] + [c_vp] * 3),
+    'tonic_value_regression_grad_torso_ranged': (ctypes.c_int, [c_i32, c_vp, c_i32] + [c_vp] * 3 + [c_f64] +
+                                                 [c_vp] * 3 + [c_i64, c_i32, c_vp, c_i64] + [c_vp] * 3),
+    'tonic_reward_range': (ctypes.c_int, [c_vp, c_i64, c_vp, c_vp]),
     'tonic_adam_step': (ctypes.c_int, [c_vp] * 5 + [c_i64, c_f64, c_f64, c_f64, c_f64, c_f64,
                                                      c_i32, c_f64, c_f64, c_vp, c_vp, c_vp, c_vp]),
     'tonic_clip_workspace_bytes': (c_i64, [c_i64]),
@@ -175,7 +186,7 @@ SIGNATURES = {
 }
 
 
-ABI_VERSION = 11       # include/tonic_hip.h: tonic_abi_version()
+ABI_VERSION = 12       # include/tonic_hip.h: tonic_abi_version()
 
 
 class TonicHipError(RuntimeError):

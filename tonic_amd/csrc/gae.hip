@@ -943,3 +943,85 @@ extern "C" int tonic_advantage_stats_from_moments(const double* d_adv_moments,
   TONIC_CHECK_LAUNCH("tonic_advantage_stats_from_moments");
   return TONIC_OK;
 }
+
+// ---- the rollout's reward range (the Return normaliser's record, tonic/torch/normalizers/returns.py:25-30)
+// Return.record keeps a running min / max of every reward it is shown, so showing it the pair [min, max] of
+// a rollout does the same as showing it every reward: one reduction per rollout instead of a record per
+// step.  NaN is skipped (the reference's `<` / `>` are false for it), +-inf is kept.  The floats go through
+// the order-preserving map onto uint32 below and the workgroups meet in two atomicMax words, so the result
+// is exact and independent of the grid, the order and the sign of zero.  The words start at 0, the identity
+// of both (no non-NaN float maps there): an input with no non-NaN value leaves them so, and decodes to
+// {+inf, -inf}, min > max.
+namespace tonic {
+
+constexpr int kRangeThreads = 256;
+std::atomic<int> g_range_blocks{0};     // tuning key "range_blocks": 0 = by n, k > 0 = at most k workgroups
+
+__device__ __forceinline__ uint32_t ordered_bits(float x) {      // x < y  <=>  ordered(x) < ordered(y)
+  const uint32_t b = __float_as_uint(x);
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
+__device__ __forceinline__ float from_ordered(uint32_t u) {
+  return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
+}
+
+// words[0] = max of ~ordered(x) (the minimum), words[1] = max of ordered(x)
+__global__ __launch_bounds__(kRangeThreads) void reward_range_kernel(const float* rewards, int64_t n,
+                                                                     uint32_t* words) {
+  __shared__ uint32_t red[kRangeThreads / 64][2];
+  uint32_t lo = 0u, hi = 0u;
+  for (int64_t i = (int64_t)blockIdx.x * kRangeThreads + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * kRangeThreads) {
+    const float x = rewards[i];
+    if (x == x) {
+      const uint32_t u = ordered_bits(x);
+      lo = max(lo, ~u);
+      hi = max(hi, u);
+    }
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    lo = max(lo, (uint32_t)__shfl_xor((int)lo, off));
+    hi = max(hi, (uint32_t)__shfl_xor((int)hi, off));
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) { red[wave][0] = lo; red[wave][1] = hi; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < kRangeThreads / 64; ++w) { lo = max(lo, red[w][0]); hi = max(hi, red[w][1]); }
+    if (lo != 0u) atomicMax(words, lo);
+    if (hi != 0u) atomicMax(words + 1, hi);
+  }
+}
+
+__global__ void reward_range_finish_kernel(uint32_t* words) {
+  const uint32_t lo = words[0], hi = words[1];
+  float* range = reinterpret_cast<float*>(words);
+  range[0] = lo == 0u ? __uint_as_float(0x7f800000u) : from_ordered(~lo);     // none: +inf
+  range[1] = hi == 0u ? __uint_as_float(0xff800000u) : from_ordered(hi);      // none: -inf
+}
+
+}  // namespace tonic
+
+extern "C" int tonic_reward_range(const float* d_rewards, int64_t n, float* d_range2, void* stream) {
+  TONIC_REQUIRE(d_range2 != nullptr && n >= 0 && (n == 0 || d_rewards != nullptr), TONIC_ERR_INVALID_ARGUMENT,
+                "tonic_reward_range: bad argument");
+  hipStream_t st = as_stream(stream);
+  uint32_t* words = reinterpret_cast<uint32_t*>(d_range2);
+  if (hipMemsetAsync(words, 0, 2 * sizeof(uint32_t), st) != hipSuccess) {
+    set_error("tonic_reward_range: hipMemsetAsync failed");
+    return TONIC_ERR_LAUNCH;
+  }
+  if (n > 0) {
+    int64_t blocks = (n + 4 * kRangeThreads - 1) / (4 * kRangeThreads);      // >= 4 rewards per thread
+    if (blocks > 256) blocks = 256;
+    const int cap = g_range_blocks.load();
+    if (cap > 0 && blocks > cap) blocks = cap;
+    hipLaunchKernelGGL(reward_range_kernel, dim3((unsigned)blocks), dim3(kRangeThreads), 0, st, d_rewards,
+                       n, words);
+    TONIC_CHECK_LAUNCH("reward_range_kernel");
+  }
+  hipLaunchKernelGGL(reward_range_finish_kernel, dim3(1), dim3(1), 0, st, words);
+  TONIC_CHECK_LAUNCH("reward_range_finish_kernel");
+  return TONIC_OK;
+}

@@ -30,7 +30,31 @@ struct MlpArgs {
   int pstride;
   int skew;                 // initial phase offset (x ~8k cycles) of the second wave per SIMD
   int prio;                 // wave priorities of the 16-sample grad kernels (tuning key "grad_prio")
+  // critic: the Return normaliser's `_low` / `_high` (float32 scalars on the device; both NULL = the plain
+  // head v = w.h + b) travel in two pointers only the actor's kernels read, so the layout of the arguments
+  // — and the code of every kernel that existed before the squashed head — stays as it is.  Only the
+  // squashed instantiations (template flag SQ) read them.
+  __host__ __device__ const float* value_low() const { return actions; }
+  __host__ __device__ const float* value_high() const { return adv; }
+  void set_value_range(const float* low, const float* high) { actions = low; adv = high; }
 };
+
+// The Return normaliser's value head (tonic/torch/normalizers/returns.py:21-23, applied by
+// models/critics.py:17-19): v = low + sigmoid(z) (high - low) in the separate float32 operations torch
+// forms — s = 1 / (1 + exp(-z)), t = high - low, m = s t, v = low + m.  `s` and `t` stay for the backward.
+__device__ __forceinline__ float squash_value(float z, float low, float high, float& s, float& t) {
+  s = 1.f / (1.f + expf(-z));
+  t = high - low;
+  const float m = s * t;
+  return low + m;
+}
+
+// The squashed head's share of the loss gradient, d(v - ret)^2 / dz / 2 = ((err t) (1 - s)) s: the
+// mul / sub / mul of torch's backward of `s * t` and sigmoid_backward (grad (1 - s) s, left to right).
+// Callers double it (exact), so the fp16x2 kernel can bound it before it scales it.
+__device__ __forceinline__ float squash_grad(float err, float s, float t) {
+  return ((err * t) * (1.f - s)) * s;
+}
 
 // tanh(x) = sign(x) (1 - t) / (1 + t), t = exp(-2|x|): one v_exp_f32 + one v_rcp_f32, no
 // branches (the libm tanhf is ~40 instructions with a divergent branch).  Absolute error
@@ -79,5 +103,8 @@ int grad16_blocks(int64_t n);
 int launch_grad16(bool actor, int blocks, hipStream_t stream, const MlpArgs& args, int chain);
 int launch_grad16_probe(int blocks, hipStream_t stream, const MlpArgs& args);
 int launch_values16(int blocks, hipStream_t stream, const MlpArgs& args, int chain);
+// the same with the Return normaliser's head (args.value_low / value_high): the shipped chain (3) only
+int launch_grad16_squashed(int blocks, hipStream_t stream, const MlpArgs& args);
+int launch_values16_squashed(int blocks, hipStream_t stream, const MlpArgs& args);
 
 }  // namespace tonic

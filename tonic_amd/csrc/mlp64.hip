@@ -34,6 +34,7 @@
 #include "mlpfwd.h"
 
 namespace tonic { extern std::atomic<int> g_gae_stream; }      // gae.hip (tuning key "gae_stream")
+namespace tonic { extern std::atomic<int> g_range_blocks; }    // gae.hip (tuning key "range_blocks")
 
 namespace tonic {
 
@@ -361,8 +362,8 @@ __global__ __launch_bounds__(WAVES * 64) void ppo_collect_kernel(CollectArgs c) 
   }
 }
 
-// Critic forward: a2c.py:92-99.
-template <int KS1, int WAVES>
+// Critic forward: a2c.py:92-99.  SQ: the Return normaliser's head (squash_value, mlp64.h).
+template <int KS1, int WAVES, bool SQ = false>
 __global__ __launch_bounds__(WAVES * 64) void value_forward_kernel(MlpArgs a) {
   using L = Lds<KS1, 1, false, WAVES>;
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -379,7 +380,12 @@ __global__ __launch_bounds__(WAVES * 64) void value_forward_kernel(MlpArgs a) {
     dense_tanh<KS1>(lds + L::W1S, lds + L::B1P, x, h1, lane);
     dense_tanh<32>(lds + L::W2S, lds + L::B2P, h1, h2, lane);
     head_linear<1, L::W3P, L::HC>(lds, h2, h, z);
-    if (valid && h == 0) a.out0[ns] = z[0];
+    if constexpr (SQ) {
+      float sg, tw;
+      if (valid && h == 0) a.out0[ns] = squash_value(z[0], *a.value_low(), *a.value_high(), sg, tw);
+    } else {
+      if (valid && h == 0) a.out0[ns] = z[0];
+    }
   }
 }
 
@@ -816,9 +822,9 @@ int launch_act(int blocks, hipStream_t st, const MlpArgs& a) {
   return launch(ppo_act_kernel<KS1, AP, kFwdWaves>, blocks, kFwdWaves * 64,
                 Lds<KS1, AP, false, kFwdWaves>::BYTES, st, a, "tonic_ppo_act");
 }
-template <int KS1>
+template <int KS1, bool SQ = false>
 int launch_value(int blocks, hipStream_t st, const MlpArgs& a) {
-  return launch(value_forward_kernel<KS1, kFwdWaves>, blocks, kFwdWaves * 64,
+  return launch(value_forward_kernel<KS1, kFwdWaves, SQ>, blocks, kFwdWaves * 64,
                 Lds<KS1, 1, false, kFwdWaves>::BYTES, st, a, "tonic_value_forward");
 }
 #ifdef TONIC_DEV
@@ -904,6 +910,12 @@ extern "C" int tonic_set_tuning(const char* key, int32_t value) {
     g_q_images = value;
     return TONIC_OK;
   }
+  if (strcmp(key, "range_blocks") == 0) {
+    TONIC_REQUIRE(value >= 0 && value <= 256, TONIC_ERR_INVALID_ARGUMENT,
+                  "range_blocks must be in [0 (by n), 256], got %d", value);
+    g_range_blocks = value;
+    return TONIC_OK;
+  }
   if (strcmp(key, "gae_stream") == 0) {
     TONIC_REQUIRE(value >= 0 && value <= 4, TONIC_ERR_INVALID_ARGUMENT,
                   "gae_stream must be 0, 1, 2 (developer probe) or 3 (dword helpers), got %d", value);
@@ -923,6 +935,7 @@ extern "C" int tonic_get_tuning(const char* key, int32_t* value) {
   if (strcmp(key, "grad_variant") == 0) { *value = g_grad_variant; return TONIC_OK; }
   if (strcmp(key, "policy_tail") == 0) { *value = g_policy_tail; return TONIC_OK; }
   if (strcmp(key, "gae_stream") == 0) { *value = g_gae_stream; return TONIC_OK; }
+  if (strcmp(key, "range_blocks") == 0) { *value = g_range_blocks; return TONIC_OK; }
   if (strcmp(key, "q_chain") == 0) { *value = g_q_chain; return TONIC_OK; }
   if (strcmp(key, "q_images") == 0) { *value = g_q_images; return TONIC_OK; }
   set_error("tonic_get_tuning: unknown key '%s'", key);
@@ -1115,6 +1128,48 @@ extern "C" int tonic_value_forward(const float* d_critic_params, const float* d_
   });
 }
 
+// ---- the Return normaliser's head (tonic/torch/normalizers/returns.py): the *_ranged entries
+// Both range pointers NULL: the plain entry itself.  Otherwise the squashed instantiations, which serve the
+// shipped grad chain (grad_variant 4) only — the developer references 0 - 3 have no squashed form.
+static int ranged_arguments(const float* d_value_low, const float* d_value_high, const char* what) {
+  TONIC_REQUIRE((d_value_low == nullptr) == (d_value_high == nullptr), TONIC_ERR_INVALID_ARGUMENT,
+                "%s: d_value_low and d_value_high must both be set or both be NULL", what);
+  TONIC_REQUIRE(d_value_low == nullptr || g_grad_variant == kDefaultGradVariant, TONIC_ERR_INVALID_ARGUMENT,
+                "%s: the squashed value head is served by grad_variant %d only", what, kDefaultGradVariant);
+  return TONIC_OK;
+}
+
+extern "C" int tonic_value_forward_ranged(const float* d_critic_params, const float* d_norm_mean,
+                                          const float* d_norm_std, double norm_clip,
+                                          const float* d_observations, float* d_values, int64_t n,
+                                          int32_t O, const float* d_value_low,
+                                          const float* d_value_high, void* stream) {
+  if (int rc = ranged_arguments(d_value_low, d_value_high, "tonic_value_forward_ranged")) return rc;
+  if (d_value_low == nullptr)
+    return tonic_value_forward(d_critic_params, d_norm_mean, d_norm_std, norm_clip, d_observations,
+                               d_values, n, O, stream);
+  TONIC_REQUIRE(d_critic_params && d_norm_mean && d_norm_std && d_observations && d_values &&
+                    n >= 0, TONIC_ERR_INVALID_ARGUMENT, "tonic_value_forward_ranged: bad argument");
+  if (int rc = check_shape(O, 1, false)) return rc;
+  if (n == 0) return TONIC_OK;
+  MlpArgs a{};
+  a.params = d_critic_params; a.obs = d_observations; a.norm_mean = d_norm_mean;
+  a.norm_std = d_norm_std; a.norm_clip = clip_bound(norm_clip);
+  a.out0 = d_values; a.n = n; a.O = O; a.A = 1;
+  a.set_value_range(d_value_low, d_value_high);
+  hipStream_t st = as_stream(stream);
+  if (n >= kValues16MinRows && grad16_supported(O, 1, false)) {      // as tonic_value_forward
+    a.out1 = d_values;
+    return launch_values16_squashed(grad16_blocks(n), st, a);
+  }
+  const int64_t tiles = (n + 31) / 32;
+  int blocks = (int)((tiles + kFwdWaves - 1) / kFwdWaves);
+  if (blocks > 1024) blocks = 1024;
+  return dispatch_ks1(ks1_bucket(O), [&](auto ks) {
+    return launch_value<decltype(ks)::value, true>(blocks, st, a);
+  });
+}
+
 extern "C" int64_t tonic_mlp64_grad_workspace_bytes(int64_t n, int64_t param_count) {
   const int64_t pstride = round_up(param_count + kStatSlots, 64);
   const int blocks = grad_blocks(n) > grad16_blocks(n) ? grad_blocks(n) : grad16_blocks(n);
@@ -1146,6 +1201,15 @@ static int run_grad(MlpArgs a, int64_t P, float* d_grad_sums, float entropy_coef
   a.prio = g_grad_prio;
   const int ap = ACTOR ? ap_bucket(a.A) : 1;
   hipStream_t st = as_stream(stream);
+  if (!ACTOR && a.value_low() != nullptr) {
+    // the Return normaliser's head: the shipped chain only (ranged_arguments checked the variant)
+    TONIC_REQUIRE(use16, TONIC_ERR_UNSUPPORTED_SHAPE, "fused grad kernel: O = %d not served", a.O);
+    const int rc = launch_grad16_squashed(blocks, st, a);
+    if (rc != TONIC_OK) return rc;
+    return launch_reduce_partials(false, static_cast<const float*>(d_workspace), blocks, (int)pstride,
+                                  (int)P, a.params, d_grad_sums, a.O, a.A, entropy_coeff, (double)a.n,
+                                  a.skip, st);
+  }
 #ifdef TONIC_DEV
   const int rc = use16 ? launch_grad16(ACTOR, blocks, st, a, variant - 1) : dispatch_ks1(ks1_bucket(a.O), [&](auto ks) {
     constexpr int KS1 = decltype(ks)::value;
@@ -1362,4 +1426,110 @@ extern "C" int tonic_value_regression_grad(const float* d_critic_params,
   if (wide) return wide_critic_grad(a, d_grad_sums, d_workspace, workspace_bytes, as_stream(stream));
   return run_grad<false>(a, tonic_v_critic_param_count(O), d_grad_sums, 0.f, max_workgroups,
                          d_workspace, workspace_bytes, stream);
+}
+
+extern "C" int tonic_value_forward_wide_ranged(const float* d_critic_params, const float* d_norm_mean,
+                                               const float* d_norm_std, double norm_clip,
+                                               const float* d_observations, float* d_values, int64_t n,
+                                               int32_t O, void* d_workspace, int64_t workspace_bytes,
+                                               const float* d_value_low, const float* d_value_high,
+                                               void* stream) {
+  if (int rc = ranged_arguments(d_value_low, d_value_high, "tonic_value_forward_wide_ranged")) return rc;
+  if (d_value_low == nullptr)
+    return tonic_value_forward_wide(d_critic_params, d_norm_mean, d_norm_std, norm_clip, d_observations,
+                                    d_values, n, O, d_workspace, workspace_bytes, stream);
+  if (!wide_shape(O, 1, false))
+    return tonic_value_forward_ranged(d_critic_params, d_norm_mean, d_norm_std, norm_clip,
+                                      d_observations, d_values, n, O, d_value_low, d_value_high, stream);
+  TONIC_REQUIRE(d_critic_params && d_norm_mean && d_norm_std && d_observations && d_values && n >= 0,
+                TONIC_ERR_INVALID_ARGUMENT, "tonic_value_forward_wide_ranged: bad argument");
+  if (int rc = check_wide(O, 1, false)) return rc;
+  if (n == 0) return TONIC_OK;
+  MlpArgs a{};
+  a.params = d_critic_params; a.obs = d_observations; a.norm_mean = d_norm_mean;
+  a.norm_std = d_norm_std; a.norm_clip = clip_bound(norm_clip);
+  a.out0 = d_values; a.n = n; a.O = O; a.A = 1;
+  a.set_value_range(d_value_low, d_value_high);
+  return wide_value(a, d_workspace, workspace_bytes, as_stream(stream));
+}
+
+extern "C" int tonic_value_forward_torso_ranged(int32_t layers, const int32_t* sizes, int32_t activation,
+                                                const float* d_critic_params, const float* d_norm_mean,
+                                                const float* d_norm_std, double norm_clip,
+                                                const float* d_observations, float* d_values, int64_t n,
+                                                int32_t O, void* d_workspace, int64_t workspace_bytes,
+                                                const float* d_value_low, const float* d_value_high,
+                                                void* stream) {
+  if (int rc = ranged_arguments(d_value_low, d_value_high, "tonic_value_forward_torso_ranged")) return rc;
+  if (d_value_low == nullptr)
+    return tonic_value_forward_torso(layers, sizes, activation, d_critic_params, d_norm_mean, d_norm_std,
+                                     norm_clip, d_observations, d_values, n, O, d_workspace,
+                                     workspace_bytes, stream);
+  TONIC_REQUIRE(d_critic_params && d_norm_mean && d_norm_std && d_observations && d_values && n >= 0,
+                TONIC_ERR_INVALID_ARGUMENT, "tonic_value_forward_torso_ranged: null argument");
+  Torso t;
+  if (int rc = torso_from(layers, sizes, activation, t)) return rc;
+  if (int rc = check_wide(O, 1, false)) return rc;
+  if (n == 0) return TONIC_OK;
+  MlpArgs a{};
+  a.params = d_critic_params; a.obs = d_observations; a.norm_mean = d_norm_mean;
+  a.norm_std = d_norm_std; a.norm_clip = clip_bound(norm_clip);
+  a.out0 = d_values; a.n = n; a.O = O; a.A = 1;
+  a.set_value_range(d_value_low, d_value_high);
+  return wide_value(a, d_workspace, workspace_bytes, as_stream(stream), t);
+}
+
+extern "C" int tonic_value_regression_grad_ranged(const float* d_critic_params, const float* d_norm_mean,
+                                                  const float* d_norm_std, double norm_clip,
+                                                  const float* d_observations, const float* d_returns,
+                                                  float* d_grad_sums, int64_t n, int32_t O,
+                                                  int32_t max_workgroups, void* d_workspace,
+                                                  int64_t workspace_bytes, const float* d_value_low,
+                                                  const float* d_value_high, void* stream) {
+  if (int rc = ranged_arguments(d_value_low, d_value_high, "tonic_value_regression_grad_ranged")) return rc;
+  if (d_value_low == nullptr)
+    return tonic_value_regression_grad(d_critic_params, d_norm_mean, d_norm_std, norm_clip, d_observations,
+                                       d_returns, d_grad_sums, n, O, max_workgroups, d_workspace,
+                                       workspace_bytes, stream);
+  TONIC_REQUIRE(d_critic_params && d_norm_mean && d_norm_std && d_observations && d_returns &&
+                    d_grad_sums && n > 0,
+                TONIC_ERR_INVALID_ARGUMENT, "tonic_value_regression_grad_ranged: bad argument");
+  const bool wide = wide_shape(O, 1, false);
+  if (int rc = wide ? check_wide(O, 1, false) : check_shape(O, 1, false)) return rc;
+  MlpArgs a{};
+  a.params = d_critic_params; a.obs = d_observations; a.returns = d_returns;
+  a.norm_mean = d_norm_mean; a.norm_std = d_norm_std; a.norm_clip = clip_bound(norm_clip);
+  a.n = n; a.O = O; a.A = 1;
+  a.set_value_range(d_value_low, d_value_high);
+  if (wide) return wide_critic_grad(a, d_grad_sums, d_workspace, workspace_bytes, as_stream(stream));
+  return run_grad<false>(a, tonic_v_critic_param_count(O), d_grad_sums, 0.f, max_workgroups,
+                         d_workspace, workspace_bytes, stream);
+}
+
+extern "C" int tonic_value_regression_grad_torso_ranged(int32_t layers, const int32_t* sizes,
+                                                        int32_t activation, const float* d_critic_params,
+                                                        const float* d_norm_mean, const float* d_norm_std,
+                                                        double norm_clip, const float* d_observations,
+                                                        const float* d_returns, float* d_grad_sums, int64_t n,
+                                                        int32_t O, void* d_workspace, int64_t workspace_bytes,
+                                                        const float* d_value_low, const float* d_value_high,
+                                                        void* stream) {
+  if (int rc = ranged_arguments(d_value_low, d_value_high, "tonic_value_regression_grad_torso_ranged"))
+    return rc;
+  if (d_value_low == nullptr)
+    return tonic_value_regression_grad_torso(layers, sizes, activation, d_critic_params, d_norm_mean,
+                                             d_norm_std, norm_clip, d_observations, d_returns, d_grad_sums, n,
+                                             O, d_workspace, workspace_bytes, stream);
+  TONIC_REQUIRE(d_critic_params && d_norm_mean && d_norm_std && d_observations && d_returns &&
+                    d_grad_sums && n > 0,
+                TONIC_ERR_INVALID_ARGUMENT, "tonic_value_regression_grad_torso_ranged: bad argument");
+  Torso t;
+  if (int rc = torso_from(layers, sizes, activation, t)) return rc;
+  if (int rc = check_wide(O, 1, false)) return rc;
+  MlpArgs a{};
+  a.params = d_critic_params; a.obs = d_observations; a.returns = d_returns;
+  a.norm_mean = d_norm_mean; a.norm_std = d_norm_std; a.norm_clip = clip_bound(norm_clip);
+  a.n = n; a.O = O; a.A = 1;
+  a.set_value_range(d_value_low, d_value_high);
+  return wide_critic_grad(a, d_grad_sums, d_workspace, workspace_bytes, as_stream(stream), t);
 }

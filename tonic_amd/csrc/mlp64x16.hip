@@ -583,10 +583,13 @@ __device__ __forceinline__ unsigned long long probe_clock() {
 // FWD (critic only): the forward half alone — values -> a.out1, nothing else is formed or written
 // (tonic_value_forward on a whole Segment: the same tile loop, input prefetch and layer arithmetic
 // as the regression step that follows it).
+// SQ (critic only): the Return normaliser's head, v = low + sigmoid(z) (high - low) with low / high read
+// from a.value_low() / a.value_high() (squash_value); the plain instantiations do not contain it.
 template <int KS1, int XT, int XR, int AP, bool ACTOR, bool EXACT, int CH, bool PROBE = false,
-          bool FWD = false>
+          bool FWD = false, bool SQ = false>
 __global__ __launch_bounds__(kWaves16 * 64, 2) void mlp64_grad16_kernel(MlpArgs a) {
   static_assert(!FWD || !ACTOR, "the forward-only form serves the critic");
+  static_assert(!SQ || !ACTOR, "the squashed head is the critic's");
   using L = Lds16<KS1, AP, CH>;
   constexpr int TS16 = L::TS;
   // CH 2: dW2 as 2 x 2 tiles of v_mfma_f32_32x32x16_bf16 on bf16x3 terms — the 16 samples of a tile
@@ -607,6 +610,11 @@ __global__ __launch_bounds__(kWaves16 * 64, 2) void mlp64_grad16_kernel(MlpArgs 
   constexpr int kW3Window = KS1 >= 8 ? 2 : 8;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   if (a.skip != nullptr && *a.skip != 0) return;
+  float v_low = 0.f, v_high = 0.f;
+  if constexpr (SQ) {
+    v_low = *a.value_low();
+    v_high = *a.value_high();
+  }
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, s = lane & 15, g = lane >> 4;
   const int i = s;   // feature index inside a 16-feature tile when the lane acts in F layout
@@ -922,7 +930,12 @@ __global__ __launch_bounds__(kWaves16 * 64, 2) void mlp64_grad16_kernel(MlpArgs 
     }
 
     if constexpr (FWD) {
-      if (counted) a.out1[ns] = z[0];
+      if constexpr (SQ) {
+        float sg, tw;
+        if (counted) a.out1[ns] = squash_value(z[0], v_low, v_high, sg, tw);
+      } else {
+        if (counted) a.out1[ns] = z[0];
+      }
       cur = nxt;
       continue;
     }
@@ -988,6 +1001,28 @@ __global__ __launch_bounds__(kWaves16 * 64, 2) void mlp64_grad16_kernel(MlpArgs 
           }
           reinterpret_cast<f32x4*>(DO + s * 16 + 8)[0] = lo;
           reinterpret_cast<f32x4*>(DO + s * 16 + 8)[1] = hi;
+        }
+      }
+    } else if constexpr (SQ) {
+      // the Return normaliser's head: dz = 2 ((err t) (1 - s)) s, and the bound of the fp16x2 unit is that
+      // of |dz| / 2 (t reaches 1e4 and more: |err| alone would put the scaled products out of fp16's range)
+      float sg, tw;
+      const float v = squash_value(z[0], v_low, v_high, sg, tw);
+      const float err = valid ? v - in_ret : 0.f;
+      const float q = valid ? squash_grad(err, sg, tw) : 0.f;
+      if constexpr (F16) {
+        enter_unit(row_max16(fabsf(q) * w3_bound));
+        dzl[0] = 2.f * (q * s_run);
+      } else {
+        dzl[0] = 2.f * q;
+      }
+      st0 += cw * err * err;
+      st1 += cw * v;
+      st3 += cw;
+      if constexpr (!H1) {
+        if (g == 0) {
+          reinterpret_cast<f32x4*>(DO + s * 16 + 8)[0] = zero4;
+          reinterpret_cast<f32x4*>(DO + s * 16 + 8)[1] = zero4;
         }
       }
     } else {
@@ -2216,9 +2251,9 @@ int grad16_blocks(int64_t n) {
 
 namespace {
 
-template <int KS1, int XT, int XR, int AP, bool ACTOR, bool EXACT, int CH>
+template <int KS1, int XT, int XR, int AP, bool ACTOR, bool EXACT, int CH, bool SQ = false>
 int go16(int blocks, hipStream_t stream, const MlpArgs& args) {
-  auto kernel = mlp64_grad16_kernel<KS1, XT, XR, AP, ACTOR, EXACT, CH>;
+  auto kernel = mlp64_grad16_kernel<KS1, XT, XR, AP, ACTOR, EXACT, CH, false, false, SQ>;
   constexpr int lds_bytes = Lds16<KS1, AP, CH>::BYTES;
   static_assert(lds_bytes <= 160 * 1024, "mlp64_grad16: LDS budget");
   static thread_local bool configured = false;
@@ -2241,9 +2276,9 @@ int go16(int blocks, hipStream_t stream, const MlpArgs& args) {
   return TONIC_OK;
 }
 
-template <int KS1, int XT, int XR, int CH>
+template <int KS1, int XT, int XR, int CH, bool SQ = false>
 int go16_values(int blocks, hipStream_t stream, const MlpArgs& args) {
-  auto kernel = mlp64_grad16_kernel<KS1, XT, XR, 1, false, true, CH, false, true>;
+  auto kernel = mlp64_grad16_kernel<KS1, XT, XR, 1, false, true, CH, false, true, SQ>;
   constexpr int lds_bytes = Lds16<KS1, 1, CH>::BYTES;
   static thread_local bool configured = false;
   if (!configured) {
@@ -2261,13 +2296,22 @@ int go16_values(int blocks, hipStream_t stream, const MlpArgs& args) {
   return TONIC_OK;
 }
 
-template <int CH>
+template <int CH, bool SQ = false>
 int values_by_inputs(int blocks, hipStream_t stream, const MlpArgs& args) {
-  if (args.O <= 4) return go16_values<1, 0, 4, CH>(blocks, stream, args);
-  if (args.O <= 16) return go16_values<4, 1, 0, CH>(blocks, stream, args);
-  if (args.O == 17) return go16_values<5, 1, 1, CH>(blocks, stream, args);
-  if (args.O <= 20) return go16_values<5, 1, 4, CH>(blocks, stream, args);
-  return go16_values<8, 2, 0, CH>(blocks, stream, args);
+  if (args.O <= 4) return go16_values<1, 0, 4, CH, SQ>(blocks, stream, args);
+  if (args.O <= 16) return go16_values<4, 1, 0, CH, SQ>(blocks, stream, args);
+  if (args.O == 17) return go16_values<5, 1, 1, CH, SQ>(blocks, stream, args);
+  if (args.O <= 20) return go16_values<5, 1, 4, CH, SQ>(blocks, stream, args);
+  return go16_values<8, 2, 0, CH, SQ>(blocks, stream, args);
+}
+
+// the critic with the Return normaliser's head (shipped chain 3 only)
+int critic_squashed_by_inputs(int blocks, hipStream_t stream, const MlpArgs& args) {
+  if (args.O <= 4) return go16<1, 0, 4, 1, false, true, 3, true>(blocks, stream, args);
+  if (args.O <= 16) return go16<4, 1, 0, 1, false, true, 3, true>(blocks, stream, args);
+  if (args.O == 17) return go16<5, 1, 1, 1, false, true, 3, true>(blocks, stream, args);
+  if (args.O <= 20) return go16<5, 1, 4, 1, false, true, 3, true>(blocks, stream, args);
+  return go16<8, 2, 0, 1, false, true, 3, true>(blocks, stream, args);
 }
 
 template <int KS1, int XT, int XR, int CH>
@@ -2316,6 +2360,14 @@ int launch_values16(int blocks, hipStream_t stream, const MlpArgs& args, int cha
   set_error("grad chain %d is a developer reference: build with TONIC_DEV=1", chain);
   return TONIC_ERR_INVALID_ARGUMENT;
 #endif
+}
+
+int launch_values16_squashed(int blocks, hipStream_t stream, const MlpArgs& args) {
+  return values_by_inputs<3, true>(blocks, stream, args);
+}
+
+int launch_grad16_squashed(int blocks, hipStream_t stream, const MlpArgs& args) {
+  return critic_squashed_by_inputs(blocks, stream, args);
 }
 
 int launch_grad16(bool actor, int blocks, hipStream_t stream, const MlpArgs& args, int chain) {

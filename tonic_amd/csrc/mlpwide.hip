@@ -540,17 +540,29 @@ struct ValueLossArgs {
   float* image; int pstride; int P;
   int64_t N, slab;
   const int32_t* skip;
+  const float* value_low; const float* value_high;    // SQ: the Return normaliser's range
 };
 
+// SQ: the value column is the pre-activation z of the Return normaliser's head (squash_value, mlp64.h);
+// the loss is that of v = low + sigmoid(z) (high - low) and dv is the gradient with respect to z.
+template <bool SQ = false>
 __global__ __launch_bounds__(kWideThreads) void value_loss_kernel(ValueLossArgs a) {
   __shared__ double red[4][3];
   if (a.skip != nullptr && *a.skip != 0) return;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   double sq = 0.0, sv = 0.0, cnt = 0.0;
+  float v_low = 0.f, v_high = 0.f;
+  if constexpr (SQ) {
+    v_low = *a.value_low;
+    v_high = *a.value_high;
+  }
   const int64_t r_begin = (int64_t)blockIdx.x * a.slab, r_end = min(a.N, r_begin + a.slab);
   for (int64_t n = r_begin + tid; n < r_end; n += kWideThreads) {
-    const float v = a.values[n * a.ld], err = v - a.returns[n];
-    a.dv[n * a.ld] = 2.f * err;                          // d sum((v - ret)^2) / dv (critics.py:22)
+    float v = a.values[n * a.ld], sg = 0.f, tw = 0.f;
+    if constexpr (SQ) v = squash_value(v, v_low, v_high, sg, tw);
+    const float err = v - a.returns[n];
+    if constexpr (SQ) a.dv[n * a.ld] = 2.f * squash_grad(err, sg, tw);
+    else a.dv[n * a.ld] = 2.f * err;                     // d sum((v - ret)^2) / dv (critics.py:22)
     sq += (double)(err * err);
     sv += (double)v;
     cnt += 1.0;
@@ -599,6 +611,17 @@ __global__ void gather_column_kernel(const float* src, int ld, float* dst, int64
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x)
     dst[i] = src[i * ld];
+}
+
+// the value column through the Return normaliser's head (squash_value, mlp64.h)
+__global__ void gather_squashed_kernel(const float* src, int ld, float* dst, int64_t n, const float* low,
+                                       const float* high) {
+  const float v_low = *low, v_high = *high;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    float sg, tw;
+    dst[i] = squash_value(src[i * ld], v_low, v_high, sg, tw);
+  }
 }
 
 // ---------------------------------------------------------------------------------- host side
@@ -853,7 +876,11 @@ int wide_critic_grad(const MlpArgs& a, float* d_grad_sums, void* d_workspace,
   l.ld = kWideLd; l.returns = a.returns;
   l.image = reinterpret_cast<float*>(ws + L.off_image); l.pstride = (int)L.pstride; l.P = L.P;
   l.N = a.n; l.slab = L.slab; l.skip = a.skip;
-  hipLaunchKernelGGL(value_loss_kernel, dim3(L.blocks), dim3(kWideThreads), 0, st, l);
+  l.value_low = a.value_low(); l.value_high = a.value_high();
+  if (a.value_low() != nullptr)
+    hipLaunchKernelGGL(value_loss_kernel<true>, dim3(L.blocks), dim3(kWideThreads), 0, st, l);
+  else
+    hipLaunchKernelGGL(value_loss_kernel<false>, dim3(L.blocks), dim3(kWideThreads), 0, st, l);
   TONIC_CHECK_LAUNCH("value_loss_kernel");
   if (int rc = wide_backward(a.params, L, a.obs, a.n, a.O, 1, false, a.norm_mean, a.norm_std,
                              a.norm_clip, ws, a.skip, st))
@@ -1036,8 +1063,13 @@ int wide_value(const MlpArgs& a, void* d_workspace, int64_t workspace_bytes, hip
     return rc;
   int64_t blocks = (a.n + kWideThreads - 1) / kWideThreads;
   if (blocks > 1024) blocks = 1024;
-  hipLaunchKernelGGL(gather_column_kernel, dim3((unsigned)blocks), dim3(kWideThreads), 0, st,
-                     reinterpret_cast<const float*>(ws + L.off_out), kWideLd, a.out0, a.n);
+  if (a.value_low() != nullptr)
+    hipLaunchKernelGGL(gather_squashed_kernel, dim3((unsigned)blocks), dim3(kWideThreads), 0, st,
+                       reinterpret_cast<const float*>(ws + L.off_out), kWideLd, a.out0, a.n, a.value_low(),
+                       a.value_high());
+  else
+    hipLaunchKernelGGL(gather_column_kernel, dim3((unsigned)blocks), dim3(kWideThreads), 0, st,
+                       reinterpret_cast<const float*>(ws + L.off_out), kWideLd, a.out0, a.n);
   TONIC_CHECK_LAUNCH("gather_column_kernel");
   return TONIC_OK;
 }

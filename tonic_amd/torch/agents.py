@@ -470,8 +470,7 @@ class A2C(Agent):
         # step() may leave the next command with the environment (Block.ring issues it)
         self._armed = False
         self.steps_issued_by_environment = 0
-        self._arm_steps = (self._speculate and not self.model.return_normalizer
-                           and os.environ.get('TONIC_AMD_ARM', '1') != '0')
+        self._arm_steps = self._speculate and os.environ.get('TONIC_AMD_ARM', '1') != '0'
 
     # -- shapes beyond the fused act kernel (O > 32 or A > 8): staged copies + separate launches
     def _wide(self):
@@ -667,7 +666,7 @@ class A2C(Agent):
         if self._block_fed and observations is block.out_next_observations \
                 and rewards is block.out_rewards and resets is block.out_resets \
                 and terminations is block.out_terminations and self._eps_ahead and self._speculate \
-                and replay.index + 2 < replay.max_size and not self.model.return_normalizer:
+                and replay.index + 2 < replay.max_size:
             # the steady state of a block-fed loop (the general form is below): the next step's
             # command goes out first, the bookkeeping runs while the GPU works
             index = replay.index
@@ -719,9 +718,6 @@ class A2C(Agent):
             if terminations is not block.out_terminations and \
                     terminations is not block.terminations_bool:
                 np.copyto(block.terminations, terminations)
-        if self.model.return_normalizer:
-            raise NotImplementedError('return normalisers are not supported (never enabled by '
-                                      'the reference defaults)')
         replay.index += 1
         if self._gate_row is not None and replay.index > self._gate_row:
             self._open_gate()
@@ -747,6 +743,41 @@ class A2C(Agent):
 
     def _open_gate(self):
         self._gate_row = None
+
+    # -- the Return normaliser (a2c.py:68-69 records every step's rewards, :126-127 updates it)
+    def _range_rewards(self):
+        """The rollout is complete: its rewards' [min, max] (tonic_reward_range, stream-ordered) — merged over
+        the ranks' worker shards — goes to the Return normaliser at the update's sync (_record_rewards).
+        Return.record keeps only the running min / max, so the pair does what recording every reward
+        does.  Launched before anything of the update touches the Segment."""
+        if not self.model.return_normalizer:
+            return
+        if getattr(self, '_reward_range', None) is None:
+            self._reward_range = torch.empty(2, dtype=torch.float32, device=self.device)
+        rewards = self.replay.buffers['rewards']
+        _lib.check(self.lib.tonic_reward_range(_lib.ptr(rewards), rewards.numel(),
+                                               _lib.ptr(self._reward_range), _lib.current_stream()),
+                   'tonic_reward_range')
+        if parallel.exchanging():
+            # MIN / MAX over the ranks as one MAX of (-min, max): an empty pair (+inf, -inf) is its identity
+            self._reward_range[0].neg_()
+            torch.distributed.all_reduce(self._reward_range, op=torch.distributed.ReduceOp.MAX)
+            self._reward_range[0].neg_()
+
+    def _record_rewards(self):
+        """Reads the pair back (after the update's own sync: nothing left to wait for) and records it."""
+        if not self.model.return_normalizer:
+            return
+        low, high = self._reward_range.cpu().numpy()
+        if low <= high:                     # (min > max: no reward that is not NaN)
+            self.model.return_normalizer.record(np.array([low, high], np.float32))
+
+    def _update_normalizers(self):
+        """a2c.py:123-127 / ppo.py:55-59 / trpo.py:93-97, after the critic's iterations."""
+        if self.model.observation_normalizer:
+            self.model.observation_normalizer.update()
+        if self.model.return_normalizer:
+            self.model.return_normalizer.update()
 
     def _evaluate(self):
         """a2c.py:92-99 on the HBM-resident segment: fills values / next_values in place."""
@@ -778,6 +809,7 @@ class A2C(Agent):
         return self._infos
 
     def _update(self):
+        self._range_rewards()
         infos = self.enqueue_update().cpu().numpy()          # the only sync of the update
         parallel.check_one_shot()
         for i, key in enumerate(updaters.ACTOR_INFO):
@@ -787,8 +819,8 @@ class A2C(Agent):
             logger.store('critic/loss', row[0])
             logger.store('critic/v', row[1])      # mean of the value batch (log-equivalent)
         self.last_infos = infos
-        if self.model.observation_normalizer:
-            self.model.observation_normalizer.update()
+        self._record_rewards()
+        self._update_normalizers()
 
 
 class TRPO(A2C):
@@ -806,6 +838,7 @@ class TRPO(A2C):
 
     def _update(self):
         replay, critic = self.replay, self.critic_updater
+        self._range_rewards()
         values, next_values = self._evaluate()
         replay.compute_returns(values, next_values)
         batch = replay.get_full('observations', 'actions', 'log_probs', 'advantages')
@@ -822,8 +855,8 @@ class TRPO(A2C):
             logger.store('critic/v', row[1])
         logger.store('critic/iterations', updates)
         self.last_infos = infos
-        if self.model.observation_normalizer:
-            self.model.observation_normalizer.update()
+        self._record_rewards()
+        self._update_normalizers()
 
 
 class PPO(A2C):
@@ -1008,14 +1041,16 @@ class PPO(A2C):
     def _update(self):
         if not self._overlap():
             self.settle()
+            self._range_rewards()
             infos = self.enqueue_update().cpu().numpy()          # the only sync of the update
             parallel.check_one_shot()
             log_ppo_update(infos)
             self.last_infos = infos
-            if self.model.observation_normalizer:
-                self.model.observation_normalizer.update()
+            self._record_rewards()
+            self._update_normalizers()
             return
         self.settle()
+        self._range_rewards()
         replay, actor, critic = self.replay, self.actor_updater, self.critic_updater
         critic.max_workgroups = self._critic_width()
         values, next_values = self._evaluate()
@@ -1034,8 +1069,11 @@ class PPO(A2C):
             actor.enqueue_grad(obs, act, raw_adv, replay.adv_stats, log_probs)
             actor.enqueue_step(n, replay.adv_stats, infos[0, it])
         last.record()
-        # the critic's iterations: same inputs, the normaliser as it is NOW, their own stream
+        # the critic's iterations: same inputs, the normalisers as they are NOW, their own stream
         snapshot = tuple(t.clone() for t in critic.norm_tensors())
+        value_range = critic.range_tensors()
+        if value_range is not None:       # (the Return normaliser is refreshed below, under the chain)
+            value_range = tuple(t.clone() for t in value_range)
         normaliser_done = False
         if parallel.exchanging() and self.model.observation_normalizer:
             # Several ranks: the normaliser's update is a collective + a read-back on THIS stream; issued
@@ -1058,7 +1096,7 @@ class PPO(A2C):
             self._arm_gate(side)
             clock.record(side)
             for it in range(updates):
-                critic.enqueue_grad(obs, returns, norm=snapshot)
+                critic.enqueue_grad(obs, returns, norm=snapshot, value_range=value_range)
                 critic.enqueue_step(n, infos[1, it])
             done.record(side)
         # (Enqueued HERE, while the GPU is busy with the actor's chain and the host has nothing else
@@ -1066,7 +1104,8 @@ class PPO(A2C):
         #  chain just finishes before the rollout does, so that the next update's first launches find
         #  the chip at its working clock (profiles/r04_clock_ramp.md): the 160 enqueues then sit on the
         #  host-bound collect loop's critical path, 82.3 against 80.9 ms per step.)
-        self._critic_pending = dict(done=done, clock=clock, infos=infos, keep=(obs, returns, snapshot))
+        self._critic_pending = dict(done=done, clock=clock, infos=infos,
+                                    keep=(obs, returns, snapshot, value_range))
         rows = infos[0].cpu().numpy()                    # waits for the actor's iterations only
         self.actor_chain_ms = first.elapsed_time(last)   # (bench.py reports it)
         parallel.check_one_shot()
@@ -1074,6 +1113,9 @@ class PPO(A2C):
         self._last_infos = np.stack([rows, np.zeros_like(rows)])
         if self.model.observation_normalizer and not normaliser_done:
             self.model.observation_normalizer.update()
+        self._record_rewards()
+        if self.model.return_normalizer:
+            self.model.return_normalizer.update()
         # What the next rollout depends on — the actor, the normaliser — is on the current stream up
         # to here: a stream of its own carries that point to the collector (step() -> begin_rollout),
         # which also moves the rollout's observations to the spare buffer.  Everything ELSE that

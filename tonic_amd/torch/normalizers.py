@@ -1,4 +1,5 @@
-"""``MeanStd`` observation normaliser — API of ``tonic/torch/normalizers/mean_stds.py``.
+"""``MeanStd`` observation normaliser — API of ``tonic/torch/normalizers/mean_stds.py`` — and ``Return``,
+the value head's normaliser of ``tonic/torch/normalizers/returns.py``.
 
 The reference accumulates ``new_sum`` / ``new_sum_sq`` with a Python loop over worker rows
 (mean_stds.py:44-48).  Here the running sums live in HBM (``device_sums``, float32[2*O]) and
@@ -88,3 +89,43 @@ class MeanStd(torch.nn.Module):
         self.new_count, self.new_sum, self.new_sum_sq = 0, 0, 0
         self._mean.data.copy_(torch.as_tensor(self.mean, dtype=torch.float32))
         self._std.data.copy_(torch.as_tensor(self.std, dtype=torch.float32))
+
+
+class Return(torch.nn.Module):
+    """``tonic/torch/normalizers/returns.py``: the value head squashes its output into
+    ``[_low, _high] = coefficient * [min_reward, max_reward]`` (forward), ``record`` keeps the running
+    reward range, ``update`` refreshes the two parameters on the host like the reference.
+
+    The on-policy agents (A2C, PPO, TRPO) record a whole rollout at once: the pair [min, max] of the
+    Segment's rewards (``tonic_reward_range``), which is what recording every reward does, since only
+    the running min / max is kept.  Their critic kernels read ``_low`` / ``_high`` from the device
+    (the ``*_ranged`` entries of include/tonic_hip.h)."""
+
+    def __init__(self, discount_factor):
+        super().__init__()
+        assert 0 <= discount_factor < 1
+        self.coefficient = 1 / (1 - discount_factor)
+        self.min_reward = np.float32(-1)
+        self.max_reward = np.float32(1)
+        self._low = torch.nn.Parameter(torch.as_tensor(
+            self.coefficient * self.min_reward, dtype=torch.float32), requires_grad=False)
+        self._high = torch.nn.Parameter(torch.as_tensor(
+            self.coefficient * self.max_reward, dtype=torch.float32), requires_grad=False)
+
+    def forward(self, val):
+        val = torch.sigmoid(val)
+        return self._low + val * (self._high - self._low)
+
+    def record(self, values):
+        for val in values:
+            if val < self.min_reward:
+                self.min_reward = np.float32(val)
+            elif val > self.max_reward:
+                self.max_reward = np.float32(val)
+
+    def update(self):
+        self._update(self.min_reward, self.max_reward)
+
+    def _update(self, min_reward, max_reward):
+        self._low.data.copy_(torch.as_tensor(self.coefficient * min_reward, dtype=torch.float32))
+        self._high.data.copy_(torch.as_tensor(self.coefficient * max_reward, dtype=torch.float32))

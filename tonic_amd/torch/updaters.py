@@ -541,6 +541,9 @@ class VRegression(_FlatUpdater):
         self.variables = model.flat_critic.params
         self.observation_size = model.critic.torso.model[0].in_features
         self.normalizer = model.observation_normalizer
+        # the Return normaliser of the value head (critics.py:17-19): the *_ranged entries squash with its
+        # _low / _high (stock torch applies it through model.critic)
+        self.return_normalizer = getattr(model.critic.head, 'return_normalizer', None) or None
         if not fused_ppo_torso(model.critic.torso):
             self.torso = hip_ppo_torso(model.critic.torso)
             if self.torso is None or self.lib.tonic_ppo_torso_param_count(
@@ -561,6 +564,12 @@ class VRegression(_FlatUpdater):
         """MeanStd(clip=...) (mean_stds.py:37-38) as the C ABI wants it: 0 = None."""
         return float(getattr(self.normalizer, 'clip', None) or 0.0)
 
+    def range_tensors(self):
+        """The Return normaliser's (_low, _high) on the device, or None without one."""
+        if self.return_normalizer is None:
+            return None
+        return self.return_normalizer._low.data, self.return_normalizer._high.data
+
     def forward_values(self, observations, out):
         if self.stock:
             with torch.no_grad():
@@ -569,6 +578,20 @@ class VRegression(_FlatUpdater):
         mean, std = self.norm_tensors()
         p = _lib.ptr
         ws = self._workspace_for(observations.shape[0])
+        value_range = self.range_tensors()
+        if value_range is not None:
+            low, high = p(value_range[0]), p(value_range[1])
+            if self.torso is not None:
+                _lib.check(self.lib.tonic_value_forward_torso_ranged(
+                    *self.torso, p(self.flat.flat), p(mean), p(std), self.norm_clip(), p(observations),
+                    p(out), observations.shape[0], self.observation_size, p(ws), ws.numel(), low, high,
+                    _lib.current_stream()), 'tonic_value_forward_torso_ranged')
+                return out
+            _lib.check(self.lib.tonic_value_forward_wide_ranged(
+                p(self.flat.flat), p(mean), p(std), self.norm_clip(), p(observations), p(out),
+                observations.shape[0], self.observation_size, p(ws), ws.numel(), low, high,
+                _lib.current_stream()), 'tonic_value_forward_wide_ranged')
+            return out
         if self.torso is not None:
             _lib.check(self.lib.tonic_value_forward_torso(
                 *self.torso, p(self.flat.flat), p(mean), p(std), self.norm_clip(), p(observations), p(out),
@@ -581,9 +604,10 @@ class VRegression(_FlatUpdater):
             _lib.current_stream()), 'tonic_value_forward_wide')
         return out
 
-    def enqueue_grad(self, observations, returns, norm=None):
+    def enqueue_grad(self, observations, returns, norm=None, value_range=None):
         """`norm`: (mean, std) to use instead of the normaliser's tensors — a snapshot, for
-        iterations that run while the normaliser is being updated (agents.PPO._update)."""
+        iterations that run while the normaliser is being updated (agents.PPO._update); `value_range`:
+        the same for the Return normaliser's (low, high)."""
         if self.stock:                                    # critics.py:18-28
             self.torch_optimizer.zero_grad()
             values = self.model.critic(observations)
@@ -595,6 +619,21 @@ class VRegression(_FlatUpdater):
         ws = self._workspace_for(n)
         mean, std = norm if norm is not None else self.norm_tensors()
         p = _lib.ptr
+        if value_range is None:
+            value_range = self.range_tensors()
+        if value_range is not None:
+            low, high = p(value_range[0]), p(value_range[1])
+            if self.torso is not None:
+                _lib.check(self.lib.tonic_value_regression_grad_torso_ranged(
+                    *self.torso, p(self.flat.flat), p(mean), p(std), self.norm_clip(), p(observations),
+                    p(returns), p(self.grad_sums), n, self.observation_size, p(ws), ws.numel(), low, high,
+                    _lib.current_stream()), 'tonic_value_regression_grad_torso_ranged')
+                return
+            _lib.check(self.lib.tonic_value_regression_grad_ranged(
+                p(self.flat.flat), p(mean), p(std), self.norm_clip(), p(observations), p(returns),
+                p(self.grad_sums), n, self.observation_size, self.max_workgroups, p(ws), ws.numel(),
+                low, high, _lib.current_stream()), 'tonic_value_regression_grad_ranged')
+            return
         if self.torso is not None:
             _lib.check(self.lib.tonic_value_regression_grad_torso(
                 *self.torso, p(self.flat.flat), p(mean), p(std), self.norm_clip(), p(observations),
