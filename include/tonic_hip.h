@@ -55,10 +55,11 @@ const char* tonic_last_error(void);
  * 9 = collector transport 3 + tonic_collector_transport, 10 = tonic_q_iteration_t.refresh_images (fp16x2 weight
  * images of the off-policy passes in the workspaces: tonic_offpolicy_workspace_bytes / tonic_q_iteration_workspace_bytes
  * grow), tonic_mlp_hidden packs with bit 30 set (plain widths of any size pass as they are), tonic_collector_q_act,
- * 12 = the *_ranged critic entries (Return normaliser's value head) + tonic_reward_range)
+ * 12 = the *_ranged critic entries (Return normaliser's value head) + tonic_reward_range, 13 = tonic_mlp_torso:
+ * 1 .. 4 layer torsos for every off-policy entry, the D4PG / MPO entries take tonic_mlp_hidden codes)
  * and the gfx target the kernels were built for.  TONIC_ABI_VERSION is what a binding was compiled against:
  * tonic_amd/_fastcall (csrc/fastcall.c) and tonic_amd/_lib.py compare it with the loaded library's answer. */
-#define TONIC_ABI_VERSION 12
+#define TONIC_ABI_VERSION 13
 int32_t tonic_abi_version(void);
 const char* tonic_target_arch(void);
 
@@ -612,15 +613,25 @@ int tonic_adam_polyak_step(float* d_online, const float* d_grad_sums, float* d_e
  *   padded block length; gradient / Adam-moment buffers use the same layout and length.
  * All scratch comes from ONE caller-provided workspace (tonic_offpolicy_workspace_bytes).
  * Torsos other than the reference's (tonic/torch/models/utils.py:4-23 accepts any MLP(sizes, activation)): for
- *   the SAC / TD3 / DDPG entries — tonic_policy_forward, tonic_twin_q_grad, tonic_actor_q_grad, the three size
- *   queries below — `H` may be tonic_mlp_hidden(H1, H2, activation): two hidden layers of H1 and H2 units
- *   (1 .. 4095: the (400, 300) class; a plain width — two ReLU layers of H units — is passed as is, any width), activation 1 = torch.nn.ReLU, 2 = Tanh, 3 = ELU; W2 is then [H2, H1],
- *   heads / w3 are H2 wide, same padding rules.  Such torsos run layer by layer (csrc/gemm16.hip) instead of in
- *   the fused kernels; tonic_q_iteration and the D4PG / MPO entries take plain widths only.
+ *   every off-policy entry — tonic_policy_forward, tonic_twin_q_grad, tonic_actor_q_grad, the three size queries
+ *   below, tonic_distributional_{workspace_bytes,q_grad,actor_grad}, tonic_mpo_workspace_bytes,
+ *   tonic_expected_sarsa_grad, tonic_mpo_actor_grad(_shard) — `H` is an `H` code:
+ *     - a plain width: two ReLU layers of H units, passed as is (bit 30 clear, any width);
+ *     - tonic_mlp_hidden(H1, H2, activation): two hidden layers of H1 and H2 units (1 .. 4095: the (400, 300)
+ *       class), activation 1 = torch.nn.ReLU, 2 = Tanh, 3 = ELU (bit 30 set, bit 29 clear);
+ *     - tonic_mlp_torso(layers, sizes, activation) for 1, 3 or 4 layers: a descriptor registered in a process-wide
+ *       table of 64 (bits 30 and 29 set, the low bits its index; the same torso always gets the same code; valid in
+ *       the process that registered it).  For two layers tonic_mlp_torso returns what tonic_mlp_hidden does.
+ *   Layer l is then W_l [H_l, H_(l-1)] b_l [H_l] (H_(-1) = the input), heads / w3 are as wide as the last layer,
+ *   same padding rules.  Every torso but the plain one runs layer by layer (csrc/gemm16.hip) instead of in the
+ *   fused kernels; tonic_q_iteration* and tonic_mlp_actor_image_bytes serve plain widths only.
  */
 int64_t tonic_offpolicy_workspace_bytes(int32_t B, int32_t O, int32_t A, int32_t H);
 int32_t tonic_mlp_weight_stride(int32_t cols);
 int32_t tonic_mlp_hidden(int32_t H1, int32_t H2, int32_t activation);
+/* `H` of MLP(sizes[0 .. layers), activation): layers 1 .. 4, widths 1 .. 4095, activation 1 ReLU / 2 Tanh / 3 ELU.
+ * Negative (tonic_last_error set): outside those limits, NULL sizes, or the descriptor table is full. */
+int32_t tonic_mlp_torso(int32_t layers, const int32_t* sizes, int32_t activation);
 int64_t tonic_mlp_actor_param_count(int32_t O, int32_t H, int32_t A, int32_t heads);
 int64_t tonic_q_critic_param_count(int32_t O, int32_t A, int32_t H);
 

@@ -87,8 +87,21 @@ struct GemmGroup {
   AdamFold adam;
 };
 
+// The weight gradients of a network deeper than two layers are more problems than GemmGroup holds (L layers + two
+// heads: up to 6): a second form of the weight-gradient kernel takes them (gemm_tn_group_wide_kernel), so that the
+// first one's arguments — and its code — stay what they are.
+constexpr int kGemmGroupWide = 6;
+struct GemmGroupWide {
+  unsigned long long* stamps;
+  GemmArgs problem[kGemmGroupWide];
+  int first[kGemmGroupWide + 1];
+  int count;
+  AdamFold adam;
+};
+
 int launch_gemm(char mode_a, char mode_b, const GemmArgs& g, int batch, hipStream_t stream);
-// `count` (<= kGemmGroupMax) GEMMs of the same layout and K in one launch (see gemm16.hip).
+// `count` (<= kGemmGroupMax; the plain TN weight-gradient form: <= kGemmGroupWide) GEMMs of the same layout and
+// K in one launch (see gemm16.hip).
 int launch_gemm_group(char mode_a, char mode_b, const GemmArgs* list, int count, int batch,
                       hipStream_t stream, const AdamFold* adam = nullptr);
 

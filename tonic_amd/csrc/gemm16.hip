@@ -271,8 +271,10 @@ __device__ __forceinline__ void adam_fold_arrive(const AdamFold& f, unsigned tot
 }
 
 // COLSUM: this tile also forms the column sums of A (the bias gradient: the tiles of the first tile
-// column) — a compile-time flag, or the six additions per chunk run (selected away) in every tile
-template <bool EDGE, bool COLSUM>
+// column) — a compile-time flag, or the six additions per chunk run (selected away) in every tile.
+// FORM: 0 gemm_tn_group_kernel, 1 gemm_tn_group_wide_kernel — one instantiation per kernel: sharing them changed
+// the first kernel's code (the LDS address arithmetic), which the second form must leave as it is.
+template <bool EDGE, bool COLSUM, int FORM = 0>
 __device__ __forceinline__ void gemm_tn_tile(const GemmArgs& g, int tm, int tn, float* part,
                                              const AdamFold& fold, unsigned total_blocks,
                                              unsigned long long* stamps) {
@@ -564,6 +566,27 @@ __global__ __launch_bounds__(64 * kTnWaves) void gemm_tn_group_kernel(GemmGroup 
   }
 }
 
+// gemm_tn_group_kernel over up to kGemmGroupWide problems (the weight gradients of torsos deeper than two layers)
+__global__ __launch_bounds__(64 * kTnWaves) void gemm_tn_group_wide_kernel(GemmGroupWide G) {
+  __shared__ float part[kTnWaves * 64 * kTnPart];
+  kernarg_prefetch<sizeof(GemmGroupWide)>();
+  int p = 0;
+#pragma unroll
+  for (int q = 1; q < kGemmGroupWide; ++q) p += (q < G.count && (int)blockIdx.x >= G.first[q]) ? 1 : 0;
+  const GemmArgs& g = G.problem[p];
+  const int tile = (int)blockIdx.x - G.first[p], tiles_n = (g.N + 31) / 32;
+  const int tm = tile / tiles_n, tn = tile - tm * tiles_n;
+  const unsigned total = gridDim.x * gridDim.z;
+  const bool sums = g.colsum != nullptr && tn == 0;
+  if (32 * tm + 32 > g.lda || 32 * tn + 32 > g.ldb) {
+    if (sums) gemm_tn_tile<true, true, 1>(g, tm, tn, part, G.adam, total, G.stamps);
+    else gemm_tn_tile<true, false, 1>(g, tm, tn, part, G.adam, total, G.stamps);
+  } else {
+    if (sums) gemm_tn_tile<false, true, 1>(g, tm, tn, part, G.adam, total, G.stamps);
+    else gemm_tn_tile<false, false, 1>(g, tm, tn, part, G.adam, total, G.stamps);
+  }
+}
+
 namespace {
 
 // waves per tile: at most kGemmGroup chunks per wave, then more while the chip is not full
@@ -575,12 +598,42 @@ int waves_per_tile(int K, int64_t tiles_total) {
   return S;
 }
 
+// More than kGemmGroupMax problems: the plain TN weight-gradient form only, on gemm_tn_group_wide_kernel.
+int launch_gemm_group_wide(char mode_a, char mode_b, const GemmArgs* list, int count, int batch,
+                           hipStream_t stream, const AdamFold* adam) {
+  bool plain = mode_a == 's' && mode_b == 's';
+  for (int p = 0; p < count; ++p) plain = plain && !list[p].bias && !list[p].mask && list[p].act == ACT_NONE;
+  TONIC_REQUIRE(plain, TONIC_ERR_INVALID_ARGUMENT,
+                "gemm group: %d problems (more than %d: the plain TN weight-gradient form only)", count, kGemmGroupMax);
+  GemmGroupWide G{};
+  G.count = count;
+  if (adam != nullptr) {
+    G.adam = *adam;
+    G.adam.on = 1;
+  }
+  int blocks = 0;
+  for (int p = 0; p < count; ++p) {
+    const GemmArgs& g = list[p];
+    TONIC_REQUIRE(g.A && g.B && g.C && g.M > 0 && g.N > 0 && g.K == list[0].K && g.K > 0,
+                  TONIC_ERR_INVALID_ARGUMENT, "gemm group: problem %d (M=%d N=%d K=%d)", p, g.M,
+                  g.N, g.K);
+    G.problem[p] = g;
+    G.first[p] = blocks;
+    blocks += ((g.M + 31) / 32) * ((g.N + 31) / 32);
+  }
+  G.first[count] = blocks;
+  hipLaunchKernelGGL(gemm_tn_group_wide_kernel, dim3(blocks, 1, batch), dim3(64, kTnWaves), 0, stream, G);
+  TONIC_CHECK_LAUNCH("gemm_tn_group_wide");
+  return TONIC_OK;
+}
+
 }  // namespace
 
 int launch_gemm_group(char mode_a, char mode_b, const GemmArgs* list, int count, int batch,
                       hipStream_t stream, const AdamFold* adam) {
-  TONIC_REQUIRE(list && count >= 1 && count <= kGemmGroupMax && batch > 0,
+  TONIC_REQUIRE(list && count >= 1 && count <= kGemmGroupWide && batch > 0,
                 TONIC_ERR_INVALID_ARGUMENT, "gemm group: %d problems", count);
+  if (count > kGemmGroupMax) return launch_gemm_group_wide(mode_a, mode_b, list, count, batch, stream, adam);
   GemmGroup G{};
   G.count = count;
   if (adam != nullptr) {

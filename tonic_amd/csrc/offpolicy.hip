@@ -1,4 +1,4 @@
-// Off-policy learner path (SAC / TD3) for 2-hidden-layer ReLU networks, gfx950.
+// Off-policy learner path (SAC / TD3 / DDPG / D4PG / MPO), gfx950.
 //
 // Restates (paths relative to the reference checkout):
 //   tonic/torch/updaters/critics.py:125-134 (TargetActionNoise), :156-182
@@ -21,63 +21,130 @@
 #include "collector_q.h"
 #include "bufstore.h"
 
+#include <mutex>
+
 namespace tonic {
 
-// Torso: MLP((H, H2), activation) of tonic/torch/models/utils.py:4-23.  The fused kernels (mlpfwd.hip) hold the
-// reference's shape — two ReLU layers of one width (H2 = 0 = "as H", act = ACT_RELU); every other two-layer torso
-// (unequal widths: the (400, 300) class; Tanh; ELU) runs layer by layer on gemm16 launches — `plain()` tells.
+// Torso: MLP(sizes, activation) of tonic/torch/models/utils.py:4-23.  The fused kernels (mlpfwd.hip) hold the
+// reference's shape — two ReLU layers of one width (H2 = 0 = "as H", act = ACT_RELU); every other torso (unequal
+// widths: the (400, 300) class; Tanh; ELU; 1, 3 or 4 layers) runs layer by layer on gemm16 launches — `plain()`
+// tells.  L: hidden layers (1 .. kTorsoMaxLayers), of H, h2(), H3, H4 units.
+constexpr int kTorsoMaxLayers = 4;
 struct ActorShape {                              // heads: 1 = deterministic (TD3), 2 = loc+scale (SAC)
   int O, H, A, heads; int H2 = 0; int act = ACT_RELU;
+  int L = 2; int H3 = 0, H4 = 0;
   __host__ __device__ int h2() const { return H2 > 0 ? H2 : H; }
-  __host__ __device__ int hp() const { return weight_ld(H > h2() ? H : h2()); }   // pitch of every hidden array
-  bool plain() const { return h2() == H && act == ACT_RELU; }
+  __host__ __device__ int width(int l) const { return l == 0 ? H : l == 1 ? h2() : l == 2 ? H3 : H4; }
+  __host__ __device__ int last() const { return width(L - 1); }              // the heads' input width
+  __host__ __device__ int hp() const {                                        // pitch of every hidden array
+    int w = 0;
+    for (int l = 0; l < L; ++l) w = width(l) > w ? width(l) : w;
+    return weight_ld(w);
+  }
+  bool plain() const { return L == 2 && h2() == H && act == ACT_RELU; }
 };
 struct CriticShape {
   int O, A, H; int H2 = 0; int act = ACT_RELU;
+  int L = 2; int H3 = 0, H4 = 0;
   __host__ __device__ int h2() const { return H2 > 0 ? H2 : H; }
-  __host__ __device__ int hp() const { return weight_ld(H > h2() ? H : h2()); }
-  bool plain() const { return h2() == H && act == ACT_RELU; }
+  __host__ __device__ int width(int l) const { return l == 0 ? H : l == 1 ? h2() : l == 2 ? H3 : H4; }
+  __host__ __device__ int last() const { return width(L - 1); }
+  __host__ __device__ int hp() const {
+    int w = 0;
+    for (int l = 0; l < L; ++l) w = width(l) > w ? width(l) : w;
+    return weight_ld(w);
+  }
+  bool plain() const { return L == 2 && h2() == H && act == ACT_RELU; }
 };
 
-// The C ABI passes ONE int32 `H`: the width of a plain torso (any width: bit 30 clear), or tonic_mlp_hidden(H1,
-// H2, activation) = 1 << 30 | H1 | H2 << 12 | activation << 24 (widths below 4096; activation: GemmAct).
+// The C ABI passes ONE int32 `H`: the width of a plain torso (any width: bit 30 clear), tonic_mlp_hidden(H1, H2,
+// activation) = 1 << 30 | H1 | H2 << 12 | activation << 24 (two layers, widths below 4096; activation: GemmAct), or
+// for 1, 3 or 4 layers a descriptor that tonic_mlp_torso registered: 1 << 30 | 1 << 29 | its index in a small
+// process-wide table.  The codes are unpacked here, on the host; no kernel sees one.
 constexpr int32_t kHiddenPacked = 1 << 30;
-struct Hidden { int H1, H2, act; };
-inline Hidden unpack_hidden(int32_t code) {
-  if ((code & kHiddenPacked) == 0) return Hidden{code, code, ACT_RELU};
-  Hidden h{code & 4095, (code >> 12) & 4095, (code >> 24) & 7};
-  if (h.H2 == 0) h.H2 = h.H1;
+constexpr int32_t kTorsoRegistered = 1 << 29;
+constexpr int kTorsoTableSize = 64;
+struct Torso { int L, width[kTorsoMaxLayers], act; };   // L == 0: not a torso this library knows
+
+struct TorsoTable {
+  std::mutex lock;
+  Torso entry[kTorsoTableSize];
+  int count = 0;
+};
+TorsoTable& torso_table() {
+  static TorsoTable table;
+  return table;
+}
+
+inline Torso unpack_torso(int32_t code) {
+  if ((code & kHiddenPacked) == 0) return Torso{2, {code, code, 0, 0}, ACT_RELU};
+  if (code & kTorsoRegistered) {
+    TorsoTable& t = torso_table();
+    const int index = code & (kTorsoRegistered - 1);
+    std::lock_guard<std::mutex> guard(t.lock);
+    return index < t.count ? t.entry[index] : Torso{0, {0, 0, 0, 0}, 0};
+  }
+  Torso h{2, {code & 4095, (code >> 12) & 4095, 0, 0}, (code >> 24) & 7};
+  if (h.width[1] == 0) h.width[1] = h.width[0];
   if (h.act == 0) h.act = ACT_RELU;
   return h;
 }
 inline ActorShape actor_shape(int O, int32_t code, int A, int heads) {
-  const Hidden h = unpack_hidden(code);
-  return ActorShape{O, h.H1, A, heads, h.H2 == h.H1 ? 0 : h.H2, h.act};
+  const Torso t = unpack_torso(code);
+  return ActorShape{O, t.width[0], A, heads, t.L >= 2 && t.width[1] != t.width[0] ? t.width[1] : 0, t.act, t.L,
+                    t.width[2], t.width[3]};
 }
 inline CriticShape critic_shape(int O, int A, int32_t code) {
-  const Hidden h = unpack_hidden(code);
-  return CriticShape{O, A, h.H1, h.H2 == h.H1 ? 0 : h.H2, h.act};
+  const Torso t = unpack_torso(code);
+  return CriticShape{O, A, t.width[0], t.L >= 2 && t.width[1] != t.width[0] ? t.width[1] : 0, t.act, t.L,
+                     t.width[2], t.width[3]};
 }
 inline int hidden_pitch(int32_t code) {
-  const Hidden h = unpack_hidden(code);
-  return weight_ld(h.H1 > h.H2 ? h.H1 : h.H2);
+  const Torso t = unpack_torso(code);
+  int w = 0;
+  for (int l = 0; l < t.L; ++l) w = t.width[l] > w ? t.width[l] : w;
+  return weight_ld(w);
 }
 inline bool hidden_plain(int32_t code) {
-  const Hidden h = unpack_hidden(code);
-  return h.H1 == h.H2 && h.act == ACT_RELU;
+  const Torso t = unpack_torso(code);
+  return t.L == 2 && t.width[0] == t.width[1] && t.act == ACT_RELU;
+}
+inline bool hidden_known(int32_t code) { return code > 0 && unpack_torso(code).L > 0; }
+// Layers of hidden activations the workspaces hold per network and pass: two at least, so that the two-layer
+// layouts (and every workspace size of a two-layer torso) stay what they are.
+inline int hidden_layers(int32_t code) {
+  const int L = unpack_torso(code).L;
+  return L > 2 ? L : 2;
 }
 
-// Floats of one network in the padded layout (mlpfwd.h: weight_ld / slot4):
-//   actor : W1 [H, O] b1 [H] W2 [H2, H] b2 [H2] then per head Wh [A, H2] bh [A]
-//   critic: W1 [H, O + A] b1 [H] W2 [H2, H] b2 [H2] w3 [1, H2] b3 [1]
+// Floats of one network in the padded layout (mlpfwd.h: weight_ld / slot4), layer by layer:
+//   actor : W1 [H, O] b1 [H] W2 [H2, H] b2 [H2] ... then per head Wh [A, H_L] bh [A]
+//   critic: W1 [H, O + A] b1 [H] W2 [H2, H] b2 [H2] ... w3 [1, H_L] b3 [1]
 __host__ __device__ inline int64_t actor_count(ActorShape s) {
-  return (int64_t)s.H * weight_ld(s.O) + slot4(s.H) + (int64_t)s.h2() * weight_ld(s.H) + slot4(s.h2()) +
-         (int64_t)s.heads * ((int64_t)s.A * weight_ld(s.h2()) + slot4(s.A));
+  int64_t n = 0;
+  int in = s.O;
+  for (int l = 0; l < s.L; ++l) {
+    n += (int64_t)s.width(l) * weight_ld(in) + slot4(s.width(l));
+    in = s.width(l);
+  }
+  return n + (int64_t)s.heads * ((int64_t)s.A * weight_ld(in) + slot4(s.A));
 }
 __host__ __device__ inline int64_t critic_count(CriticShape s) {
-  return (int64_t)s.H * weight_ld(s.O + s.A) + slot4(s.H) + (int64_t)s.h2() * weight_ld(s.H) +
-         slot4(s.h2()) + weight_ld(s.h2()) + slot4(1);
+  int64_t n = 0;
+  int in = s.O + s.A;
+  for (int l = 0; l < s.L; ++l) {
+    n += (int64_t)s.width(l) * weight_ld(in) + slot4(s.width(l));
+    in = s.width(l);
+  }
+  return n + weight_ld(in) + slot4(1);
 }
+
+// Hidden activations of the layer-by-layer passes: the callers take a network's L layers as ONE region and pass
+// its first two layers (h1, h2): layer l lies at h1 + l (h2 - h1).  The input-gradient chains run the other way
+// and are passed (dh2, dh1) = (dz of the last layer, dz of the one below): dz of layer l lies at
+// dh2 + (L - 1 - l) (dh1 - dh2).  For two layers these are the arrays the fused kernels take.
+template <typename T>
+inline T* layer_at(T* first, T* second, int l) { return first + (int64_t)l * (second - first); }
 
 // ------------------------------------------------------------------ element-wise kernels
 
@@ -606,17 +673,29 @@ inline int pad16(int x) { return (x + 15) / 16 * 16; }
 inline int pitch16(int x) { return weight_ld(pad16(x)); }
 
 // Pointers into one actor's block of a flat buffer (parameters, or the gradient sums of the same
-// layout); ld1 / ldH: row strides of W1 and of the H-column weights.
+// layout); ld1 / ldH: row strides of W1 and of the H-column weights; W[l] / b[l] / ld[l]: layer l of any depth.
 template <typename T>
 struct ActorBlock {
   T *W1, *b1, *W2, *b2, *Wh;                    // Wh: first head; the second follows head_stride on
+  T *W[kTorsoMaxLayers], *b[kTorsoMaxLayers];   // (W1 = W[0], W2 = W[1])
+  int ld[kTorsoMaxLayers];                      // row pitch of W[l]: weight_ld of the layer's input width
   ActorShape s;
   int ld1, ldH;
   int64_t head_stride;
-  int ldO;                                       // row pitch of the heads (their inputs: the second layer)
-  ActorBlock(T* p, ActorShape sh) : s(sh), ld1(weight_ld(sh.O)), ldH(weight_ld(sh.H)), ldO(weight_ld(sh.h2())) {
-    W1 = p; b1 = W1 + (int64_t)s.H * ld1; W2 = b1 + slot4(s.H); b2 = W2 + (int64_t)s.h2() * ldH;
-    Wh = b2 + slot4(s.h2());
+  int ldO;                                       // row pitch of the heads (their inputs: the last layer)
+  ActorBlock(T* p, ActorShape sh) : s(sh), ldO(weight_ld(sh.last())) {
+    T* at = p;
+    int in = s.O;
+    for (int l = 0; l < kTorsoMaxLayers; ++l) {
+      W[l] = b[l] = nullptr;
+      ld[l] = 0;
+      if (l >= s.L) continue;
+      ld[l] = weight_ld(in);
+      W[l] = at; b[l] = at + (int64_t)s.width(l) * ld[l]; at = b[l] + slot4(s.width(l));
+      in = s.width(l);
+    }
+    W1 = W[0]; b1 = b[0]; W2 = W[1]; b2 = b[1]; ld1 = ld[0]; ldH = ld[1];
+    Wh = at;
     head_stride = (int64_t)s.A * ldO + slot4(s.A);
   }
   T* head_w(int h) const { return Wh + h * head_stride; }
@@ -626,10 +705,22 @@ using ActorParams = ActorBlock<const float>;
 
 struct CriticOffsets {
   int64_t W1, b1, W2, b2, w3, b3, count;
-  int ld1, ldH, ldO;                             // ldO: pitch of the value head's row (second layer wide)
-  explicit CriticOffsets(CriticShape s) : ld1(weight_ld(s.O + s.A)), ldH(weight_ld(s.H)), ldO(weight_ld(s.h2())) {
-    W1 = 0; b1 = W1 + (int64_t)s.H * ld1; W2 = b1 + slot4(s.H); b2 = W2 + (int64_t)s.h2() * ldH;
-    w3 = b2 + slot4(s.h2()); b3 = w3 + ldO; count = b3 + slot4(1);
+  int64_t W[kTorsoMaxLayers], b[kTorsoMaxLayers];   // layer l of any depth (W1 = W[0], W2 = W[1])
+  int ld[kTorsoMaxLayers];
+  int ld1, ldH, ldO;                             // ldO: pitch of the value head's row (last layer wide)
+  explicit CriticOffsets(CriticShape s) : ldO(weight_ld(s.last())) {
+    int64_t at = 0;
+    int in = s.O + s.A;
+    for (int l = 0; l < kTorsoMaxLayers; ++l) {
+      W[l] = b[l] = 0;
+      ld[l] = 0;
+      if (l >= s.L) continue;
+      ld[l] = weight_ld(in);
+      W[l] = at; b[l] = at + (int64_t)s.width(l) * ld[l]; at = b[l] + slot4(s.width(l));
+      in = s.width(l);
+    }
+    W1 = W[0]; b1 = b[0]; W2 = W[1]; b2 = b[1]; ld1 = ld[0]; ldH = ld[1];
+    w3 = at; b3 = w3 + ldO; count = b3 + slot4(1);
   }
 };
 
@@ -711,7 +802,7 @@ int actor_forward(const float* params, ActorShape s, const float* obs, int B, fl
   ActorParams p(params, s);
   if (ldx <= 0) ldx = s.O;                      // dense observation rows unless told otherwise
   if (tail_done != nullptr) *tail_done = false;
-  const int HP = s.hp(), H2 = s.h2();
+  const int HP = s.hp();
   if (s.plain() && mlp_forward_supported(s.H, s.A, s.heads)) {      // one launch for torso + heads
     MlpFwdArgs f{};
     f.X = obs; f.ldx = ldx; f.K1 = s.O;
@@ -740,17 +831,21 @@ int actor_forward(const float* params, ActorShape s, const float* obs, int B, fl
     }
     return launch_mlp_forward(f, 1, st);
   }
-  GemmArgs g = gemm(obs, ldx, p.W1, p.ld1, h1, HP, B, s.H, s.O);
-  g.bias = p.b1; g.act = s.act;
-  TRY(launch_gemm('c', 'c', g, 1, st));
-  g = gemm(h1, HP, p.W2, p.ldH, h2, HP, B, H2, s.H);
-  g.bias = p.b2; g.act = s.act;
-  TRY(launch_gemm('c', 'c', g, 1, st));
-  g = gemm(h2, HP, p.head_w(0), p.ldO, head0, ldh, B, s.A, H2);
+  // layer by layer: one launch per layer (bias + activation in the epilogue), then one per head
+  GemmArgs g;
+  for (int l = 0; l < s.L; ++l) {
+    g = l == 0 ? gemm(obs, ldx, p.W[0], p.ld[0], h1, HP, B, s.H, s.O)
+               : gemm(layer_at(h1, h2, l - 1), HP, p.W[l], p.ld[l], layer_at(h1, h2, l), HP, B, s.width(l),
+                      s.width(l - 1));
+    g.bias = p.b[l]; g.act = s.act;
+    TRY(launch_gemm('c', 'c', g, 1, st));
+  }
+  const float* top = layer_at(h1, h2, s.L - 1);
+  g = gemm(top, HP, p.head_w(0), p.ldO, head0, ldh, B, s.A, s.last());
   g.bias = p.head_b(0); g.act = tanh_head ? ACT_TANH : ACT_NONE;
   TRY(launch_gemm('c', 'c', g, 1, st));
   if (s.heads == 2) {
-    g = gemm(h2, HP, p.head_w(1), p.ldO, head1, ldh, B, s.A, H2);
+    g = gemm(top, HP, p.head_w(1), p.ldO, head1, ldh, B, s.A, s.last());
     g.bias = p.head_b(1);
     TRY(launch_gemm('c', 'c', g, 1, st));
   }
@@ -797,7 +892,7 @@ int critics_forward(const float* params, CriticShape s, int nets, const float* X
                     const CriticImg* img = nullptr) {
   const CriticOffsets o(s);
   const int in = s.O + s.A;
-  const int HP = s.hp(), H2 = s.h2();
+  const int HP = s.hp();
   const int64_t hs = (int64_t)Bp * HP;
   if (s.plain() && mlp_forward_supported(s.H, 1, 1)) {              // one launch for all `nets` critics
     int launch_nets = 0;
@@ -811,15 +906,16 @@ int critics_forward(const float* params, CriticShape s, int nets, const float* X
     return critics_forward(params2, s, nets, X2, ldx, B, Bp, h1 + nets * hs, h2 + nets * hs,
                            q + (int64_t)nets * Bp, st);
   }
-  GemmArgs g = gemm(X, ldx, params + o.W1, o.ld1, h1, HP, B, s.H, in);
-  g.bias = params + o.b1; g.act = s.act;
-  g.strideB = o.count; g.strideBias = o.count; g.strideC = hs;
-  TRY(launch_gemm('c', 'c', g, nets, st));
-  g = gemm(h1, HP, params + o.W2, o.ldH, h2, HP, B, H2, s.H);
-  g.bias = params + o.b2; g.act = s.act;
-  g.strideA = hs; g.strideB = o.count; g.strideBias = o.count; g.strideC = hs;
-  TRY(launch_gemm('c', 'c', g, nets, st));
-  g = gemm(h2, HP, params + o.w3, o.ldO, q, 1, B, 1, H2);
+  GemmArgs g;
+  for (int l = 0; l < s.L; ++l) {
+    g = l == 0 ? gemm(X, ldx, params + o.W[0], o.ld[0], h1, HP, B, s.H, in)
+               : gemm(layer_at(h1, h2, l - 1), HP, params + o.W[l], o.ld[l], layer_at(h1, h2, l), HP, B,
+                      s.width(l), s.width(l - 1));
+    g.bias = params + o.b[l]; g.act = s.act;
+    g.strideA = l == 0 ? 0 : hs; g.strideB = o.count; g.strideBias = o.count; g.strideC = hs;
+    TRY(launch_gemm('c', 'c', g, nets, st));
+  }
+  g = gemm(layer_at(h1, h2, s.L - 1), HP, params + o.w3, o.ldO, q, 1, B, 1, s.last());
   g.bias = params + o.b3;
   g.strideA = hs; g.strideB = o.count; g.strideBias = o.count; g.strideC = Bp;
   TRY(launch_gemm('c', 'c', g, nets, st));
@@ -865,27 +961,30 @@ MlpBwdArgs critics_chain_args(const float* params, CriticShape s, int nets, int 
   return b;
 }
 
-// The three weight gradients of `nets` critics (all contract over the batch) in ONE launch:
+// The weight gradients of `nets` critics (all contract over the batch) in ONE launch:
 //   dw3[1,H] = dq^T h2, db3 = sum dq ; dW2[H,H] = dz2^T h1, db2 ; dW1[H,in] = dz1^T X, db1
+// (L layers: the value head, then dW_l = dz_l^T h_{l-1} from the top layer down; L + 1 problems)
 int critics_weight_gradients(CriticShape s, int nets, const float* X, int ldx, int B, int Bp,
                              const float* h1, const float* h2, const float* dq, const float* dh2,
                              const float* dh1, float* grads, hipStream_t st, const AdamFold* fold,
                              const CriticImg* img = nullptr) {
   const CriticOffsets o(s);
   const int in = s.O + s.A;
-  const int HP = s.hp(), H2 = s.h2();
+  const int HP = s.hp();
   const int64_t hs = (int64_t)Bp * HP;
-  GemmArgs w[3];
-  w[0] = gemm(dq, 1, h2, HP, grads + o.w3, o.ldO, 1, H2, B);
+  GemmArgs w[kTorsoMaxLayers + 1];
+  w[0] = gemm(dq, 1, layer_at(h1, h2, s.L - 1), HP, grads + o.w3, o.ldO, 1, s.last(), B);
   w[0].colsum = grads + o.b3; w[0].strideColsum = o.count;
   w[0].strideA = Bp; w[0].strideB = hs; w[0].strideC = o.count;
-  w[1] = gemm(dh2, HP, h1, HP, grads + o.W2, o.ldH, H2, s.H, B);
-  w[1].colsum = grads + o.b2; w[1].strideColsum = o.count;
-  w[1].strideA = hs; w[1].strideB = hs; w[1].strideC = o.count;
-  w[2] = gemm(dh1, HP, X, ldx, grads + o.W1, o.ld1, s.H, in, B);
-  w[2].colsum = grads + o.b1; w[2].strideColsum = o.count;
-  w[2].strideA = hs; w[2].strideC = o.count;
-  if (fold != nullptr && img != nullptr && img->block != nullptr) {
+  for (int l = s.L - 1; l >= 0; --l) {
+    GemmArgs& g = w[s.L - l];
+    const float* dz = layer_at(dh2, dh1, s.L - 1 - l);
+    g = l > 0 ? gemm(dz, HP, layer_at(h1, h2, l - 1), HP, grads + o.W[l], o.ld[l], s.width(l), s.width(l - 1), B)
+              : gemm(dz, HP, X, ldx, grads + o.W[0], o.ld[0], s.H, in, B);
+    g.colsum = grads + o.b[l]; g.strideColsum = o.count;
+    g.strideA = hs; g.strideB = l > 0 ? hs : 0; g.strideC = o.count;
+  }
+  if (fold != nullptr && img != nullptr && img->block != nullptr) {      // (images: the plain torso, L == 2)
     // the optimizer epilogue keeps the stepped tensors' weight images (and their targets') up to date
     const int64_t to_target = img->target != nullptr ? img->target - img->block : 0;
     w[1].img = ImgTarget{img->block + img->v.f2.off, img->v.f2.chunks, img->block + img->v.t2.off,
@@ -893,7 +992,7 @@ int critics_weight_gradients(CriticShape s, int nets, const float* X, int ldx, i
     w[2].img = ImgTarget{img->block + img->v.f1.off, img->v.f1.chunks, img->block + img->v.t1a.off,
                          img->v.t1a.chunks, s.O, s.A, img->v.bytes, to_target};
   }
-  return launch_gemm_group('s', 's', w, 3, nets, st, fold);
+  return launch_gemm_group('s', 's', w, s.L + 1, nets, st, fold);
 }
 
 int critics_backward(const float* params, CriticShape s, int nets, const float* X, int ldx, int B,
@@ -913,7 +1012,7 @@ int critics_backward(const float* params, CriticShape s, int nets, const float* 
                          loss->alpha, nets == 2 ? 1 : 0, dq, loss->stats, B, Bp);
     }
   }
-  const int HP = s.hp(), H2 = s.h2();
+  const int HP = s.hp();
   const int64_t hs = (int64_t)Bp * HP;
   const int ldxa = pad16(s.A);
   GemmArgs g;
@@ -923,18 +1022,21 @@ int critics_backward(const float* params, CriticShape s, int nets, const float* 
     b.skip_dz = grads == nullptr ? 1 : 0;          // (a frozen critic's chain: only its action columns are read)
     TRY(launch_mlp_backward(b, nets, st));
   } else {
-    // dz2 = (dq w3) * relu'(h2)
-    g = gemm(dq, 1, params + o.w3, o.ldO, dh2, HP, B, H2, 1);
-    g.mask = h2; g.ldmask = HP; g.mask_act = s.act;
+    // dz_top = (dq w3) * act'(h_top)   (two layers: dz2, with h2)
+    g = gemm(dq, 1, params + o.w3, o.ldO, dh2, HP, B, s.last(), 1);
+    g.mask = layer_at(h1, h2, s.L - 1); g.ldmask = HP; g.mask_act = s.act;
     g.strideA = Bp; g.strideB = o.count; g.strideC = hs; g.strideMask = hs;
     TRY(launch_gemm('c', 's', g, nets, st));
-    // dz1 = (dz2 W2) * act'(h1)
-    g = gemm(dh2, HP, params + o.W2, o.ldH, dh1, HP, B, s.H, H2);
-    g.mask = h1; g.ldmask = HP; g.mask_act = s.act;
-    g.strideA = hs; g.strideB = o.count; g.strideC = hs; g.strideMask = hs;
-    TRY(launch_gemm('c', 's', g, nets, st));
+    // dz_{l-1} = (dz_l W_l) * act'(h_{l-1})   (two layers: dz1 = (dz2 W2) * act'(h1))
+    for (int l = s.L - 1; l >= 1; --l) {
+      g = gemm(layer_at(dh2, dh1, s.L - 1 - l), HP, params + o.W[l], o.ld[l], layer_at(dh2, dh1, s.L - l), HP, B,
+               s.width(l - 1), s.width(l));
+      g.mask = layer_at(h1, h2, l - 1); g.ldmask = HP; g.mask_act = s.act;
+      g.strideA = hs; g.strideB = o.count; g.strideC = hs; g.strideMask = hs;
+      TRY(launch_gemm('c', 's', g, nets, st));
+    }
     if (dxa) {     // dxa = dz1 W1[:, O : O + A]
-      g = gemm(dh1, HP, params + o.W1 + s.O, o.ld1, dxa, ldxa, B, s.A, s.H);
+      g = gemm(layer_at(dh2, dh1, s.L - 1), HP, params + o.W1 + s.O, o.ld1, dxa, ldxa, B, s.A, s.H);
       g.strideA = hs; g.strideB = o.count; g.strideC = (int64_t)Bp * ldxa;
       TRY(launch_gemm('c', 's', g, nets, st));
     }
@@ -978,7 +1080,8 @@ ImageSet take_images(Workspace& ws, int O, int A, int H, int heads, bool on) {
 }
 
 int64_t offpolicy_workspace_floats(int B, int O, int A, int H) {
-  const int64_t Bp = pad16(B), ldx = pitch16(O + A), ldh = pad16(A), HP = hidden_pitch(H);
+  // (every hidden array below holds hidden_layers(H) layers: HP stands for half of them, two layers' pitch)
+  const int64_t Bp = pad16(B), ldx = pitch16(O + A), ldh = pad16(A), HP = hidden_pitch(H) * hidden_layers(H) / 2;
   // actor h1,h2 + 2 heads + act + sigma + logp ; X ; critics h1,h2,q,dq,dh2,dh1 (x2) ; dX ; dloc,dspre,dah2,dah1
   return 2 * Bp * HP + 2 * Bp * ldh + 2 * Bp * A + Bp + Bp * ldx + 2 * (4 * Bp * HP + 2 * Bp) +
          Bp * ldx + 2 * Bp * ldh + 2 * Bp * HP + 2 * Bp * ldh + 64 * 16 +
@@ -1012,6 +1115,40 @@ extern "C" int32_t tonic_mlp_hidden(int32_t H1, int32_t H2, int32_t activation) 
   return kHiddenPacked | H1 | (H2 << 12) | (activation << 24);
 }
 
+// The `H` argument for MLP(sizes[0 .. layers), activation), 1 .. 4 layers: two layers give tonic_mlp_hidden's
+// code; 1, 3 or 4 a descriptor registered in a process-wide table (the same torso: the same code).  Negative:
+// not representable, or the table is full (tonic_last_error says which).
+extern "C" int32_t tonic_mlp_torso(int32_t layers, const int32_t* sizes, int32_t activation) {
+  if (layers < 1 || layers > kTorsoMaxLayers || sizes == nullptr || activation < ACT_RELU || activation > ACT_ELU) {
+    set_error("tonic_mlp_torso: %d layers, activation %d (1 .. %d layers; 1 ReLU, 2 Tanh, 3 ELU)", layers,
+              activation, kTorsoMaxLayers);
+    return -1;
+  }
+  Torso t{layers, {0, 0, 0, 0}, activation};
+  for (int l = 0; l < layers; ++l) {
+    if (sizes[l] < 1 || sizes[l] > 4095) {
+      set_error("tonic_mlp_torso: layer %d has %d units (1 .. 4095)", l, sizes[l]);
+      return -1;
+    }
+    t.width[l] = sizes[l];
+  }
+  if (layers == 2) return tonic_mlp_hidden(sizes[0], sizes[1], activation);
+  TorsoTable& table = torso_table();
+  std::lock_guard<std::mutex> guard(table.lock);
+  for (int i = 0; i < table.count; ++i) {
+    const Torso& e = table.entry[i];
+    bool same = e.L == t.L && e.act == t.act;
+    for (int l = 0; l < kTorsoMaxLayers; ++l) same = same && e.width[l] == t.width[l];
+    if (same) return kHiddenPacked | kTorsoRegistered | i;
+  }
+  if (table.count == kTorsoTableSize) {
+    set_error("tonic_mlp_torso: %d distinct torsos registered already", kTorsoTableSize);
+    return -1;
+  }
+  table.entry[table.count] = t;
+  return kHiddenPacked | kTorsoRegistered | table.count++;
+}
+
 // Policy forward for acting / evaluation.  kind: 0 = deterministic tanh head (TD3,
 // actors.py:113-115), 1 = squashed Gaussian sample tanh(loc + sigma * eps) (SAC
 // `_stochastic_actions`, sac.py:40-43; eps = NULL gives the greedy `loc` of sac.py:48-51).
@@ -1019,14 +1156,14 @@ extern "C" int tonic_policy_forward(const float* d_actor_params, const float* d_
                                     const float* d_eps, float* d_actions, int32_t kind, int32_t B,
                                     int32_t O, int32_t H, int32_t A, void* d_workspace,
                                     int64_t workspace_bytes, void* stream) {
-  TONIC_REQUIRE(d_actor_params && d_observations && d_actions && d_workspace && B > 0,
+  TONIC_REQUIRE(d_actor_params && d_observations && d_actions && d_workspace && B > 0 && hidden_known(H),
                 TONIC_ERR_INVALID_ARGUMENT, "tonic_policy_forward: bad argument");
   TONIC_REQUIRE(workspace_bytes >= tonic_offpolicy_workspace_bytes(B, O, A, H),
                 TONIC_ERR_WORKSPACE, "tonic_policy_forward: workspace too small");
   hipStream_t st = as_stream(stream);
   const int Bp = pad16(B), ldh = pad16(A), HP = hidden_pitch(H);
   Workspace ws{static_cast<char*>(d_workspace), 0, workspace_bytes};
-  float* h1 = ws.take((int64_t)Bp * HP); float* h2 = ws.take((int64_t)Bp * HP);
+  float* h1 = ws.take((int64_t)hidden_layers(H) * Bp * HP); float* h2 = h1 + (int64_t)Bp * HP;
   float* head0 = ws.take((int64_t)Bp * ldh); float* head1 = ws.take((int64_t)Bp * ldh);
   const ActorShape s = actor_shape(O, H, A, kind == 0 ? 1 : 2);
   const int threads = 256;
@@ -1143,7 +1280,7 @@ extern "C" int tonic_twin_q_grad(int32_t kind, const float* d_policy_params,
   TONIC_REQUIRE(d_policy_params && d_target_critics && d_critics && d_norm_mean && d_norm_std &&
                     d_observations && d_actions && d_next_observations && d_rewards &&
                     d_discounts && (d_eps || kind == 2) && d_grad_sums && d_workspace && B > 0 &&
-                    kind >= 0 && kind <= 2,
+                    kind >= 0 && kind <= 2 && hidden_known(H),
                 TONIC_ERR_INVALID_ARGUMENT, "tonic_twin_q_grad: bad argument");
   TONIC_REQUIRE(workspace_bytes >= tonic_offpolicy_workspace_bytes(B, O, A, H),
                 TONIC_ERR_WORKSPACE, "tonic_twin_q_grad: workspace too small");
@@ -1152,20 +1289,20 @@ extern "C" int tonic_twin_q_grad(int32_t kind, const float* d_policy_params,
   const CriticShape cs = critic_shape(O, A, H);
   const int64_t Pc = critic_count(cs);
   Workspace ws{static_cast<char*>(d_workspace), 0, workspace_bytes};
-  float* a_h1 = ws.take((int64_t)Bp * HP); float* a_h2 = ws.take((int64_t)Bp * HP);
+  const int64_t hs = (int64_t)Bp * HP, layers = hidden_layers(H);     // (layers: see layer_at)
+  float* a_h1 = ws.take(layers * hs); float* a_h2 = a_h1 + hs;
   float* head0 = ws.take((int64_t)Bp * ldh); float* head1 = ws.take((int64_t)Bp * ldh);
   float* next_act = ws.take((int64_t)Bp * A); float* logp = ws.take(Bp);
   const int nets = kind == 2 ? 1 : 2;
-  const int64_t hs = (int64_t)Bp * HP;
   // target critics on (s', a') and online critics on (s, a) share ONE forward launch: inputs X /
   // X2, activations and values laid out [targets | online]
   float* X = ws.take((int64_t)Bp * ldx); float* X2 = ws.take((int64_t)Bp * ldx);
-  float* h1_all = ws.take(4 * hs); float* h2_all = ws.take(4 * hs);
+  float* h1_all = ws.take(layers * 4 * hs); float* h2_all = h1_all + 4 * hs;
   float* q_all = ws.take(4LL * Bp);
   float* c_h1 = h1_all + nets * hs; float* c_h2 = h2_all + nets * hs;
   float* tq = q_all; float* q = q_all + (int64_t)nets * Bp;
   float* dq = ws.take(2LL * Bp);
-  float* dh2 = ws.take(2 * hs); float* dh1 = ws.take(2 * hs);
+  float* dh2 = ws.take(layers * 2 * hs); float* dh1 = dh2 + 2 * hs;
 
   // ---- targets (no grad)
   const ActorShape as = actor_shape(O, H, A, kind == 1 ? 2 : 1);
@@ -1257,30 +1394,35 @@ MlpBwdArgs actor_chain_args(const float* params, ActorShape as, int B, const flo
 
 // All weight gradients of an actor-shaped network (they contract over the batch) in ONE launch:
 //   dWh[A,H] = dhead^T h2, dbh (per head) ; dW2 = dz2^T h1, db2 ; dW1 = dz1^T X, db1
+// (L layers: dW_l = dz_l^T h_{l-1} from the top layer down; heads + L problems, up to 6)
 int actor_weight_gradients(ActorShape as, const float* X, int ldx, int B, const float* a_h1,
                            const float* a_h2, const float* dloc, const float* dspre, int ldh,
                            const float* da_h2, const float* da_h1, float* grads, hipStream_t st,
                            const AdamFold* fold, const ActorImg* img = nullptr) {
-  const int H = as.H, A = as.A, HP = as.hp(), H2 = as.h2();
+  const int H = as.H, A = as.A, HP = as.hp(), top = as.last();
   const ActorBlock<float> gp(grads, as);               // the gradient sums share the layout
-  GemmArgs w[4];
+  GemmArgs w[2 + kTorsoMaxLayers];
   int count = 0;
+  // (images: the plain torso, L == 2)
   const bool images = fold != nullptr && img != nullptr && img->block != nullptr;
   const int64_t to_target = images && img->target != nullptr ? img->target - img->block : 0;
   for (int h = 0; h < as.heads; ++h) {
     const float* dhead = h == 0 ? dloc : dspre;
-    w[count] = gemm(dhead, ldh, a_h2, HP, gp.head_w(h), gp.ldO, A, H2, B);
+    w[count] = gemm(dhead, ldh, layer_at(a_h1, a_h2, as.L - 1), HP, gp.head_w(h), gp.ldO, A, top, B);
     if (images)
       w[count].img = ImgTarget{img->block + img->v.fh[h].off, img->v.fh[h].chunks, img->block + img->v.th[h].off,
-                               img->v.th[h].chunks, 0, H2, 0, to_target};
+                               img->v.th[h].chunks, 0, top, 0, to_target};
     w[count++].colsum = gp.head_b(h);
   }
-  w[count] = gemm(da_h2, HP, a_h1, HP, gp.W2, gp.ldH, H2, H, B);
-  if (images)
-    w[count].img = ImgTarget{img->block + img->v.f2.off, img->v.f2.chunks, img->block + img->v.t2.off,
-                             img->v.t2.chunks, 0, H, 0, to_target};
-  w[count++].colsum = gp.b2;
-  w[count] = gemm(da_h1, HP, X, ldx, gp.W1, gp.ld1, H, as.O, B);
+  for (int l = as.L - 1; l >= 1; --l) {
+    w[count] = gemm(layer_at(da_h2, da_h1, as.L - 1 - l), HP, layer_at(a_h1, a_h2, l - 1), HP, gp.W[l], gp.ld[l],
+                    as.width(l), as.width(l - 1), B);
+    if (images)
+      w[count].img = ImgTarget{img->block + img->v.f2.off, img->v.f2.chunks, img->block + img->v.t2.off,
+                               img->v.t2.chunks, 0, H, 0, to_target};
+    w[count++].colsum = gp.b[l];
+  }
+  w[count] = gemm(layer_at(da_h2, da_h1, as.L - 1), HP, X, ldx, gp.W1, gp.ld1, H, as.O, B);
   if (images) w[count].img = ImgTarget{img->block + img->v.f1.off, img->v.f1.chunks, nullptr, 0, 0, 0, 0, to_target};
   w[count++].colsum = gp.b1;
   return launch_gemm_group('s', 's', w, count, 1, st, fold);
@@ -1292,7 +1434,7 @@ int actor_shaped_backward(const float* params, ActorShape as, const float* X, in
                           float* dxa, int xa_first, int xa_count, hipStream_t st,
                           const MlpBwdArgs* head_fold = nullptr, const AdamFold* fold = nullptr,
                           const ActorImg* img = nullptr) {
-  const int H = as.H, A = as.A, HP = as.hp(), H2 = as.h2();
+  const int H = as.H, A = as.A, HP = as.hp();
   ActorParams p(params, as);
   GemmArgs g;
   // the input-gradient chain first: dz2 = (dloc Wloc [+ dspre Wscale]) * act'(h2) ; dz1
@@ -1301,17 +1443,21 @@ int actor_shaped_backward(const float* params, ActorShape as, const float* X, in
                                           dxa, xa_first, xa_count, head_fold, img);
     TRY(launch_mlp_backward(b, 1, st));
   } else {
+    // (L layers: dz of the top layer from the heads, then dz_{l-1} = (dz_l W_l) * act'(h_{l-1}) down to dz1)
     for (int h = 0; h < as.heads; ++h) {
       const float* dhead = h == 0 ? dloc : dspre;
-      g = gemm(dhead, ldh, p.head_w(h), p.ldO, da_h2, HP, B, H2, A);
-      g.mask = a_h2; g.ldmask = HP; g.accumulate = h > 0; g.mask_act = as.act;
+      g = gemm(dhead, ldh, p.head_w(h), p.ldO, da_h2, HP, B, as.last(), A);
+      g.mask = layer_at(a_h1, a_h2, as.L - 1); g.ldmask = HP; g.accumulate = h > 0; g.mask_act = as.act;
       TRY(launch_gemm('c', 's', g, 1, st));
     }
-    g = gemm(da_h2, HP, p.W2, p.ldH, da_h1, HP, B, H, H2);
-    g.mask = a_h1; g.ldmask = HP; g.mask_act = as.act;
-    TRY(launch_gemm('c', 's', g, 1, st));
+    for (int l = as.L - 1; l >= 1; --l) {
+      g = gemm(layer_at(da_h2, da_h1, as.L - 1 - l), HP, p.W[l], p.ld[l], layer_at(da_h2, da_h1, as.L - l), HP, B,
+               as.width(l - 1), as.width(l));
+      g.mask = layer_at(a_h1, a_h2, l - 1); g.ldmask = HP; g.mask_act = as.act;
+      TRY(launch_gemm('c', 's', g, 1, st));
+    }
     if (dxa) {
-      g = gemm(da_h1, HP, p.W1 + xa_first, p.ld1, dxa, pad16(xa_count), B, xa_count, H);
+      g = gemm(layer_at(da_h2, da_h1, as.L - 1), HP, p.W1 + xa_first, p.ld1, dxa, pad16(xa_count), B, xa_count, H);
       TRY(launch_gemm('c', 's', g, 1, st));
     }
   }
@@ -1636,27 +1782,28 @@ extern "C" int tonic_q_iteration(const tonic_q_iteration_t* it, void* stream) {
 
 namespace {
 
+// Every (h1, h2) / (dz2, dz1) pair is the first two layers of a region of `layers` (hidden_layers; see layer_at).
 struct DistributionalBuffers {
   float *a_h1, *a_h2, *head, *act, *X, *X2, *t_h1, *t_h2, *t_logits, *c_h1, *c_h2, *logits,
       *dlogits, *loss_m, *dz2, *dz1, *dxa, *dloc, *da_h2, *da_h1;
-  static int64_t floats(int Bp, int HP, int ldh, int ldx, int ldl, int A) {
-    const int64_t hid = (int64_t)Bp * HP;
+  static int64_t floats(int Bp, int HP, int layers, int ldh, int ldx, int ldl, int A) {
+    const int64_t hid = (int64_t)Bp * HP * layers / 2;          // (two of these: one region)
     return 2 * hid + (int64_t)Bp * ldh + (int64_t)Bp * A + 2LL * Bp * ldx + 4 * hid +
            3LL * Bp * ldl + Bp + 2 * hid + 2LL * Bp * ldh + 2 * hid + 64 * 24;
   }
-  DistributionalBuffers(void* d_workspace, int64_t bytes, int Bp, int HP, int ldh, int ldx,
+  DistributionalBuffers(void* d_workspace, int64_t bytes, int Bp, int HP, int layers, int ldh, int ldx,
                         int ldl, int A) {
     Workspace ws{static_cast<char*>(d_workspace), 0, bytes};
-    const int64_t hid = (int64_t)Bp * HP;
-    a_h1 = ws.take(hid); a_h2 = ws.take(hid);
+    const int64_t hid = (int64_t)Bp * HP, region = hid * layers;
+    a_h1 = ws.take(region); a_h2 = a_h1 + hid;
     head = ws.take((int64_t)Bp * ldh); act = ws.take((int64_t)Bp * A);
     X = ws.take((int64_t)Bp * ldx); X2 = ws.take((int64_t)Bp * ldx);
-    t_h1 = ws.take(hid); t_h2 = ws.take(hid); c_h1 = ws.take(hid); c_h2 = ws.take(hid);
+    t_h1 = ws.take(region); t_h2 = t_h1 + hid; c_h1 = ws.take(region); c_h2 = c_h1 + hid;
     t_logits = ws.take((int64_t)Bp * ldl); logits = ws.take((int64_t)Bp * ldl);
     dlogits = ws.take((int64_t)Bp * ldl); loss_m = ws.take(Bp);
-    dz2 = ws.take(hid); dz1 = ws.take(hid);
+    dz2 = ws.take(region); dz1 = dz2 + hid;
     dxa = ws.take((int64_t)Bp * ldh); dloc = ws.take((int64_t)Bp * ldh);
-    da_h2 = ws.take(hid); da_h1 = ws.take(hid);
+    da_h2 = ws.take(region); da_h1 = da_h2 + hid;
   }
 };
 
@@ -1664,8 +1811,8 @@ struct DistributionalBuffers {
 
 extern "C" int64_t tonic_distributional_workspace_bytes(int32_t B, int32_t O, int32_t A, int32_t H,
                                                         int32_t NA) {
-  return DistributionalBuffers::floats(pad16(B), weight_ld(H), pad16(A), pitch16(O + A), pad16(NA),
-                                       A) * 4;
+  return DistributionalBuffers::floats(pad16(B), hidden_pitch(H), hidden_layers(H), pad16(A), pitch16(O + A),
+                                       pad16(NA), A) * 4;
 }
 
 extern "C" int tonic_distributional_q_grad(
@@ -1678,14 +1825,15 @@ extern "C" int tonic_distributional_q_grad(
   TONIC_REQUIRE(d_target_actor && d_target_critic && d_critic && d_norm_mean && d_norm_std &&
                     d_observations && d_actions && d_next_observations && d_rewards &&
                     d_discounts && d_values && d_grad_sums && d_workspace && B > 0 && NA >= 2 &&
-                    NA <= 64,
+                    NA <= 64 && hidden_known(H),
                 TONIC_ERR_INVALID_ARGUMENT, "tonic_distributional_q_grad: bad argument (2 <= atoms <= 64)");
   TONIC_REQUIRE(workspace_bytes >= tonic_distributional_workspace_bytes(B, O, A, H, NA),
                 TONIC_ERR_WORKSPACE, "tonic_distributional_q_grad: workspace too small");
   hipStream_t st = as_stream(stream);
   const int Bp = pad16(B), ldx = pitch16(O + A), ldh = pad16(A), ldl = pad16(NA), threads = 256;
-  const DistributionalBuffers w(d_workspace, workspace_bytes, Bp, weight_ld(H), ldh, ldx, ldl, A);
-  const ActorShape as{O, H, A, 1}, cs{O + A, H, NA, 1};
+  const DistributionalBuffers w(d_workspace, workspace_bytes, Bp, hidden_pitch(H), hidden_layers(H), ldh, ldx,
+                                ldl, A);
+  const ActorShape as = actor_shape(O, H, A, 1), cs = actor_shape(O + A, H, NA, 1);
   // a' = target_actor(s') (critics.py:104); its tail encodes (s', a') -> X and the stored (s, a) -> X2
   PolicyTail tail{};
   tail.post = POST_COPY; tail.actions = w.act;
@@ -1723,14 +1871,15 @@ extern "C" int tonic_distributional_actor_grad(
     float* d_grad_sums, int32_t B, int32_t O, int32_t H, int32_t A, int32_t NA, void* d_workspace,
     int64_t workspace_bytes, void* stream) {
   TONIC_REQUIRE(d_actor_params && d_critic && d_norm_mean && d_norm_std && d_observations &&
-                    d_values && d_grad_sums && d_workspace && B > 0 && NA >= 2 && NA <= 64,
+                    d_values && d_grad_sums && d_workspace && B > 0 && NA >= 2 && NA <= 64 && hidden_known(H),
                 TONIC_ERR_INVALID_ARGUMENT, "tonic_distributional_actor_grad: bad argument");
   TONIC_REQUIRE(workspace_bytes >= tonic_distributional_workspace_bytes(B, O, A, H, NA),
                 TONIC_ERR_WORKSPACE, "tonic_distributional_actor_grad: workspace too small");
   hipStream_t st = as_stream(stream);
   const int Bp = pad16(B), ldx = pitch16(O + A), ldh = pad16(A), ldl = pad16(NA), threads = 256;
-  const DistributionalBuffers w(d_workspace, workspace_bytes, Bp, weight_ld(H), ldh, ldx, ldl, A);
-  const ActorShape as{O, H, A, 1}, cs{O + A, H, NA, 1};
+  const DistributionalBuffers w(d_workspace, workspace_bytes, Bp, hidden_pitch(H), hidden_layers(H), ldh, ldx,
+                                ldl, A);
+  const ActorShape as = actor_shape(O, H, A, 1), cs = actor_shape(O + A, H, NA, 1);
   PolicyTail tail{};                              // a = actor(s); the tail encodes (s, a) -> X
   tail.post = POST_COPY; tail.actions = w.act;
   tail.enc_obs = d_observations; tail.enc_mean = d_norm_mean; tail.enc_std = d_norm_std;
@@ -1771,23 +1920,24 @@ namespace {
 struct MpoBuffers {
   float *a_h1, *a_h2, *loc_t, *spre_t, *loc, *spre, *o_h1, *o_h2, *act, *X, *X2, *t_h1, *t_h2, *tq,
       *tq_mean, *c_h1, *c_h2, *q, *dq, *dh2, *dh1, *dloc, *dspre, *da_h2, *da_h1, *part, *klm, *kls;
-  static int64_t floats(int B, int S, int HP, int ldh, int ldx, int A) {
+  static int64_t floats(int B, int S, int HP, int ldh, int ldx, int A) {    // (HP: see tonic_mpo_workspace_bytes)
     const int64_t Bp = pad16(B), Rp = pad16(S * B);
     return 4 * Bp * HP + 4 * Bp * ldh + Rp * A + Rp * ldx + Bp * ldx + 2 * Rp * HP + Rp + Bp +
            2 * Bp * HP + 2 * Bp + 2 * Bp * HP + 2 * Bp * ldh + 2 * Bp * HP + Bp * kMpoStats +
            2 * Bp * A + 64 * 32;
   }
-  MpoBuffers(void* d_workspace, int64_t bytes, int B, int S, int HP, int ldh, int ldx, int A) {
+  // every (h1, h2) / (dh2, dh1) pair: the first two layers of a region of `layers` (hidden_layers; see layer_at)
+  MpoBuffers(void* d_workspace, int64_t bytes, int B, int S, int HP, int layers, int ldh, int ldx, int A) {
     Workspace ws{static_cast<char*>(d_workspace), 0, bytes};
     const int64_t Bp = pad16(B), Rp = pad16(S * B), hid = Bp * HP;
-    a_h1 = ws.take(hid); a_h2 = ws.take(hid); o_h1 = ws.take(hid); o_h2 = ws.take(hid);
+    a_h1 = ws.take(layers * hid); a_h2 = a_h1 + hid; o_h1 = ws.take(layers * hid); o_h2 = o_h1 + hid;
     loc_t = ws.take(Bp * ldh); spre_t = ws.take(Bp * ldh); loc = ws.take(Bp * ldh);
     spre = ws.take(Bp * ldh);
     act = ws.take(Rp * A); X = ws.take(Rp * ldx); X2 = ws.take(Bp * ldx);
-    t_h1 = ws.take(Rp * HP); t_h2 = ws.take(Rp * HP); tq = ws.take(Rp); tq_mean = ws.take(Bp);
-    c_h1 = ws.take(hid); c_h2 = ws.take(hid); q = ws.take(Bp); dq = ws.take(Bp);
-    dh2 = ws.take(hid); dh1 = ws.take(hid);
-    dloc = ws.take(Bp * ldh); dspre = ws.take(Bp * ldh); da_h2 = ws.take(hid); da_h1 = ws.take(hid);
+    t_h1 = ws.take(layers * Rp * HP); t_h2 = t_h1 + Rp * HP; tq = ws.take(Rp); tq_mean = ws.take(Bp);
+    c_h1 = ws.take(layers * hid); c_h2 = c_h1 + hid; q = ws.take(Bp); dq = ws.take(Bp);
+    dh2 = ws.take(layers * hid); dh1 = dh2 + hid;
+    dloc = ws.take(Bp * ldh); dspre = ws.take(Bp * ldh); da_h2 = ws.take(layers * hid); da_h1 = da_h2 + hid;
     part = ws.take(Bp * kMpoStats); klm = ws.take(Bp * A); kls = ws.take(Bp * A);
   }
 };
@@ -1798,20 +1948,21 @@ int mpo_sampled_values(const float* d_target_actor, const float* d_target_critic
                        const float* d_obs, const float* d_eps, int B, int O, int H, int A, int S,
                        const MpoBuffers& w, hipStream_t st) {
   const int ldx = pitch16(O + A), ldh = pad16(A), threads = 256;
-  const ActorShape as{O, H, A, 2};
+  const ActorShape as = actor_shape(O, H, A, 2);
   TRY(actor_forward(d_target_actor, as, d_obs, B, w.a_h1, w.a_h2, w.loc_t, w.spre_t, ldh, true, st));
   const int64_t items = (int64_t)S * B * (O + A);
   hipLaunchKernelGGL(gaussian_tile_kernel, dim3((unsigned)((items + threads - 1) / threads)),
                      dim3(threads), 0, st, d_obs, w.loc_t, w.spre_t, d_eps, ldh, d_norm_mean,
                      d_norm_std, clip_bound(norm_clip), w.act, w.X, B, O, A, S, ldx);
-  return critics_forward(d_target_critic, CriticShape{O, A, H}, 1, w.X, ldx, S * B, pad16(S * B),
+  return critics_forward(d_target_critic, critic_shape(O, A, H), 1, w.X, ldx, S * B, pad16(S * B),
                          w.t_h1, w.t_h2, w.tq, st);
 }
 
 }  // namespace
 
 extern "C" int64_t tonic_mpo_workspace_bytes(int32_t B, int32_t O, int32_t A, int32_t H, int32_t S) {
-  return MpoBuffers::floats(B, S, weight_ld(H), pad16(A), pitch16(O + A), A) * 4;
+  // (every hidden array holds hidden_layers(H) layers: the floats' HP stands for half of them, two layers' pitch)
+  return MpoBuffers::floats(B, S, hidden_pitch(H) * hidden_layers(H) / 2, pad16(A), pitch16(O + A), A) * 4;
 }
 
 extern "C" int tonic_expected_sarsa_grad(
@@ -1824,14 +1975,14 @@ extern "C" int tonic_expected_sarsa_grad(
   TONIC_REQUIRE(d_target_actor && d_target_critic && d_critic && d_norm_mean && d_norm_std &&
                     d_observations && d_actions && d_next_observations && d_rewards &&
                     d_discounts && d_eps && d_grad_sums && d_workspace && B > 0 && S >= 1 &&
-                    S <= kMpoMaxSamples,
+                    S <= kMpoMaxSamples && hidden_known(H),
                 TONIC_ERR_INVALID_ARGUMENT, "tonic_expected_sarsa_grad: bad argument (1 <= samples <= 64)");
   TONIC_REQUIRE(workspace_bytes >= tonic_mpo_workspace_bytes(B, O, A, H, S), TONIC_ERR_WORKSPACE,
                 "tonic_expected_sarsa_grad: workspace too small");
   hipStream_t st = as_stream(stream);
   const int Bp = pad16(B), ldx = pitch16(O + A), threads = 256;
-  const MpoBuffers w(d_workspace, workspace_bytes, B, S, weight_ld(H), pad16(A), ldx, A);
-  const CriticShape cs{O, A, H};
+  const MpoBuffers w(d_workspace, workspace_bytes, B, S, hidden_pitch(H), hidden_layers(H), pad16(A), ldx, A);
+  const CriticShape cs = critic_shape(O, A, H);
   TRY(mpo_sampled_values(d_target_actor, d_target_critic, d_norm_mean, d_norm_std, norm_clip,
                          d_next_observations, d_eps, B, O, H, A, S, w, st));
   hipLaunchKernelGGL(sample_mean_kernel, dim3((B + threads - 1) / threads), dim3(threads), 0, st,
@@ -1859,14 +2010,15 @@ int mpo_actor_grad(
   TONIC_REQUIRE(d_actor_params && d_target_actor && d_target_critic && d_duals && d_norm_mean &&
                     d_norm_std && d_observations && d_eps && d_grad_sums &&
                     (d_column_sums || (d_dual_grads && d_stats)) &&
-                    d_workspace && B > 0 && S >= 1 && S <= kMpoMaxSamples && A <= 64,
+                    d_workspace && B > 0 && S >= 1 && S <= kMpoMaxSamples && A <= 64 && hidden_known(H),
                 TONIC_ERR_INVALID_ARGUMENT, "tonic_mpo_actor_grad: bad argument");
   TONIC_REQUIRE(workspace_bytes >= tonic_mpo_workspace_bytes(B, O, A, H, S), TONIC_ERR_WORKSPACE,
                 "tonic_mpo_actor_grad: workspace too small");
   hipStream_t st = as_stream(stream);
   const int ldh = pad16(A);
-  const MpoBuffers w(d_workspace, workspace_bytes, B, S, weight_ld(H), ldh, pitch16(O + A), A);
-  const ActorShape as{O, H, A, 2};
+  const MpoBuffers w(d_workspace, workspace_bytes, B, S, hidden_pitch(H), hidden_layers(H), ldh, pitch16(O + A),
+                     A);
+  const ActorShape as = actor_shape(O, H, A, 2);
   TRY(mpo_sampled_values(d_target_actor, d_target_critic, d_norm_mean, d_norm_std, norm_clip,
                          d_observations, d_eps, B, O, H, A, S, w, st));
   TRY(actor_forward(d_actor_params, as, d_observations, B, w.o_h1, w.o_h2, w.loc, w.spre, ldh, true,
@@ -1939,7 +2091,7 @@ extern "C" int tonic_actor_q_grad(int32_t kind, const float* d_actor_params,
                                   int32_t H, int32_t A, double entropy_coeff, void* d_workspace,
                                   int64_t workspace_bytes, void* stream) {
   TONIC_REQUIRE(d_actor_params && d_critics && d_norm_mean && d_norm_std && d_observations &&
-                    d_grad_sums && d_workspace && B > 0 && (kind == 0 || d_eps),
+                    d_grad_sums && d_workspace && B > 0 && (kind == 0 || d_eps) && hidden_known(H),
                 TONIC_ERR_INVALID_ARGUMENT, "tonic_actor_q_grad: bad argument");
   TONIC_REQUIRE(workspace_bytes >= tonic_offpolicy_workspace_bytes(B, O, A, H),
                 TONIC_ERR_WORKSPACE, "tonic_actor_q_grad: workspace too small");
@@ -1950,17 +2102,18 @@ extern "C" int tonic_actor_q_grad(int32_t kind, const float* d_actor_params,
   const ActorShape as = actor_shape(O, H, A, kind == 0 ? 1 : 2);
   const int64_t Pa = actor_count(as);
   Workspace ws{static_cast<char*>(d_workspace), 0, workspace_bytes};
-  float* a_h1 = ws.take((int64_t)Bp * HP); float* a_h2 = ws.take((int64_t)Bp * HP);
+  const int64_t hs = (int64_t)Bp * HP, layers = hidden_layers(H);     // (layers: see layer_at)
+  float* a_h1 = ws.take(layers * hs); float* a_h2 = a_h1 + hs;
   float* head0 = ws.take((int64_t)Bp * ldh); float* head1 = ws.take((int64_t)Bp * ldh);
   float* act = ws.take((int64_t)Bp * A); float* sigma = ws.take((int64_t)Bp * A);
   float* logp = ws.take(Bp);
   float* X = ws.take((int64_t)Bp * ldx);
-  float* c_h1 = ws.take(2LL * Bp * HP); float* c_h2 = ws.take(2LL * Bp * HP);
+  float* c_h1 = ws.take(layers * 2 * hs); float* c_h2 = c_h1 + 2 * hs;
   float* q = ws.take(2LL * Bp); float* dq = ws.take(2LL * Bp);
-  float* dh2 = ws.take(2LL * Bp * HP); float* dh1 = ws.take(2LL * Bp * HP);
+  float* dh2 = ws.take(layers * 2 * hs); float* dh1 = dh2 + 2 * hs;
   float* dxa = ws.take(2LL * Bp * ldh);         // action columns of the critics' input gradients
   float* dloc = ws.take((int64_t)Bp * ldh); float* dspre = ws.take((int64_t)Bp * ldh);
-  float* da_h2 = ws.take((int64_t)Bp * HP); float* da_h1 = ws.take((int64_t)Bp * HP);
+  float* da_h2 = ws.take(layers * hs); float* da_h1 = da_h2 + hs;
   // the weight images of the actor and the critics (mlpimg.h), formed by this call (see tonic_twin_q_grad)
   ImageSet im = take_images(ws, O, A, H, as.heads, hidden_plain(H) && images_serve(O, A, H) &&
                                                     mlp_forward_supported(H, A, as.heads) &&

@@ -675,22 +675,25 @@ _Q_ACTIVATIONS = {torch.nn.ReLU: 1, torch.nn.Tanh: 2, torch.nn.ELU: 3}       # G
 
 def _torso_width(torso, generic=False):
     """The `H` argument of the off-policy entries: the width of the reference's torso — two ReLU layers of one
-    width, which the fused kernels hold (csrc/mlpfwd.hip) — or, `generic`, tonic_mlp_hidden(H1, H2, activation)
-    for any other two-layer torso with ReLU / Tanh / ELU (unequal widths: the (400, 300) class), which the SAC /
-    TD3 / DDPG entries run layer by layer on gemm16 launches.  Anything else raises (callers with a stock-torch
-    form catch it)."""
+    width, which the fused kernels hold (csrc/mlpfwd.hip) — or tonic_mlp_torso(layers, sizes, activation) for any
+    other torso of 1 .. 4 layers of 1 .. 4095 units with ReLU / Tanh / ELU (unequal widths: the (400, 300) class;
+    deeper or shallower torsos), which every off-policy entry runs layer by layer on gemm16 launches.  `generic`:
+    the caller has a stock-torch form, which TONIC_AMD_TORSO_STOCK=1 selects for such torsos.  Anything else
+    raises (callers with a stock-torch form catch it)."""
     sizes = tuple(int(v) for v in torso.sizes)
     plain = len(sizes) == 2 and sizes[0] == sizes[1] and torso.activation is torch.nn.ReLU
     if plain:                              # (a plain width goes through the C ABI's `H` as is)
         return sizes[0]
     code = _Q_ACTIVATIONS.get(torso.activation)
-    if (generic and len(sizes) == 2 and code is not None
-            and os.environ.get('TONIC_AMD_TORSO_STOCK', '0') != '1'):
-        packed = _lib.load().tonic_mlp_hidden(sizes[0], sizes[1], code)
+    to_stock = generic and os.environ.get('TONIC_AMD_TORSO_STOCK', '0') == '1'
+    if code is not None and 1 <= len(sizes) <= 4 and all(1 <= v <= 4095 for v in sizes) and not to_stock:
+        import ctypes
+        packed = _lib.load().tonic_mlp_torso(len(sizes), (ctypes.c_int32 * len(sizes))(*sizes), code)
         if packed > 0:
             return packed
-    raise NotImplementedError('the off-policy kernels serve two-layer torsos (ReLU / Tanh / ELU for SAC, TD3 '
-                              f'and DDPG; equal-width ReLU for D4PG and MPO), got {sizes} / {torso.activation}')
+    raise NotImplementedError('the off-policy kernels serve torsos of 1 .. 4 layers of 1 .. 4095 units with ReLU / '
+                              'Tanh / ELU, the same for actor and critic (SAC, TD3 and DDPG run any other torso on '
+                              f'stock torch operators), got {sizes} / {torso.activation}')
 
 
 class _QUpdater(_FlatUpdater):
