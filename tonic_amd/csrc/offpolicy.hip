@@ -398,7 +398,11 @@ __device__ __forceinline__ float dual_value(float log_dual) { return softplus_f(
 //   d/d loc   = -sum_s W_s (a_s - loc) / sigma_t^2 + alpha_mean (loc - loc_t) / sigma_t^2
 //   d/d sigma = -sum_s W_s ((a_s - loc_t)^2 / sigma^3 - 1 / sigma) + alpha_std (1 / sigma - sigma_t^2 / sigma^3)
 // with W = softmax_s(q / T) + softmax_s(bound cost / T_penalty).  part[m][.] = {policy_mean, policy_std,
-// LSE, sum_s w q / T, LSE_penalty, sum_s w_p cost / T_p}; klm / kls [m][a] = the per-dimension KLs.
+// LSE, LSE - sum_s w q / T, LSE_penalty, LSE_penalty - sum_s w_p cost / T_p}; klm / kls [m][a] = the
+// per-dimension KLs.  The temperatures' gradients need the differences LSE - sum_s w x (the entropy of w, in
+// [0, log S]): they are formed here in the max-shifted frame, log(sum) - sum_s w (x - max), because at a cold
+// temperature LSE and sum_s w x are each of the order of |x| (~1e7 for a penalty temperature on the dual floor)
+// and their difference would be lost to float32 rounding.
 __global__ __launch_bounds__(256) void mpo_state_kernel(
     const float* q, const float* act, const float* loc_t, const float* spre_t, const float* loc,
     const float* spre, int ldh, const float* duals, float floor, int penalize, float* dloc, float* dspre,
@@ -418,7 +422,7 @@ __global__ __launch_bounds__(256) void mpo_state_kernel(
   const float sum = wave_sum(e);
   const float lse = mx + logf(sum);
   float w = e / sum;
-  const float wq = wave_sum(sample ? w * tempered : 0.f);
+  const float wq = logf(sum) - wave_sum(sample ? w * (tempered - mx) : 0.f);
   float lse_p = 0.f, wc = 0.f;
   if (penalize) {                                              // actors.py:388-398
     float n2 = 0.f;
@@ -435,7 +439,7 @@ __global__ __launch_bounds__(256) void mpo_state_kernel(
     const float sp = wave_sum(ep);
     lse_p = mp + logf(sp);
     const float wp = ep / sp;
-    wc = wave_sum(sample ? wp * cost : 0.f);
+    wc = logf(sp) - wave_sum(sample ? wp * (cost - mp) : 0.f);
     w += wp;
   }
   // lane = action dimension: the sums over the samples in sample order
@@ -535,16 +539,16 @@ __global__ void mpo_dual_kernel(const float* part, const float* klm, const float
   kl_mean_loss = wave_sum(kl_mean_loss); kl_std_loss = wave_sum(kl_std_loss);
   alpha_mean_loss = wave_sum(alpha_mean_loss); alpha_std_loss = wave_sum(alpha_std_loss);
   if (tid != 0) return;
-  // temperature * (epsilon + mean(logsumexp) - log S): d / dT = epsilon + mean(LSE) - log S - mean(sum_s w q / T)
+  // temperature * (epsilon + mean(logsumexp) - log S): d / dT = epsilon + mean(LSE - sum_s w q / T) - log S
   float temperature_loss = T * (epsilon + (float)col[2] - log_S);
-  dual_grads[0] = (epsilon + (float)col[2] - log_S - (float)col[3]) * sigmoid(log_T);
+  dual_grads[0] = (epsilon + (float)col[3] - log_S) * sigmoid(log_T);
   duals[0] = log_T;
   if (penalize) duals[2 * A + 1] = log_Tp;
   dual_grads[2 * A + 1] = 0.f;
   if (penalize) {
     temperature_loss += Tp * (epsilon_penalty + (float)col[4] - log_S);
     dual_grads[2 * A + 1] =
-        (epsilon_penalty + (float)col[4] - log_S - (float)col[5]) * sigmoid(log_Tp);
+        (epsilon_penalty + (float)col[5] - log_S) * sigmoid(log_Tp);
   }
   for (int i = 0; i < 8; ++i) dual_grads[2 * A + 2 + i] = i == 5 ? 1.f : 0.f;
   stats[0] = -(float)col[0]; stats[1] = -(float)col[1]; stats[2] = kl_mean_loss; stats[3] = kl_std_loss;
