@@ -28,21 +28,22 @@ def probe(kind, o_dim, a_dim, batch, workers, count=2000):
         agent.update(**infos, steps=steps)
     torch.cuda.synchronize()
     out = {}
-    state = agent._block_of(observations, agent.policy_kind)
-    block, collector = state['block'], state['collector']
+    registry = agent._q
+    q = registry.find(observations, agent.policy_kind)
+    block, collector = q.block, q.collector
     kind_code, stochastic = agent.policy_kind, kind == 'sac'
-    parts = dict(block_of=0.0, noise=0.0, launch=0.0, wait=0.0, copy_out=0.0)
+    parts = dict(find=0.0, noise=0.0, launch=0.0, wait=0.0, copy_out=0.0)
     for _ in range(count):
         t0 = clock()
-        agent._block_of(observations, kind_code)
+        registry.find(observations, kind_code)
         t1 = clock()
         if stochastic:
             np.copyto(block.eps[0], agent._randn(workers, a_dim).numpy())
         t2 = clock()
-        _lib.check(agent._q_act(
-            collector.handle, _lib.ptr(agent.model.flat_actor.flat), _lib.ptr(agent._actor_images), 0, kind_code,
-            agent.hidden, 0 if stochastic else -1, _lib.ptr(state['rows'][0]), None, _lib.ptr(state['workspace']),
-            state['workspace'].numel(), _lib.current_stream()), 'q_act')
+        _lib.check(registry.launch(
+            collector.handle, _lib.ptr(agent.model.flat_actor.flat), _lib.ptr(registry.images), 0, kind_code,
+            agent.hidden, 0 if stochastic else -1, q.row_pointers[0], None, _lib.ptr(q.workspace),
+            q.workspace.numel(), _lib.current_stream()), 'q_act')
         t3 = clock()
         collector.wait_actions()
         t4 = clock()
@@ -64,7 +65,7 @@ def probe(kind, o_dim, a_dim, batch, workers, count=2000):
     # the store launch alone
     t0 = clock()
     for _ in range(count):
-        replay.store(normalizer=agent.model.observation_normalizer, observations=state['rows'][0], **state['fields'])
+        replay.store(normalizer=agent.model.observation_normalizer, observations=q.rows[0], **q.fields)
     out['store_call_us'] = round((clock() - t0) / count * 1e6, 2)
     torch.cuda.synchronize()
     return out

@@ -297,6 +297,92 @@ def test_offpolicy_agent_drop_in_trajectory(lib, golden, name, kind):
     assert updated
 
 
+def _run_on_own_arrays(g, kind, mixed):
+    """agent.step -> env.step -> agent.update with the environment's own arrays passed through untouched.
+    `mixed`: two greedy test steps on a second environment after every third training step, and one step in
+    the middle on copies of the arrays.  Returns what the run left behind, on the host."""
+    import tonic_amd
+    O, A, W, hidden, B, iterations, seed, loop_steps = (int(x) for x in g['cfg'])
+    agent = _agent_from_golden(g, kind)
+
+    def environment(env_seed):
+        env = tonic_amd.environments.distribute(
+            lambda: tonic_amd.environments.Synthetic(O, A, max_episode_steps=5), 1, W)
+        env.initialize(seed=env_seed)
+        return env, env.start()
+    env, observations = environment(seed)
+    if mixed:
+        test_env, test_observations = environment(seed + 100)
+    updated_at = None
+    for t in range(loop_steps):
+        foreign = mixed and t == loop_steps // 2
+        actions = agent.step(observations.copy() if foreign else observations, t * W)
+        observations, infos = env.step(actions)
+        if foreign:
+            infos = {k: v.copy() for k, v in infos.items()}
+        agent.update(**infos, steps=t * W)
+        if updated_at is None and hasattr(agent, 'last_infos'):
+            updated_at = t
+        if mixed and t % 3 == 2:
+            for _ in range(2):
+                test_observations, _ = test_env.step(agent.test_step(test_observations, t * W))
+    agent.settle()
+    replay, normalizer = agent.replay, agent.model.observation_normalizer
+    out = {k: v.cpu().numpy() for k, v in replay.buffers.items()}
+    out.update(index=replay.index, size=replay.size, mean=np.array(normalizer.mean), std=np.array(normalizer.std),
+               counts=(normalizer.count, normalizer.new_count), device_sums=normalizer.device_sums.cpu().numpy(),
+               start_steps=agent.exploration.start_steps, return_steps=replay.return_steps, updated_at=updated_at)
+    agent.close()
+    return out
+
+
+@pytest.mark.parametrize('mixed', [False, True], ids=['plain', 'mixed'])
+@pytest.mark.parametrize('name,kind', [('sac_small', 'sac'), ('td3_small', 'td3'), ('ddpg_small', 'ddpg')])
+def test_block_store_path_fills_the_buffer_like_the_staged_path(lib, golden, monkeypatch, name, kind, mixed):
+    """Acting and storing on the environment's block (the default) against the staged copies
+    (TONIC_AMD_Q_BLOCK=0), same seeds: everything that does not depend on the policy's actions bit for bit over
+    the whole run; the warm-up actions and rewards bit for bit; the policy's rows before the first learner update
+    within the acting bound of test_offpolicy_agent_drop_in_trajectory (after it the parameters differ at
+    rounding); no reserved row left unwritten; and the reserving path was really taken."""
+    import tonic_amd
+    g = golden(name)
+    O, A, W, hidden, B, iterations, seed, loop_steps = (int(x) for x in g['cfg'])
+    reserved = []
+    reserve_row = tonic_amd.replays.Buffer.reserve_row
+    monkeypatch.setattr(tonic_amd.replays.Buffer, 'reserve_row',
+                        lambda self, *args, **kwargs: reserved.append(1) or reserve_row(self, *args, **kwargs))
+    monkeypatch.delenv('TONIC_AMD_Q_BLOCK', raising=False)
+    block = _run_on_own_arrays(g, kind, mixed)
+    on_block = len(reserved)
+    monkeypatch.setenv('TONIC_AMD_Q_BLOCK', '0')
+    staged = _run_on_own_arrays(g, kind, mixed)
+    assert len(reserved) == on_block, 'the staged path reserved a row'
+    assert block['return_steps'] == staged['return_steps'] == 1
+    # the policy acts when steps > start_steps (explorations); its rows are reserved unless the step was foreign
+    policy_steps = [t for t in range(loop_steps) if t * W > block['start_steps']]
+    assert on_block == len(policy_steps) - (1 if mixed and loop_steps // 2 in policy_steps else 0)
+    assert on_block > 0
+
+    def bits(x):
+        return np.ascontiguousarray(x, np.float32).view(np.uint32)
+    assert (block['index'], block['size']) == (staged['index'], staged['size']) == (loop_steps, loop_steps)
+    assert block['counts'] == staged['counts']
+    for key in ('observations', 'next_observations', 'resets', 'terminations', 'discounts',
+                'mean', 'std', 'device_sums'):
+        np.testing.assert_array_equal(bits(block[key]), bits(staged[key]), err_msg=key)
+    size = block['size']
+    for key in ('observations', 'actions', 'next_observations', 'rewards', 'resets', 'terminations', 'discounts'):
+        assert not np.isnan(block[key][:size]).any(), key
+        assert not np.isnan(staged[key][:size]).any(), key
+    first_policy, updated_at = policy_steps[0], block['updated_at']
+    assert 0 < first_policy < updated_at < loop_steps and updated_at == staged['updated_at']
+    for key in ('actions', 'rewards'):          # row t = the transition of step t (no wrap: size == loop_steps)
+        np.testing.assert_array_equal(bits(block[key][:first_policy]), bits(staged[key][:first_policy]), err_msg=key)
+    rows = slice(first_policy, updated_at + 1)      # (the transition of the update's own step is stored before it)
+    np.testing.assert_allclose(block['actions'][rows], staged['actions'][rows], rtol=0, atol=5e-6)
+    np.testing.assert_allclose(block['rewards'][rows], staged['rewards'][rows], rtol=0, atol=2 * A * 5e-6)
+
+
 @pytest.mark.parametrize('kind,O,A,W,B,support', [
     ('sac', 111, 8, 1, 1024, None), ('td3', 67, 21, 64, 100, None), ('ddpg', 17, 6, 4, 100, None),
     ('d4pg', 24, 6, 4, 256, (-150., 150., 51)), ('d4pg', 6, 3, 4, 100, (-2., 12., 51)),

@@ -53,53 +53,30 @@ class Buffer:
         self.global_workers = num_workers * self.world
         self.max_size = self.full_max_size // self.global_workers
         self.observation_size, self.action_size = observation_size, action_size
-        R, W = self.max_size, num_workers
-
-        def new(*shape):
-            return torch.full(shape, float('nan'), dtype=torch.float32, device=self.device)
-        self.buffers = dict(
-            observations=new(R, W, observation_size), actions=new(R, W, action_size),
-            next_observations=new(R, W, observation_size), rewards=new(R, W), resets=new(R, W),
-            terminations=new(R, W), discounts=new(R, W))
-        B = self.batch_size
-        self.batch = dict(
-            observations=torch.empty(B, observation_size, device=self.device),
-            actions=torch.empty(B, action_size, device=self.device),
-            next_observations=torch.empty(B, observation_size, device=self.device),
-            rewards=torch.empty(B, device=self.device), discounts=torch.empty(B, device=self.device))
+        widths = dict(observations=(observation_size,), actions=(action_size,), next_observations=(observation_size,))
+        self.buffers = {k: torch.full((self.max_size, num_workers) + widths.get(k, ()), float('nan'),
+                                      dtype=torch.float32, device=self.device) for k in KEYS}
+        self.batch = {k: torch.empty((self.batch_size,) + widths.get(k, ()), device=self.device) for k in BATCH_KEYS}
 
     def store(self, normalizer=None, **kwargs):
         """One time row from float32 device tensors [W, ...] (buffers.py:33-56)."""
         if self.buffers is None:
             self._allocate(kwargs['observations'].shape[0], kwargs['observations'].shape[1],
                            kwargs['actions'].shape[1])
-        b, p = self.buffers, _lib.ptr
-        sums = normalizer.device_sums if normalizer is not None else None
-        _lib.check(self.lib.tonic_buffer_store(
-            p(b['observations']), p(b['actions']), p(b['next_observations']), p(b['rewards']),
-            p(b['resets']), p(b['terminations']), p(b['discounts']), p(kwargs['observations']),
-            p(kwargs['actions']), p(kwargs['next_observations']), p(kwargs['rewards']),
-            p(kwargs['resets']), p(kwargs['terminations']), p(sums), self.index,
-            self.num_workers, self.observation_size, self.action_size,
-            float(self.discount_factor), _lib.current_stream()), 'tonic_buffer_store')
-        if normalizer is not None:
-            normalizer.note_device_rows(self.num_workers)
+        self.store_at(self.index, normalizer, **kwargs)
         if self.return_steps > 1:                                    # buffers.py:52-53
+            b, p = self.buffers, _lib.ptr
             _lib.check(self.lib.tonic_buffer_accumulate_n_steps(
                 p(b['next_observations']), p(b['rewards']), p(b['discounts']), p(b['resets']),
                 p(kwargs['next_observations']), p(kwargs['rewards']), p(kwargs['terminations']),
                 self.index, self.size, self.max_size, self.num_workers, self.observation_size,
                 self.return_steps, float(self.discount_factor), _lib.current_stream()),
                 'tonic_buffer_accumulate_n_steps')
-        self.index = (self.index + 1) % self.max_size
-        self.size = min(self.size + 1, self.max_size)
+        self._take_row(normalizer)
 
-    def reserve_row(self, normalizer=None):
-        """The host half of `store` for a transition whose device write is issued later (the off-policy agents'
-        acting launch carries it: tonic_collector_q_act): the row it will occupy, the circular index and the size
-        advanced (buffers.py:54-56), the normaliser's record count noted.  Needs an allocated Buffer and
-        return_steps == 1 (the n-step accumulation reads the stored row right away)."""
-        assert self.buffers is not None and self.return_steps == 1
+    def _take_row(self, normalizer):
+        """The host half of a store (buffers.py:54-56): the circular index and the size advanced, the normaliser's
+        record count noted.  Returns the row taken."""
         row = self.index
         if normalizer is not None:
             normalizer.note_device_rows(self.num_workers)
@@ -107,26 +84,33 @@ class Buffer:
         self.size = min(self.size + 1, self.max_size)
         return row
 
+    def reserve_row(self, normalizer=None):
+        """The host half of `store` for a transition whose device write is issued later (the off-policy agents'
+        acting launch carries it: tonic_collector_q_act): the row it will occupy.  Needs an allocated Buffer and
+        return_steps == 1 (the n-step accumulation reads the stored row right away)."""
+        assert self.buffers is not None and self.return_steps == 1
+        return self._take_row(normalizer)
+
     def store_at(self, row, normalizer=None, **kwargs):
-        """The device half of a reserved transition on its own (tonic_buffer_store into `row`): what the acting
-        launch would have carried, when no acting launch follows (an update is due first, the policy sits out)."""
-        b, p = self.buffers, _lib.ptr
+        """The device half of a store (tonic_buffer_store into `row`) — on its own: what the acting launch would
+        have carried for a reserved transition, when no acting launch follows (an update is due first, the policy
+        sits out)."""
+        p = _lib.ptr
         sums = normalizer.device_sums if normalizer is not None else None
         _lib.check(self.lib.tonic_buffer_store(
-            p(b['observations']), p(b['actions']), p(b['next_observations']), p(b['rewards']),
-            p(b['resets']), p(b['terminations']), p(b['discounts']), p(kwargs['observations']),
-            p(kwargs['actions']), p(kwargs['next_observations']), p(kwargs['rewards']),
-            p(kwargs['resets']), p(kwargs['terminations']), p(sums), row,
+            *self._pointers(self.buffers, KEYS), *self._pointers(kwargs, KEYS[:-1]), p(sums), row,
             self.num_workers, self.observation_size, self.action_size,
             float(self.discount_factor), _lib.current_stream()), 'tonic_buffer_store')
 
     def store_arguments(self, row, observations, normalizer=None):
         """tonic_q_store_t for `row` (see reserve_row): the Buffer's arrays, the observation rows' device copy."""
-        b, p = self.buffers, _lib.ptr
         sums = normalizer.device_sums if normalizer is not None else None
-        return _lib.QStore(p(b['observations']), p(b['actions']), p(b['next_observations']), p(b['rewards']),
-                           p(b['resets']), p(b['terminations']), p(b['discounts']), p(observations), p(sums),
+        return _lib.QStore(*self._pointers(self.buffers, KEYS), _lib.ptr(observations), _lib.ptr(sums),
                            row, float(self.discount_factor))
+
+    @staticmethod
+    def _pointers(arrays, keys):
+        return [_lib.ptr(arrays[k]) for k in keys]
 
     def sample_indices(self, iterations=None):
         """The index stream of `iterations` successive Buffer.get draws (buffers.py:85-86)."""
@@ -157,14 +141,8 @@ class Buffer:
     def gather(self, device_indices, out=None):
         """Gathers one batch (int64 device indices [B]) into `out` (default: the reusable batch)."""
         out = out or self.batch
-        b, p = self.buffers, _lib.ptr
-        _lib.check(self.lib.tonic_buffer_gather(
-            p(device_indices), p(b['observations']), p(b['actions']), p(b['next_observations']),
-            p(b['rewards']), p(b['discounts']), p(out['observations']), p(out['actions']),
-            p(out['next_observations']), p(out['rewards']), p(out['discounts']),
-            self.num_workers, device_indices.shape[0], self.observation_size, self.action_size,
-            _lib.current_stream()), 'tonic_buffer_gather')
         count = device_indices.shape[0]
+        self._gather(device_indices, count, out)
         if count != out['rewards'].shape[0]:
             return {k: v[:count] for k, v in out.items()}
         return out
@@ -179,14 +157,14 @@ class Buffer:
             store = self._many = {
                 k: torch.empty((iterations, count) + tuple(v.shape[1:]), dtype=v.dtype,
                                device=self.device) for k, v in self.batch.items()}
-        b, p = self.buffers, _lib.ptr
-        _lib.check(self.lib.tonic_buffer_gather(
-            p(device_indices), p(b['observations']), p(b['actions']), p(b['next_observations']),
-            p(b['rewards']), p(b['discounts']), p(store['observations']), p(store['actions']),
-            p(store['next_observations']), p(store['rewards']), p(store['discounts']),
-            self.num_workers, iterations * count, self.observation_size, self.action_size,
-            _lib.current_stream()), 'tonic_buffer_gather')
+        self._gather(device_indices, iterations * count, store)
         return store
+
+    def _gather(self, device_indices, count, out):
+        _lib.check(self.lib.tonic_buffer_gather(
+            _lib.ptr(device_indices), *self._pointers(self.buffers, BATCH_KEYS), *self._pointers(out, BATCH_KEYS),
+            self.num_workers, count, self.observation_size, self.action_size, _lib.current_stream()),
+            'tonic_buffer_gather')
 
     def get(self, *keys, steps):
         """Generator form of the reference API (buffers.py:81-91): yields device-tensor batches.

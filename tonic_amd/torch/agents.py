@@ -29,6 +29,7 @@ import torch
 
 from tonic_amd import _lib, agents, explorations, logger, parallel, replays
 from tonic_amd.collector import Block, Collector
+from tonic_amd.q_block import QBlocks
 from tonic_amd.torch import models, normalizers, updaters
 
 
@@ -48,20 +49,6 @@ def default_model():
 
 _SIDE_STREAMS = {}
 _ARMED_GATES = weakref.WeakSet()      # agents whose critic chain waits behind a tonic_stream_gate
-
-
-class _DevicePointer:
-    """A raw device address where the entry-point wrappers expect a contiguous float32 tensor (`_lib.ptr`): fields
-    of a page-locked collector block as the GPU addresses them."""
-
-    def __init__(self, address, shape):
-        self.address, self.shape = address, tuple(shape)
-
-    def is_contiguous(self):
-        return True
-
-    def data_ptr(self):
-        return self.address
 
 
 def _side_stream(name):
@@ -208,6 +195,15 @@ class _Staging:
         done = self.done
         while not done.query():
             pass
+
+
+def _read_back_actions(stage_in, stage_out):
+    """The tail of a staged forward: the actions, once everything enqueued so far is through (both blocks free)."""
+    stage_out.download()
+    stage_out.mark()
+    stage_in.done = stage_out.done
+    stage_out.wait()
+    return stage_out.host_view('actions').copy()
 
 
 class _NoiseAhead:
@@ -411,11 +407,7 @@ class A2C(Agent):
                 if want_log_probs:
                     stage_out.device_view('log_probs').copy_(
                         distribution.log_prob(actions).sum(dim=-1), non_blocking=True)
-            stage_out.download()
-            stage_out.mark()
-            stage_in.done = stage_out.done
-            stage_out.wait()
-            return stage_out.host_view('actions').copy()
+            return _read_back_actions(stage_in, stage_out)
         p = _lib.ptr
         torso = getattr(self.actor_updater, 'torso', None)
         if torso is not None:
@@ -438,11 +430,7 @@ class A2C(Agent):
                 p(stage_out.device_view('log_probs')) if want_log_probs else None,
                 W, self.observation_size, A, p(self._act_workspace), self._act_workspace.numel(),
                 _lib.current_stream()), 'tonic_ppo_act_wide')
-        stage_out.download()
-        stage_out.mark()
-        stage_in.done = stage_out.done
-        stage_out.wait()
-        return stage_out.host_view('actions').copy()
+        return _read_back_actions(stage_in, stage_out)
 
     def _bind(self, observations):
         """First step (or a new worker count): find the environment's block — the arrays of
@@ -1301,141 +1289,35 @@ class DDPG(Agent):
         self._replicate([self.model.flat_online, self.model.flat_target], own_noise=False)
         self._workers = None
         self._policy_io = {}
-        self._q_blocks = {}
-        self._q_last = None
-        self._q_act = _lib.hot('tonic_collector_q_act')      # (per environment step: the vectorcall shim if built)
-        self._actor_images = None             # the acting launch's weight images of the actor (tonic_collector_q_act)
-        self._actor_images_stale = True
-        self._actor_images_version = -1
+        self._q = QBlocks(self)      # acting / storing on the environments' own blocks (tonic_amd.q_block)
         self._graph, self._static_key = None, None       # a re-initialised agent re-captures
         self._slots, self._slot_index = {}, 0
 
     def close(self):
-        """Stores what is still deferred; gives back what the agent holds beyond its tensors (the process's CPU
-        binding: parallel.bind_near_gpu)."""
-        self.settle()
+        """Stores what is still deferred and lets go of the environments' blocks; gives back what the agent holds
+        beyond its tensors (the process's CPU binding: parallel.bind_near_gpu)."""
+        if getattr(self, '_q', None) is not None:
+            self._q.settle()
+            self._q.clear()
         if getattr(self, '_holds_affinity', False):
             self._holds_affinity = False
             parallel.release_affinity()
 
     # ------------------------------------------------------------------ acting
-    def _block_of(self, observations, kind):
-        """The collector block these observations live in when the policy can act on it in place
-        (tonic_collector_q_act: the environments of tonic_amd.environments hand out views of their shared block;
-        plain torsos the fused forward holds; one process per block's GPU handle) — None: the staged copies."""
-        cached = self._q_last                      # (three look-ups per loop iteration: the same view each time)
-        if cached is not None and cached[0] is observations and cached[1] == kind:
-            return cached[2]
-        state = self._find_block(observations, kind)
-        if isinstance(observations, np.ndarray):
-            self._q_last = (observations, kind, state)
-        return state
-
-    def _find_block(self, observations, kind):
-        if kind not in (0, 1) or self.hidden is None or os.environ.get('TONIC_AMD_Q_BLOCK', '1') == '0':
-            return None
-        if self._actor_images is None:          # (once: does the fused forward on weight images serve this policy?)
-            need = self.lib.tonic_mlp_actor_image_bytes(self.observation_size, self.hidden, self.action_size,
-                                                        2 if kind == 1 else 1)
-            self._actor_images = torch.zeros(need, dtype=torch.uint8, device=self.device) if need > 0 else False
-            self._actor_images_stale = True
-        if self._actor_images is False:
-            return None
-        if not isinstance(observations, np.ndarray):
-            return None
-        block = Block.owner_of(observations)
-        if block is None:
-            return None
-        state = self._q_blocks.get(id(block))
-        if state is None:
-            W = block.workers
-            need = self.lib.tonic_offpolicy_workspace_bytes(W, self.observation_size, self.action_size, self.hidden)
-            state = dict(block=block, collector=Collector.for_block(block, 0),
-                         workspace=torch.empty(need, dtype=torch.uint8, device=self.device),
-                         rows=[torch.zeros(W, self.observation_size, device=self.device) for _ in range(2)],
-                         turn=0, deferred=None, rows_of=None, actions_of=None, store_pending=False, usable=True)
-            # the block's fields as the GPU sees them (page-locked by the collector): the store reads them in place
-            def mapped(view, shape):
-                address = self.lib.tonic_host_device_pointer(view.ctypes.data)
-                return _DevicePointer(address, shape) if address else None
-            W, O, A = block.workers, self.observation_size, self.action_size
-            state['fields'] = dict(actions=mapped(block.actions, (W, A)),
-                                   next_observations=mapped(block.next_observations, (W, O)),
-                                   rewards=mapped(block.rewards, (W,)), resets=mapped(block.resets, (W,)),
-                                   terminations=mapped(block.terminations, (W,)))
-            if any(v is None for v in state['fields'].values()):
-                state['usable'] = False
-            self._q_blocks[id(block)] = state
-        return state if state['usable'] else None
-
-    def _act_on_block(self, state, kind, stochastic):
-        """One launch on the environment's block, no copies: ddpg.py:45-52 / sac.py:40-51 (tonic_collector_q_act)."""
-        block, collector = state['block'], state['collector']
-        W = block.workers
-        if stochastic:          # Normal.sample() of sac.py:43 == loc + scale * randn (SURVEY A.7)
-            np.copyto(block.eps[0], self._randn(W, self.action_size).numpy())
-        workspace = state['workspace']
-        # the images follow the float32 parameters: rebuilt after every learner update (raw-pointer writes: the
-        # flag) and whenever torch has written the flat block in place since (load_state_dict, an optimizer of the
-        # caller's: the tensor's version counter, which every in-place operation on a view of it advances)
-        flat = self.model.flat_online
-        stale = self._actor_images_stale or flat._version != self._actor_images_version
-        self._actor_images_version = flat._version
-        # the transition of the step before (reserved by update(), its sources still in the block) rides in this
-        # launch: one more workgroup stores it while the tiles compute these actions
-        deferred, store = state['deferred'], None
-        if deferred is not None:
-            held = state.get('store_struct')        # (one tonic_q_store_t per block: two fields change per step)
-            if held is None or state.get('store_struct_of') is not self.replay.buffers:
-                held = state['store_struct'] = self.replay.store_arguments(
-                    0, state['rows'][0], self.model.observation_normalizer)
-                state['store_struct_of'] = self.replay.buffers
-                state['store_struct_rows'] = [_lib.ptr(r) for r in state['rows']]
-            held.row = deferred['row']
-            held.d_observations = state['store_struct_rows'][deferred['turn']]
-            store = ctypes.addressof(held)
-        turn = state['turn'] ^ 1          # (these rows' device copy: the buffer the pending store does not read)
-        status = self._q_act(
-            collector.handle, _lib.ptr(self.model.flat_actor.flat), _lib.ptr(self._actor_images),
-            int(stale), kind, self.hidden, 0 if stochastic else -1,
-            _lib.ptr(state['rows'][turn]), store, _lib.ptr(workspace), workspace.numel(), _lib.current_stream())
-        if status != 0:
-            _lib.check(status, 'tonic_collector_q_act')
-        self._actor_images_stale = False
-        collector.wait_actions()          # (every completion word, the store's included)
-        state['deferred'], state['store_pending'] = None, False
-        state['turn'], state['rows_of'] = turn, block
-        return block.eps[1].copy()
-
-    def _flush_store(self, state):
-        """A reserved transition goes out as a launch of its own (no acting launch will carry it in time)."""
-        deferred = state['deferred']
-        if deferred is None:
-            return
-        self.replay.store_at(deferred['row'], self.model.observation_normalizer,
-                             observations=state['rows'][deferred['turn']], **state['fields'])
-        state['deferred'], state['store_pending'] = None, True
-
     def settle(self):
         """Everything this agent has deferred is on the device: reserved transitions stored, their launches through
         (readers of `replay.buffers` between two steps call this; `close` does)."""
-        for state in getattr(self, '_q_blocks', {}).values():
-            self._flush_store(state)
-            if state['store_pending']:
-                torch.cuda.current_stream().synchronize()
-                state['store_pending'] = False
+        if getattr(self, '_q', None) is not None:
+            self._q.settle()
 
     def _forward_policy(self, observations, kind, stochastic):
-        state = self._block_of(observations, kind)
-        for other in self._q_blocks.values():
-            # a transition reserved on ANOTHER block (test episodes between training steps, a second environment)
-            # does not wait for that block's next acting launch
-            if other is not state and other['deferred'] is not None:
-                self._flush_store(other)
-        if state is not None:
-            actions = self._act_on_block(state, kind, stochastic)
-            if actions is not None:
-                return actions
+        q = self._q.find(observations, kind)
+        self._q.flush(but=q)      # (a transition reserved on another block does not wait for that block's next launch)
+        if q is not None:
+            return q.act(kind, stochastic)
+        return self._forward_staged(observations, kind, stochastic)
+
+    def _forward_staged(self, observations, kind, stochastic):
         observations = np.asarray(observations, np.float32)
         W = observations.shape[0]
         io = self._policy_io.get(W)
@@ -1467,11 +1349,7 @@ class DDPG(Agent):
                 else:
                     actions = out.loc + out.scale * eps if stochastic else out.loc
                 stage_out.device_view('actions').copy_(actions, non_blocking=True)
-            stage_out.download()
-            stage_out.mark()
-            stage_in.done = stage_out.done
-            stage_out.wait()
-            return stage_out.host_view('actions').copy()
+            return _read_back_actions(stage_in, stage_out)
         p = _lib.ptr
         _lib.check(self.lib.tonic_policy_forward(
             p(self.model.flat_actor.flat), p(stage_in.device_view('observations')),
@@ -1479,11 +1357,7 @@ class DDPG(Agent):
             p(stage_out.device_view('actions')), kind, W, self.observation_size, self.hidden,
             self.action_size, p(workspace), workspace.numel(), _lib.current_stream()),
             'tonic_policy_forward')
-        stage_out.download()
-        stage_out.mark()
-        stage_in.done = stage_out.done
-        stage_out.wait()
-        return stage_out.host_view('actions').copy()
+        return _read_back_actions(stage_in, stage_out)
 
     def _greedy_actions(self, observations):
         return self._forward_policy(observations, self.policy_kind, False)
@@ -1492,77 +1366,30 @@ class DDPG(Agent):
         return self._greedy_actions(observations)
 
     def step(self, observations, steps):
-        for state in self._q_blocks.values():
-            state['rows_of'] = state['actions_of'] = None
+        self._q.begin_step()
         actions = self.exploration(observations, steps)
         self.last_observations = observations.copy()
         self.last_actions = actions.copy()
-        self._stepped_on = observations
-        state = self._block_of(observations, self.policy_kind)
-        if state is not None:
-            block = state['block']
-            if state['rows_of'] is not block:
-                # the policy sat this step out (warm-up: uniform actions): no acting launch carried the reserved
-                # transition or was waited for behind a store launch — they read the block in place and must be
-                # through before the environment overwrites it
-                self._flush_store(state)
-                if state['store_pending']:
-                    torch.cuda.current_stream().synchronize()
-            state['store_pending'] = False
-            # the executed actions go into the environment's block (where the store launch reads them); policy
-            # actions (float32) are handed out as the block's own view — value-identical, and the environments of
-            # tonic_amd.environments take their one-call step then — the warm-up's float64 draws as they are
-            np.copyto(block.actions, actions)
-            state['actions_of'] = block
-            if actions.dtype == np.float32:
-                return block.out_actions
-        return actions
+        q = self._q.stepped = self._q.find(observations, self.policy_kind)
+        return actions if q is None else q.feed(actions)
 
     def test_step(self, observations, steps):
         return self._greedy_actions(observations)
 
     # ---------------------------------------------------------------- learning
-    def _store_from_block(self, observations, rewards):
-        """The transition straight from the environment's block (Buffer.store, buffers.py:33-56): next observations,
-        outcome and the executed actions are read by the store launch IN PLACE (page-locked block), the observations
-        from the device copy the acting launch made — or, when the policy did not act on this step (warm-up), from one
-        staged copy.  False: not this step's layout (foreign arrays, another block): the staged path."""
-        block = Block.owner_of(getattr(self, '_stepped_on', None)) if isinstance(
-            getattr(self, '_stepped_on', None), np.ndarray) else None
-        if block is None or observations is not block.out_next_observations or rewards is not block.out_rewards:
-            return False
-        state = self._block_of(self._stepped_on, self.policy_kind)
-        if state is None or state.get('actions_of') is not block:      # (step() put the executed actions there)
-            return False
-        normalizer = self.model.observation_normalizer
-        if state['rows_of'] is block and self.replay.buffers is not None and self.replay.return_steps == 1:
-            # the usual step: the row is reserved now (Buffer bookkeeping, buffers.py:54-56) and written by the next
-            # acting launch, which reads the block before the environment's next step can touch it
-            state['deferred'] = dict(row=self.replay.reserve_row(normalizer), turn=state['turn'])
-            return True
-        rows = state['rows'][state['turn']]
-        if state['rows_of'] is not block:       # (warm-up: uniform actions, the policy never saw these rows)
-            staged = state.setdefault('staged_rows', torch.zeros(
-                block.workers, self.observation_size, dtype=torch.float32).pin_memory())
-            torch.cuda.current_stream().synchronize()        # (the previous store may still read it)
-            staged.numpy()[:] = self.last_observations
-            rows.copy_(staged, non_blocking=True)
-        self.replay.store(normalizer=normalizer, observations=rows, **state['fields'])
-        state['store_pending'] = True
-        return True
-
     def update(self, observations, rewards, resets, terminations, steps):
-        if self._store_from_block(observations, rewards):
-            if self.model.return_normalizer:
-                raise NotImplementedError('return normalisers are not supported')
-            if self.replay.ready(steps):
-                for state in self._q_blocks.values():
-                    self._flush_store(state)         # the update samples this transition too
-                self._update(steps)          # (ends with a read-back: the store launches are through)
-                for state in self._q_blocks.values():
-                    state['store_pending'] = False
-            self.exploration.update(resets)
-            return
+        q = self._q.stepped
+        if q is None or not q.store(observations, rewards, self.last_observations):
+            self._store_staged(observations, rewards, resets, terminations)
+        if self.model.return_normalizer:
+            raise NotImplementedError('return normalisers are not supported')
+        if self.replay.ready(steps):
+            self._q.flush()              # the update samples the reserved transitions too
+            self._update(steps)          # (ends with a read-back: the store launches are through)
+            self._q.stores_through()
+        self.exploration.update(resets)
+
+    def _store_staged(self, observations, rewards, resets, terminations):
         W = len(rewards)
         if self._workers != W:
             self._workers = W
@@ -1575,23 +1402,14 @@ class DDPG(Agent):
             self._transition_turn = 0
         self._transition_turn ^= 1
         stage = self._transitions[self._transition_turn].writable()
-        stage.host_view('observations')[:] = self.last_observations
-        stage.host_view('actions')[:] = self.last_actions          # float64 warm-up -> float32
-        stage.host_view('next_observations')[:] = observations
-        stage.host_view('rewards')[:] = rewards
-        stage.host_view('resets')[:] = resets
-        stage.host_view('terminations')[:] = terminations
+        record = dict(observations=self.last_observations, actions=self.last_actions, next_observations=observations,
+                      rewards=rewards, resets=resets, terminations=terminations)
+        for key, value in record.items():
+            stage.host_view(key)[:] = value          # (actions: float64 warm-up -> float32)
         stage.upload()
-        self.replay.store(
-            normalizer=self.model.observation_normalizer,
-            **{k: stage.device_view(k) for k in ('observations', 'actions', 'next_observations',
-                                                 'rewards', 'resets', 'terminations')})
+        self.replay.store(normalizer=self.model.observation_normalizer,
+                          **{key: stage.device_view(key) for key in record})
         stage.mark()                  # the store kernel(s) read the pinned fields in place
-        if self.model.return_normalizer:
-            raise NotImplementedError('return normalisers are not supported')
-        if self.replay.ready(steps):
-            self._update(steps)
-        self.exploration.update(resets)
 
     def _actor_due(self, iteration):
         return True                       # ddpg.py:105-112: actor + targets every iteration
@@ -1604,7 +1422,7 @@ class DDPG(Agent):
         grouped weight-gradient launches, Adam + polyak: 13 per SAC iteration — is captured once into a hipGraph
         reading fixed index / noise buffers and replayed on later calls."""
         iterations, global_batch = indices.shape
-        self._actor_images_stale = True          # (the acting launch rebuilds its weight images after an update)
+        self._q.parameters_changed()
         world = self.critic_updater.world_size
         counts = None
         if world > 1:
