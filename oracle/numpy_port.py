@@ -47,6 +47,30 @@ def lambda_returns(next_values, rewards, resets, terminations, discount_factor,
     return out
 
 
+def lambda_returns_f64(next_values, rewards, resets, terminations, discount_factor,
+                       trace_decay):
+    """The recurrence of ``lambda_returns`` (lines 13-18, same operation order) evaluated in
+    float64 on the float32 inputs, with the three scalars rounded as the float32 chain rounds
+    them: ``float32(gamma)``, ``float32(lambda)`` and ``float32(1.0 - lambda)`` (a Python float
+    meets a float32 array).  With unrounded scalars the result is off by ~3e-7 relative on its
+    own.  The reference for the HIP forms that re-associate the chain (the one-pass scan)."""
+    gamma = np.float64(F32(discount_factor))
+    lam = np.float64(F32(trace_decay))
+    one_minus_lambda = np.float64(F32(1.0 - trace_decay))
+    steps = rewards.shape[0]
+    out = np.zeros(rewards.shape, np.float64)
+    carry = next_values[steps - 1].astype(np.float64)
+    for t in range(steps - 1, -1, -1):
+        nv, rs = next_values[t].astype(np.float64), resets[t].astype(np.float64)
+        boot = one_minus_lambda * nv + lam * carry
+        boot = boot * (1.0 - rs)
+        boot = boot + rs * nv
+        boot = boot * (1.0 - terminations[t].astype(np.float64))
+        carry = rewards[t].astype(np.float64) + gamma * boot
+        out[t] = carry
+    return out
+
+
 def lambda_returns_affine(next_values, rewards, resets, terminations, gamma, lam):
     """Affine form ``ret[t] = A[t] + B[t] * ret[t+1]`` of the same scan (SURVEY.md
     Appendix A.1) evaluated in float64 — the property the chunked HIP scan relies on.

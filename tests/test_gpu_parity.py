@@ -33,18 +33,23 @@ def flat(params):
     return np.concatenate([np.asarray(p, np.float32).reshape(-1) for p in params])
 
 
-def run_gae(lib, nv, rew, rst, term, val, gamma, lam, chunks):
+def run_gae(lib, nv, rew, rst, term, val, gamma, lam, chunks, moments=False):
+    """-> returns, advantages, stats (and, with `moments`, the float64 vector d_adv_moments).  The outputs
+    start as NaN, so that an element the kernel never wrote cannot pass for a result."""
     from tonic_amd import _lib
     T, W = rew.shape
     d = [dev(a) for a in (nv, rew, rst, term, val)]
-    ret, adv = torch.empty(T, W).cuda(), torch.empty(T, W).cuda()
-    stats = torch.zeros(4).cuda()
-    ws = torch.empty(max(lib.tonic_gae_workspace_bytes(T, W, chunks), 16), dtype=torch.uint8).cuda()
+    ret, adv = (torch.full((T, W), float('nan'), device='cuda') for _ in range(2))
+    stats = torch.full((4,), float('nan'), device='cuda')
+    mom = torch.full((5,), float('nan'), dtype=torch.float64, device='cuda') if moments else None
+    ws = torch.empty(max(lib.tonic_gae_workspace_bytes(T, W, chunks), 16), dtype=torch.uint8, device='cuda')
     _lib.check(lib.tonic_gae_lambda_returns(
-        *[t.data_ptr() for t in d], ret.data_ptr(), adv.data_ptr(), stats.data_ptr(), None, T, W,
+        *[t.data_ptr() for t in d], ret.data_ptr(), adv.data_ptr(), stats.data_ptr(),
+        mom.data_ptr() if moments else None, T, W,
         float(gamma), float(lam), chunks, ws.data_ptr(), ws.numel(), None), 'gae')
     torch.cuda.synchronize()
-    return ret.cpu().numpy(), adv.cpu().numpy(), stats.cpu().numpy()
+    out = ret.cpu().numpy(), adv.cpu().numpy(), stats.cpu().numpy()
+    return out + (mom.cpu().numpy(),) if moments else out
 
 
 def normalise(adv, stats):

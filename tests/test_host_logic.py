@@ -50,6 +50,12 @@ def test_library_exports_every_declared_symbol():
     assert status == -1 and b'null' in loaded.tonic_last_error()
     status = loaded.tonic_set_tuning(b'no_such_knob', 1)
     assert status == -1 and b'unknown key' in loaded.tonic_last_error()
+    # "gae_stream": the check and its message name the same values, 0 .. 4 (csrc/gae.hip reads all five)
+    for bad in (-1, 5):
+        assert loaded.tonic_set_tuning(b'gae_stream', bad) == -1
+        message = loaded.tonic_last_error()
+        assert all(b'%d (' % v in message for v in range(5)) and b'got %d' % bad in message, message
+    assert loaded.tonic_set_tuning(b'gae_stream', 1) == 0
 
 
 def test_offpolicy_size_queries_and_hidden_codes():

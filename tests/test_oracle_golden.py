@@ -30,6 +30,32 @@ def test_lambda_returns_bit_exact(golden):
     assert np.array_equal(const.reshape(-1), g['const_advantages'])
 
 
+def test_lambda_returns_f64_reference(golden):
+    """lambda_returns_f64 is the float32 chain's recurrence with the float32 chain's scalars: it
+    stays within float32 rounding of the chain on the goldens (per column, no floor), equals it
+    exactly where every operation is exact in float32, and its output depends on the scalars'
+    float32 rounding, not on their Python value."""
+    g = golden('lambda_returns')
+    for i in range(int(g['n_cases'])):
+        for j in range(4):
+            k = f'c{i}_{j}_'
+            args = [g[k + n] for n in ('next_values', 'rewards', 'resets', 'terminations')]
+            gamma, lam = float(g[k + 'gamma']), float(g[k + 'lambda'])
+            ref = port.lambda_returns_f64(*args, gamma, lam)
+            assert ref.dtype == np.float64
+            err = np.abs(ref - g[k + 'returns']).max(axis=0)
+            assert (err <= 1e-5 * np.abs(ref).max(axis=0)).all(), k
+            nudged = port.lambda_returns_f64(*args, float(np.float32(gamma)), lam)
+            assert np.array_equal(nudged, ref), k
+    # small integers, gamma = lambda = 1: every product and sum is exact in both precisions
+    rng = np.random.RandomState(3)
+    nv, rew = (rng.randint(-8, 9, size=(40, 6)).astype(np.float32) for _ in range(2))
+    rst = (rng.uniform(size=(40, 6)) < 0.2).astype(np.float32)
+    term = rst * (rng.uniform(size=(40, 6)) < 0.5).astype(np.float32)
+    assert np.array_equal(port.lambda_returns_f64(nv, rew, rst, term, 1.0, 1.0),
+                          port.lambda_returns(nv, rew, rst, term, 1.0, 1.0).astype(np.float64))
+
+
 def test_meanstd_bit_exact(golden):
     g = golden('meanstd')
     norm = port.MeanStdPort((5,))

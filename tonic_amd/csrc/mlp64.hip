@@ -918,7 +918,8 @@ extern "C" int tonic_set_tuning(const char* key, int32_t value) {
   }
   if (strcmp(key, "gae_stream") == 0) {
     TONIC_REQUIRE(value >= 0 && value <= 4, TONIC_ERR_INVALID_ARGUMENT,
-                  "gae_stream must be 0, 1, 2 (developer probe) or 3 (dword helpers), got %d", value);
+                  "gae_stream must be 0 (lane = column scan), 1 (streamed), 2 (developer probe: chain only), "
+                  "3 (dword helpers) or 4 (developer probe: no retiring), got %d", value);
     g_gae_stream = value;
     return TONIC_OK;
   }
