@@ -56,10 +56,11 @@ const char* tonic_last_error(void);
  * images of the off-policy passes in the workspaces: tonic_offpolicy_workspace_bytes / tonic_q_iteration_workspace_bytes
  * grow), tonic_mlp_hidden packs with bit 30 set (plain widths of any size pass as they are), tonic_collector_q_act,
  * 12 = the *_ranged critic entries (Return normaliser's value head) + tonic_reward_range, 13 = tonic_mlp_torso:
- * 1 .. 4 layer torsos for every off-policy entry, the D4PG / MPO entries take tonic_mlp_hidden codes)
+ * 1 .. 4 layer torsos for every off-policy entry, the D4PG / MPO entries take tonic_mlp_hidden codes,
+ * 14 = the tonic_trpo_* entries)
  * and the gfx target the kernels were built for.  TONIC_ABI_VERSION is what a binding was compiled against:
  * tonic_amd/_fastcall (csrc/fastcall.c) and tonic_amd/_lib.py compare it with the loaded library's answer. */
-#define TONIC_ABI_VERSION 13
+#define TONIC_ABI_VERSION 14
 int32_t tonic_abi_version(void);
 const char* tonic_target_arch(void);
 
@@ -215,6 +216,53 @@ int tonic_value_regression_grad_torso(int32_t layers, const int32_t* sizes, int3
                                       const float* d_observations, const float* d_returns,
                                       float* d_grad_sums, int64_t n, int32_t O, void* d_workspace,
                                       int64_t workspace_bytes, void* stream);
+
+/* ---- TRPO: the truncated natural-gradient actor step ------------------------------------------
+ * replaces: tonic/torch/updaters/actors.py:115-156 (TrustRegionPolicyGradient: surrogate loss :142-150, KL
+ *   :152-156) under tonic/torch/updaters/optimizers.py:25-115 (ConjugateGradient: the loss gradient :52-53,
+ *   the Hessian-vector products :36-48, the line-search trials :68-74), for the actor MLP(sizes, activation)
+ *   + DetachedScaleGaussianPolicyHead (tonic/torch/models/actors.py:37-66) in the dense parameters() layout
+ *   of the tonic_*_torso entries above ((layers, sizes, activation) as there; the default torso is
+ *   layers = 2, sizes = {64, 64}, activation = 1).  O in 1 .. 384, A in 1 .. 32.
+ * The conjugate-gradient recurrences and the backtracking rule stay with the caller; these entries are what
+ *   it evaluates over the batch.  The parameters do not move between the first product and the last, so
+ *   tonic_trpo_prepare runs ONE forward pass and leaves the hidden activations, the locations mu_o [n, A]
+ *   and the scales sigma_o [A] of the behaviour policy in the workspace (d_locs / d_scales: optional copies
+ *   out, NULL = none).  The other three entries need a prepared workspace of the same (n, O, A, torso).
+ * tonic_trpo_loss_grad: d_grad_sums [P + 8] = gradient SUMS of
+ *     L = -mean_n(exp(logp(a) - old_logp) * adv) - entropy_coeff * mean_{n,A}(entropy)   (actors.py:142-150)
+ *   at the prepared parameters (d_actor_params = those of prepare) and the statistic sums
+ *   {loss_sum without the entropy term, sum(old_logp - logp), 0, n * entropy, n * mean_sigma, n, 0, 0};
+ *   d_advantages are final (Segment.get_full normalised them, segments.py:41-46).
+ * tonic_trpo_fisher_vector: d_out_sums [P + 8] (the 8 statistic slots carry nothing) = sum over the n rows
+ *   of J^T M J v, the Gauss-Newton form of the Hessian of sum_{n,A} KL(pi_theta || (mu_o, sigma_o)) at the
+ *   prepared parameters — what optimizers.py:36-48 takes by double backward when (mu_o, sigma_o) are this
+ *   network's own outputs; dividing by n * A gives the product with the Hessian of actors.py:152-156's mean.
+ *   d_vector [P] in the parameter layout.  No damping term.  The same input gives the same bits.
+ * tonic_trpo_evaluate: one line-search trial (optimizers.py:68-74), forward only at d_trial_params into
+ *   scratch that leaves the prepared activations alone: d_out[2] = {sum_n(-ratio * adv) - entropy_coeff *
+ *   n * mean_A(entropy), sum_{n,A} KL(pi_trial || (mu_o, sigma_o))}, accumulated in float64.
+ * tonic_trpo_workspace_bytes: the scratch for n rows; -1 where the shape or the torso is not served.
+ */
+int64_t tonic_trpo_workspace_bytes(int64_t n, int32_t O, int32_t A, int32_t layers, const int32_t* sizes);
+int tonic_trpo_prepare(int32_t layers, const int32_t* sizes, int32_t activation,
+                       const float* d_actor_params, const float* d_observations, int64_t n, int32_t O,
+                       int32_t A, float* d_locs, float* d_scales, void* d_workspace,
+                       int64_t workspace_bytes, void* stream);
+int tonic_trpo_loss_grad(int32_t layers, const int32_t* sizes, int32_t activation,
+                         const float* d_actor_params, const float* d_observations, const float* d_actions,
+                         const float* d_advantages, const float* d_old_log_probs, float* d_grad_sums,
+                         int64_t n, int32_t O, int32_t A, double entropy_coeff, void* d_workspace,
+                         int64_t workspace_bytes, void* stream);
+int tonic_trpo_fisher_vector(int32_t layers, const int32_t* sizes, int32_t activation,
+                             const float* d_actor_params, const float* d_observations,
+                             const float* d_vector, float* d_out_sums, int64_t n, int32_t O, int32_t A,
+                             void* d_workspace, int64_t workspace_bytes, void* stream);
+int tonic_trpo_evaluate(int32_t layers, const int32_t* sizes, int32_t activation,
+                        const float* d_trial_params, const float* d_observations, const float* d_actions,
+                        const float* d_advantages, const float* d_old_log_probs, int64_t n, int32_t O,
+                        int32_t A, double entropy_coeff, float* d_out, void* d_workspace,
+                        int64_t workspace_bytes, void* stream);
 
 /* ---- the Return normaliser (on-policy critics: A2C, PPO, TRPO) ------------------------------
  * The *_ranged entries replace the same reference code as the entry they are named after, for a model

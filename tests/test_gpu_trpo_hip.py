@@ -1,0 +1,515 @@
+"""TRPO's actor step on the HIP kernels (csrc/trpo_body.h, the tonic_trpo_* entries): every entry against the
+float64 statement of the mathematics (tests/trpo_fisher_ref.py, itself pinned on float64 autograd by
+test_trpo_fisher_host.py) with the stock float32 autograd path as the yardstick, and the whole step against
+the stock path, the reference's golden update and a two-rank run."""
+import ctypes
+import functools
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import trpo_fisher_ref as ref
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+WORKER = os.path.join(ROOT, 'tests', 'mp_trpo_worker.py')
+
+TORSOS = {'default': ((64, 64), 'tanh'), 'relu32': ((32,), 'relu'), 'tanh3': ((64, 64, 64), 'tanh'),
+          'relu4': ((48, 32, 24, 16), 'relu')}
+ACTIVATIONS = {'tanh': torch.nn.Tanh, 'relu': torch.nn.ReLU}
+CODES = {'tanh': 1, 'relu': 2}
+# (O, A, n): one row; either side of a 64-row slab; a single column; ragged over many slabs; A > 16; the widest
+# served shape; more than 1 024 row slabs (slab > 64)
+SHAPES = [(17, 6, 1), (17, 6, 63), (17, 6, 65), (3, 1, 777), (111, 8, 4099), (9, 21, 1500), (384, 32, 300),
+          (17, 6, 66003)]
+CASES = [(*shape, 'default') for shape in SHAPES] + [(17, 6, 1000, name) for name in TORSOS]
+
+
+@pytest.fixture(scope='module')
+def lib():
+    from tonic_amd import _lib
+    assert torch.cuda.is_available(), 'GPU tests need a ROCm device'
+    return _lib.load()
+
+
+def dev(x):
+    return torch.as_tensor(np.ascontiguousarray(x), dtype=torch.float32).cuda().contiguous()
+
+
+@functools.lru_cache(maxsize=4)
+def problem(O, A, n, torso):
+    """Float32 parameters and batch, and the float64 values every test of the shape shares (read-only)."""
+    sizes, activation = TORSOS[torso]
+    rng = np.random.RandomState(O * 31 + A * 7 + n + len(sizes))
+    slots, P = ref.layout(O, A, sizes)
+    theta = np.zeros(P, np.float32)
+    for name, shape, at in slots:
+        scale = 0.3 if name == 'log_scale' else 0.1 if len(shape) == 1 else 0.6 / np.sqrt(shape[1])
+        theta[at:at + int(np.prod(shape))] = rng.standard_normal(int(np.prod(shape))) * scale
+    x = (rng.standard_normal((n, O)) * 1.5).astype(np.float32)
+    args = (O, A, sizes, activation)
+    while activation == 'relu':
+        # ReLU' jumps at zero: a pre-activation within float32 rounding of it (|z| ~ 1e-7 for sums of this size)
+        # has no defined mask in float32 — float32 NumPy, torch and the kernels each pick their own, and one
+        # flipped unit moves a gradient sum by 1e-3 of its scale.  Such rows are drawn again (the first
+        # (17, 6, 1000, (32,)) draw held one unit at |z| = 8.5e-8).
+        hs = ref.forward(theta, x, *args)[0]
+        unpacked = ref.unpack(theta, *args[:3])
+        close = np.zeros(n, bool)
+        for l in range(len(sizes)):
+            close |= (np.abs(hs[l] @ unpacked[f'W{l}'].T + unpacked[f'b{l}']) < 1e-5).any(1)
+        if not close.any():
+            break
+        x[close] = (rng.standard_normal((int(close.sum()), O)) * 1.5).astype(np.float32)
+    _, mu, sigma, _ = ref.forward(theta, x, *args)
+    actions = (mu + sigma * rng.standard_normal((n, A))).astype(np.float32)
+    old = (ref.log_probs(mu, sigma, actions.astype(np.float64)) + rng.standard_normal(n) * 0.3).astype(np.float32)
+    adv = rng.standard_normal(n).astype(np.float32)
+    ls = dict((name, at) for name, _, at in slots)['log_scale']
+    vectors = {'random': rng.standard_normal(P).astype(np.float32)}
+    vectors['log_scale only'] = np.zeros(P, np.float32)
+    vectors['log_scale only'][ls:ls + A] = rng.standard_normal(A)
+    vectors['first layer only'] = np.zeros(P, np.float32)
+    vectors['first layer only'][:sizes[0] * (O + 1)] = rng.standard_normal(sizes[0] * (O + 1))
+    trial = (theta * (1 + 1e-2 * rng.standard_normal(P))).astype(np.float32)     # log_scale included
+    p = dict(O=O, A=A, n=n, sizes=sizes, activation=activation, args=args, slots=slots, P=P, theta=theta, x=x,
+             actions=actions, old=old, adv=adv, vectors=vectors, trial=trial, mu=mu, sigma=sigma)
+    p['fisher'] = {k: ref.fisher_vector_sums(theta, x, v, *args) for k, v in vectors.items()}
+    return p
+
+
+class Entries:
+    """The C entries on one problem's device copies."""
+
+    def __init__(self, lib, p):
+        from tonic_amd import _lib
+        self.lib, self.p, self.check = lib, p, _lib.check
+        sizes = p['sizes']
+        self.torso = (len(sizes), (ctypes.c_int32 * len(sizes))(*sizes), CODES[p['activation']])
+        self.shape = (p['n'], p['O'], p['A'])
+        need = lib.tonic_trpo_workspace_bytes(p['n'], p['O'], p['A'], self.torso[0], self.torso[1])
+        assert need > 0
+        assert lib.tonic_ppo_torso_param_count(p['O'], p['A'], 1, self.torso[0], self.torso[1]) == p['P']
+        self.ws = torch.empty(need, dtype=torch.uint8, device='cuda')
+        self.theta, self.x, self.actions, self.adv, self.old = (
+            dev(p[k]) for k in ('theta', 'x', 'actions', 'adv', 'old'))
+        self.scratch = (self.ws.data_ptr(), self.ws.numel(), None)
+
+    def prepare(self, locs=None, scales=None):
+        self.check(self.lib.tonic_trpo_prepare(
+            *self.torso, self.theta.data_ptr(), self.x.data_ptr(), *self.shape,
+            None if locs is None else locs.data_ptr(), None if scales is None else scales.data_ptr(),
+            *self.scratch), 'tonic_trpo_prepare')
+        return self
+
+    def batch(self):
+        return self.x.data_ptr(), self.actions.data_ptr(), self.adv.data_ptr(), self.old.data_ptr()
+
+    def loss_grad(self, coeff):
+        out = torch.full((self.p['P'] + 8,), float('nan'), device='cuda')
+        self.check(self.lib.tonic_trpo_loss_grad(*self.torso, self.theta.data_ptr(), *self.batch(), out.data_ptr(),
+                                                 *self.shape, coeff, *self.scratch), 'tonic_trpo_loss_grad')
+        return out.cpu().numpy().astype(np.float64)
+
+    def fisher(self, v):
+        v = v if isinstance(v, torch.Tensor) else dev(v)
+        out = torch.full((self.p['P'] + 8,), float('nan'), device='cuda')
+        self.check(self.lib.tonic_trpo_fisher_vector(*self.torso, self.theta.data_ptr(), self.x.data_ptr(),
+                                                     v.data_ptr(), out.data_ptr(), *self.shape, *self.scratch),
+                   'tonic_trpo_fisher_vector')
+        return out.cpu().numpy()[:self.p['P']]
+
+    def evaluate(self, trial, coeff):
+        trial = dev(trial)
+        out = torch.full((2,), float('nan'), device='cuda')
+        self.check(self.lib.tonic_trpo_evaluate(*self.torso, trial.data_ptr(), *self.batch(), *self.shape, coeff,
+                                                out.data_ptr(), *self.scratch), 'tonic_trpo_evaluate')
+        return out.cpu().numpy().astype(np.float64)
+
+
+def stock_actor(p, theta=None):
+    """A float32 `models.Actor` on the device holding the problem's parameters, and the stock updater on it."""
+    from tonic_amd.environments import Box
+    from tonic_amd.torch import models
+    from tonic_amd.torch.updaters import TrustRegionPolicyGradient
+    actor = models.Actor(encoder=models.ObservationEncoder(),
+                         torso=models.MLP(p['sizes'], ACTIVATIONS[p['activation']]),
+                         head=models.DetachedScaleGaussianPolicyHead())
+    actor.initialize(Box(-np.inf, np.inf, (p['O'],)), Box(-1, 1, (p['A'],)))
+    actor.cuda()
+    variables = models.network_variables(actor)
+    flat, offset = dev(p['theta'] if theta is None else theta), 0
+    with torch.no_grad():
+        for v in variables:
+            v.copy_(flat[offset:offset + v.numel()].view(v.shape))
+            offset += v.numel()
+    assert offset == p['P']
+    updater = TrustRegionPolicyGradient()
+    updater.model = type('Model', (), {'actor': actor})()
+    return actor, variables, updater
+
+
+def flat_grad(tensors):
+    return torch.cat([t.reshape(-1) for t in tensors]).detach().cpu().numpy().astype(np.float64)
+
+
+def assert_per_tensor(p, got, want, stock, what):
+    """Per parameter tensor: max |got - want| <= max(1e-5 max |want|, 2 max |stock - want|), the float64 values
+    `want`, the stock float32 path the yardstick.  Prints the observed ratios before asserting."""
+    failures = []
+    for name, shape, at in p['slots']:
+        sl = slice(at, at + int(np.prod(shape)))
+        err = np.abs(got[sl] - want[sl]).max()
+        ours = np.abs(stock[sl] - want[sl]).max()
+        scale = np.abs(want[sl]).max()
+        bound = max(1e-5 * scale, 2 * ours)
+        print(f'ACC {what} O={p["O"]} A={p["A"]} n={p["n"]} torso={p["sizes"]} {name}: hip_err/scale='
+              f'{err / scale if scale else 0.0:.2e} stock_err/scale={ours / scale if scale else 0.0:.2e} '
+              f'err/bound={err / bound if bound else 0.0:.2f}')
+        if not err <= bound:
+            failures.append((name, err, bound, scale))
+    assert not failures, (what, failures)
+
+
+# ------------------------------------------------------------------------ 1. Fisher-vector product
+
+@pytest.mark.parametrize('O,A,n,torso', CASES)
+def test_fisher_vector_vs_float64(lib, O, A, n, torso):
+    p = problem(O, A, n, torso)
+    e = Entries(lib, p).prepare()
+    actor, variables, updater = stock_actor(p)
+    with torch.no_grad():
+        behaviour = actor(e.x)
+        locs, scales = behaviour.loc, behaviour.stddev
+    for name, v in p['vectors'].items():
+        first = torch.cat([t.reshape(-1) for t in torch.autograd.grad(
+            updater._kl(e.x, locs, scales), variables, create_graph=True)])
+        stock = flat_grad(torch.autograd.grad((first * dev(v)).sum(), variables)) * n * A
+        assert_per_tensor(p, e.fisher(v).astype(np.float64), p['fisher'][name], stock, 'fisher ' + name)
+
+
+# ------------------------------------------------------------------------ 2. loss gradient, line-search trial
+
+@pytest.mark.parametrize('coeff', [0.0, 0.01])
+@pytest.mark.parametrize('O,A,n,torso', CASES)
+def test_loss_grad_and_evaluate_vs_float64(lib, O, A, n, torso, coeff):
+    p = problem(O, A, n, torso)
+    e = Entries(lib, p).prepare()
+    batch64 = (p['x'], p['actions'], p['adv'].astype(np.float64), p['old'].astype(np.float64), coeff)
+    actor, variables, updater = stock_actor(p)
+    updater.entropy_coeff = coeff
+    loss = updater._loss(e.x, e.actions, e.old, e.adv)
+    stock = flat_grad(torch.autograd.grad(loss, variables)) * n
+    got = e.loss_grad(coeff)
+    P = p['P']
+    assert_per_tensor(p, got[:P], ref.loss_grad_sums(p['theta'], *batch64, *p['args']), stock, f'loss grad c={coeff}')
+    entropy = (0.5 + ref.LOG_SQRT_2PI + np.log(p['sigma'])).mean()
+    want_loss = ref.loss_sum(p['theta'], *batch64, *p['args'])
+    print(f'ACC loss_sum rel err {abs(got[P] - coeff * got[P + 3] - want_loss) / abs(want_loss):.2e}')
+    np.testing.assert_allclose(got[P] - coeff * got[P + 3], want_loss, rtol=1e-5)
+    np.testing.assert_allclose(got[P + 3], entropy * n, rtol=1e-5)
+    assert got[P + 5] == n
+    # the trial: parameters displaced by a step of relative size 1e-2, against the prepared (mu_o, sigma_o)
+    out = e.evaluate(p['trial'], coeff)
+    want = (ref.loss_sum(p['trial'], *batch64, *p['args']),
+            ref.kl_sum(p['trial'], p['x'], p['mu'], p['sigma'], *p['args']))
+    print(f'ACC evaluate O={O} A={A} n={n} torso={p["sizes"]} c={coeff}: loss_sum rel err '
+          f'{abs(out[0] - want[0]) / abs(want[0]):.2e} kl_sum rel err {abs(out[1] - want[1]) / abs(want[1]):.2e}')
+    np.testing.assert_allclose(out[0], want[0], rtol=1e-5)
+    if n > 1:
+        np.testing.assert_allclose(out[1], want[1], rtol=1e-5)
+    else:
+        # ONE row: the KL of a 1 % step is a sum of six squared differences of two float32 forward passes,
+        # (mu - mu_o) ~ 2e-3 against a rounding of 3e-8 in each mu and ~1e-7 in each pre-activation: 1e-5 of it
+        # is below what float32 arithmetic resolves (measured: 1.13e-5 with the scales in float64; the stock path: 9.1e-4).  For this
+        # case alone the bound is case 1's rule, the stock float32 path's own trial the yardstick.
+        actor, variables, updater = stock_actor(p)
+        with torch.no_grad():
+            behaviour = actor(e.x)
+            locs, scales = behaviour.loc.clone(), behaviour.stddev.clone()
+        actor, variables, updater = stock_actor(p, p['trial'])
+        with torch.no_grad():
+            stock = float(updater._kl(e.x, locs, scales)) * n * A
+        print(f'ACC evaluate n=1 kl_sum: stock rel err {abs(stock - want[1]) / abs(want[1]):.2e}')
+        assert abs(out[1] - want[1]) <= max(1e-5 * abs(want[1]), 2 * abs(stock - want[1]))
+    # ... and at the prepared parameters themselves the KL is zero
+    assert abs(e.evaluate(p['theta'], coeff)[1]) <= 1e-9 * n * A
+
+
+# ------------------------------------------------------------------------ 3. prepare is not disturbed
+
+@pytest.mark.parametrize('O,A,n,torso', [(17, 6, 4099, 'default'), (111, 8, 4099, 'default'), (17, 6, 1000, 'relu4')])
+def test_evaluate_leaves_the_prepared_activations_alone(lib, O, A, n, torso):
+    p = problem(O, A, n, torso)
+    locs, scales = torch.zeros(n, A, device='cuda'), torch.zeros(A, device='cuda')
+    e = Entries(lib, p).prepare(locs, scales)
+    np.testing.assert_allclose(locs.cpu().numpy(), p['mu'], rtol=0, atol=2e-6)
+    np.testing.assert_allclose(scales.cpu().numpy(), p['sigma'], rtol=1e-6)
+    v = p['vectors']['random']
+    before = e.fisher(v)
+    assert np.array_equal(before, e.fisher(v))
+    rng = np.random.RandomState(3)
+    for _ in range(3):
+        e.evaluate((p['theta'] + 0.05 * rng.standard_normal(p['P'])).astype(np.float32), 0.01)
+    assert np.array_equal(before, e.fisher(v))
+    e.loss_grad(0.0)
+    assert np.array_equal(before, e.fisher(v))
+
+
+# ------------------------------------------------------------------------ 4. the whole step, HIP vs stock
+
+STEP_SEED = 5
+
+
+def step_problem(seed, adv_scale, O=17, A=6, n=2048):
+    """One TRPO batch as the agent hands it over: the default model's initial parameters, actions drawn from it,
+    their exact log-probabilities, standardised advantages (times `adv_scale`)."""
+    from tonic_amd.environments import Box
+    from tonic_amd.torch import agents
+    torch.manual_seed(seed)
+    model = agents.default_model()
+    model.initialize(Box(-np.inf, np.inf, (O,)), Box(-1, 1, (A,)))
+    rng = np.random.RandomState(seed)
+    x = torch.as_tensor((rng.standard_normal((n, O)) * 1.5).astype(np.float32))
+    with torch.no_grad():
+        # (a step away from the initial zero head bias, so that the locations differ between the rows)
+        for q in model.actor.parameters():
+            q.add_(torch.as_tensor((rng.standard_normal(tuple(q.shape)) * 0.05).astype(np.float32)))
+        d = model.actor(x)
+        actions = d.loc + d.scale * torch.as_tensor(rng.standard_normal((n, A)).astype(np.float32))
+        log_probs = d.log_prob(actions).sum(-1)
+    adv = rng.standard_normal(n)
+    adv = ((adv - adv.mean()) / adv.std() * adv_scale).astype(np.float32)
+    return model, dict(observations=x.numpy(), actions=actions.numpy(), log_probs=log_probs.numpy(), advantages=adv)
+
+
+def run_step(monkeypatch, switch, seed, adv_scale, optimizer=None, entropy_coeff=0):
+    from tonic_amd.torch import updaters
+    monkeypatch.setenv('TONIC_AMD_TRPO_HIP', switch)
+    model, batch = step_problem(seed, adv_scale)
+    model.pack('cuda')
+    updater = updaters.TrustRegionPolicyGradient(optimizer=optimizer, entropy_coeff=entropy_coeff)
+    updater.initialize(model)
+    assert updater.hip is (switch == '1')
+    start = model.flat_actor.flat.detach().cpu().numpy().copy()
+    out = updater(**{k: dev(v) for k, v in batch.items()})
+    return ({k: np.asarray(v.numpy()) for k, v in out.items()},
+            model.flat_actor.flat.detach().cpu().numpy() - start, updater)
+
+
+def assert_steps_agree(got, want, what=''):
+    """The tolerances test_trpo_update_matches_reference grants the stock path against the reference."""
+    (out_a, step_a), (out_b, step_b) = got, want
+    print('STEP', what, out_a, out_b, np.abs(step_a - step_b).max(), np.abs(step_b).max())
+    assert int(out_a['backtrack_steps']) == int(out_b['backtrack_steps'])
+    for key in ('loss', 'kl'):
+        np.testing.assert_allclose(out_a[key], out_b[key], rtol=2e-4, atol=1e-6, err_msg=key)
+    np.testing.assert_allclose(step_a, step_b, rtol=0, atol=2e-5 + 2e-3 * np.abs(step_b).max())
+
+
+@pytest.mark.parametrize('adv_scale,steps', [(1.0, 1), (50.0, 1), (4000.0, 3)])
+def test_whole_step_matches_the_stock_path(monkeypatch, adv_scale, steps):
+    """Seed 5 at (17, 6, 2048), checked on the CPU with oracle/torch_port.TorchTRPO (float32, threshold 0.01,
+    start_loss = 0 to rounding: the advantages are standardised and the ratios start at 1):
+      advantages x1:    trial 1 accepted, kl = 0.005525 (44.8 % under the threshold), loss = -0.0847;
+      advantages x50:   trial 1 accepted, kl = 0.005527 (44.7 % under), loss = -4.237 — scaling the advantages
+                        alone rejects nothing: the step is scaled back to the trust region, only `eps` under the
+                        square root of the step length sees the scale;
+      advantages x4000: there `eps` lengthens the step: trial 1 REJECTED with kl = 0.019253 (92.5 % over),
+                        trial 2 (0.8) rejected with kl = 0.012408 (24.1 % over), trial 3 (0.64) accepted with
+                        kl = 0.007973 (20.3 % under), loss = -413.8
+    — no accept / reject decision is within 2 % of its threshold, and every loss is far from start_loss."""
+    hip = run_step(monkeypatch, '1', STEP_SEED, adv_scale)
+    stock = run_step(monkeypatch, '0', STEP_SEED, adv_scale)
+    assert_steps_agree(hip[:2], stock[:2], f'x{adv_scale}')
+    assert int(stock[0]['backtrack_steps']) == steps
+    assert np.abs(stock[1]).max() > 0
+
+
+# ------------------------------------------------------------------------ 5. the reference's golden update
+
+@pytest.mark.parametrize('switch', ['1', '0'])
+def test_golden_update_on_either_path(golden, monkeypatch, switch):
+    """The assertions of test_gpu_parity.test_trpo_update_matches_reference, with the switch either way."""
+    import tonic_amd
+    import tonic_amd.torch as tt
+    from tonic_amd.environments import Box
+    from tonic_amd.torch import agents as agents_module
+    monkeypatch.setenv('TONIC_AMD_TRPO_HIP', switch)
+    g = golden('trpo_small')
+    O, A, W, steps, seed, iterations, updates = (int(x) for x in g['cfg'])
+    agent = tt.agents.TRPO(replay=tonic_amd.replays.Segment(size=steps, batch_iterations=iterations))
+    agent.initialize(Box(-np.inf, np.inf, (O,)), Box(-1, 1, (A,)), seed=seed)
+    assert agent.actor_updater.hip is (switch == '1')
+    records = {}
+    monkeypatch.setattr(agents_module.logger, 'store',
+                        lambda key, value, stats=False: records.setdefault(key, []).append(np.asarray(value)))
+    monkeypatch.setattr(agent.model.observation_normalizer, 'update', lambda: None)
+    for u in range(updates):
+        state = {k[len(f'pre{u}/'):]: torch.as_tensor(g[k]) for k in g.files if k.startswith(f'pre{u}/')}
+        if u == 0:
+            agent.model.load_state_dict(state)
+        else:
+            for key in ('observation_normalizer._mean', 'observation_normalizer._std'):
+                dict(agent.model.state_dict())[key].copy_(state[key])
+        before = {k: v.detach().cpu().numpy().copy() for k, v in agent.model.state_dict().items()}
+        agent.replay.index = 0
+        for t in range(agent.replay.max_size):
+            row = {k: dev(g[f'u{u}/segment/{k}'][t]) for k in (
+                'observations', 'actions', 'next_observations', 'rewards', 'resets', 'terminations', 'log_probs')}
+            agent.replay.store(normalizer=None, **row)
+        records.clear()
+        agent._update()
+        for key in ('loss', 'kl'):
+            np.testing.assert_allclose(records['actor/' + key][0], g[f'u{u}/info/actor/{key}'][0],
+                                       rtol=2e-4, atol=1e-6, err_msg=key)
+        assert int(records['actor/backtrack_steps'][0]) == int(g[f'u{u}/info/actor/backtrack_steps'][0])
+        np.testing.assert_allclose(np.array(records['critic/loss']), g[f'u{u}/info/critic/loss'],
+                                   rtol=1e-5, atol=1e-5)
+        after = agent.model.state_dict()
+        for key, start in before.items():
+            if 'normalizer' in key:
+                continue
+            got = after[key].detach().cpu().numpy() - start
+            want = g[f'post{u}/' + key] - start
+            np.testing.assert_allclose(got, want, rtol=0, atol=2e-5 + 2e-3 * np.abs(want).max(),
+                                       err_msg=f'update {u}: {key}')
+
+
+# ------------------------------------------------------------------------ 6. the path is really taken
+
+def _updater(torso=None, optimizer=None):
+    from tonic_amd.environments import Box
+    from tonic_amd.torch import agents, models, updaters
+    torch.manual_seed(3)
+    model = agents.default_model()
+    if torso is not None:
+        model.actor.torso = models.MLP(*torso)
+    model.initialize(Box(-np.inf, np.inf, (17,)), Box(-1, 1, (6,)))
+    model.pack('cuda')
+    updater = updaters.TrustRegionPolicyGradient(optimizer=optimizer)
+    updater.initialize(model)
+    return updater
+
+
+def _no_autograd(monkeypatch):
+    def refuse(*args, **kwargs):
+        raise AssertionError('torch.autograd.grad on the HIP path')
+    monkeypatch.setattr(torch.autograd, 'grad', refuse)
+
+
+def _small_batch():
+    _, batch = step_problem(9, 1.0, n=256)
+    return {k: dev(v) for k, v in batch.items()}
+
+
+def test_the_default_model_takes_the_hip_path(monkeypatch):
+    monkeypatch.delenv('TONIC_AMD_TRPO_HIP', raising=False)
+    updater = _updater()
+    assert updater.hip is True
+    batch = _small_batch()
+    _no_autograd(monkeypatch)
+    out = updater(**batch)
+    assert int(out['backtrack_steps'].numpy()) >= 1 and np.isfinite(out['kl'].numpy())
+    relu = _updater(((32, 16), torch.nn.ReLU))
+    assert relu.hip is True
+    relu(**batch)
+
+
+def test_the_stock_path_is_kept_where_the_kernels_do_not_serve(monkeypatch):
+    monkeypatch.delenv('TONIC_AMD_TRPO_HIP', raising=False)
+    batch = _small_batch()
+    sigmoid, default = _updater(((64, 64), torch.nn.Sigmoid)), _updater()
+    assert sigmoid.hip is False and default.hip is True
+    with torch.no_grad():
+        behaviour = default.model.actor(batch['observations'])
+        locs, scales = behaviour.loc.clone(), behaviour.stddev.clone()
+    monkeypatch.setenv('TONIC_AMD_TRPO_HIP', '0')
+    switched = _updater()
+    assert switched.hip is False
+    _no_autograd(monkeypatch)
+    with pytest.raises(AssertionError, match='autograd'):
+        sigmoid(**batch)
+    with pytest.raises(AssertionError, match='autograd'):
+        default(**batch, locs=locs, scales=scales)
+    with pytest.raises(AssertionError, match='autograd'):
+        switched(**batch)
+
+
+def test_the_library_exports_the_entries(lib):
+    for name in ('tonic_trpo_workspace_bytes', 'tonic_trpo_prepare', 'tonic_trpo_loss_grad',
+                 'tonic_trpo_fisher_vector', 'tonic_trpo_evaluate'):
+        assert hasattr(lib, name)
+    two, five = (ctypes.c_int32 * 2)(64, 64), (ctypes.c_int32 * 5)(64, 64, 64, 64, 64)
+    assert lib.tonic_trpo_workspace_bytes(100, 384, 32, 2, two) > 0
+    assert lib.tonic_trpo_workspace_bytes(100, 385, 6, 2, two) == -1
+    assert lib.tonic_trpo_workspace_bytes(100, 17, 33, 2, two) == -1
+    assert lib.tonic_trpo_workspace_bytes(100, 17, 6, 5, five) == -1
+    assert lib.tonic_trpo_workspace_bytes(0, 17, 6, 2, two) == -1
+    # arguments are validated before anything is launched: a workspace that is too small is an error
+    p = problem(17, 6, 63, 'default')
+    e = Entries(lib, p)
+    assert lib.tonic_trpo_prepare(*e.torso, e.theta.data_ptr(), e.x.data_ptr(), *e.shape, None, None,
+                                  e.ws.data_ptr(), 16, None) != 0
+    assert lib.tonic_trpo_prepare(*e.torso, None, e.x.data_ptr(), *e.shape, None, None, *e.scratch) != 0
+
+
+# ------------------------------------------------------------------------ 7. edges
+
+def test_all_zero_advantages_return_the_zero_dict(monkeypatch):
+    monkeypatch.delenv('TONIC_AMD_TRPO_HIP', raising=False)
+    updater, batch = _updater(), _small_batch()
+    start = updater.model.flat_actor.flat.clone()
+    out = updater(**dict(batch, advantages=torch.zeros_like(batch['advantages'])))
+    assert float(out['loss']) == 0 and float(out['kl']) == 0 and int(out['backtrack_steps']) == 0
+    assert torch.equal(start, updater.model.flat_actor.flat)
+
+
+def test_a_zero_gradient_returns_zeros(lib, monkeypatch):
+    """Actions at the locations (no gradient through mu) and scales clamped at scale_max (none through
+    log_scale): the gradient is exactly zero, optimizers.py:55-56, 87-91."""
+    monkeypatch.delenv('TONIC_AMD_TRPO_HIP', raising=False)
+    updater, batch = _updater(), _small_batch()
+    n = batch['observations'].shape[0]
+    with torch.no_grad():
+        updater.model.actor.head.log_scale.fill_(5.0)
+    locs = torch.zeros(n, 6, device='cuda')
+    ws = updater._hip_workspace_for(n)
+    assert lib.tonic_trpo_prepare(*updater.hip_torso, updater.model.flat_actor.flat.data_ptr(),
+                                  batch['observations'].data_ptr(), n, 17, 6, locs.data_ptr(), None, ws.data_ptr(),
+                                  ws.numel(), None) == 0
+    start = updater.model.flat_actor.flat.clone()
+    out = updater(**dict(batch, actions=locs))
+    assert float(out['loss']) == 0 and float(out['kl']) == 0 and int(out['backtrack_steps']) == 0
+    assert torch.equal(start, updater.model.flat_actor.flat)
+
+
+def test_single_trial_and_no_damping(monkeypatch):
+    from tonic_amd.torch.updaters import ConjugateGradient
+    monkeypatch.delenv('TONIC_AMD_TRPO_HIP', raising=False)
+    batch = _small_batch()
+    # backtrack_steps=None: the single full trial; optimize returns (constraint, loss) as the reference does
+    updater = _updater(optimizer=ConjugateGradient(backtrack_steps=None))
+    start = updater.model.flat_actor.flat.clone()
+    out = updater._hip_optimize(batch['observations'], batch['actions'], batch['log_probs'], batch['advantages'])
+    assert len(out) == 2 and np.isfinite(float(out[0])) and float(out[0]) > 0
+    assert not torch.equal(start, updater.model.flat_actor.flat)
+    out, step, _ = run_step(monkeypatch, '1', 5, 1.0, optimizer=ConjugateGradient(damping_coefficient=0),
+                            entropy_coeff=0.01)
+    assert int(out['backtrack_steps']) >= 1 and np.isfinite(step).all() and np.isfinite(out['kl'])
+
+
+# ------------------------------------------------------------------------ 8. two ranks
+
+def test_two_ranks_equal_one(tmp_path):
+    """gloo on one device: the HIP step on two half-batches against the one-rank step on the whole batch."""
+    from test_gpu_multirank import launch
+    one, two = str(tmp_path / 'one.npz'), str(tmp_path / 'two.npz')
+    launch(1, one, 29911, command=(WORKER,))
+    launch(2, two, 29912, command=(WORKER,))
+    a, b = np.load(one), np.load(two)
+    assert int(a['hip']) == 1 and int(b['hip']) == 1
+    assert_steps_agree(({k: b[k] for k in ('loss', 'kl', 'backtrack_steps')}, b['step']),
+                       ({k: a[k] for k in ('loss', 'kl', 'backtrack_steps')}, a['step']), 'two ranks')

@@ -80,6 +80,15 @@ SIGNATURES = {
                                    [c_i64, c_i32, c_i32, c_f64, c_f64, c_vp, c_vp, c_i64, c_vp]),
     'tonic_value_regression_grad_torso': (ctypes.c_int, [c_i32, c_vp, c_i32] + [c_vp] * 3 + [c_f64] +
                                           [c_vp] * 3 + [c_i64, c_i32, c_vp, c_i64, c_vp]),
+    'tonic_trpo_workspace_bytes': (c_i64, [c_i64, c_i32, c_i32, c_i32, c_vp]),
+    'tonic_trpo_prepare': (ctypes.c_int, [c_i32, c_vp, c_i32] + [c_vp] * 2 + [c_i64, c_i32, c_i32] +
+                           [c_vp] * 3 + [c_i64, c_vp]),
+    'tonic_trpo_loss_grad': (ctypes.c_int, [c_i32, c_vp, c_i32] + [c_vp] * 6 + [c_i64, c_i32, c_i32, c_f64,
+                                                                              c_vp, c_i64, c_vp]),
+    'tonic_trpo_fisher_vector': (ctypes.c_int, [c_i32, c_vp, c_i32] + [c_vp] * 4 + [c_i64, c_i32, c_i32,
+                                                                                  c_vp, c_i64, c_vp]),
+    'tonic_trpo_evaluate': (ctypes.c_int, [c_i32, c_vp, c_i32] + [c_vp] * 5 + [c_i64, c_i32, c_i32, c_f64,
+                                                                             c_vp, c_vp, c_i64, c_vp]),
     'tonic_value_forward_ranged': (ctypes.c_int, [c_vp] * 3 + [c_f64] + [c_vp] * 2 + [c_i64, c_i32] +
                                    [c_vp] * 3),
     'tonic_value_forward_wide_ranged': (ctypes.c_int, [c_vp] * 3 + [c_f64] + [c_vp] * 2 +
@@ -187,7 +196,7 @@ SIGNATURES = {
 }
 
 
-ABI_VERSION = 13       # include/tonic_hip.h: tonic_abi_version()
+ABI_VERSION = 14       # include/tonic_hip.h: tonic_abi_version()
 
 
 class TonicHipError(RuntimeError):

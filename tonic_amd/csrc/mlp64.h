@@ -80,7 +80,7 @@ constexpr int kMaxTorsoLayers = 4;
 struct Torso {
   int layers;
   int size[kMaxTorsoLayers];
-  int act;                                   // 1 Tanh, 2 ReLU
+  int act;                                   // 1 Tanh, 2 ReLU (what callers may pass; wide_activation's 3 is internal)
   static Torso standard() { return Torso{2, {64, 64, 0, 0}, 1}; }
 };
 bool torso_supported(const Torso& t);

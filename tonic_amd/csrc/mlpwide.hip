@@ -21,6 +21,7 @@
 //   ppo_loss_kernel, value_loss_kernel   the element-wise losses and their gradients with respect
 //                  to the head outputs (tonic/torch/updaters/actors.py:81-108, critics.py:18-24).
 //   sample_kernel  actions = loc + sigma * eps, log-probabilities (a2c.py:75-85).
+//   trpo_body.h    (included at the end) TRPO's Fisher-vector products and line-search trials on these kernels.
 #include "mlp64.h"
 #include "collect16.h"
 
@@ -44,12 +45,13 @@ struct DenseArgs {
   int dkind;                               //   1 tanh: 1 - D^2;  2 ReLU: D > 0
   float* Y; int ldy;
   int64_t N;
-  int K, NOUT, act;                        // act: 0 none, 1 tanh, 2 ReLU
+  int K, NOUT, act;                        // act: 0 none, 1 tanh, 2 ReLU, 3 libm tanh (internal: TRPO's heads)
   const int32_t* skip;
 };
 
+// (3: libm's tanh — TRPO's heads, whose KL is a DIFFERENCE of two forward passes' locations)
 __device__ __forceinline__ float wide_activation(float z, int act) {
-  return act == 1 ? tanh_fast(z) : act == 2 ? fmaxf(z, 0.f) : z;
+  return act == 1 ? tanh_fast(z) : act == 2 ? fmaxf(z, 0.f) : act == 3 ? tanhf(z) : z;
 }
 __device__ __forceinline__ float wide_derivative(float v, float d, int dkind) {
   return dkind == 2 ? (d > 0.f ? v : 0.f) : v * (1.f - d * d);
@@ -732,6 +734,7 @@ struct WideLayout {        // offsets (floats) inside the flat parameter block, 
   Torso t;
   int W[kMaxTorsoLayers], b[kMaxTorsoLayers], ls, Wh, bh, P;     // parameters() order (models/utils.py:12-23)
   int blocks; int64_t slab, pstride;
+  int head_act = 1;                              // the actor head's activation code (wide_activation)
   int64_t off_h[kMaxTorsoLayers], off_dz[kMaxTorsoLayers], off_out, off_dzh, off_image, bytes;
   WideLayout(int64_t n, int O, int A, bool actor, const Torso& torso) : t(torso) {
     int at = 0, in = O;
@@ -773,7 +776,7 @@ int wide_forward(const float* params, const WideLayout& L, const float* obs, int
   }
   d.W = params + L.Wh; d.ldw = d.K; d.bias = params + L.bh; d.NOUT = actor ? A : 1;
   d.Y = reinterpret_cast<float*>(ws + L.off_out); d.ldy = kWideLd;
-  d.act = actor ? 1 : 0;                         // loc_activation Tanh (actors.py:44-48) / none (critics.py:11)
+  d.act = actor ? L.head_act : 0;                // loc_activation Tanh (actors.py:44-48) / none (critics.py:11)
   return launch_dense(d, st);
 }
 
@@ -1075,3 +1078,6 @@ int wide_value(const MlpArgs& a, void* d_workspace, int64_t workspace_bytes, hip
 }
 
 }  // namespace tonic
+
+// TRPO's actor step on this file's kernels: the tonic_trpo_* entries
+#include "trpo_body.h"

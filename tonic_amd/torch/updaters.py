@@ -468,14 +468,78 @@ class ConjugateGradient:
                 i = self.backtrack_steps
         return constraint.cpu(), loss.cpu(), torch.as_tensor(i + 1, dtype=torch.int32)
 
+    def optimize_flat(self, parameters, loss_gradient, fisher_vector, evaluate):
+        """The same step — same `eps`, recurrences, step length, backtracking rule and `trial(0)` fallback as
+        `optimize`, line for line — for a caller that evaluates the batch itself (TrustRegionPolicyGradient's
+        HIP kernels) on ONE flat parameter vector instead of a list of views:
+
+            loss_gradient()   -> (gradient [P], loss), batch means over all ranks, at `parameters`
+            fisher_vector(x)  -> H x [P] without the damping term, a batch mean over all ranks
+            evaluate()        -> tensor {constraint, loss} at what `parameters` holds now
+
+        `parameters` is moved in place to the accepted trial, as `optimize` leaves its variables."""
+        eps = 1e-8                                              # optimizers.py:5
+
+        def hessian_vector(x):                                  # optimizers.py:36-48
+            second = fisher_vector(x)
+            if self.damping_coefficient > 0:
+                second = second + self.damping_coefficient * x
+            return second
+
+        def trial(scale):                                       # optimizers.py:68-74
+            parameters.copy_(start - alpha * direction * scale)
+            both = evaluate()
+            return both[0], both[1]
+
+        start = parameters.detach().clone()
+        gradient, loss = loss_gradient()
+        start_loss = float(loss)
+        zero = torch.zeros((), dtype=torch.float32)
+        residual_dot = gradient.dot(gradient)
+        if float(residual_dot) == 0:                            # optimizers.py:55-56, 87-91
+            return zero, zero, torch.as_tensor(0, dtype=torch.int32)
+        direction = torch.zeros_like(gradient)
+        residual, search = gradient.clone(), gradient.clone()
+        for _ in range(self.conjugate_gradient_steps):          # optimizers.py:58-65
+            z = hessian_vector(search)
+            step = residual_dot / (search.dot(z) + eps)
+            direction += step * search
+            residual -= step * z
+            new_dot = residual.dot(residual)
+            search = residual + (new_dot / residual_dot) * search
+            residual_dot = new_dot
+        alpha = torch.sqrt(2 * self.constraint_threshold /
+                           direction.dot(hessian_vector(direction)) + eps)      # optimizers.py:93-94
+        if self.backtrack_steps is None or self.backtrack_coefficient is None:
+            constraint, loss = trial(1)
+            return constraint.cpu(), loss.cpu()
+        for i in range(self.backtrack_steps):                   # optimizers.py:101-113
+            constraint, loss = trial(self.backtrack_coefficient ** i)
+            if float(constraint) <= self.constraint_threshold and float(loss) <= start_loss:
+                break
+            if i == self.backtrack_steps - 1:
+                constraint, loss = trial(0)
+                i = self.backtrack_steps
+        return constraint.cpu(), loss.cpu(), torch.as_tensor(i + 1, dtype=torch.int32)
+
 
 class TrustRegionPolicyGradient:
-    """actors.py:115-156 (TRPO).  The one updater of this package that is not a fused HIP kernel:
-    SURVEY.md §8(f4) scopes A2C / TRPO as the stock-torch path — the loss, the KL and the
-    Fisher-vector products are PyTorch autograd over `model.actor`, whose parameters ARE views of
-    the flat HBM buffer the act kernels read, on the HBM-resident Segment (no host copy of the
-    batch).  `locs` / `scales` of the behaviour policy may be omitted: the parameters have not
-    moved since the rollout, so the actor itself reproduces them."""
+    """actors.py:115-156 (TRPO): the truncated natural-gradient step of `ConjugateGradient` on the
+    HBM-resident Segment.  `locs` / `scales` of the behaviour policy may be omitted: the parameters have not
+    moved since the rollout, so the actor itself reproduces them.
+
+    HIP path (csrc/trpo_body.h, the tonic_trpo_* entries; `self.hip` after `initialize`): the loss gradient,
+    the Fisher-vector products and the line-search trials are kernels over the batch.  The parameters do
+    not move during the conjugate-gradient loop, so ONE forward pass per update leaves the activations in
+    the workspace and every product reuses them; with the behaviour policy this network's own output the
+    Hessian of the KL is the Gauss-Newton product J^T M J v the kernels form.  Taken for an
+    `MLP(sizes, activation)` torso the layer-by-layer kernels serve (the default one included), a
+    `DetachedScaleGaussianPolicyHead` as the reference builds it (Tanh locations, Normal, scales clamped to
+    [1e-4, 1]) and a `ConjugateGradient` optimizer, when the behaviour policy is not passed in.
+
+    Stock path, exactly as before: every other network or optimizer, explicit `locs` / `scales` (Gauss-Newton
+    is then not the Hessian), or TONIC_AMD_TRPO_HIP=0 — the loss, the KL and the products are PyTorch autograd
+    over `model.actor`, whose parameters ARE views of the flat HBM buffer the act kernels read."""
 
     def __init__(self, optimizer=None, entropy_coeff=0):
         self.optimizer = optimizer or ConjugateGradient()
@@ -485,6 +549,50 @@ class TrustRegionPolicyGradient:
         self.model = model
         self.variables = list(model.flat_actor.params)
         self.world_size = 1
+        self.hip_workspace = None
+        served = self._served_torso(model)                      # decided once; None: the stock path
+        self.hip, self.hip_torso = served is not None, None
+        if self.hip:
+            self.lib = _lib.load()
+            self.hip_torso, self.observation_size, self.action_size = served
+
+    def _served_torso(self, model):
+        """((layers, sizes, activation) for the tonic_trpo_* entries, O, A), or None."""
+        import ctypes
+        from tonic_amd.torch import models
+        if os.environ.get('TONIC_AMD_TRPO_HIP', '1') == '0':
+            return None
+        actor, flat = model.actor, model.flat_actor
+        torso, head = getattr(actor, 'torso', None), getattr(actor, 'head', None)
+        if not isinstance(self.optimizer, ConjugateGradient) or not flat.flat.is_cuda:
+            return None
+        if type(getattr(actor, 'encoder', None)) is not models.ObservationEncoder or \
+                actor.encoder.observation_normalizer or not isinstance(torso, models.MLP):
+            return None
+        if type(head) is not models.DetachedScaleGaussianPolicyHead or head.loc_activation is not torch.nn.Tanh \
+                or head.loc_fn is not None or head.distribution is not torch.distributions.normal.Normal \
+                or (head.scale_min, head.scale_max) != (1e-4, 1.):
+            return None                      # (the kernels clamp the scales to the reference's defaults, actors.py:39-40)
+        if fused_ppo_torso(torso):
+            served = 2, (ctypes.c_int32 * 2)(64, 64), 1
+        else:
+            served = hip_ppo_torso(torso)
+            if served is None:
+                return None
+        lib = _lib.load()
+        O, A = torso.model[0].in_features, head.log_scale.shape[1]
+        if lib.tonic_ppo_torso_param_count(O, A, 1, served[0], served[1]) != flat.count:
+            return None
+        if lib.tonic_trpo_workspace_bytes(1, O, A, served[0], served[1]) < 0:
+            return None
+        return served, O, A
+
+    def _hip_workspace_for(self, n):
+        need = self.lib.tonic_trpo_workspace_bytes(n, self.observation_size, self.action_size,
+                                                   self.hip_torso[0], self.hip_torso[1])
+        if self.hip_workspace is None or self.hip_workspace.numel() < need:
+            self.hip_workspace = torch.empty(need, dtype=torch.uint8, device=self.model.flat_actor.flat.device)
+        return self.hip_workspace
 
     def __call__(self, observations, actions, log_probs, advantages, locs=None, scales=None):
         from tonic_amd import parallel
@@ -492,7 +600,10 @@ class TrustRegionPolicyGradient:
         observations, actions, log_probs, advantages = (
             torch.as_tensor(v, dtype=torch.float32, device=device)
             for v in (observations, actions, log_probs, advantages))
-        if locs is None or scales is None:
+        hip = self.hip and locs is None and scales is None
+        if hip:
+            pass                                               # (tonic_trpo_prepare forms them)
+        elif locs is None or scales is None:
             with torch.no_grad():
                 behaviour = self.model.actor(observations)
                 locs, scales = behaviour.loc, behaviour.stddev
@@ -505,11 +616,64 @@ class TrustRegionPolicyGradient:
         if bool(nothing):
             zero = torch.zeros((), dtype=torch.float32)
             return dict(loss=zero, kl=zero, backtrack_steps=torch.as_tensor(0, dtype=torch.int32))
+        if hip:
+            kl, loss, steps = self._hip_optimize(observations, actions, log_probs, advantages)
+            return dict(loss=loss, kl=kl, backtrack_steps=steps)
         kl, loss, steps = self.optimizer.optimize(
             loss_function=lambda: self._loss(observations, actions, log_probs, advantages),
             constraint_function=lambda: self._kl(observations, locs, scales),
             variables=self.variables)
         return dict(loss=loss, kl=kl, backtrack_steps=steps)
+
+    def _hip_optimize(self, observations, actions, log_probs, advantages):
+        """`ConjugateGradient.optimize_flat` over the tonic_trpo_* entries.  The entries return SUMS over this
+        rank's rows; they become batch means here (/ n_local; the KL and its products / (n_local * A)) and
+        means over the ranks through the same `across` as the stock path."""
+        from tonic_amd import parallel
+        lib, p, stream = self.lib, _lib.ptr, _lib.current_stream()
+        flat = self.model.flat_actor.flat
+        P, O, A = flat.numel(), self.observation_size, self.action_size
+        observations, actions, log_probs, advantages = (
+            v.contiguous() for v in (observations, actions, log_probs, advantages))
+        n = observations.shape[0]
+        ws = self._hip_workspace_for(n)
+        shape, scratch = (n, O, A), (p(ws), ws.numel(), stream)
+        batch = (p(observations), p(actions), p(advantages), p(log_probs))
+        coeff = float(self.entropy_coeff)
+        world = parallel.world_size() if parallel.exchanging() else 1
+
+        def across(tensor):
+            if world > 1:
+                torch.distributed.all_reduce(tensor)
+                tensor /= world
+            return tensor
+
+        _lib.check(lib.tonic_trpo_prepare(*self.hip_torso, p(flat), p(observations), *shape, None, None,
+                                          *scratch), 'tonic_trpo_prepare')
+
+        def loss_gradient():
+            sums = torch.empty(P + INFO_WIDTH, dtype=torch.float32, device=flat.device)
+            _lib.check(lib.tonic_trpo_loss_grad(*self.hip_torso, p(flat), *batch, p(sums), *shape, coeff,
+                                                *scratch), 'tonic_trpo_loss_grad')
+            loss = sums[P] / n
+            if coeff != 0:
+                loss = loss - coeff * (sums[P + 3] / n)         # actors.py:148-149 (slot 3: n * entropy)
+            return across(sums[:P] / n), across(loss.clone())
+
+        def fisher_vector(x):
+            x = x.contiguous()
+            sums = torch.empty(P + INFO_WIDTH, dtype=torch.float32, device=flat.device)
+            _lib.check(lib.tonic_trpo_fisher_vector(*self.hip_torso, p(flat), p(observations), p(x), p(sums),
+                                                    *shape, *scratch), 'tonic_trpo_fisher_vector')
+            return across(sums[:P] / (n * A))
+
+        def evaluate():
+            out = torch.empty(2, dtype=torch.float32, device=flat.device)
+            _lib.check(lib.tonic_trpo_evaluate(*self.hip_torso, p(flat), *batch, *shape, coeff, p(out),
+                                               *scratch), 'tonic_trpo_evaluate')
+            return across(torch.stack([out[1] / (n * A), out[0] / n]))
+
+        return self.optimizer.optimize_flat(flat, loss_gradient, fisher_vector, evaluate)
 
     def _loss(self, observations, actions, old_log_probs, advantages):        # actors.py:142-150
         distributions = self.model.actor(observations)
