@@ -361,7 +361,12 @@ def value_regression_grads(params, mean, std, observations, returns, clip=None):
 class AdamPort:
     """``torch.optim.Adam`` single-tensor CPU path —
     ``torch/optim/adam.py:395-547`` (betas 0.9/0.999, eps 1e-8, no weight decay),
-    as constructed at ``tonic/torch/updaters/actors.py:58-59`` / ``critics.py:9-10``."""
+    as constructed at ``tonic/torch/updaters/actors.py:58-59`` / ``critics.py:9-10``.
+
+    The goldens were made with this form and it stays as it is.  It is NOT the expression of the HIP kernels in
+    one place: the second moment here adds ``(w2 * g) * g`` (torch's ``addcmul_`` order; bit-identical with torch's
+    CPU ``exp_avg_sq`` on the first step), the kernels add ``w2 * (g * g)`` — one float32 ulp of `v` in about a
+    third of the elements.  ``adam_statement`` below is the kernels' expression."""
 
     def __init__(self, params, lr, betas=(0.9, 0.999), eps=1e-8):
         self.lr, self.betas, self.eps = lr, betas, eps
@@ -385,6 +390,84 @@ class AdamPort:
             self.exp_avg[i], self.exp_avg_sq[i] = m, v
             out.append(p)
         return out
+
+
+def adam_statement_constants(step, lr, betas=(0.9, 0.999), eps=1e-8):
+    """The float32 scalars of optimizer step `step` (1-based) as ``adam_kernel`` (csrc/optim.hip) forms them:
+    bias corrections and step size in float64 and only then rounded (``adam.py:530-536``,
+    ``updaters.adam_step_constants``), the weights ``1 - beta`` subtracted in float64, then rounded.
+    -> step_size, bias2_sqrt, w1, w2, beta2, eps (all float32)."""
+    beta1, beta2 = betas
+    bias1 = 1.0 - beta1 ** step
+    bias2 = 1.0 - beta2 ** step
+    return (F32(lr / bias1), F32(math.sqrt(bias2)), F32(1.0 - beta1), F32(1.0 - beta2), F32(beta2), F32(eps))
+
+
+def adam_statement(p, g_sum, m, v, step, grad_scale, lr, betas=(0.9, 0.999), eps=1e-8):
+    """THE float32 expression the HIP optimizer kernels are: ``adam_kernel`` (csrc/optim.hip) and
+    ``adam_element`` (csrc/gemm16.hip), operation by operation, in the kernels' order, every operation rounded to
+    float32 once (no FMA: the library is built with -ffp-contract=off; divide and sqrt are correctly rounded).
+    `g_sum` holds gradient SUMS, `grad_scale` turns them into means, `step` is the 1-based step being taken
+    (``state[0] + 1``).  -> new p, m, v (float32).
+
+        g     = g_sum * F32(grad_scale)
+        m     = m + w1 * (g - m)                       w1 = F32(1 - beta1)
+        v     = v * F32(beta2) + w2 * (g * g)          w2 = F32(1 - beta2)
+        denom = sqrt(v) / bias2_sqrt + F32(eps)
+        p     = p - step_size * (m / denom)
+
+    This differs from ``AdamPort`` / torch's ``addcmul_`` in ONE place: the second moment adds ``w2 * (g * g)``
+    where torch's single-tensor CPU path forms ``(w2 * g) * g`` — one float32 ulp of `v` in about a third of the
+    elements, at most one ulp of a parameter after several steps (tests/test_oracle_golden.py measures both)."""
+    step_size, bias2_sqrt, w1, w2, beta2, eps = adam_statement_constants(step, lr, betas, eps)
+    p, g_sum, m, v = (np.asarray(a, F32) for a in (p, g_sum, m, v))
+    g = g_sum * F32(grad_scale)
+    m = m + w1 * (g - m)
+    v = v * beta2 + w2 * (g * g)
+    denom = np.sqrt(v) / bias2_sqrt + eps
+    p = p - step_size * (m / denom)
+    assert p.dtype == F32 and m.dtype == F32 and v.dtype == F32
+    return p, m, v
+
+
+def adam_f64(p, g_sum, m, v, step, grad_scale, lr, betas=(0.9, 0.999), eps=1e-8):
+    """The update of ``adam_statement`` evaluated in float64 from the same inputs, with the statement's float32
+    scalars (like ``lambda_returns_f64``: the difference between the two is the rounding of the element-wise
+    operations alone).  `p`, `m`, `v` may be float32 (a first step) or the float64 results of an earlier call.
+    -> new p, m, v (float64)."""
+    step_size, bias2_sqrt, w1, w2, beta2, eps = (np.float64(c) for c in
+                                                 adam_statement_constants(step, lr, betas, eps))
+    p, m, v = (np.asarray(a, np.float64) for a in (p, m, v))
+    g = np.asarray(g_sum, F32).astype(np.float64) * np.float64(F32(grad_scale))
+    m = m + w1 * (g - m)
+    v = v * beta2 + w2 * (g * g)
+    denom = np.sqrt(v) / bias2_sqrt + eps
+    return p - step_size * (m / denom), m, v
+
+
+def adam_f64_unit(p64, lr):
+    """The unit the statement's distance from ``adam_f64`` is counted in, per element: one float32 ulp of the
+    parameter (its final rounding, once per step) plus one float32 ulp of the largest step Adam takes,
+    ``lr * 2**-23`` (the rounding of the moments and of the quotient; what is left of the error where the
+    parameter is near zero and its own ulp vanishes)."""
+    return np.spacing(np.abs(np.asarray(p64, np.float64)).astype(F32)).astype(np.float64) + lr * 2.0 ** -23
+
+
+# Largest |adam_statement - adam_f64| / adam_f64_unit over 7 steps, measured on the CPU
+# (test_adam_statement_against_torch_and_float64: 2.9 from zero state, 8.0 from step 1000 with warm moments);
+# the GPU tests hold the kernels to TWICE this figure.
+ADAM_F64_UNITS = 8.0
+
+
+def clip_grad_norm_f64(sums, grad_scale, max_norm):
+    """``tonic_clip_grad_norm`` in float64 on a flat float32 block of gradient SUMS: the norm of the MEAN gradient
+    ``sqrt(sum g^2) * grad_scale`` with an exactly rounded sum (a float32 square is exact in float64, ``math.fsum``
+    adds without error), the factor ``min(1, max_norm / (norm + 1e-6))`` (clip_grad.py) and the scaled sums.
+    -> norm, coef (Python floats), scaled (float64 array)."""
+    g = np.asarray(sums, F32).astype(np.float64).reshape(-1)
+    norm = math.sqrt(math.fsum(g * g)) * float(grad_scale)
+    coef = min(1.0, float(max_norm) / (norm + 1e-6))
+    return norm, coef, g * coef
 
 
 def polyak(targets, onlines, coeff=0.005):

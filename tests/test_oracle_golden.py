@@ -56,6 +56,112 @@ def test_lambda_returns_f64_reference(golden):
                           port.lambda_returns(nv, rew, rst, term, 1.0, 1.0).astype(np.float64))
 
 
+ADAM_LR, ADAM_GRAD_SCALE = 3e-4, 1.0 / 37
+
+
+def adam_case(n, steps, seed, warm=False):
+    """Inputs of the optimizer tests here and in test_gpu_optim.py -> p, m, v, [gradient SUMS of each step].
+    Parameters ~ N(0, 1); gradient means N(0, 1) x 10 ** U(-6, 1), drawn anew per step and element, with a block of
+    exact zeros [n/2, n/2 + n/5) in every step; `warm`: moments as a long run leaves them (m ~ 0.3 s N(0, 1),
+    v = (s U(0.5, 1.5)) ** 2 with s = 10 ** U(-6, 1) per element) instead of zeros."""
+    rng = np.random.RandomState([n % 65521, steps, seed, int(warm)])
+    p = rng.normal(size=n).astype(np.float32)
+    sums = []
+    for _ in range(steps):
+        g = (rng.normal(size=n) * 10 ** rng.uniform(-6, 1, size=n) / ADAM_GRAD_SCALE).astype(np.float32)
+        g[n // 2:n // 2 + n // 5] = 0.0
+        sums.append(g)
+    if warm:
+        s = 10 ** rng.uniform(-6, 1, size=n)
+        m = (rng.normal(size=n) * 0.3 * s).astype(np.float32)
+        v = np.square(s * rng.uniform(0.5, 1.5, size=n)).astype(np.float32)
+    else:
+        m, v = np.zeros(n, np.float32), np.zeros(n, np.float32)
+    return p, m, v, sums
+
+
+def test_adam_statement_against_torch_and_float64():
+    """`adam_statement` (the float32 expression of the HIP kernels) over 7 steps of 50 000 elements.
+
+    Against `adam_f64`: the largest distance in `adam_f64_unit`s (one ulp of the parameter + lr * 2**-23) is
+    MEASURED here and must not exceed `ADAM_F64_UNITS`, which the GPU tests double.  Measured (torch 2.10 / NumPy
+    2.2): from zero state 0.9 / 1.2 / 1.7 / 2.5 / 2.7 / 2.6 / 2.9 units after steps 1 .. 7, from step 1000 with warm
+    moments 1.6 / 2.5 / 4.1 / 7.0 / 5.1 / 8.0 / 8.0; the largest absolute error 7.9e-7 = 1.7 ulps of that parameter
+    = 2.6e-3 x lr.
+
+    Against torch.optim.Adam on the CPU: step 1 — `exp_avg` bit-identical, `exp_avg_sq` bit-identical for AdamPort
+    and within 2 ulps for the statement (measured: 13 771 elements differ); later torch's `lerp_` fuses
+    and matches neither (`exp_avg_sq`: the addend's ulp and one flipped rounding per step, so 2 ulps per step are
+    allowed; measured 3 after 7).  Parameters: each step can flip the parameter's
+    rounding (one ulp) and moves the update by a few ulps of lr, so the bound is 2 units per step; measured after
+    7 steps 3.1 units, 2.4e-7 at most (one ulp of a parameter >= 2; the bound is one ulp of the largest)."""
+    torch = pytest.importorskip('torch')
+    n, steps = 50_000, 7
+    worst_units = worst_abs = 0.0
+    for start, warm in ((0, False), (999, True)):
+        p, m, v, sums = adam_case(n, steps, 11, warm)
+        if not warm:
+            assert 4.0 < np.abs(p).max() < 8.0          # (the largest ulp: 4.8e-7)
+        p64, m64, v64 = p, m, v
+        for k in range(steps):
+            before = p
+            p, m, v = port.adam_statement(p, sums[k], m, v, start + k + 1, ADAM_GRAD_SCALE, ADAM_LR)
+            p64, m64, v64 = port.adam_f64(p64, sums[k], m64, v64, start + k + 1, ADAM_GRAD_SCALE, ADAM_LR)
+            assert p64.dtype == np.float64 and p.dtype == np.float32
+            err = np.abs(p - p64)
+            units = float((err / port.adam_f64_unit(p64, ADAM_LR)).max())
+            i = int(err.argmax())
+            print(f'adam_statement vs float64, start {start}, step {k + 1}: {units:.2f} units, largest error '
+                  f'{err[i]:.2e} = {err[i] / np.spacing(np.abs(np.float32(p64[i]))):.2f} ulps = '
+                  f'{err[i] / ADAM_LR:.2e} x lr')
+            worst_units, worst_abs = max(worst_units, units), max(worst_abs, float(err[i]))
+            zero = slice(n // 2, n // 2 + n // 5)
+            if not warm:     # m = v = 0 and denom = eps: a zero gradient leaves the parameter where it is
+                assert np.array_equal(p[zero], before[zero]) and not m[zero].any() and not v[zero].any()
+    assert worst_units <= port.ADAM_F64_UNITS, worst_units
+    assert worst_units >= 0.5 * port.ADAM_F64_UNITS, 'ADAM_F64_UNITS is a measurement: bring it down to it'
+    assert worst_abs <= 1e-6
+
+    p, m, v, sums = adam_case(n, steps, 11)
+    ref = [torch.nn.Parameter(torch.tensor(p))]
+    opt = torch.optim.Adam(ref, lr=ADAM_LR)
+    adam_port, ported = port.AdamPort([p], ADAM_LR), [p]
+    for k in range(steps):
+        g = sums[k] * np.float32(ADAM_GRAD_SCALE)
+        ref[0].grad = torch.tensor(g)
+        opt.step()
+        p, m, v = port.adam_statement(p, sums[k], m, v, k + 1, ADAM_GRAD_SCALE, ADAM_LR)
+        ported = adam_port.step(ported, [g])
+        state = opt.state[ref[0]]
+        t_m, t_v, t_p = state['exp_avg'].numpy(), state['exp_avg_sq'].numpy(), ref[0].detach().numpy()
+        if k == 0:
+            assert np.array_equal(m, t_m) and np.array_equal(adam_port.exp_avg_sq[0], t_v)
+            differ = int((v != t_v).sum())
+            print(f'step 1: exp_avg_sq of the statement differs from torch in {differ} of {n} elements')
+            assert 0 < differ and (np.abs(v - t_v) <= 2 * np.spacing(t_v)).all()
+        units = float((np.abs(p - t_p) / port.adam_f64_unit(t_p, ADAM_LR)).max())
+        print(f'adam_statement vs torch, step {k + 1}: {units:.2f} units, {np.abs(p - t_p).max():.2e}')
+        assert units <= 2 * (k + 1)
+        assert (np.abs(v - t_v) <= 2 * (k + 1) * np.spacing(t_v)).all()
+    assert np.abs(p - t_p).max() <= np.spacing(np.float32(4.0))      # one ulp of the largest parameters
+
+
+def test_clip_grad_norm_f64_reference():
+    """clip_grad_norm_f64 against the float32 port (torch's clip_grad_norm_) and on cases with exact answers."""
+    rng = np.random.RandomState(4)
+    sums = (rng.standard_normal(4099) * 1000).astype(np.float32)
+    for max_norm in (0.5, 4000.0):
+        norm, coef, scaled = port.clip_grad_norm_f64(sums, 1.0 / 64, max_norm)
+        (want,), total = port.clip_grad_norm([sums * np.float32(1.0 / 64)], max_norm)
+        assert abs(norm - total) <= 4e-6 * norm and scaled.dtype == np.float64
+        np.testing.assert_allclose(scaled * (1.0 / 64), want, rtol=4e-6, atol=0)
+        assert (coef == 1.0) == (max_norm == 4000.0)
+    norm, coef, scaled = port.clip_grad_norm_f64(np.array([3, 0, -4], np.float32), 0.5, 1.0)
+    assert norm == 2.5 and coef == 1.0 / (2.5 + 1e-6) and np.array_equal(scaled, np.array([3, 0, -4]) * coef)
+    norm, coef, scaled = port.clip_grad_norm_f64(np.zeros(5, np.float32), 1.0, 0.25)
+    assert norm == 0.0 and coef == 1.0 and not scaled.any()
+
+
 def test_meanstd_bit_exact(golden):
     g = golden('meanstd')
     norm = port.MeanStdPort((5,))

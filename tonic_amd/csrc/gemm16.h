@@ -55,7 +55,8 @@ constexpr int kGemmGroupMax = 4;
 // the group are the tensors of ONE network's flat gradient-sum block, so the offset of an output
 // element from `grads` also addresses its parameter, its Adam moments and its target copy.  The
 // workgroup that forms a tile of gradient sums applies torch.optim.Adam's step to the tile's
-// parameters right away (same expressions as adam_kernel in optim.hip -> same bits) and, with
+// parameters right away (the expressions of adam_kernel in optim.hip, i.e. numpy_port.adam_statement;
+// tests/test_gpu_offpolicy.py holds the two launches' results equal bit for bit) and, with
 // `target`, the polyak update of the same entries; the last workgroup to arrive bumps the step
 // counter and writes the logged statistics (adam_finalize).  Saves the optimizer launch and one
 // round trip of the gradients through HBM.  Single rank, no gradient clipping (both need the

@@ -222,7 +222,9 @@ __device__ __forceinline__ AdamConsts adam_consts(const AdamFold& f) {
   return c;
 }
 
-// One element: the gradient SUM just formed -> new parameter (moments updated in place).
+// One element: the gradient SUM just formed -> new parameter (moments updated in place).  The float32
+// expression of adam_kernel (optim.hip), stated operation by operation in oracle/numpy_port.py
+// (adam_statement); like it, one ulp of `v` away from torch's addcmul_ order.
 __device__ __forceinline__ float adam_element(float sum, float p, float& m, float& v,
                                               const AdamFold& f, const AdamConsts& c) {
   const float gr = sum * f.grad_scale;

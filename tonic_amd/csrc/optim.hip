@@ -3,7 +3,12 @@
 // Restates torch.optim.Adam's single-tensor CPU path (torch/optim/adam.py:395-547; betas
 // (0.9, 0.999), eps 1e-8, no weight decay / amsgrad) as constructed by
 // tonic/torch/updaters/actors.py:58-59 and critics.py:9-10, applied to ONE flat buffer per
-// network (28 B/param of HBM traffic: read p,g,m,v, write p,m,v), plus the tail of
+// network (28 B/param of HBM traffic: read p,g,m,v, write p,m,v).  WHICH float32 expression this is,
+// operation by operation, is oracle/numpy_port.py's adam_statement; tests/test_gpu_optim.py holds
+// adam_kernel to it bit for bit.  It is NOT bit-identical with torch's CPU Adam, and nothing unfused can
+// be: torch's lerp_ fuses from the second step on, and its addcmul_ forms (w2 * g) * g where this file
+// forms w2 * (g * g) — one ulp of exp_avg_sq in a third of the elements, at most one ulp of a parameter
+// after 7 steps.  The file also holds the tail of
 // ClippedRatio.__call__ (actors.py:101-112: loss/kl/entropy/clip_fraction/std/stop) and of
 // VRegression.__call__ (critics.py:28).  The optimizer step counter and the PPO early-stop
 // flag live on the device so the 80-iteration loop of ppo.py:33-46 needs no host sync.
@@ -141,6 +146,8 @@ __global__ __launch_bounds__(256) void adam_kernel(AdamPair pair) {
 }
 
 // ---- gradient-norm clipping: torch.nn.utils.clip_grad_norm_ on the flat gradient-sum block ----
+// Norm and factor are formed in float64 and rounded once (torch: float32 throughout): within one
+// float32 ulp of numpy_port.clip_grad_norm_f64, the scaled sums within two (tests/test_gpu_optim.py).
 // Pass 1: fixed-order partial sums of squares (float64) of a contiguous slice per workgroup.
 constexpr int kClipBlocks = 64;
 
@@ -176,10 +183,13 @@ __global__ __launch_bounds__(256) void clip_scale_kernel(float* sums, int64_t n,
   if (threadIdx.x == 0) {
     double total = 0.0;
     for (int b = 0; b < blocks; ++b) total += partials[b];
-    const float norm = (float)(sqrt(total) * grad_scale);        // norm of the MEAN gradient
-    const float c = max_norm / (norm + 1e-6f);                    // clip_grad.py: clip_coef ...
-    coef_shared = c < 1.0f ? c : 1.0f;                            // ... clamped to 1
-    if (blockIdx.x == 0 && report != nullptr) { report[0] = coef_shared; report[1] = norm; }
+    const double norm = sqrt(total) * grad_scale;                 // norm of the MEAN gradient
+    // clip_grad.py: clip_coef, clamped to 1 — formed in float64 like the norm and rounded ONCE.  (From the
+    // float32 norm with a float32 add and divide, as torch forms it, it was up to 1.2 ulps from the exact
+    // factor: tests/test_gpu_optim.py holds norm and factor to one ulp of numpy_port.clip_grad_norm_f64.)
+    const double c = (double)max_norm / (norm + 1e-6);
+    coef_shared = (float)(c < 1.0 ? c : 1.0);
+    if (blockIdx.x == 0 && report != nullptr) { report[0] = coef_shared; report[1] = (float)norm; }
   }
   __syncthreads();
   const float coef = coef_shared;
