@@ -57,10 +57,10 @@ const char* tonic_last_error(void);
  * grow), tonic_mlp_hidden packs with bit 30 set (plain widths of any size pass as they are), tonic_collector_q_act,
  * 12 = the *_ranged critic entries (Return normaliser's value head) + tonic_reward_range, 13 = tonic_mlp_torso:
  * 1 .. 4 layer torsos for every off-policy entry, the D4PG / MPO entries take tonic_mlp_hidden codes,
- * 14 = the tonic_trpo_* entries)
+ * 14 = the tonic_trpo_* entries, 15 = tonic_optimizer_step / tonic_optimizer_state_slots)
  * and the gfx target the kernels were built for.  TONIC_ABI_VERSION is what a binding was compiled against:
  * tonic_amd/_fastcall (csrc/fastcall.c) and tonic_amd/_lib.py compare it with the loaded library's answer. */
-#define TONIC_ABI_VERSION 14
+#define TONIC_ABI_VERSION 15
 int32_t tonic_abi_version(void);
 const char* tonic_target_arch(void);
 
@@ -360,6 +360,38 @@ int tonic_adam_step_pair(
     int32_t* d_state_b, int64_t param_count_b, double lr_b, int32_t stats_kind_b,
     float* d_info_row_b,
     double grad_scale, double beta1, double beta2, double eps, void* stream);
+
+/* The optimizer family behind `optimizer=lambda params: torch.optim.X(params, ...)` of every reference updater:
+ * the single-tensor CPU paths of torch/optim/adam.py:395-547 (Adam with weight_decay / amsgrad / maximize, and
+ * AdamW = decoupled weight decay, :419), sgd.py:343-380 and rmsprop.py:287-339 on the flat parameter block.  Plain
+ * Adam stays on tonic_adam_step*.  WHICH float32 expression each rule is: tests/optim_family_ref.py.
+ * Hyper-parameters are Python floats in torch: they arrive as float64 and every derived constant (1 - beta,
+ * 1 - alpha, 1 - dampening, 1 - lr * weight_decay, the bias corrections) is formed in float64 and rounded once. */
+enum { TONIC_OPT_ADAM = 0, TONIC_OPT_ADAMW = 1, TONIC_OPT_SGD = 2, TONIC_OPT_RMSPROP = 3 };
+enum { TONIC_OPT_AMSGRAD = 1, TONIC_OPT_NESTEROV = 2, TONIC_OPT_CENTERED = 4, TONIC_OPT_MAXIMIZE = 8 };
+typedef struct tonic_optimizer_t {
+  int32_t kind;               /* TONIC_OPT_ADAM .. TONIC_OPT_RMSPROP */
+  int32_t flags;              /* TONIC_OPT_AMSGRAD (Adam, AdamW) | _NESTEROV (SGD) | _CENTERED (RMSprop) | _MAXIMIZE */
+  double lr, beta1, beta2, eps, weight_decay, momentum, dampening, alpha;
+} tonic_optimizer_t;
+/* How many param_count-float state buffers the rule keeps (0 .. 3; -1: not a rule of the family), in the order
+ * they lie in d_slots (slot k = d_slots + k * param_count, zero before the first step):
+ *   Adam / AdamW : exp_avg, exp_avg_sq [, max_exp_avg_sq with amsgrad]
+ *   SGD          : [momentum_buffer with momentum != 0]
+ *   RMSprop      : square_avg [, grad_avg when centered] [, momentum_buffer with momentum > 0] */
+int32_t tonic_optimizer_state_slots(const tonic_optimizer_t* rule);
+/* One step of `rule` — gradient = d_grad_sums[i] * grad_scale; d_state, stats_kind, kl_threshold, entropy_coeff,
+ * d_adv_stats, d_info_row and d_skip_flag exactly as tonic_adam_step (the same finalisation code).  SGD's first
+ * step TAKEN (d_state[0] == 0, read on the device) sets momentum_buffer = gradient (sgd.py:361-363).
+ * d_target != NULL: the polyak update of tonic_adam_polyak_step rides in the launch — d_params must be
+ * d_online + block_offset, all total_count entries of d_target move by `coeff`.  Otherwise pass NULL, NULL, 0, 0, 0.
+ * d_slots may be NULL for a rule without state. */
+int tonic_optimizer_step(float* d_params, const float* d_grad_sums, float* d_slots, int32_t* d_state,
+                         int64_t param_count, double grad_scale, const tonic_optimizer_t* rule,
+                         int32_t stats_kind, double kl_threshold, double entropy_coeff,
+                         const float* d_adv_stats, float* d_info_row, const int32_t* d_skip_flag,
+                         float* d_target, const float* d_online, int64_t total_count, int64_t block_offset,
+                         double coeff, void* stream);
 
 /* ---- replay: HBM-resident Segment -----------------------------------------------------------
  * replaces: tonic/replays/segments.py:27-36 (Segment.store, one time row for all W workers)

@@ -20,6 +20,17 @@ class QOptimizer(ctypes.Structure):
                 ('lr', c_f64), ('beta1', c_f64), ('beta2', c_f64), ('eps', c_f64)]
 
 
+class Optimizer(ctypes.Structure):
+    """tonic_optimizer_t of include/tonic_hip.h (field for field)."""
+    _fields_ = [('kind', c_i32), ('flags', c_i32), ('lr', c_f64), ('beta1', c_f64), ('beta2', c_f64),
+                ('eps', c_f64), ('weight_decay', c_f64), ('momentum', c_f64), ('dampening', c_f64),
+                ('alpha', c_f64)]
+
+
+OPTIMIZER_KINDS = {'adam': 0, 'adamw': 1, 'sgd': 2, 'rmsprop': 3}                 # TONIC_OPT_ADAM ..
+OPTIMIZER_FLAGS = {'amsgrad': 1, 'nesterov': 2, 'centered': 4, 'maximize': 8}     # TONIC_OPT_AMSGRAD ..
+
+
 class QStore(ctypes.Structure):
     """tonic_q_store_t of include/tonic_hip.h (field for field)."""
     _fields_ = [('d_buf_observations', c_vp), ('d_buf_actions', c_vp), ('d_buf_next_observations', c_vp),
@@ -107,6 +118,9 @@ SIGNATURES = {
     'tonic_adam_step_pair': (ctypes.c_int,
                              [c_vp] * 5 + [c_i64, c_f64, c_i32, c_f64, c_f64, c_vp, c_vp, c_vp] +
                              [c_vp] * 5 + [c_i64, c_f64, c_i32, c_vp] + [c_f64] * 4 + [c_vp]),
+    'tonic_optimizer_state_slots': (c_i32, [c_vp]),
+    'tonic_optimizer_step': (ctypes.c_int, [c_vp] * 4 + [c_i64, c_f64, c_vp, c_i32, c_f64, c_f64] + [c_vp] * 5 +
+                             [c_i64, c_i64, c_f64, c_vp]),
     'tonic_segment_store': (ctypes.c_int, [c_vp] * 15 + [c_i64, c_i64, c_i32, c_i32, c_vp]),
     'tonic_meanstd_record': (ctypes.c_int, [c_vp, c_vp, c_i64, c_i32, c_vp]),
     'tonic_segment_gather': (ctypes.c_int, [c_vp] * 11 + [c_i64, c_i64, c_i32, c_i32, c_vp]),
@@ -196,7 +210,7 @@ SIGNATURES = {
 }
 
 
-ABI_VERSION = 14       # include/tonic_hip.h: tonic_abi_version()
+ABI_VERSION = 15       # include/tonic_hip.h: tonic_abi_version()
 
 
 class TonicHipError(RuntimeError):

@@ -1,4 +1,4 @@
-// Flat fused Adam + PPO statistic finalisation (gfx950).
+// Flat fused Adam, the optimizer family beside it (family_kernel, below) + PPO statistic finalisation (gfx950).
 //
 // Restates torch.optim.Adam's single-tensor CPU path (torch/optim/adam.py:395-547; betas
 // (0.9, 0.999), eps 1e-8, no weight decay / amsgrad) as constructed by
@@ -86,6 +86,27 @@ __device__ void adam_finalize(const AdamArgs& a) {
   }
 }
 
+// The LAST optimizer workgroup to get here finalises (step counter, logged statistics, KL stop
+// flag) — it used to be a launch of its own (4.6 us for an 8-float row).  Every workgroup has
+// read state[0] / the skip flag before it arrives, so the writes below race with nobody: the
+// barrier in front of the arrival is a workgroup-scope fence (s_waitcnt vmcnt(0) in every wave:
+// all of this workgroup's loads have returned and its stores are acknowledged by L2) and the
+// counter is an agent-scope atomic performed at L2; what the finaliser READS was written by
+// earlier launches.  (A release / acquire pair at agent scope instead would be an L2 write-back
+// + invalidate per workgroup.)
+__device__ __forceinline__ void last_arrival_finalizes(const AdamArgs& a, int64_t grid) {
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned* arrivals = reinterpret_cast<unsigned*>(a.state + 3);
+    const unsigned before = __hip_atomic_fetch_add(arrivals, 1u, __ATOMIC_RELAXED,
+                                                   __HIP_MEMORY_SCOPE_AGENT);
+    if (before == (unsigned)grid - 1) {
+      __hip_atomic_store(arrivals, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      adam_finalize(a);
+    }
+  }
+}
+
 __global__ __launch_bounds__(256) void adam_kernel(AdamPair pair) {
   const AdamArgs& a = blockIdx.y == 0 ? pair.net[0] : pair.net[1];
   if (a.polyak_target != nullptr && (int)blockIdx.x >= a.adam_blocks) {
@@ -125,24 +146,135 @@ __global__ __launch_bounds__(256) void adam_kernel(AdamPair pair) {
       }
     }
   }
-  // The LAST optimizer workgroup to get here finalises (step counter, logged statistics, KL stop
-  // flag) — it used to be a launch of its own (4.6 us for an 8-float row).  Every workgroup has
-  // read state[0] / the skip flag before it arrives, so the writes below race with nobody: the
-  // barrier in front of the arrival is a workgroup-scope fence (s_waitcnt vmcnt(0) in every wave:
-  // all of this workgroup's loads have returned and its stores are acknowledged by L2) and the
-  // counter is an agent-scope atomic performed at L2; what the finaliser READS was written by
-  // earlier launches.  (A release / acquire pair at agent scope instead would be an L2 write-back
-  // + invalidate per workgroup.)
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned* arrivals = reinterpret_cast<unsigned*>(a.state + 3);
-    const unsigned before = __hip_atomic_fetch_add(arrivals, 1u, __ATOMIC_RELAXED,
-                                                   __HIP_MEMORY_SCOPE_AGENT);
-    if (before == (unsigned)grid - 1) {
-      __hip_atomic_store(arrivals, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      adam_finalize(a);
+  last_arrival_finalizes(a, grid);
+}
+
+// ---- the optimizer family: Adam with weight decay / amsgrad / maximize, AdamW, SGD, RMSprop ----
+// The single-tensor CPU paths of torch/optim/adam.py:395-547, sgd.py:343-380 and rmsprop.py:287-339 on one flat
+// block, launched, skipped, counted and finalised exactly like adam_kernel (same grid, same arrival counter, the
+// same adam_finalize); plain Adam stays on adam_kernel.  WHICH float32 expression each rule is, operation by
+// operation, is tests/optim_family_ref.py; tests/test_gpu_optim_family.py holds the kernels to it bit for bit.
+// Bytes of HBM traffic per parameter (p and g read, p written = 12, + 8 per state buffer): Adam / AdamW 28, with
+// amsgrad 36; SGD 12, with momentum 20; RMSprop 20, + 8 centered, + 8 with momentum.
+struct FamilyArgs {
+  AdamArgs a;                 // params, sums, state, n, lr, eps, beta2, the float64 betas, statistics, skip, polyak
+  float* slot[3];             // the rule's state buffers (tonic_optimizer_state_slots' order)
+  int decoupled, nesterov, maximize;
+  float weight_decay;         // 0: no `g += wd * p` (adam.py:429, sgd.py:356, rmsprop.py:308)
+  float decay_keep;           // AdamW: F32(1 - lr * wd) (adam.py:419)
+  float momentum, undamped;   // SGD / RMSprop: mu; SGD: F32(1 - dampening)
+  float alpha, unalpha;       // RMSprop: alpha, F32(1 - alpha)
+};
+
+// The rules as types: what is known at compile time decides which state buffers an instantiation streams.  Every
+// rule LOADS all of its state before it stores any of it: the buffers may alias as far as the compiler knows, so a
+// load behind a store waits for it, and each thread walks ~n / 32 768 elements one after the other.  With one
+// round trip per element instead of one per buffer, at n = 4 194 304: SGD with momentum 75.0 -> 49.7 us, centered
+// RMSprop with momentum 114.9 -> 66.3 us (profiles/optim_family_timing.json).
+template <bool kAmsgrad>
+struct AdamRule {
+  float step_size, bias2_sqrt, w1, w2;
+  __device__ void prepare(const FamilyArgs& f) {
+    const AdamArgs& a = f.a;
+    const int step = a.state[0] + 1;
+    const double bias1 = 1.0 - pow(a.beta1_d, (double)step);
+    const double bias2 = 1.0 - pow(a.beta2_d, (double)step);
+    step_size = (float)(a.lr_d / bias1);                             // adam.py:534
+    bias2_sqrt = (float)sqrt(bias2);                                 // :536
+    w1 = (float)(1.0 - a.beta1_d); w2 = (float)(1.0 - a.beta2_d);
+  }
+  __device__ float apply(const FamilyArgs& f, int64_t i, float p, float g) const {
+    float m = f.slot[0][i], v = f.slot[1][i];
+    const float seen = kAmsgrad ? f.slot[2][i] : 0.f;
+    if (f.decoupled) p = p * f.decay_keep;                           // AdamW: param.mul_(1 - lr * wd), :419
+    m = m + w1 * (g - m);                                            // lerp_, :457
+    v = v * f.a.beta2 + w2 * (g * g);                                // mul_().addcmul_(), :476
+    float root = v;
+    if (kAmsgrad) root = (v > seen || v != v) ? v : seen;            // torch.maximum (NaN propagates), :540
+    const float denom = sqrtf(root) / bias2_sqrt + f.a.eps;          // :543 / :545
+    f.slot[0][i] = m;
+    f.slot[1][i] = v;
+    if (kAmsgrad) f.slot[2][i] = root;
+    return p - step_size * (m / denom);                              // addcdiv_, :547
+  }
+};
+
+template <bool kMomentum>
+struct SgdRule {
+  bool first;
+  __device__ void prepare(const FamilyArgs& f) { first = f.a.state[0] == 0; }     // no step taken yet
+  __device__ float apply(const FamilyArgs& f, int64_t i, float p, float g) const {
+    float d = g;
+    if (kMomentum) {
+      const float kept = f.slot[0][i] * f.momentum + f.undamped * g; // mul_().add_(alpha = 1 - dampening), sgd.py:365
+      const float buf = first ? g : kept;                            // buf = grad.clone(), :361-363 (a select: what
+      f.slot[0][i] = buf;                                            //  the buffer held before the first step is unused)
+      d = f.nesterov ? g + f.momentum * buf : buf;                   // :367-370
+    }
+    return p - f.a.lr * d;                                           // param.add_(grad, alpha = -lr), :380
+  }
+};
+
+template <bool kCentered, bool kMomentum>
+struct RmspropRule {
+  __device__ void prepare(const FamilyArgs&) {}
+  __device__ float apply(const FamilyArgs& f, int64_t i, float p, float g) const {
+    float* const momentum_slot = f.slot[kCentered ? 2 : 1];
+    float sq = f.slot[0][i];
+    float ga = kCentered ? f.slot[1][i] : 0.f;
+    const float held = kMomentum ? momentum_slot[i] : 0.f;
+    sq = sq * f.alpha + f.unalpha * (g * g);                         // mul_().addcmul_(), rmsprop.py:316
+    float avg;
+    if (kCentered) {
+      ga = ga + f.unalpha * (g - ga);                                // lerp_, :322
+      avg = sqrtf(sq - ga * ga) + f.a.eps;                           // addcmul(value = -1).sqrt_(), add_(eps), :323-330
+    } else {
+      avg = sqrtf(sq) + f.a.eps;                                     // :325-330
+    }
+    f.slot[0][i] = sq;
+    if (kCentered) f.slot[1][i] = ga;
+    if (kMomentum) {
+      const float buf = held * f.momentum + g / avg;                 // mul_().addcdiv_(), :336
+      momentum_slot[i] = buf;
+      return p - f.a.lr * buf;                                       // :337
+    }
+    return p - f.a.lr * (g / avg);                                   // addcdiv_(value = -lr), :339
+  }
+};
+
+template <typename Rule>
+__global__ __launch_bounds__(256) void family_kernel(FamilyArgs f) {
+  const AdamArgs& a = f.a;
+  if (a.polyak_target != nullptr && (int)blockIdx.x >= a.adam_blocks) {
+    // the target entries OUTSIDE this optimizer block, as in adam_kernel
+    const int64_t first = (int64_t)((int)blockIdx.x - a.adam_blocks) * blockDim.x + threadIdx.x;
+    const int64_t stride = (int64_t)((int)gridDim.x - a.adam_blocks) * blockDim.x;
+    for (int64_t i = first; i < a.polyak_total; i += stride) {
+      if (i >= a.polyak_offset && i < a.polyak_offset + a.n) continue;
+      a.polyak_target[i] = polyak(a.polyak_target[i], a.polyak_online[i], a.polyak_keep, a.polyak_mix);
+    }
+    return;
+  }
+  if (a.skip != nullptr && *a.skip != 0) return;
+  const int64_t grid = a.polyak_target != nullptr ? a.adam_blocks : (int64_t)gridDim.x;
+  const bool all_zero = a.stats_kind == 1 && a.adv_stats != nullptr && a.adv_stats[2] != 0.f;  // actors.py:71
+  if (!all_zero) {
+    Rule rule;
+    rule.prepare(f);
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += grid * blockDim.x) {
+      const float before = a.params[i];
+      float g = a.grad_sums[i] * a.grad_scale;
+      if (f.maximize) g = -g;                                        // adam.py:397, sgd.py:344, rmsprop.py:302
+      if (f.weight_decay != 0.f && !f.decoupled) g = g + f.weight_decay * before;   // grad.add(param, alpha = wd)
+      const float p = rule.apply(f, i, before, g);
+      a.params[i] = p;
+      if (a.polyak_target != nullptr) {                               // this entry's target, same thread
+        float* t = a.polyak_target + a.polyak_offset + i;
+        *t = polyak(*t, p, a.polyak_keep, a.polyak_mix);
+      }
     }
   }
+  last_arrival_finalizes(a, grid);
 }
 
 // ---- gradient-norm clipping: torch.nn.utils.clip_grad_norm_ on the flat gradient-sum block ----
@@ -270,7 +402,98 @@ int adam_launch(float* d_params, const float* d_grad_sums, float* d_exp_avg, flo
   return TONIC_OK;
 }
 
+template <typename Rule>
+void family_launch(const FamilyArgs& f, unsigned blocks, hipStream_t st) {
+  hipLaunchKernelGGL(family_kernel<Rule>, dim3(blocks), dim3(256), 0, st, f);
+}
+
+bool family_rule_valid(const tonic_optimizer_t* rule) {
+  if (rule == nullptr || rule->kind < TONIC_OPT_ADAM || rule->kind > TONIC_OPT_RMSPROP) return false;
+  const int32_t allowed = TONIC_OPT_MAXIMIZE |
+      (rule->kind <= TONIC_OPT_ADAMW ? TONIC_OPT_AMSGRAD
+                                     : rule->kind == TONIC_OPT_SGD ? TONIC_OPT_NESTEROV : TONIC_OPT_CENTERED);
+  if (rule->flags & ~allowed) return false;
+  // sgd.py:57-58: Nesterov momentum requires a momentum and zero dampening
+  if ((rule->flags & TONIC_OPT_NESTEROV) && (rule->momentum <= 0.0 || rule->dampening != 0.0)) return false;
+  return rule->lr >= 0.0 && rule->weight_decay >= 0.0 && rule->momentum >= 0.0;
+}
+
 }  // namespace
+
+extern "C" int32_t tonic_optimizer_state_slots(const tonic_optimizer_t* rule) {
+  if (!family_rule_valid(rule)) return -1;
+  switch (rule->kind) {
+    case TONIC_OPT_SGD: return rule->momentum != 0.0 ? 1 : 0;
+    case TONIC_OPT_RMSPROP:
+      return 1 + ((rule->flags & TONIC_OPT_CENTERED) ? 1 : 0) + (rule->momentum > 0.0 ? 1 : 0);
+    default: return (rule->flags & TONIC_OPT_AMSGRAD) ? 3 : 2;
+  }
+}
+
+extern "C" int tonic_optimizer_step(float* d_params, const float* d_grad_sums, float* d_slots,
+                                    int32_t* d_state, int64_t param_count, double grad_scale,
+                                    const tonic_optimizer_t* rule, int32_t stats_kind,
+                                    double kl_threshold, double entropy_coeff, const float* d_adv_stats,
+                                    float* d_info_row, const int32_t* d_skip_flag, float* d_target,
+                                    const float* d_online, int64_t total_count, int64_t block_offset,
+                                    double coeff, void* stream) {
+  const int slots = tonic_optimizer_state_slots(rule);
+  TONIC_REQUIRE(slots >= 0, TONIC_ERR_INVALID_ARGUMENT,
+                "tonic_optimizer_step: not a rule of the family (kind %d, flags %d)",
+                rule ? rule->kind : -1, rule ? rule->flags : -1);
+  TONIC_REQUIRE(d_params && d_grad_sums && d_state && param_count > 0 && (d_slots || slots == 0),
+                TONIC_ERR_INVALID_ARGUMENT, "tonic_optimizer_step: bad argument");
+  TONIC_REQUIRE(stats_kind >= 0 && stats_kind <= 4, TONIC_ERR_INVALID_ARGUMENT,
+                "tonic_optimizer_step: stats_kind %d", stats_kind);
+  FamilyArgs f{};
+  AdamArgs& a = f.a;
+  a.params = d_params; a.grad_sums = d_grad_sums; a.state = d_state; a.n = param_count;
+  a.grad_scale = (float)grad_scale; a.lr = (float)rule->lr; a.beta1 = (float)rule->beta1;
+  a.beta2 = (float)rule->beta2; a.eps = (float)rule->eps;
+  a.beta1_d = rule->beta1; a.beta2_d = rule->beta2; a.lr_d = rule->lr;
+  a.stats_kind = stats_kind; a.kl_threshold = (float)kl_threshold;
+  a.entropy_coeff = (float)entropy_coeff;
+  a.adv_stats = d_adv_stats; a.info_row = d_info_row; a.skip = d_skip_flag;
+  for (int k = 0; k < slots; ++k) f.slot[k] = d_slots + (int64_t)k * param_count;
+  f.decoupled = rule->kind == TONIC_OPT_ADAMW && rule->weight_decay != 0.0;
+  f.nesterov = (rule->flags & TONIC_OPT_NESTEROV) != 0;
+  f.maximize = (rule->flags & TONIC_OPT_MAXIMIZE) != 0;
+  f.weight_decay = (float)rule->weight_decay;
+  f.decay_keep = (float)(1.0 - rule->lr * rule->weight_decay);
+  f.momentum = (float)rule->momentum; f.undamped = (float)(1.0 - rule->dampening);
+  f.alpha = (float)rule->alpha; f.unalpha = (float)(1.0 - rule->alpha);
+  const int blocks = adam_blocks_for(param_count);
+  int64_t extra = 0;
+  if (d_target != nullptr) {
+    TONIC_REQUIRE(d_online && block_offset >= 0 && block_offset + param_count <= total_count &&
+                      d_params == d_online + block_offset,
+                  TONIC_ERR_INVALID_ARGUMENT, "tonic_optimizer_step: block [%lld, +%lld) of %lld",
+                  (long long)block_offset, (long long)param_count, (long long)total_count);
+    a.polyak_target = d_target; a.polyak_online = d_online; a.polyak_total = total_count;
+    a.polyak_offset = block_offset; a.polyak_keep = (float)(1.0 - coeff); a.polyak_mix = (float)coeff;
+    a.adam_blocks = blocks;
+    extra = (total_count - param_count + 255) / 256;
+    if (extra > 2048) extra = 2048;
+  }
+  const unsigned grid = (unsigned)(blocks + extra);
+  hipStream_t st = as_stream(stream);
+  const bool momentum = rule->momentum != 0.0, centered = (rule->flags & TONIC_OPT_CENTERED) != 0;
+  if (rule->kind == TONIC_OPT_SGD) {
+    if (momentum) family_launch<SgdRule<true>>(f, grid, st);
+    else family_launch<SgdRule<false>>(f, grid, st);
+  } else if (rule->kind == TONIC_OPT_RMSPROP) {
+    if (centered && momentum) family_launch<RmspropRule<true, true>>(f, grid, st);
+    else if (centered) family_launch<RmspropRule<true, false>>(f, grid, st);
+    else if (momentum) family_launch<RmspropRule<false, true>>(f, grid, st);
+    else family_launch<RmspropRule<false, false>>(f, grid, st);
+  } else if (rule->flags & TONIC_OPT_AMSGRAD) {
+    family_launch<AdamRule<true>>(f, grid, st);
+  } else {
+    family_launch<AdamRule<false>>(f, grid, st);
+  }
+  TONIC_CHECK_LAUNCH("tonic_optimizer_step");
+  return TONIC_OK;
+}
 
 extern "C" int tonic_adam_step_pair(
     float* d_params_a, const float* d_grad_sums_a, float* d_exp_avg_a, float* d_exp_avg_sq_a,

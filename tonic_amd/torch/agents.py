@@ -1555,6 +1555,8 @@ class DDPG(Agent):
         kind, actor_class = self._FUSED.get(type(critic), (None, None))
         if kind is None or type(actor) is not actor_class or critic.stock or actor.stock:
             return None
+        if not (critic.plain and actor.plain):        # tonic_q_iteration's epilogues are plain Adam: the split entries
+            return None
         if os.environ.get('TONIC_AMD_FUSED_ITERATION', '1') == '0':
             return None
         if not self.lib.tonic_q_iteration_supported(self.observation_size, self.hidden,
@@ -1680,7 +1682,7 @@ class DDPG(Agent):
         for updater in (self.actor_updater, self.critic_updater):
             hyper = updater.hyper
             noise = getattr(updater, 'target_action_noise', None)
-            parts.append((hyper['lr'], hyper['betas'], hyper['eps'],
+            parts.append((tuple(sorted(hyper.items())),
                           float(getattr(updater, 'entropy_coeff', 0.0)),
                           float(getattr(updater, 'gradient_clip', 0.0) or 0.0),
                           (noise.scale, noise.clip) if noise is not None else None))

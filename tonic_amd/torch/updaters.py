@@ -12,6 +12,7 @@ stream, with no host synchronisation:
 The PPO agent drives them through ``enqueue`` for all 80 iterations and reads the
 statistics back once; ``__call__`` (enqueue + read back) exists for drop-in compatibility.
 """
+import ctypes
 import os
 
 import numpy as np
@@ -35,6 +36,68 @@ def adam_hyperparameters(factory, default_lr):
     if d.get('weight_decay', 0) != 0 or d.get('amsgrad', False) or d.get('maximize', False):
         raise NotImplementedError('Adam with weight_decay / amsgrad / maximize is not fused')
     return dict(lr=float(d['lr']), betas=tuple(float(b) for b in d['betas']), eps=float(d['eps']))
+
+
+_FAMILY = {torch.optim.Adam: 'adam', torch.optim.AdamW: 'adamw', torch.optim.SGD: 'sgd',
+           torch.optim.RMSprop: 'rmsprop'}
+
+
+def optimizer_hyperparameters(factory, default_lr):
+    """The rule behind the reference-style ``optimizer=lambda params: torch.optim.X(params, ...)`` factory
+    (actors.py:58-59), probed like `adam_hyperparameters`: Adam (with weight_decay / amsgrad / maximize), AdamW, SGD
+    (momentum, dampening, nesterov) and RMSprop (centered, momentum) run on the HIP engine (tonic_optimizer_step;
+    plain Adam on tonic_adam_step*).  -> dict(kind=, lr=, weight_decay=, maximize=, ...) with the rule's own keys,
+    every number a Python float (float64) as torch keeps it.  Anything else is rejected by name."""
+    if factory is None:
+        return dict(kind='adam', lr=float(default_lr), betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
+                    amsgrad=False, maximize=False)
+    probe = factory([torch.nn.Parameter(torch.zeros(1))])
+    kind = _FAMILY.get(type(probe))
+    if kind is None:
+        raise NotImplementedError(
+            f'{type(probe).__module__}.{type(probe).__name__} does not run on the HIP engine: the optimizers served '
+            'are torch.optim.Adam, AdamW, SGD and RMSprop')
+    if len(probe.param_groups) != 1:
+        raise NotImplementedError(f'{type(probe).__name__} with {len(probe.param_groups)} parameter groups: one flat '
+                                  'block has one set of hyper-parameters')
+    d = probe.param_groups[0]
+    if isinstance(d['lr'], torch.Tensor):
+        raise NotImplementedError(f'{type(probe).__name__} with a tensor lr: the step takes a Python float')
+    rule = dict(kind=kind, lr=float(d['lr']), weight_decay=float(d['weight_decay']), maximize=bool(d['maximize']))
+    if kind in ('adam', 'adamw'):
+        rule.update(betas=tuple(float(b) for b in d['betas']), eps=float(d['eps']), amsgrad=bool(d['amsgrad']))
+    elif kind == 'sgd':
+        rule.update(momentum=float(d['momentum']), dampening=float(d['dampening']), nesterov=bool(d['nesterov']))
+    else:
+        rule.update(alpha=float(d['alpha']), eps=float(d['eps']), momentum=float(d['momentum']),
+                    centered=bool(d['centered']))
+    return rule
+
+
+def plain_adam(rule):
+    """The rule `adam_hyperparameters` accepts: what tonic_adam_step*, tonic_adam_polyak_step and the fused
+    off-policy iteration compute (AdamW without decay is the same arithmetic)."""
+    return rule['kind'] in ('adam', 'adamw') and rule.get('weight_decay', 0.0) == 0 and \
+        not rule.get('amsgrad', False) and not rule.get('maximize', False)
+
+
+def optimizer_rule(rule):
+    """`optimizer_hyperparameters`' dict as the tonic_optimizer_t of the C ABI."""
+    betas = rule.get('betas', (0.0, 0.0))
+    flags = sum(bit for name, bit in _lib.OPTIMIZER_FLAGS.items() if rule.get(name, False))
+    return _lib.Optimizer(kind=_lib.OPTIMIZER_KINDS[rule['kind']], flags=flags, lr=rule['lr'], beta1=betas[0],
+                          beta2=betas[1], eps=rule.get('eps', 0.0), weight_decay=rule['weight_decay'],
+                          momentum=rule.get('momentum', 0.0), dampening=rule.get('dampening', 0.0),
+                          alpha=rule.get('alpha', 0.0))
+
+
+def optimizer_slots(lib, rule, count, device):
+    """(tonic_optimizer_t, its zeroed state buffers as ONE tensor of slots x count floats, None without state)."""
+    packed = optimizer_rule(rule)
+    slots = lib.tonic_optimizer_state_slots(ctypes.byref(packed))
+    if slots < 0:
+        raise NotImplementedError(f'{rule}: {lib.tonic_last_error().decode() or "not a rule of the family"}')
+    return packed, (torch.zeros(slots * count, dtype=torch.float32, device=device) if slots else None)
 
 
 def fused_ppo_torso(torso):
@@ -120,8 +183,14 @@ class _FlatUpdater(_StockTorch):
         device = flat.flat.device
         self.count = flat.count
         self.grad_sums = torch.zeros(self.count + INFO_WIDTH, dtype=torch.float32, device=device)
-        self.exp_avg = torch.zeros(self.count, dtype=torch.float32, device=device)
-        self.exp_avg_sq = torch.zeros(self.count, dtype=torch.float32, device=device)
+        # plain Adam: the two moments tonic_adam_step* take; any other rule: tonic_optimizer_t and its state slots
+        self.plain = plain_adam(hyper)
+        self.rule = self.slots = self.exp_avg = self.exp_avg_sq = None
+        if self.plain:
+            self.exp_avg = torch.zeros(self.count, dtype=torch.float32, device=device)
+            self.exp_avg_sq = torch.zeros(self.count, dtype=torch.float32, device=device)
+        else:
+            self.rule, self.slots = optimizer_slots(self.lib, hyper, self.count, device)
         self.state = torch.zeros(4, dtype=torch.int32, device=device)   # {step, stop, -, -}
         self.steps_enqueued = 0     # host mirror of state[0] (off-policy: every enqueued step is taken)
         self.workspace = None
@@ -177,7 +246,7 @@ class _FlatUpdater(_StockTorch):
 
     def _step(self, n_global, info_row, adv_stats=None, skip=None, kl_threshold=0.0,
               entropy_coeff=0.0, allreduce=True, targets=None):
-        """All-reduce of the gradient sums (world > 1) + Adam + statistics.  `targets` =
+        """All-reduce of the gradient sums (world > 1) + optimizer step + statistics.  `targets` =
         (flat target buffer, flat online buffer, offset of this block in them, coeff): the
         polyak update of ALL targets rides in the same launch (update_targets right after the
         step, as ddpg.py:105-112 orders them)."""
@@ -191,6 +260,18 @@ class _FlatUpdater(_StockTorch):
                 torch.distributed.all_reduce(self.grad_sums)     # RCCL sum over xGMI
         self.enqueue_clip(n_global, skip)
         h = self.hyper
+        if not self.plain:
+            polyak = (None, None, 0, 0, 0.0)
+            if targets is not None:
+                target, online, offset, coeff = targets
+                assert online.data_ptr() + 4 * offset == self.flat.flat.data_ptr()
+                polyak = (_lib.ptr(target), _lib.ptr(online), online.numel(), offset, float(coeff))
+            _lib.check(self.lib.tonic_optimizer_step(
+                _lib.ptr(self.flat.flat), _lib.ptr(self.grad_sums), _lib.ptr(self.slots), _lib.ptr(self.state),
+                self.count, 1.0 / n_global, ctypes.byref(self.rule), self.stats_kind, float(kl_threshold),
+                float(entropy_coeff), _lib.ptr(adv_stats), _lib.ptr(info_row), skip, *polyak,
+                _lib.current_stream()), 'tonic_optimizer_step')
+            return
         if targets is not None:
             target, online, offset, coeff = targets
             assert online.data_ptr() + 4 * offset == self.flat.flat.data_ptr()
@@ -222,7 +303,8 @@ def enqueue_step_pair(actor, critic, n_local, adv_stats, actor_info, critic_info
     """The optimizer steps of a PPO iteration (ppo.py:33-46: actor, then critic) as ONE launch
     pair.  The gradient sums are final (all-reduced by the caller when world > 1)."""
     ha, hc = actor.hyper, critic.hyper
-    if actor.stock or critic.stock or (ha['betas'], ha['eps']) != (hc['betas'], hc['eps']):   # separately
+    if actor.stock or critic.stock or not (actor.plain and critic.plain) or \
+            (ha['betas'], ha['eps']) != (hc['betas'], hc['eps']):                            # separately
         actor.enqueue_step(n_local, adv_stats, actor_info, allreduce=False)
         critic.enqueue_step(n_local, critic_info, allreduce=False)
         return
@@ -253,7 +335,7 @@ class ClippedRatio(_FlatUpdater):
 
     def initialize(self, model):
         self.model = model
-        self._setup(model.flat_actor, adam_hyperparameters(self.optimizer, 3e-4))
+        self._setup(model.flat_actor, optimizer_hyperparameters(self.optimizer, 3e-4))
         self.variables = model.flat_actor.params
         self.observation_size = model.actor.torso.model[0].in_features
         self.action_size = model.actor.head.log_scale.shape[1]
@@ -701,7 +783,7 @@ class VRegression(_FlatUpdater):
 
     def initialize(self, model):
         self.model = model
-        self._setup(model.flat_critic, adam_hyperparameters(self.optimizer, 1e-3))
+        self._setup(model.flat_critic, optimizer_hyperparameters(self.optimizer, 1e-3))
         self.variables = model.flat_critic.params
         self.observation_size = model.critic.torso.model[0].in_features
         self.normalizer = model.observation_normalizer
@@ -981,7 +1063,7 @@ class _TwinCriticQLearning(_QUpdater):
 
     def initialize(self, model):
         self._shapes(model)
-        self._setup(model.flat_critics, adam_hyperparameters(self.optimizer, self.default_lr))
+        self._setup(model.flat_critics, optimizer_hyperparameters(self.optimizer, self.default_lr))
         self.variables = model.flat_critics.params
         if self.hidden is None:
             self._stock_setup(self.optimizer, self.default_lr)
@@ -1195,7 +1277,7 @@ class _ActorQGradient(_QUpdater):
 
     def initialize(self, model):
         self._shapes(model)
-        self._setup(model.flat_actor, adam_hyperparameters(self.optimizer, self.default_lr))
+        self._setup(model.flat_actor, optimizer_hyperparameters(self.optimizer, self.default_lr))
         self.variables = model.flat_actor.params
         if self.hidden is None:
             self._stock_setup(self.optimizer, self.default_lr)
@@ -1321,7 +1403,7 @@ class MaximumAPosterioriPolicyOptimization(_ActorQGradient):
         self.min_log_dual = min_log_dual
         self.action_penalization = action_penalization
         self.optimizer = actor_optimizer
-        self.dual_hyper = adam_hyperparameters(actor_optimizer, 1e-2)      # actors.py:291-292
+        self.dual_hyper = optimizer_hyperparameters(actor_optimizer, 1e-2)      # actors.py:291-292
         self.gradient_clip = gradient_clip
 
     def initialize(self, model, action_space=None):
@@ -1331,8 +1413,12 @@ class MaximumAPosterioriPolicyOptimization(_ActorQGradient):
             [self.initial_log_alpha_std] * A + [self.initial_log_temperature]
         self.duals = torch.tensor(duals, dtype=torch.float32, device=device)
         self.dual_grads = torch.zeros(2 * A + 2 + INFO_WIDTH, dtype=torch.float32, device=device)
-        self.dual_exp_avg = torch.zeros(2 * A + 2, dtype=torch.float32, device=device)
-        self.dual_exp_avg_sq = torch.zeros(2 * A + 2, dtype=torch.float32, device=device)
+        self.dual_rule = self.dual_slots = self.dual_exp_avg = self.dual_exp_avg_sq = None
+        if plain_adam(self.dual_hyper):
+            self.dual_exp_avg = torch.zeros(2 * A + 2, dtype=torch.float32, device=device)
+            self.dual_exp_avg_sq = torch.zeros(2 * A + 2, dtype=torch.float32, device=device)
+        else:
+            self.dual_rule, self.dual_slots = optimizer_slots(self.lib, self.dual_hyper, 2 * A + 2, device)
         self.dual_state = torch.zeros(4, dtype=torch.int32, device=device)
         self.mpo_stats = torch.zeros(9 + 2 * A, dtype=torch.float32, device=device)
         self.dual_info = torch.zeros(INFO_WIDTH, dtype=torch.float32, device=device)
@@ -1399,6 +1485,12 @@ class MaximumAPosterioriPolicyOptimization(_ActorQGradient):
                 p(self.dual_grads), self.duals.numel(), 1.0, self.gradient_clip, None,
                 p(self.dual_clip_workspace), self.dual_clip_workspace.numel(),
                 _lib.current_stream()), 'tonic_clip_grad_norm (duals)')
+        if self.dual_rule is not None:
+            _lib.check(self.lib.tonic_optimizer_step(
+                p(self.duals), p(self.dual_grads), p(self.dual_slots), p(self.dual_state), self.duals.numel(), 1.0,
+                ctypes.byref(self.dual_rule), 0, 0.0, 0.0, None, p(self.dual_info), None, None, None, 0, 0, 0.0,
+                _lib.current_stream()), 'tonic_optimizer_step (duals)')
+            return
         _lib.check(self.lib.tonic_adam_step(
             p(self.duals), p(self.dual_grads), p(self.dual_exp_avg), p(self.dual_exp_avg_sq),
             p(self.dual_state), self.duals.numel(), 1.0, h['lr'], h['betas'][0], h['betas'][1],
