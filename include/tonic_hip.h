@@ -57,10 +57,12 @@ const char* tonic_last_error(void);
  * grow), tonic_mlp_hidden packs with bit 30 set (plain widths of any size pass as they are), tonic_collector_q_act,
  * 12 = the *_ranged critic entries (Return normaliser's value head) + tonic_reward_range, 13 = tonic_mlp_torso:
  * 1 .. 4 layer torsos for every off-policy entry, the D4PG / MPO entries take tonic_mlp_hidden codes,
- * 14 = the tonic_trpo_* entries, 15 = tonic_optimizer_step / tonic_optimizer_state_slots)
+ * 14 = the tonic_trpo_* entries, 15 = tonic_optimizer_step / tonic_optimizer_state_slots,
+ * 16 = tonic_critic_loss_t: tonic_critic_loss_check, tonic_twin_q_grad_loss, tonic_expected_sarsa_grad_loss,
+ * tonic_q_iteration_t.critic_loss)
  * and the gfx target the kernels were built for.  TONIC_ABI_VERSION is what a binding was compiled against:
  * tonic_amd/_fastcall (csrc/fastcall.c) and tonic_amd/_lib.py compare it with the loaded library's answer. */
-#define TONIC_ABI_VERSION 15
+#define TONIC_ABI_VERSION 16
 int32_t tonic_abi_version(void);
 const char* tonic_target_arch(void);
 
@@ -773,6 +775,36 @@ int tonic_twin_q_grad(int32_t kind, const float* d_policy_params, const float* d
                       int32_t O, int32_t H, int32_t A, double entropy_coeff, double noise_scale,
                       double noise_clip, void* d_workspace, int64_t workspace_bytes, void* stream);
 
+/* The critic's loss: `loss=` of DeterministicQLearning, TwinCriticDeterministicQLearning, TwinCriticSoftQLearning
+ * and ExpectedSARSA (tonic/torch/updaters/critics.py:58,142,189,243: `self.loss = loss or torch.nn.MSELoss()`,
+ * `loss = self.loss(values, returns)`, reduction 'mean').  Per sample, on the float32 error e = q - y and with
+ * `param` (beta / delta; ignored for MSE and L1) rounded to float32 once, torch.nn.functional.{mse, l1, smooth_l1,
+ * huber}_loss and their backward:
+ *   kind                   loss term                                    d term / d q
+ *   MSE                    e*e                                          2*e
+ *   L1                     |e|                                          (e > 0) - (e < 0)
+ *   SMOOTH_L1, beta > 0    |e| < beta ? 0.5*e*e/beta : |e| - 0.5*beta   e <= -beta ? -1 : e >= beta ? 1 : e/beta
+ *   SMOOTH_L1, beta = 0    as L1                                        as L1
+ *   HUBER, delta > 0       |e| < delta ? 0.5*e*e                        e <= -delta ? -delta : e >= delta ? delta : e
+ *                                      : delta*(|e| - 0.5*delta)
+ * A NaN error gives a NaN term; its gradient is NaN except for L1 and smooth-L1 with beta = 0 (0), as in torch.
+ * Statistics slot 0 of the critic's row is the sum of the loss terms over the batch and both critics.  An all-zero
+ * struct (and NULL where a pointer is taken) is MSE. */
+enum { TONIC_LOSS_MSE = 0, TONIC_LOSS_L1 = 1, TONIC_LOSS_SMOOTH_L1 = 2, TONIC_LOSS_HUBER = 3 };
+typedef struct tonic_critic_loss_t { int32_t kind; int32_t reserved; double param; } tonic_critic_loss_t;
+/* Host-only validation: 0, or TONIC_ERR_INVALID_ARGUMENT (message in tonic_last_error) for an unknown kind,
+ * beta < 0, delta <= 0 or a `param` that is not finite.  NULL is valid (MSE). */
+int tonic_critic_loss_check(const tonic_critic_loss_t* loss);
+/* tonic_twin_q_grad under `loss` (NULL: MSE, the same launches and bits as tonic_twin_q_grad). */
+int tonic_twin_q_grad_loss(int32_t kind, const float* d_policy_params, const float* d_target_critics,
+                           const float* d_critics, const float* d_norm_mean, const float* d_norm_std,
+                           double norm_clip, const float* d_observations, const float* d_actions,
+                           const float* d_next_observations, const float* d_rewards,
+                           const float* d_discounts, const float* d_eps, float* d_grad_sums, int32_t B,
+                           int32_t O, int32_t H, int32_t A, double entropy_coeff, double noise_scale,
+                           double noise_clip, const tonic_critic_loss_t* loss, void* d_workspace,
+                           int64_t workspace_bytes, void* stream);
+
 /* replaces: kind 0 DeterministicPolicyGradient.__call__ on critic_1 (tonic/torch/updaters/
  *   actors.py:170-189, td3.py:36), kind 1 TwinCriticSoftDeterministicPolicyGradient.__call__
  *   (actors.py:238-267).  Critics are frozen (no weight gradients).  Output: gradient SUMS for
@@ -860,6 +892,7 @@ typedef struct tonic_q_iteration_t {
                                   launch, into set ahead->slot (the other one).  Only when this iteration does not
                                   step the actor (actor_due = 0: delayed updates, td3.py:43-46) and
                                   tonic_q_iteration_ahead_supported says so; the next call then passes stage = 2.   */
+  tonic_critic_loss_t critic_loss;   /* the critic step's loss (all-zero: MSE), every phase and stage             */
 } tonic_q_iteration_t;
 
 int64_t tonic_q_iteration_workspace_bytes(int32_t B, int32_t O, int32_t A, int32_t H);
@@ -945,7 +978,7 @@ int tonic_distributional_actor_grad(const float* d_actor_params, const float* d_
  *
  * tonic_expected_sarsa_grad — ExpectedSARSA.__call__ (updaters/critics.py:253-282) up to the
  *   optimizer step: returns = r + discount * mean_s target_critic(s', a'_s), a'_s ~ target_actor(s');
- *   MSE against critic(s, a).  Output: gradient SUMS of the critic + {sq_err_sum, q_sum, 0, 0, 0, B, 0, 0}.
+ *   MSE against critic(s, a).  Output: gradient SUMS of the critic + {loss_term_sum, q_sum, 0, 0, 0, B, 0, 0}.
  * tonic_mpo_actor_grad — MaximumAPosterioriPolicyOptimization.__call__ (updaters/actors.py:318-464)
  *   up to the optimizer steps, per-dimension KL constraints: E-step weights softmax_s(Q / temperature)
  *   (+ the action-bound penalty weights), decomposed fixed-std / fixed-mean policy losses, the
@@ -966,6 +999,17 @@ int tonic_expected_sarsa_grad(const float* d_target_actor, const float* d_target
                               const float* d_discounts, const float* d_eps, float* d_grad_sums,
                               int32_t B, int32_t O, int32_t H, int32_t A, int32_t S,
                               void* d_workspace, int64_t workspace_bytes, void* stream);
+/* ... under `loss` (tonic_critic_loss_t; critics.py:243 calls self.loss with returns first: every rule served is
+ * symmetric in the error).  NULL: MSE, the same launches and bits as tonic_expected_sarsa_grad. */
+int tonic_expected_sarsa_grad_loss(const float* d_target_actor, const float* d_target_critic,
+                                   const float* d_critic, const float* d_norm_mean,
+                                   const float* d_norm_std, double norm_clip,
+                                   const float* d_observations, const float* d_actions,
+                                   const float* d_next_observations, const float* d_rewards,
+                                   const float* d_discounts, const float* d_eps, float* d_grad_sums,
+                                   int32_t B, int32_t O, int32_t H, int32_t A, int32_t S,
+                                   const tonic_critic_loss_t* loss, void* d_workspace,
+                                   int64_t workspace_bytes, void* stream);
 int tonic_mpo_actor_grad(const float* d_actor_params, const float* d_target_actor,
                          const float* d_target_critic, float* d_duals, double min_log_dual,
                          const float* d_norm_mean, const float* d_norm_std, double norm_clip,

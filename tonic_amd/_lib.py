@@ -31,6 +31,14 @@ OPTIMIZER_KINDS = {'adam': 0, 'adamw': 1, 'sgd': 2, 'rmsprop': 3}               
 OPTIMIZER_FLAGS = {'amsgrad': 1, 'nesterov': 2, 'centered': 4, 'maximize': 8}     # TONIC_OPT_AMSGRAD ..
 
 
+class CriticLoss(ctypes.Structure):
+    """tonic_critic_loss_t of include/tonic_hip.h (field for field); all-zero: MSE."""
+    _fields_ = [('kind', c_i32), ('reserved', c_i32), ('param', c_f64)]
+
+
+CRITIC_LOSS_KINDS = {'mse': 0, 'l1': 1, 'smooth_l1': 2, 'huber': 3}                # TONIC_LOSS_MSE ..
+
+
 class QStore(ctypes.Structure):
     """tonic_q_store_t of include/tonic_hip.h (field for field)."""
     _fields_ = [('d_buf_observations', c_vp), ('d_buf_actions', c_vp), ('d_buf_next_observations', c_vp),
@@ -54,7 +62,8 @@ class QIteration(ctypes.Structure):
                 ('noise_scale', c_f64), ('noise_clip', c_f64), ('target_coeff', c_f64),
                 ('critic', QOptimizer), ('actor', QOptimizer),
                 ('d_workspace', c_vp), ('workspace_bytes', c_i64), ('phase', c_i32),
-                ('refresh_images', c_i32), ('stage', c_i32), ('slot', c_i32), ('ahead', ctypes.c_void_p)]
+                ('refresh_images', c_i32), ('stage', c_i32), ('slot', c_i32), ('ahead', ctypes.c_void_p),
+                ('critic_loss', CriticLoss)]
 
 
 # name -> (restype, argtypes); mirrors include/tonic_hip.h one to one.
@@ -151,6 +160,9 @@ SIGNATURES = {
     'tonic_twin_q_grad': (ctypes.c_int, [c_i32] + [c_vp] * 5 + [c_f64] + [c_vp] * 7 + [c_i32] * 4 +
                           [c_f64] * 3 +
                           [c_vp, c_i64, c_vp]),
+    'tonic_critic_loss_check': (ctypes.c_int, [c_vp]),
+    'tonic_twin_q_grad_loss': (ctypes.c_int, [c_i32] + [c_vp] * 5 + [c_f64] + [c_vp] * 7 + [c_i32] * 4 +
+                               [c_f64] * 3 + [c_vp, c_vp, c_i64, c_vp]),
     'tonic_actor_q_grad': (ctypes.c_int, [c_i32] + [c_vp] * 4 + [c_f64] + [c_vp] * 3 + [c_i32] * 4 +
                            [c_f64] +
                            [c_vp, c_i64, c_vp]),
@@ -162,6 +174,8 @@ SIGNATURES = {
     'tonic_mpo_workspace_bytes': (c_i64, [c_i32] * 5),
     'tonic_expected_sarsa_grad': (ctypes.c_int, [c_vp] * 5 + [c_f64] + [c_vp] * 7 + [c_i32] * 5 +
                                   [c_vp, c_i64, c_vp]),
+    'tonic_expected_sarsa_grad_loss': (ctypes.c_int, [c_vp] * 5 + [c_f64] + [c_vp] * 7 + [c_i32] * 5 +
+                                       [c_vp, c_vp, c_i64, c_vp]),
     'tonic_mpo_actor_grad': (ctypes.c_int, [c_vp] * 4 + [c_f64] + [c_vp] * 2 + [c_f64] + [c_vp] * 5 +
                              [c_i32] * 5 + [c_f64] * 4 + [c_i32] + [c_vp, c_i64, c_vp]),
     'tonic_mpo_actor_grad_shard': (ctypes.c_int, [c_vp] * 4 + [c_f64] + [c_vp] * 2 + [c_f64] + [c_vp] * 4 +
@@ -210,7 +224,7 @@ SIGNATURES = {
 }
 
 
-ABI_VERSION = 15       # include/tonic_hip.h: tonic_abi_version()
+ABI_VERSION = 16       # include/tonic_hip.h: tonic_abi_version()
 
 
 class TonicHipError(RuntimeError):

@@ -176,8 +176,8 @@ struct MlpBwdArgs {
   // heads == 0, loss != LOSS_GIVEN: dq is formed HERE from the forward outputs — the element-wise
   // loss of the step folded into its backward launch (one launch and one pass over q less) — and
   // written to dq for the weight-gradient GEMM; workgroup (0, 0) also folds the logged sums.
-  //   LOSS_TD     y = r + disc * (min over the target critics - alpha * logp'), dq_z = 2 (q_z - y)
-  //               (critics.py:72-79, 166-175, 219-227); stats {sq_err_sum, q1_sum, q2_sum, 0, 0, B, 0, 0}
+  //   LOSS_TD     y = r + disc * (min over the target critics - alpha * logp'), dq_z = loss'(q_z - y)
+  //               (critics.py:72-79, 166-175, 219-227; MSE: 2 (q_z - y)); stats {loss_term_sum, q1_sum, q2_sum, 0, 0, B, 0, 0}
   //   LOSS_ACTOR  SAC: alpha * logp - min(q1, q2); TD3 / DDPG: -q1 (actors.py:177-179, 254-257);
   //               dq_z = -1 on the smaller critic (-1/2 each on ties); stats {loss_sum, 0, ..., B, ..}
   int loss;
@@ -185,6 +185,7 @@ struct MlpBwdArgs {
   const float* l_q; float* l_stats;
   float l_alpha;
   int l_nets, l_Bp;
+  int l_kind; float l_param;   // LOSS_TD: the critic's loss on q_z - y (critic_loss_term / critic_loss_dq; 0: MSE)
   ValueLines l_tq_at, l_q_at;   // where value z of row r lives in l_tq / l_q (dense: {Bp, 16})
   // heads >= 1, hb_dxa0 != null: the gradients at the head outputs are not given but FORMED here
   // from the critics' action-column input gradients (actor_head_backward_kernel folded into this
@@ -268,6 +269,32 @@ __device__ __forceinline__ float td_target(const float* rewards, const float* di
   float next = fminf(both[0], both[1]);
   if (logp_next) next = next - alpha * logp_next[m];
   return rewards[m] + discounts[m] * next;
+}
+
+// The critic's loss on one error e = q - y (tonic_critic_loss_t: torch.nn.functional.{mse,l1,smooth_l1,huber}_loss
+// and their backward, float32; `param` = beta / delta rounded once by the host).  The ONLY two places that know
+// what the TD loss is: critic_loss_kernel, mlp_loss_stats and the LOSS_TD branches of both backward bodies call
+// them, so the split entries and the fused iteration keep the same bits.  `kind` / `param` are kernel arguments
+// (wave-uniform: the branch is scalar).  A NaN error: every term is NaN; the gradient is NaN except where the
+// rule is the sign alone (L1, smooth-L1 with beta = 0), which gives 0 — as torch does.
+struct CriticLoss { int kind; float param; };
+__device__ __forceinline__ float critic_loss_term(float e, int kind, float param) {
+  if (kind == TONIC_LOSS_MSE) return e * e;
+  const float z = fabsf(e);
+  if (kind == TONIC_LOSS_HUBER) return z < param ? 0.5f * e * e : param * (z - 0.5f * param);
+  if (kind == TONIC_LOSS_SMOOTH_L1 && param > 0.f) return z < param ? 0.5f * e * e / param : z - 0.5f * param;
+  return z;
+}
+// d term / d q (unscaled by 1 / B)
+__device__ __forceinline__ float critic_loss_dq(float e, int kind, float param) {
+  if (kind == TONIC_LOSS_MSE) return 2.f * e;
+  if (kind == TONIC_LOSS_HUBER) return e <= -param ? -param : e >= param ? param : e;
+  if (kind == TONIC_LOSS_SMOOTH_L1 && param > 0.f) return e <= -param ? -1.f : e >= param ? 1.f : e / param;
+  return (float)(e > 0.f) - (float)(e < 0.f);
+}
+// NULL / all-zero: MSE
+inline CriticLoss critic_loss_rule(const tonic_critic_loss_t* loss) {
+  return loss == nullptr ? CriticLoss{TONIC_LOSS_MSE, 0.f} : CriticLoss{loss->kind, (float)loss->param};
 }
 
 // d (actor objective) / d q_z of one sample (shared by actor_loss_kernel and the folded form)

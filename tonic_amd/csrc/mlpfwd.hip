@@ -562,12 +562,12 @@ __device__ __forceinline__ void mlp_loss_stats(const MlpBwdArgs& a) {
                                 a.l_nets, co);
       const float q1 = load_shared(a.l_q + a.l_q_at.index(0, r), co);
       const float e1 = q1 - y;
-      float sq = e1 * e1;
+      float sq = critic_loss_term(e1, a.l_kind, a.l_param);
       s1 += q1;
       if (a.l_nets == 2) {
         const float q2 = load_shared(a.l_q + a.l_q_at.index(1, r), co);
         const float e2 = q2 - y;
-        sq = sq + e2 * e2;
+        sq = sq + critic_loss_term(e2, a.l_kind, a.l_param);
         s2 += q2;
       }
       s0 += sq;
@@ -726,7 +726,7 @@ __device__ __forceinline__ void mlp_backward_body(const MlpBwdArgs& a, const int
       if (a.loss == LOSS_TD) {
         const float y = td_target(a.l_rewards, a.l_discounts, a.l_tq, a.l_logp, a.l_alpha, row,
                                   a.l_tq_at, a.l_nets, co);
-        dq = 2.f * (load_shared(a.l_q + a.l_q_at.index(net, row), co) - y);
+        dq = critic_loss_dq(load_shared(a.l_q + a.l_q_at.index(net, row), co) - y, a.l_kind, a.l_param);
       } else {
         dq = actor_dq(a.l_q, row, a.l_q_at, a.l_nets == 2, net, co);
       }

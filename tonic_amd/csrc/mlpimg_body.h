@@ -556,7 +556,7 @@ __device__ __forceinline__ void mlp_backward_body_img(const MlpBwdArgs& a, const
       if (a.loss == LOSS_TD) {
         const float y = td_target(a.l_rewards, a.l_discounts, a.l_tq, a.l_logp, a.l_alpha, row, a.l_tq_at,
                                   a.l_nets, co);
-        dq = 2.f * (load_shared(a.l_q + a.l_q_at.index(net, row), co) - y);
+        dq = critic_loss_dq(load_shared(a.l_q + a.l_q_at.index(net, row), co) - y, a.l_kind, a.l_param);
       } else {
         dq = actor_dq(a.l_q, row, a.l_q_at, a.l_nets == 2, net, co);
       }

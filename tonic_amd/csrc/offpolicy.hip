@@ -203,26 +203,26 @@ __global__ void copy_actions_kernel(const float* loc, int ld, float* act, int B,
 }
 
 // y = r + disc * (min(q1', q2') - alpha * logp')  (critics.py:219-221; alpha = 0 and logp = null
-// give TD3's critics.py:166-167), then dq_z = 2 (q_z - y) and the statistics.
-// nets == 1 (DDPG, critics.py:72-79): y = r + disc * q', one critic, statistics {sq_err, q, 0}.
+// give TD3's critics.py:166-167), then dq_z = loss'(q_z - y) (critic_loss_dq, mlpfwd.h; MSE: 2 (q_z - y)) and the
+// statistics.  nets == 1 (DDPG, critics.py:72-79): y = r + disc * q', one critic, statistics {loss_terms, q, 0}.
 __global__ void critic_loss_kernel(const float* rewards, const float* discounts,
                                    const float* tq, const float* logp_next, float alpha,
                                    const float* q, float* dq, float* stats, int B, int Bp,
-                                   int nets) {
+                                   int nets, CriticLoss loss) {
   float s_loss = 0.f, s_q1 = 0.f, s_q2 = 0.f;
   for (int m = threadIdx.x; m < B; m += blockDim.x) {
     const float y = td_target(rewards, discounts, tq, logp_next, alpha, m, ValueLines{Bp, 16}, nets);
     if (nets == 1) {
       const float e1 = q[m] - y;
-      dq[m] = 2.f * e1;
-      s_loss += e1 * e1;
+      dq[m] = critic_loss_dq(e1, loss.kind, loss.param);
+      s_loss += critic_loss_term(e1, loss.kind, loss.param);
       s_q1 += q[m];
       continue;
     }
     const float e1 = q[m] - y, e2 = q[Bp + m] - y;
-    dq[m] = 2.f * e1;
-    dq[Bp + m] = 2.f * e2;
-    s_loss += e1 * e1 + e2 * e2;
+    dq[m] = critic_loss_dq(e1, loss.kind, loss.param);
+    dq[Bp + m] = critic_loss_dq(e2, loss.kind, loss.param);
+    s_loss += critic_loss_term(e1, loss.kind, loss.param) + critic_loss_term(e2, loss.kind, loss.param);
     s_q1 += q[m];
     s_q2 += q[Bp + m];
   }
@@ -937,6 +937,7 @@ struct StepLoss {
   const float* rewards; const float* discounts; const float* tq; const float* logp;
   float alpha;
   const float* q; float* stats;
+  CriticLoss rule;                            // LOSS_TD: tonic_critic_loss_t (all-zero: MSE)
 };
 
 // The one-launch chain's arguments (mlp_backward_supported(H, 1, 0, dxa ? A : 0)).
@@ -952,6 +953,7 @@ MlpBwdArgs critics_chain_args(const float* params, CriticShape s, int nets, int 
     b.l_tq = loss->tq; b.l_logp = loss->logp; b.l_alpha = loss->alpha; b.l_q = loss->q;
     b.l_stats = loss->stats; b.l_nets = nets; b.l_Bp = Bp;
     b.l_tq_at = b.l_q_at = ValueLines{Bp, 16};
+    b.l_kind = loss->rule.kind; b.l_param = loss->rule.param;
   }
   b.W2 = params + o.W2; b.W1 = params + o.W1; b.K1 = s.O + s.A; b.ldw1 = o.ld1; b.ldw2 = o.ldH;
   b.xa_first = s.O; b.xa_count = dxa ? s.A : 0;
@@ -1010,7 +1012,7 @@ int critics_backward(const float* params, CriticShape s, int nets, const float* 
     if (loss->kind == LOSS_TD) {
       hipLaunchKernelGGL(critic_loss_kernel, dim3(1), dim3(1024), 0, st, loss->rewards,
                          loss->discounts, loss->tq, loss->logp, loss->alpha, loss->q, dq,
-                         loss->stats, B, Bp, nets);
+                         loss->stats, B, Bp, nets, loss->rule);
     } else {
       hipLaunchKernelGGL(actor_loss_kernel, dim3(1), dim3(1024), 0, st, loss->q, loss->logp,
                          loss->alpha, nets == 2 ? 1 : 0, dq, loss->stats, B, Bp);
@@ -1271,6 +1273,23 @@ extern "C" int tonic_collector_q_act(tonic_collector_t* collector, const float* 
 // ONE critic, target actor, no noise; gradient sums for [critic] + 8 statistics).  Writes gradient SUMS
 // for [critic_1 | critic_2] + 8 statistics {sq_err_sum(both), q1_sum, q2_sum, 0, 0, B, 0, 0}
 // into d_grad_sums; the caller follows with tonic_adam_step(grad_scale = 1/B).
+// The rule of `loss=` (tonic_critic_loss_t): host-only validation.  NULL: MSE.
+extern "C" int tonic_critic_loss_check(const tonic_critic_loss_t* loss) {
+  if (loss == nullptr) return TONIC_OK;
+  const int kind = loss->kind;
+  TONIC_REQUIRE(kind >= TONIC_LOSS_MSE && kind <= TONIC_LOSS_HUBER, TONIC_ERR_INVALID_ARGUMENT,
+                "tonic_critic_loss_t: unknown kind %d (0 MSE, 1 L1, 2 smooth-L1, 3 Huber)", kind);
+  if (kind == TONIC_LOSS_MSE || kind == TONIC_LOSS_L1) return TONIC_OK;      // (param is ignored)
+  const float param = (float)loss->param;             // what the kernels see
+  TONIC_REQUIRE(param - param == 0.f, TONIC_ERR_INVALID_ARGUMENT, "tonic_critic_loss_t: %s = %g is not finite",
+                kind == TONIC_LOSS_HUBER ? "delta" : "beta", loss->param);
+  TONIC_REQUIRE(kind != TONIC_LOSS_SMOOTH_L1 || param >= 0.f, TONIC_ERR_INVALID_ARGUMENT,
+                "tonic_critic_loss_t: smooth-L1 needs beta >= 0, got %g", loss->param);
+  TONIC_REQUIRE(kind != TONIC_LOSS_HUBER || param > 0.f, TONIC_ERR_INVALID_ARGUMENT,
+                "tonic_critic_loss_t: Huber needs delta > 0, got %g", loss->param);
+  return TONIC_OK;
+}
+
 extern "C" int tonic_twin_q_grad(int32_t kind, const float* d_policy_params,
                                  const float* d_target_critics, const float* d_critics,
                                  const float* d_norm_mean, const float* d_norm_std,
@@ -1281,6 +1300,25 @@ extern "C" int tonic_twin_q_grad(int32_t kind, const float* d_policy_params,
                                  float* d_grad_sums, int32_t B, int32_t O, int32_t H, int32_t A,
                                  double entropy_coeff, double noise_scale, double noise_clip,
                                  void* d_workspace, int64_t workspace_bytes, void* stream) {
+  return tonic_twin_q_grad_loss(kind, d_policy_params, d_target_critics, d_critics, d_norm_mean, d_norm_std,
+                                norm_clip, d_observations, d_actions, d_next_observations, d_rewards, d_discounts,
+                                d_eps, d_grad_sums, B, O, H, A, entropy_coeff, noise_scale, noise_clip, nullptr,
+                                d_workspace, workspace_bytes, stream);
+}
+
+// ... with the critic's loss (`loss=` of the reference's updaters, critics.py:58,142,189): NULL = MSE
+extern "C" int tonic_twin_q_grad_loss(int32_t kind, const float* d_policy_params,
+                                      const float* d_target_critics, const float* d_critics,
+                                      const float* d_norm_mean, const float* d_norm_std,
+                                      double norm_clip,
+                                      const float* d_observations, const float* d_actions,
+                                      const float* d_next_observations, const float* d_rewards,
+                                      const float* d_discounts, const float* d_eps,
+                                      float* d_grad_sums, int32_t B, int32_t O, int32_t H, int32_t A,
+                                      double entropy_coeff, double noise_scale, double noise_clip,
+                                      const tonic_critic_loss_t* loss,
+                                      void* d_workspace, int64_t workspace_bytes, void* stream) {
+  TRY(tonic_critic_loss_check(loss));
   TONIC_REQUIRE(d_policy_params && d_target_critics && d_critics && d_norm_mean && d_norm_std &&
                     d_observations && d_actions && d_next_observations && d_rewards &&
                     d_discounts && (d_eps || kind == 2) && d_grad_sums && d_workspace && B > 0 &&
@@ -1358,7 +1396,7 @@ extern "C" int tonic_twin_q_grad(int32_t kind, const float* d_policy_params,
   TRY(critics_forward(d_target_critics, cs, nets, X, ldx, B, Bp, h1_all, h2_all, q_all, st,
                       d_critics, X2, im.on ? &im.target_critics : nullptr));
   const StepLoss td{LOSS_TD, d_rewards, d_discounts, tq, kind == 1 ? logp : (const float*)nullptr,
-                    (float)entropy_coeff, q, d_grad_sums + nets * Pc};
+                    (float)entropy_coeff, q, d_grad_sums + nets * Pc, critic_loss_rule(loss)};
   TRY(critics_backward(d_critics, cs, nets, X2, ldx, B, Bp, c_h1, c_h2, dq, dh2, dh1, d_grad_sums,
                        nullptr, st, &td, nullptr, im.on ? &im.critics : nullptr));
   TONIC_CHECK_LAUNCH("tonic_twin_q_grad");
@@ -1539,6 +1577,7 @@ extern "C" int tonic_q_iteration_supported(int32_t O, int32_t H, int32_t A, int3
 extern "C" int tonic_q_iteration(const tonic_q_iteration_t* it, void* stream) {
   TONIC_REQUIRE(it != nullptr, TONIC_ERR_INVALID_ARGUMENT, "tonic_q_iteration: null arguments");
   const tonic_q_iteration_t& a = *it;
+  TRY(tonic_critic_loss_check(&a.critic_loss));
   const int kind = a.kind, B = a.B, O = a.O, H = a.H, A = a.A;
   const bool due = a.actor_due != 0;
   const int phase = a.phase;                 // 0 whole iteration | 1 critic half | 2 actor half (sums only)
@@ -1689,7 +1728,7 @@ extern "C" int tonic_q_iteration(const tonic_q_iteration_t* it, void* stream) {
   }
   const StepLoss td{LOSS_TD, a.d_rewards, a.d_discounts, tq,
                     kind == 1 ? logp_next : (const float*)nullptr, (float)a.critic_entropy_coeff, q,
-                    a.critic.d_grad_sums + nets * Pc};
+                    a.critic.d_grad_sums + nets * Pc, critic_loss_rule(&a.critic_loss)};
   const AdamFold* critic_fold = phase == 0 ? &cf : nullptr;       // phases: gradient sums only
   if (phase == 2) {
     // (the critic half ran in an earlier call)
@@ -1976,6 +2015,20 @@ extern "C" int tonic_expected_sarsa_grad(
     const float* d_rewards, const float* d_discounts, const float* d_eps, float* d_grad_sums,
     int32_t B, int32_t O, int32_t H, int32_t A, int32_t S, void* d_workspace,
     int64_t workspace_bytes, void* stream) {
+  return tonic_expected_sarsa_grad_loss(d_target_actor, d_target_critic, d_critic, d_norm_mean, d_norm_std, norm_clip,
+                                        d_observations, d_actions, d_next_observations, d_rewards, d_discounts, d_eps,
+                                        d_grad_sums, B, O, H, A, S, nullptr, d_workspace, workspace_bytes, stream);
+}
+
+// ... with the critic's loss (critics.py:243: `self.loss(returns, values)`, symmetric in the error): NULL = MSE
+extern "C" int tonic_expected_sarsa_grad_loss(
+    const float* d_target_actor, const float* d_target_critic, const float* d_critic,
+    const float* d_norm_mean, const float* d_norm_std, double norm_clip,
+    const float* d_observations, const float* d_actions, const float* d_next_observations,
+    const float* d_rewards, const float* d_discounts, const float* d_eps, float* d_grad_sums,
+    int32_t B, int32_t O, int32_t H, int32_t A, int32_t S, const tonic_critic_loss_t* loss, void* d_workspace,
+    int64_t workspace_bytes, void* stream) {
+  TRY(tonic_critic_loss_check(loss));
   TONIC_REQUIRE(d_target_actor && d_target_critic && d_critic && d_norm_mean && d_norm_std &&
                     d_observations && d_actions && d_next_observations && d_rewards &&
                     d_discounts && d_eps && d_grad_sums && d_workspace && B > 0 && S >= 1 &&
@@ -1996,7 +2049,7 @@ extern "C" int tonic_expected_sarsa_grad(
                      w.X2, B, O, A, ldx);
   TRY(critics_forward(d_critic, cs, 1, w.X2, ldx, B, Bp, w.c_h1, w.c_h2, w.q, st));
   const StepLoss td{LOSS_TD, d_rewards, d_discounts, w.tq_mean, nullptr, 0.f, w.q,
-                    d_grad_sums + critic_count(cs)};
+                    d_grad_sums + critic_count(cs), critic_loss_rule(loss)};
   TRY(critics_backward(d_critic, cs, 1, w.X2, ldx, B, Bp, w.c_h1, w.c_h2, w.dq, w.dh2, w.dh1,
                        d_grad_sums, nullptr, st, &td));
   TONIC_CHECK_LAUNCH("tonic_expected_sarsa_grad");

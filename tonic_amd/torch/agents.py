@@ -1673,6 +1673,7 @@ class DDPG(Agent):
             actor=optimizer(actor, self._infos[1, iteration],
                             self._static_adam[iteration, 1] if phase == 0 else None),
             d_workspace=p(ws), workspace_bytes=ws.numel(), phase=phase, stage=stage, slot=slot,
+            critic_loss=critic.loss_rule,
             # the workspace's fp16x2 weight images follow the optimizer epilogues INSIDE an update call; between
             # calls anybody may have written parameters (load_state_dict, another path): rebuilt on iteration 0
             refresh_images=int(iteration == 0 or phase != 0))
@@ -1682,7 +1683,9 @@ class DDPG(Agent):
         for updater in (self.actor_updater, self.critic_updater):
             hyper = updater.hyper
             noise = getattr(updater, 'target_action_noise', None)
+            rule = getattr(updater, 'loss_rule', None)
             parts.append((tuple(sorted(hyper.items())),
+                          (rule.kind, rule.param) if rule is not None else None,
                           float(getattr(updater, 'entropy_coeff', 0.0)),
                           float(getattr(updater, 'gradient_clip', 0.0) or 0.0),
                           (noise.scale, noise.clip) if noise is not None else None))

@@ -91,6 +91,49 @@ def optimizer_rule(rule):
                           alpha=rule.get('alpha', 0.0))
 
 
+_CRITIC_LOSSES = {torch.nn.MSELoss: ('mse', None), torch.nn.L1Loss: ('l1', None),
+                  torch.nn.SmoothL1Loss: ('smooth_l1', 'beta'), torch.nn.HuberLoss: ('huber', 'delta')}
+
+
+def critic_loss_rule(loss):
+    """The reference-style ``loss=`` of the off-policy critic updaters (critics.py:58,142,189,243) as the
+    tonic_critic_loss_t of the C ABI: exactly torch.nn.MSELoss (and None, the default), L1Loss, SmoothL1Loss(beta)
+    and HuberLoss(delta) with reduction 'mean' run on the HIP engine; `param` is beta / delta as the float32 the
+    kernels compare with.  A subclass, any other module or callable, or another reduction is rejected by name."""
+    if loss is None:
+        return _lib.CriticLoss()
+    served = 'the critic losses served are torch.nn.MSELoss, L1Loss, SmoothL1Loss and HuberLoss with ' \
+             "reduction='mean'"
+    entry = _CRITIC_LOSSES.get(type(loss))
+    if entry is None:
+        name = f'{type(loss).__module__}.{type(loss).__qualname__}' if isinstance(loss, torch.nn.Module) else \
+            repr(loss)
+        raise NotImplementedError(f'loss={name} does not run on the HIP engine: {served}')
+    if loss.reduction != 'mean':
+        raise NotImplementedError(f"{type(loss).__name__}(reduction={loss.reduction!r}) does not run on the HIP "
+                                  f'engine: {served}')
+    kind, key = entry
+    param = float(np.float32(getattr(loss, key))) if key else 0.0
+    rule = _lib.CriticLoss(kind=_lib.CRITIC_LOSS_KINDS[kind], param=param)
+    lib = _lib.load()
+    if lib.tonic_critic_loss_check(ctypes.byref(rule)) != 0:
+        raise NotImplementedError(f'loss={loss!r}: {lib.tonic_last_error().decode()}')
+    return rule
+
+
+def critic_loss_sum(rule, values, returns):
+    """The SUM over the batch of the rule's loss terms as stock torch operators (the stock-torch updaters divide
+    by the global batch size themselves)."""
+    functional = torch.nn.functional
+    if rule.kind == _lib.CRITIC_LOSS_KINDS['mse']:
+        return ((values - returns) ** 2).sum()
+    if rule.kind == _lib.CRITIC_LOSS_KINDS['l1']:
+        return functional.l1_loss(values, returns, reduction='sum')
+    if rule.kind == _lib.CRITIC_LOSS_KINDS['smooth_l1']:
+        return functional.smooth_l1_loss(values, returns, reduction='sum', beta=rule.param)
+    return functional.huber_loss(values, returns, reduction='sum', delta=rule.param)
+
+
 def optimizer_slots(lib, rule, count, device):
     """(tonic_optimizer_t, its zeroed state buffers as ONE tensor of slots x count floats, None without state)."""
     packed = optimizer_rule(rule)
@@ -1060,6 +1103,17 @@ class _TwinCriticQLearning(_QUpdater):
     stats_kind = 3          # {loss, q1 mean, q2 mean}
     default_lr = 1e-3
     kind = 0
+    loss_rule = _lib.CriticLoss()       # MSE (the distributional critic has no `loss`)
+
+    @property
+    def loss(self):
+        """critics.py:58: the loss object as given (None: MSE); assigning one that is not served raises."""
+        return self._loss
+
+    @loss.setter
+    def loss(self, loss):
+        self.loss_rule = critic_loss_rule(loss)
+        self._loss = loss
 
     def initialize(self, model):
         self._shapes(model)
@@ -1101,7 +1155,7 @@ class _TwinCriticQLearning(_QUpdater):
         self.torch_optimizer.zero_grad()
         critics = (model.critic_1, model.critic_2) if twin else (model.critic,)
         values = [critic(batch['observations'], batch['actions']) for critic in critics]
-        loss = sum(((v - returns) ** 2).sum() for v in values) / n
+        loss = sum(critic_loss_sum(self.loss_rule, v, returns) for v in values) / n
         loss.backward()
         row = torch.stack([loss.detach()] + [v.detach().sum() / n for v in values])
         if parallel.exchanging():
@@ -1124,15 +1178,15 @@ class _TwinCriticQLearning(_QUpdater):
         mean, std = self.norm_tensors()
         noise = getattr(self, 'target_action_noise', None)
         p = _lib.ptr
-        _lib.check(self.lib.tonic_twin_q_grad(
+        _lib.check(self.lib.tonic_twin_q_grad_loss(
             self.kind, p(self._policy_params()), p(self.model.flat_target_critics.flat),
             p(self.flat.flat), p(mean), p(std), self.norm_clip(), p(batch['observations']),
             p(batch['actions']),
             p(batch['next_observations']), p(batch['rewards']), p(batch['discounts']), p(eps),
             p(self.grad_sums), B, self.observation_size, self.hidden, self.action_size,
             float(getattr(self, 'entropy_coeff', 0.0)), float(noise.scale if noise else 0.0),
-            float(noise.clip if noise else 0.0), p(ws), ws.numel(), _lib.current_stream()),
-            'tonic_twin_q_grad')
+            float(noise.clip if noise else 0.0), ctypes.addressof(self.loss_rule), p(ws), ws.numel(),
+            _lib.current_stream()), 'tonic_twin_q_grad_loss')
         self._step(n_global or B * self.world_size, info_row)
 
     def __call__(self, observations, actions, next_observations, rewards, discounts):
@@ -1149,7 +1203,7 @@ class DeterministicQLearning(_TwinCriticQLearning):
     kind, default_lr = 2, 1e-3
 
     def __init__(self, loss=None, optimizer=None, gradient_clip=0):
-        _check_plain(loss, gradient_clip)
+        self.loss = loss
         self.optimizer = optimizer
         self.gradient_clip = gradient_clip
 
@@ -1168,7 +1222,7 @@ class TwinCriticDeterministicQLearning(_TwinCriticQLearning):
     kind, default_lr = 0, 1e-3
 
     def __init__(self, loss=None, optimizer=None, target_action_noise=None, gradient_clip=0):
-        _check_plain(loss, gradient_clip)
+        self.loss = loss
         self.optimizer = optimizer
         self.gradient_clip = gradient_clip
         self.target_action_noise = target_action_noise or TargetActionNoise(scale=0.2, clip=0.5)
@@ -1182,7 +1236,7 @@ class TwinCriticSoftQLearning(_TwinCriticQLearning):
     kind, default_lr = 1, 3e-4
 
     def __init__(self, loss=None, optimizer=None, entropy_coeff=0.2, gradient_clip=0):
-        _check_plain(loss, gradient_clip)
+        self.loss = loss
         self.optimizer = optimizer
         self.gradient_clip = gradient_clip
         self.entropy_coeff = entropy_coeff
@@ -1234,7 +1288,7 @@ class ExpectedSARSA(_TwinCriticQLearning):
     stock_capable = False
 
     def __init__(self, num_samples=20, loss=None, optimizer=None, gradient_clip=0):
-        _check_plain(loss, gradient_clip)
+        self.loss = loss
         self.num_samples = num_samples
         self.optimizer = optimizer
         self.gradient_clip = gradient_clip
@@ -1252,13 +1306,13 @@ class ExpectedSARSA(_TwinCriticQLearning):
         ws = self._offpolicy_workspace(B)
         mean, std = self.norm_tensors()
         p = _lib.ptr
-        _lib.check(self.lib.tonic_expected_sarsa_grad(
+        _lib.check(self.lib.tonic_expected_sarsa_grad_loss(
             p(self.model.flat_target_actor.flat), p(self.model.flat_target_critics.flat),
             p(self.flat.flat), p(mean), p(std), self.norm_clip(), p(batch['observations']),
             p(batch['actions']), p(batch['next_observations']), p(batch['rewards']),
             p(batch['discounts']), p(eps), p(self.grad_sums), B, self.observation_size, self.hidden,
-            self.action_size, self.num_samples, p(ws), ws.numel(), _lib.current_stream()),
-            'tonic_expected_sarsa_grad')
+            self.action_size, self.num_samples, ctypes.addressof(self.loss_rule), p(ws), ws.numel(),
+            _lib.current_stream()), 'tonic_expected_sarsa_grad_loss')
         self._step(n_global or B, info_row)
 
     def __call__(self, observations, actions, next_observations, rewards, discounts):
@@ -1341,7 +1395,6 @@ class DeterministicPolicyGradient(_ActorQGradient):
     kind, default_lr = 0, 1e-3
 
     def __init__(self, optimizer=None, gradient_clip=0):
-        _check_plain(None, gradient_clip)
         self.optimizer = optimizer
         self.gradient_clip = gradient_clip
 
@@ -1393,7 +1446,6 @@ class MaximumAPosterioriPolicyOptimization(_ActorQGradient):
                  gradient_clip=0):
         if not per_dim_constraining:
             raise NotImplementedError('only per-dimension KL constraints are fused')
-        _check_plain(None, gradient_clip)
         self.num_samples = num_samples
         self.epsilon, self.epsilon_penalty = epsilon, epsilon_penalty
         self.epsilon_mean, self.epsilon_std = epsilon_mean, epsilon_std
@@ -1524,12 +1576,6 @@ class TwinCriticSoftDeterministicPolicyGradient(_ActorQGradient):
     kind, default_lr = 1, 3e-4
 
     def __init__(self, optimizer=None, entropy_coeff=0.2, gradient_clip=0):
-        _check_plain(None, gradient_clip)
         self.optimizer = optimizer
         self.gradient_clip = gradient_clip
         self.entropy_coeff = entropy_coeff
-
-
-def _check_plain(loss, gradient_clip):
-    if loss is not None and not isinstance(loss, torch.nn.MSELoss):
-        raise NotImplementedError('only the default MSE loss is fused')
