@@ -366,7 +366,8 @@ int tonic_adam_step_pair(
 /* The optimizer family behind `optimizer=lambda params: torch.optim.X(params, ...)` of every reference updater:
  * the single-tensor CPU paths of torch/optim/adam.py:395-547 (Adam with weight_decay / amsgrad / maximize, and
  * AdamW = decoupled weight decay, :419), sgd.py:343-380 and rmsprop.py:287-339 on the flat parameter block.  Plain
- * Adam stays on tonic_adam_step*.  WHICH float32 expression each rule is: tests/optim_family_ref.py.
+ * Adam is one of its rules: tonic_adam_step* are this step with their four numbers as the rule and their two
+ * moments as its state buffers.  WHICH float32 expression each rule is: tests/optim_family_ref.py.
  * Hyper-parameters are Python floats in torch: they arrive as float64 and every derived constant (1 - beta,
  * 1 - alpha, 1 - dampening, 1 - lr * weight_decay, the bias corrections) is formed in float64 and rounded once. */
 enum { TONIC_OPT_ADAM = 0, TONIC_OPT_ADAMW = 1, TONIC_OPT_SGD = 2, TONIC_OPT_RMSPROP = 3 };

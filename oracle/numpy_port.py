@@ -393,7 +393,7 @@ class AdamPort:
 
 
 def adam_statement_constants(step, lr, betas=(0.9, 0.999), eps=1e-8):
-    """The float32 scalars of optimizer step `step` (1-based) as ``adam_kernel`` (csrc/optim.hip) forms them:
+    """The float32 scalars of optimizer step `step` (1-based) as ``adam_step_consts`` (csrc/optim_rule.h) forms them:
     bias corrections and step size in float64 and only then rounded (``adam.py:530-536``,
     ``updaters.adam_step_constants``), the weights ``1 - beta`` subtracted in float64, then rounded.
     -> step_size, bias2_sqrt, w1, w2, beta2, eps (all float32)."""
@@ -404,8 +404,8 @@ def adam_statement_constants(step, lr, betas=(0.9, 0.999), eps=1e-8):
 
 
 def adam_statement(p, g_sum, m, v, step, grad_scale, lr, betas=(0.9, 0.999), eps=1e-8):
-    """THE float32 expression the HIP optimizer kernels are: ``adam_kernel`` (csrc/optim.hip) and
-    ``adam_element`` (csrc/gemm16.hip), operation by operation, in the kernels' order, every operation rounded to
+    """THE float32 expression the HIP optimizer kernels are: ``adam_element`` (csrc/optim_rule.h), which
+    ``optimizer_kernel`` (csrc/optim.hip) and the weight-gradient epilogue (csrc/gemm16.hip) call, operation by operation, in the kernels' order, every operation rounded to
     float32 once (no FMA: the library is built with -ffp-contract=off; divide and sqrt are correctly rounded).
     `g_sum` holds gradient SUMS, `grad_scale` turns them into means, `step` is the 1-based step being taken
     (``state[0] + 1``).  -> new p, m, v (float32).

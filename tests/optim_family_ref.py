@@ -1,4 +1,4 @@
-"""The float32 statements of the optimizer family (csrc/optim.hip: family_kernel behind tonic_optimizer_step), operation
+"""The float32 statements of the optimizer family (csrc/optim.hip: optimizer_kernel behind tonic_optimizer_step), operation
 by operation, in the kernels' order — what `numpy_port.adam_statement` is for plain Adam.  (oracle/ is frozen: these live
 with the tests.)
 
@@ -134,7 +134,7 @@ def _step(rule, p, g_sum, slots, step, grad_scale, T):
 
 
 def family_statement(rule, p, g_sum, slots, step, grad_scale):
-    """THE float32 expression family_kernel is for `rule` (module docstring).  `g_sum` holds gradient SUMS, `step` is the
+    """THE float32 expression optimizer_kernel is for `rule` (module docstring).  `g_sum` holds gradient SUMS, `step` is the
     1-based step being taken (state[0] + 1; SGD's momentum buffer starts at step 1).  -> new p, [new state buffers]."""
     return _step(rule, p, g_sum, slots, step, grad_scale, F32)
 

@@ -4,8 +4,8 @@ Each case names the constant in optim.hip that makes it what it is: whoever move
 
 | entry / kernel                | case                                    | decided by                                           |
 |-------------------------------|-----------------------------------------|------------------------------------------------------|
-| tonic_adam_step / adam_kernel | n = 1, 255, 256, 257                    | 256 threads: one ragged / full workgroup, two        |
-|                               | n = 32 768, 32 769                      | adam_blocks_for caps the grid at 128 workgroups:     |
+| tonic_adam_step / optimizer_  | n = 1, 255, 256, 257                    | 256 threads: one ragged / full workgroup, two        |
+| kernel<AdamRule<false>>       | n = 32 768, 32 769                      | adam_blocks_for caps the grid at 128 workgroups:     |
 |                               |                                         | the last size without and the first with a second    |
 |                               |                                         | pass of the grid-stride loop                         |
 |                               | n = 98 311                              | three passes, the last one ragged                    |
@@ -22,6 +22,8 @@ Each case names the constant in optim.hip that makes it what it is: whoever move
 | tonic_adam_polyak_step        | offset 0; block ending at total;        | workgroups >= adam_blocks update the targets OUTSIDE |
 |                               | block = whole buffer (extra = 0);       | the block, `extra` = ceil((total - n) / 256) capped  |
 |                               | total - n = 2048 x 256 + 777; (2, 1)    | at 2048: beyond it their loop strides                |
+| the Adam entries ==           | n = 1, 257, 32 769, 40 000; step 0, 999 | optim_fill: the entries' four numbers as the plain-  |
+| tonic_optimizer_step          | polyak: block last / whole              | Adam tonic_optimizer_t, their moments as slot 0, 1   |
 | tonic_clip_grad_norm          | n = 1, 7, 1023, 1024, 1025              | 1024 elements per partial workgroup: one, then two   |
 |                               | n = 65 536, 65 537                      | kClipBlocks = 64: slices of 1024, then of 1025 with  |
 |                               |                                         | a short last one                                     |
@@ -442,6 +444,150 @@ def test_adam_polyak_step_edges(lib, offset, n, total):
         assert state.tolist() == [k + 1, 0, STATE_MARK, 0], state
         assert same_bits(info, expected_row(4)[0]), info
     assert same_bits(net.p.read(), p), 'the block is updated in the online buffer, nowhere else'
+
+
+# ------------------------------------------------------------------ the Adam entries are the optimizer entry
+
+class SlotNet(Net):
+    """The same buffers with both moments in ONE allocation, as tonic_optimizer_step takes its state slots."""
+
+    def __init__(self, p, m, v, step=0):
+        super().__init__(p, m, v, step)
+        self.m = self.v = None
+        self.slots = Guarded(np.concatenate([m, v]))
+
+    def read(self):
+        assert same_bits(self.sums.read(), self.sums_host), 'the optimizer only READS the gradient sums'
+        slots = self.slots.read()
+        return self.p.read(), slots[:self.n], slots[self.n:], self.state.read(), self.info.read()
+
+
+def plain_adam_rule(lr=LR):
+    from tonic_amd.torch import updaters
+    rule = dict(kind='adam', lr=lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False, maximize=False)
+    assert updaters.plain_adam(rule)
+    return updaters.optimizer_rule(rule)
+
+
+def optimizer_step(lib, net, params, kind, kl_threshold=0.0, entropy_coeff=0.0, adv_stats=None, skip=None,
+                   polyak=(None, None, 0, 0, 0.0)):
+    import ctypes
+    from tonic_amd import _lib
+    rule = plain_adam_rule()
+    _lib.check(lib.tonic_optimizer_step(
+        params, net.sums.ptr(), net.slots.ptr(), net.state.ptr(), net.n, GRAD_SCALE, ctypes.byref(rule), kind,
+        kl_threshold, entropy_coeff, adv_stats, net.info.ptr(), skip, *polyak, None), 'tonic_optimizer_step')
+
+
+RESULT_NAMES = ('parameters', 'exp_avg', 'exp_avg_sq', 'state', 'info row')
+
+
+@pytest.mark.parametrize('start', [0, 999], ids=['from-zero', 'from-999'])
+@pytest.mark.parametrize('n', [1, 257, 32_769, 40_000])
+def test_adam_step_is_optimizer_step(lib, n, start):
+    """tonic_adam_step and tonic_optimizer_step with the plain-Adam rule from identical inputs — the PPO actor's
+    statistics (kind 1) with an adv_stats row, an info row and a skip pointer holding 0: parameters, both moments,
+    `state` and the info row equal bit for bit.  (Both are held to adam_statement elsewhere in this module and in
+    test_gpu_optim_family.py; this pins the wrappers' translation of arguments.)  32 768 = 128 workgroups x 256
+    threads: n = 32 769 is the first size at which one thread walks two elements."""
+    p, m, v, sums = adam_case(n, 1, 21, warm=start != 0)
+    adv = Guarded(np.array([0.0, 1.0, 0.0, 1.0], F32))
+    flag = Guarded(np.array([0], np.int32))
+    threshold, entropy_coeff = 0.0, 0.01                     # (kl = STATS[1] x scale > 0: the stop flag is raised)
+    entry, family = Net(p, m, v, step=start), SlotNet(p, m, v, step=start)
+    entry.load(sums[0])
+    family.load(sums[0])
+    adam_step(lib, entry, kind=1, kl_threshold=threshold, entropy_coeff=entropy_coeff, adv_stats=adv.ptr(),
+              skip=flag.ptr())
+    optimizer_step(lib, family, family.p.ptr(), 1, threshold, entropy_coeff, adv.ptr(), flag.ptr())
+    got, want = family.read(), entry.read()
+    for name, g, w in zip(RESULT_NAMES, got, want):
+        assert same_bits(g, w), f'n = {n}: {name} of tonic_optimizer_step differ from tonic_adam_step'
+    assert want[3].tolist() == [start + 1, 1, STATE_MARK, 0], want[3]
+    assert same_bits(want[4], expected_row(1, entropy_coeff=entropy_coeff, kl_threshold=threshold)[0]), want[4]
+    assert not same_bits(want[0], p) and not same_bits(want[1], m) and not same_bits(want[2], v)
+
+
+@pytest.mark.parametrize('offset,n,total', [(4000, 1000, 5000), (0, 5000, 5000)], ids=['block-last', 'block-whole'])
+def test_adam_polyak_step_is_optimizer_step(lib, offset, n, total):
+    """tonic_adam_polyak_step and tonic_optimizer_step with the plain-Adam rule and a target, from identical inputs:
+    the whole online buffer, both moments, `state`, the info row and EVERY target entry, inside and outside the
+    block, equal bit for bit."""
+    from tonic_amd import _lib
+    coeff = 0.005
+    p, m, v, sums = adam_case(n, 1, 22, warm=True)
+    rng = np.random.RandomState([offset, n, total])
+    online = rng.standard_normal(total).astype(F32)
+    online[offset:offset + n] = p
+    target = rng.standard_normal(total).astype(F32)
+    entry, family = Net(p, m, v, step=3), SlotNet(p, m, v, step=3)
+    buffers = []
+    for net in (entry, family):
+        net.load(sums[0])
+        d_online, d_target = Guarded(online), Guarded(target)
+        if net is entry:
+            _lib.check(lib.tonic_adam_polyak_step(
+                d_online.ptr(), net.sums.ptr(), net.m.ptr(), net.v.ptr(), net.state.ptr(), offset, n, total,
+                GRAD_SCALE, LR, 0.9, 0.999, 1e-8, 4, net.info.ptr(), d_target.ptr(), coeff, None),
+                'tonic_adam_polyak_step')
+        else:
+            optimizer_step(lib, net, d_online.ptr(offset), 4,
+                           polyak=(d_target.ptr(), d_online.ptr(), total, offset, coeff))
+        buffers.append((d_online.read(), d_target.read()) + net.read()[1:])
+    names = ('online buffer', 'target buffer') + RESULT_NAMES[1:]
+    for name, w, g in zip(names, *buffers):
+        assert same_bits(g, w), f'{name} of tonic_optimizer_step differ from tonic_adam_polyak_step'
+    got_online, got_target, _, _, state, info = buffers[0]
+    outside = np.ones(total, bool)
+    outside[offset:offset + n] = False
+    assert same_bits(got_online[outside], online[outside]) and not same_bits(got_online[~outside], p)
+    assert (bits(got_target) != bits(target)).mean() > 0.9, 'the targets moved, inside and outside the block'
+    assert state.tolist() == [4, 0, STATE_MARK, 0] and same_bits(info, expected_row(4)[0])
+    assert same_bits(entry.p.read(), p) and same_bits(family.p.read(), p)
+
+
+# ------------------------------------------------------------------ one storage for the optimizer state
+
+def assert_moment_views(optim, what):
+    """`exp_avg` / `exp_avg_sq` are the first two state slots, and a step has been taken into them."""
+    assert optim.slots.numel() == 2 * optim.count, what
+    assert optim.exp_avg.data_ptr() == optim.slots.data_ptr(), what
+    assert optim.exp_avg_sq.data_ptr() == optim.slots.data_ptr() + 4 * optim.count, what
+    torch.cuda.synchronize()
+    assert int(optim.state[0]) >= 1, f'{what}: no step was taken'
+    slots = optim.slots.cpu().numpy()
+    assert np.isfinite(slots).all() and slots[:optim.count].any() and slots[optim.count:].any(), what
+
+
+@pytest.mark.parametrize('kind', ['ppo', 'ddpg', 'mpo'])
+def test_default_agents_keep_their_moments_in_the_slots(lib, kind):
+    """Default (plain Adam) PPO, DDPG and MPO agents after their first updates on `Synthetic` (O = 3, A = 2, two
+    workers; PPO on 2 x 8 rows, the others at B = 17): what the pair launch and the fused off-policy iteration step
+    through `exp_avg` / `exp_avg_sq` IS the updater's one `slots` tensor — for MPO's duals too."""
+    import tonic_amd
+    import tonic_amd.torch as tt
+    O, A, W = 3, 2, 2
+    env = tonic_amd.environments.distribute(lambda: tonic_amd.environments.Synthetic(O, A, max_episode_steps=5), 1, W)
+    env.initialize(seed=5)
+    if kind == 'ppo':
+        agent = tt.agents.PPO(replay=tonic_amd.replays.Segment(size=8, batch_iterations=2))
+    else:
+        replay = tonic_amd.replays.Buffer(size=200, batch_iterations=1, batch_size=17, steps_before_batches=W * 4,
+                                          steps_between_batches=W * 4)
+        agent = (tt.agents.DDPG if kind == 'ddpg' else tt.agents.MPO)(replay=replay)
+    agent.initialize(env.observation_space, env.action_space, seed=5)
+    observations = env.start()
+    for t in range(16 if kind == 'ppo' else 12):
+        actions = agent.step(observations, t * W)
+        observations, infos = env.step(actions)
+        agent.update(**infos, steps=t * W)
+    for name in ('actor_updater', 'critic_updater'):
+        updater = getattr(agent, name)
+        assert updater.plain and not updater.stock
+        assert_moment_views(updater, f'{kind} {name}')
+    if kind == 'mpo':
+        assert_moment_views(agent.actor_updater.dual_optim, 'mpo duals')
+    agent.close()
 
 
 # ------------------------------------------------------------------ tonic_clip_grad_norm

@@ -1,7 +1,7 @@
-"""tonic_optimizer_step (csrc/optim.hip: family_kernel) through the C ABI: every rule of the optimizer family against
+"""tonic_optimizer_step (csrc/optim.hip: optimizer_kernel) through the C ABI: every rule of the optimizer family against
 its float32 statement (tests/optim_family_ref.py) BIT FOR BIT — parameters and every state buffer, after each launch.
 
-The launch is adam_kernel's, so the sizes are those of tests/test_gpu_optim.py, decided by the same constants:
+The launch is the one behind tonic_adam_step, so the sizes are those of tests/test_gpu_optim.py, decided by the same constants:
 
 | case                                    | decided by                                                                  |
 |-----------------------------------------|-----------------------------------------------------------------------------|
@@ -15,7 +15,7 @@ The launch is adam_kernel's, so the sizes are those of tests/test_gpu_optim.py, 
 | skip flag set                           | `if (a.skip != nullptr && *a.skip != 0) return` ahead of everything         |
 | polyak: block first / last / whole,     | workgroups >= adam_blocks update the targets OUTSIDE the block, `extra` =   |
 | total - n = 2048 x 256 + 777, (2, 1)    | ceil((total - n) / 256) capped at 2048                                      |
-| stats_kind 1 .. 4, kl above threshold,  | adam_finalize, shared with adam_kernel: rows, stop flag and counter must    |
+| stats_kind 1 .. 4, kl above threshold,  | adam_finalize, as behind tonic_adam_step: rows, stop flag and counter must    |
 | adv_stats[2] = 1; n = 300, 40 000       | equal what tonic_adam_step writes for the same sums (2 / 128 workgroups)    |
 
 Every buffer lies between sentinel margins (test_gpu_optim.Guarded) that must come back untouched; the state buffers

@@ -43,12 +43,21 @@ def host(tensor):
     return tensor.detach().cpu().numpy().copy()
 
 
+def assert_moment_views(updater):
+    """`exp_avg` / `exp_avg_sq` are the first two state slots, not buffers of their own."""
+    assert updater.exp_avg.data_ptr() == updater.slots.data_ptr()
+    assert updater.exp_avg_sq.data_ptr() == updater.slots.data_ptr() + 4 * updater.count
+
+
 class Follow:
     """An updater's parameters and state buffers, advanced by the statement from the sums the updater holds."""
 
     def __init__(self, updater):
         self.u, self.rule = updater, updater.hyper
-        assert not updater.plain and not updater.stock and updater.exp_avg is None
+        assert not updater.plain and not updater.stock
+        assert (updater.exp_avg is None) == (self.rule['kind'] in ('sgd', 'rmsprop'))
+        if updater.exp_avg is not None:
+            assert_moment_views(updater)
         self.names = ref.slot_names(self.rule)
         assert (updater.slots.numel() if updater.slots is not None else 0) == len(self.names) * updater.count
         self.p, self.slots, self.step = host(updater.flat.flat), self.read_slots(), 0
@@ -176,7 +185,9 @@ def test_ddpg_updaters_with_sgd_momentum_and_polyak_targets(lib):
     agent = q_agent('ddpg', O, A, B, 256, actor_optimizer=sgd, critic_optimizer=sgd)
     assert agent._fused_kind() is None
     plain = q_agent('ddpg', O, A, B, 256)
-    assert plain._fused_kind() == 2 and plain.actor_updater.plain and plain.actor_updater.slots is None
+    assert plain._fused_kind() == 2 and plain.actor_updater.plain
+    assert plain.actor_updater.slots.numel() == 2 * plain.actor_updater.count
+    assert_moment_views(plain.actor_updater)
     model, critic, actor = agent.model, agent.critic_updater, agent.actor_updater
     coeff = float(model.target_coeff)
     assert 0 < coeff < 1

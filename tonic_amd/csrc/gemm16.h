@@ -55,7 +55,7 @@ constexpr int kGemmGroupMax = 4;
 // the group are the tensors of ONE network's flat gradient-sum block, so the offset of an output
 // element from `grads` also addresses its parameter, its Adam moments and its target copy.  The
 // workgroup that forms a tile of gradient sums applies torch.optim.Adam's step to the tile's
-// parameters right away (the expressions of adam_kernel in optim.hip, i.e. numpy_port.adam_statement;
+// parameters right away (adam_element of optim_rule.h, the one optimizer_kernel calls, i.e. numpy_port.adam_statement;
 // tests/test_gpu_offpolicy.py holds the two launches' results equal bit for bit) and, with
 // `target`, the polyak update of the same entries; the last workgroup to arrive bumps the step
 // counter and writes the logged statistics (adam_finalize).  Saves the optimizer launch and one
@@ -70,7 +70,7 @@ struct AdamFold {
   int64_t n;                 // parameters in the block: the 8 statistic sums follow at grads + n
   float grad_scale, beta2, eps, polyak_keep, polyak_mix;
   double beta1_d, beta2_d, lr_d;
-  int stats_kind;            // 3 twin Q critics, 4 Q actor (see adam_finalize in optim.hip)
+  int stats_kind;            // 3 twin Q critics, 4 Q actor (the rows: optim_rule.h)
   float* info_row;
   // A chained launch ahead of this one may have given up on a value that never came (mlpfwd.h:
   // exchange_read): its failure word.  Non-zero = the gradient sums are not a gradient — no

@@ -1,5 +1,6 @@
 // gemm16: see gemm16.h.  gfx950, v_mfma_f32_16x16x4_f32, one wave per 16 x 32 output tile.
 #include "gemm16.h"
+#include "optim_rule.h"
 
 namespace tonic {
 
@@ -201,52 +202,20 @@ __device__ __forceinline__ void tn_load(const float* __restrict__ base, unsigned
   }
 }
 
-// The step's constants (adam.py:530-547: float64 bias corrections, then rounded) — the expressions
-// of adam_kernel.
-struct AdamConsts { float step_size, bias2_sqrt, w1, w2; };
-
-__device__ __forceinline__ AdamConsts adam_consts(const AdamFold& f) {
-  if (f.consts != nullptr) {          // formed by the host in float64 like the reference's Python
-    AdamConsts c;                     // floats (adam.py:530-536): no float64 pow on the device
-    c.step_size = f.consts[0]; c.bias2_sqrt = f.consts[1];
-    c.w1 = (float)(1.0 - f.beta1_d); c.w2 = (float)(1.0 - f.beta2_d);
-    return c;
-  }
-  const int step = f.state[0] + 1;
-  const double bias1 = 1.0 - pow(f.beta1_d, (double)step);
-  const double bias2 = 1.0 - pow(f.beta2_d, (double)step);
-  AdamConsts c;
-  c.step_size = (float)(f.lr_d / bias1);
-  c.bias2_sqrt = (float)sqrt(bias2);
-  c.w1 = (float)(1.0 - f.beta1_d); c.w2 = (float)(1.0 - f.beta2_d);
-  return c;
-}
-
-// One element: the gradient SUM just formed -> new parameter (moments updated in place).  The float32
-// expression of adam_kernel (optim.hip), stated operation by operation in oracle/numpy_port.py
-// (adam_statement); like it, one ulp of `v` away from torch's addcmul_ order.
-__device__ __forceinline__ float adam_element(float sum, float p, float& m, float& v,
-                                              const AdamFold& f, const AdamConsts& c) {
-  const float gr = sum * f.grad_scale;
-  m = m + c.w1 * (gr - m);                                         // lerp_, adam.py:457
-  v = v * f.beta2 + c.w2 * (gr * gr);                              // mul_().addcmul_(), :476
-  const float denom = sqrtf(v) / c.bias2_sqrt + f.eps;             // :545
-  return p - c.step_size * (m / denom);                            // addcdiv_, :547
-}
-
+// One element off the tile path (a bias gradient): the gradient SUM just formed -> its parameter, moments, target.
 __device__ __forceinline__ void adam_apply(const AdamFold& f, const AdamConsts& c, int64_t off,
                                            float sum) {
   float m = f.exp_avg[off], v = f.exp_avg_sq[off];
-  const float p = adam_element(sum, f.params[off], m, v, f, c);
+  const float p = adam_element(sum * f.grad_scale, f.params[off], m, v, nullptr, f.beta2, f.eps, c);
   f.params[off] = p; f.exp_avg[off] = m; f.exp_avg_sq[off] = v;
-  if (f.target != nullptr) f.target[off] = f.target[off] * f.polyak_keep + f.polyak_mix * p;
+  if (f.target != nullptr) f.target[off] = polyak(f.target[off], p, f.polyak_keep, f.polyak_mix);
 }
 
-// The last workgroup of the launch: step counter and logged statistics (adam_finalize, optim.hip).
+// The last workgroup of the launch: step counter and logged statistics (like adam_finalize, optim.hip).
 __device__ __forceinline__ void adam_fold_arrive(const AdamFold& f, unsigned total, bool stepping) {
   unsigned* arrivals = reinterpret_cast<unsigned*>(f.state + 3);
   // (this wave's loads of the step's state / constants have returned before it arrives: the
-  //  finaliser's write of the step counter races with nobody, see adam_kernel in optim.hip)
+  //  finaliser's write of the step counter races with nobody, see last_arrival_finalizes in optim.hip)
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   const unsigned before = __hip_atomic_fetch_add(arrivals, 1u, __ATOMIC_RELAXED,
                                                  __HIP_MEMORY_SCOPE_AGENT);
@@ -261,15 +230,8 @@ __device__ __forceinline__ void adam_fold_arrive(const AdamFold& f, unsigned tot
   f.state[0] += 1;
   if (f.info_row == nullptr) return;
   const float* st = f.grads + f.n;
-  if (f.stats_kind == 3) {
-    f.info_row[0] = st[0] * f.grad_scale;      // loss_1 + loss_2 (critics.py:172,224)
-    f.info_row[1] = st[1] * f.grad_scale;      // mean q1
-    f.info_row[2] = st[2] * f.grad_scale;      // mean q2
-    f.info_row[6] = 1.f;
-  } else if (f.stats_kind == 4) {
-    f.info_row[0] = st[0] * f.grad_scale;      // actor loss (actors.py:179,257)
-    f.info_row[6] = 1.f;
-  }
+  if (f.stats_kind == 3) stats_row_twin_q(st, f.grad_scale, f.info_row);
+  else if (f.stats_kind == 4) stats_row_q_actor(st, f.grad_scale, f.info_row);
 }
 
 // COLSUM: this tile also forms the column sums of A (the bias gradient: the tiles of the first tile
@@ -367,7 +329,7 @@ __device__ __forceinline__ void gemm_tn_tile(const GemmArgs& g, int tm, int tn, 
   bool stepping = fold.on != 0;               // (uniform)
   if (fold.on) {
     __builtin_amdgcn_sched_barrier(0);
-    consts = adam_consts(fold);
+    consts = adam_step_consts(fold.consts, fold);
     if (fold.skip != nullptr)
       stepping = __hip_atomic_load(fold.skip, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0;
     __builtin_amdgcn_sched_barrier(0);
@@ -447,7 +409,7 @@ __device__ __forceinline__ void gemm_tn_tile(const GemmArgs& g, int tm, int tn, 
     }
   }
   // optimizer epilogue: parameter / moment / target loads of this wave's two rows first
-  const bool polyak = fold.on && fold.target != nullptr;
+  const bool with_target = fold.on && fold.target != nullptr;
   float pm[2][4][2];
   if (fold.on) {
 #pragma unroll
@@ -455,7 +417,7 @@ __device__ __forceinline__ void gemm_tn_tile(const GemmArgs& g, int tm, int tn, 
       const int m = min(m0 + 2 * (4 * kg + w) + jm, g.M - 1);
       const int64_t off = goff + (int64_t)m * g.ldc + min(cb, g.N - 1);
       const float* src[4] = {fold.params + off, fold.exp_avg + off, fold.exp_avg_sq + off,
-                             (polyak ? fold.target : fold.params) + off};
+                             (with_target ? fold.target : fold.params) + off};
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         if (!EDGE) {
@@ -495,15 +457,16 @@ __device__ __forceinline__ void gemm_tn_tile(const GemmArgs& g, int tm, int tn, 
 #pragma unroll
     for (int e = 0; e < 2; ++e) {
       float mo = pm[jm][1][e], vo = pm[jm][2][e];
-      const float p = adam_element(sum[e], pm[jm][0][e], mo, vo, fold, consts);
+      const float p = adam_element(sum[e] * fold.grad_scale, pm[jm][0][e], mo, vo, nullptr, fold.beta2,
+                                   fold.eps, consts);
       out[0][e] = p; out[1][e] = mo; out[2][e] = vo;
-      out[3][e] = pm[jm][3][e] * fold.polyak_keep + fold.polyak_mix * p;
+      out[3][e] = polyak(pm[jm][3][e], p, fold.polyak_keep, fold.polyak_mix);
       newp[jm][e] = p; newt[jm][e] = out[3][e];
     }
     float* to[4] = {fold.params + off, fold.exp_avg + off, fold.exp_avg_sq + off, fold.target + off};
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      if (q == 3 && !polyak) continue;
+      if (q == 3 && !with_target) continue;
       if (cb + 1 < g.N) {
         *reinterpret_cast<f32x2_dword*>(to[q]) = f32x2_dword{out[q][0], out[q][1]};
       } else if (cb < g.N) {
@@ -524,7 +487,7 @@ __device__ __forceinline__ void gemm_tn_tile(const GemmArgs& g, int tm, int tn, 
         if (r_even + jm >= g.M) continue;
         const bool second = cb + 1 < g.N;
         img_store_pair(im.fwd + zoff, im.fwd_chunks, r_even + jm, cb, newp[jm][0], second ? newp[jm][1] : 0.f);
-        if (polyak)
+        if (with_target)
           img_store_pair(im.fwd + zoff + im.target_delta, im.fwd_chunks, r_even + jm, cb, newt[jm][0],
                          second ? newt[jm][1] : 0.f);
       }
@@ -536,7 +499,7 @@ __device__ __forceinline__ void gemm_tn_tile(const GemmArgs& g, int tm, int tn, 
         if (cb + e >= g.N || k < 0 || k >= im.bwd_cols) continue;
         const bool second = r_even + 1 < g.M;
         img_store_pair(im.bwd + zoff, im.bwd_chunks, k, r_even, newp[0][e], second ? newp[1][e] : 0.f);
-        if (polyak)
+        if (with_target)
           img_store_pair(im.bwd + zoff + im.target_delta, im.bwd_chunks, k, r_even, newt[0][e],
                          second ? newt[1][e] : 0.f);
       }

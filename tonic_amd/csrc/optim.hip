@@ -1,61 +1,63 @@
-// Flat fused Adam, the optimizer family beside it (family_kernel, below) + PPO statistic finalisation (gfx950).
+// The flat fused optimizer step (one kernel template: optimizer_kernel) + PPO statistic finalisation (gfx950).
 //
-// Restates torch.optim.Adam's single-tensor CPU path (torch/optim/adam.py:395-547; betas
-// (0.9, 0.999), eps 1e-8, no weight decay / amsgrad) as constructed by
-// tonic/torch/updaters/actors.py:58-59 and critics.py:9-10, applied to ONE flat buffer per
-// network (28 B/param of HBM traffic: read p,g,m,v, write p,m,v).  WHICH float32 expression this is,
-// operation by operation, is oracle/numpy_port.py's adam_statement; tests/test_gpu_optim.py holds
-// adam_kernel to it bit for bit.  It is NOT bit-identical with torch's CPU Adam, and nothing unfused can
-// be: torch's lerp_ fuses from the second step on, and its addcmul_ forms (w2 * g) * g where this file
-// forms w2 * (g * g) — one ulp of exp_avg_sq in a third of the elements, at most one ulp of a parameter
-// after 7 steps.  The file also holds the tail of
+// Restates the single-tensor CPU paths of torch.optim.Adam / AdamW (torch/optim/adam.py:395-547), SGD
+// (sgd.py:343-380) and RMSprop (rmsprop.py:287-339), applied to ONE flat buffer per network.  Plain Adam (betas
+// (0.9, 0.999), eps 1e-8, no weight decay / amsgrad, as constructed by tonic/torch/updaters/actors.py:58-59 and
+// critics.py:9-10) is the AdamRule<false> instantiation: 28 B/param of HBM traffic (read p,g,m,v, write p,m,v).
+// WHICH float32 expression Adam is, operation by operation, is oracle/numpy_port.py's adam_statement (the
+// statements themselves: optim_rule.h); tests/test_gpu_optim.py holds the kernel to it bit for bit.  It is NOT
+// bit-identical with torch's CPU Adam, and nothing unfused can be: torch's lerp_ fuses from the second step on, and
+// its addcmul_ forms (w2 * g) * g where adam_element forms w2 * (g * g) — one ulp of exp_avg_sq in a third of the
+// elements, at most one ulp of a parameter after 7 steps.  The other rules, operation by operation, are tests/optim_family_ref.py;
+// tests/test_gpu_optim_family.py holds the kernels to it bit for bit.  The file also holds the tail of
 // ClippedRatio.__call__ (actors.py:101-112: loss/kl/entropy/clip_fraction/std/stop) and of
 // VRegression.__call__ (critics.py:28).  The optimizer step counter and the PPO early-stop
 // flag live on the device so the 80-iteration loop of ppo.py:33-46 needs no host sync.
+// Bytes of HBM traffic per parameter (p and g read, p written = 12, + 8 per state buffer): Adam / AdamW 28, with
+// amsgrad 36; SGD 12, with momentum 20; RMSprop 20, + 8 centered, + 8 with momentum.
 #include "common.h"
+#include "optim_rule.h"
 
 namespace tonic {
 
-struct AdamArgs {
+struct OptimArgs {
   float* params;
   const float* grad_sums;
-  float* exp_avg;
-  float* exp_avg_sq;
-  int32_t* state;            // {step_count, stop_flag, -, -}
+  float* slot[3];            // the rule's state buffers (tonic_optimizer_state_slots' order; Adam: exp_avg, exp_avg_sq)
+  int32_t* state;            // {step_count, stop_flag, -, arrivals}
   int64_t n;
-  float grad_scale, lr, beta1, beta2, eps;
+  float grad_scale, lr, beta2, eps;
   double beta1_d, beta2_d, lr_d;
   int stats_kind;            // 0 none, 1 PPO actor, 2 V critic, 3 twin Q critics, 4 Q actor
   float kl_threshold, entropy_coeff;
   const float* adv_stats;
   float* info_row;
   const int32_t* skip;
-  // optional target-network update in the same launch (tonic_adam_polyak_step): `params` is the
-  // block [polyak_offset, polyak_offset + n) of the online buffer `polyak_online`
+  // optional target-network update in the same launch: `params` is the block
+  // [polyak_offset, polyak_offset + n) of the online buffer `polyak_online`
   float* polyak_target;
   const float* polyak_online;
   int64_t polyak_total, polyak_offset;
   float polyak_keep, polyak_mix;
   int adam_blocks;
+  int decoupled, nesterov, maximize;
+  float weight_decay;         // 0: no `g += wd * p` (adam.py:429, sgd.py:356, rmsprop.py:308)
+  float decay_keep;           // AdamW: F32(1 - lr * wd) (adam.py:419)
+  float momentum, undamped;   // SGD / RMSprop: mu; SGD: F32(1 - dampening)
+  float alpha, unalpha;       // RMSprop: alpha, F32(1 - alpha)
 };
-
-// t = t*(1-c) + c*o with three roundings (actor_critics.py:126-130); used by SAC / TD3 / DDPG.
-__device__ __forceinline__ float polyak(float target, float online, float keep, float mix) {
-  const float scaled = target * keep;
-  const float add = mix * online;
-  return scaled + add;
-}
 
 // Up to two independent optimizer steps in one launch (blockIdx.y): PPO steps its actor and its
 // critic together.
-struct AdamPair { AdamArgs net[2]; };
+struct OptimPair { OptimArgs net[2]; };
 
 // One thread: bump the step counter, turn the statistic sums into the logged values.
-__device__ void adam_finalize(const AdamArgs& a) {
+__device__ void adam_finalize(const OptimArgs& a) {
   const float* st = a.grad_sums + a.n;
   const bool all_zero = a.stats_kind == 1 && a.adv_stats != nullptr && a.adv_stats[2] != 0.f;
   if (!all_zero) a.state[0] += 1;
-  if (a.stats_kind == 1 && a.info_row != nullptr) {
+  if (a.info_row == nullptr) return;
+  if (a.stats_kind == 1) {
     const float entropy = st[3] * a.grad_scale, std = st[4] * a.grad_scale;
     float loss = st[0] * a.grad_scale, kl = st[1] * a.grad_scale;
     float clip_fraction = st[2] * a.grad_scale;
@@ -71,18 +73,12 @@ __device__ void adam_finalize(const AdamArgs& a) {
     a.info_row[6] = 1.f;
     a.info_row[7] = 0.f;
     if (stop) a.state[1] = 1;
-  } else if (a.stats_kind == 2 && a.info_row != nullptr) {
-    a.info_row[0] = st[0] * a.grad_scale;      // MSE loss
-    a.info_row[1] = st[1] * a.grad_scale;      // mean of the pre-step values ('v')
-    a.info_row[6] = 1.f;
-  } else if (a.stats_kind == 3 && a.info_row != nullptr) {
-    a.info_row[0] = st[0] * a.grad_scale;      // loss_1 + loss_2 (critics.py:172,224)
-    a.info_row[1] = st[1] * a.grad_scale;      // mean q1
-    a.info_row[2] = st[2] * a.grad_scale;      // mean q2
-    a.info_row[6] = 1.f;
-  } else if (a.stats_kind == 4 && a.info_row != nullptr) {
-    a.info_row[0] = st[0] * a.grad_scale;      // actor loss (actors.py:179,257)
-    a.info_row[6] = 1.f;
+  } else if (a.stats_kind == 2) {
+    stats_row_v(st, a.grad_scale, a.info_row);
+  } else if (a.stats_kind == 3) {
+    stats_row_twin_q(st, a.grad_scale, a.info_row);
+  } else if (a.stats_kind == 4) {
+    stats_row_q_actor(st, a.grad_scale, a.info_row);
   }
 }
 
@@ -94,7 +90,7 @@ __device__ void adam_finalize(const AdamArgs& a) {
 // counter is an agent-scope atomic performed at L2; what the finaliser READS was written by
 // earlier launches.  (A release / acquire pair at agent scope instead would be an L2 write-back
 // + invalidate per workgroup.)
-__device__ __forceinline__ void last_arrival_finalizes(const AdamArgs& a, int64_t grid) {
+__device__ __forceinline__ void last_arrival_finalizes(const OptimArgs& a, int64_t grid) {
   __syncthreads();
   if (threadIdx.x == 0) {
     unsigned* arrivals = reinterpret_cast<unsigned*>(a.state + 3);
@@ -107,8 +103,73 @@ __device__ __forceinline__ void last_arrival_finalizes(const AdamArgs& a, int64_
   }
 }
 
-__global__ __launch_bounds__(256) void adam_kernel(AdamPair pair) {
-  const AdamArgs& a = blockIdx.y == 0 ? pair.net[0] : pair.net[1];
+// The rules as types: what is known at compile time decides which state buffers an instantiation streams.  Every
+// rule LOADS all of its state before it stores any of it: the buffers may alias as far as the compiler knows, so a
+// load behind a store waits for it, and each thread walks ~n / 32 768 elements one after the other.  With one
+// round trip per element instead of one per buffer, at n = 4 194 304: SGD with momentum 75.0 -> 49.7 us, centered
+// RMSprop with momentum 114.9 -> 66.3 us (profiles/optim_family_timing.json, DESIGN.md 4.4).
+template <bool kAmsgrad>
+struct AdamRule {
+  AdamConsts c;
+  __device__ void prepare(const OptimArgs& a) { c = adam_step_consts(nullptr, a); }
+  __device__ float apply(const OptimArgs& a, int64_t i, float p, float g) const {
+    float m = a.slot[0][i], v = a.slot[1][i];
+    float seen = kAmsgrad ? a.slot[2][i] : 0.f;
+    if (a.decoupled) p = p * a.decay_keep;                           // AdamW: param.mul_(1 - lr * wd), adam.py:419
+    p = adam_element(g, p, m, v, kAmsgrad ? &seen : nullptr, a.beta2, a.eps, c);
+    a.slot[0][i] = m;
+    a.slot[1][i] = v;
+    if (kAmsgrad) a.slot[2][i] = seen;
+    return p;
+  }
+};
+
+template <bool kMomentum>
+struct SgdRule {
+  bool first;
+  __device__ void prepare(const OptimArgs& a) { first = a.state[0] == 0; }        // no step taken yet
+  __device__ float apply(const OptimArgs& a, int64_t i, float p, float g) const {
+    float d = g;
+    if (kMomentum) {
+      const float kept = a.slot[0][i] * a.momentum + a.undamped * g; // mul_().add_(alpha = 1 - dampening), sgd.py:365
+      const float buf = first ? g : kept;                            // buf = grad.clone(), :361-363 (a select: what
+      a.slot[0][i] = buf;                                            //  the buffer held before the first step is unused)
+      d = a.nesterov ? g + a.momentum * buf : buf;                   // :367-370
+    }
+    return p - a.lr * d;                                             // param.add_(grad, alpha = -lr), :380
+  }
+};
+
+template <bool kCentered, bool kMomentum>
+struct RmspropRule {
+  __device__ void prepare(const OptimArgs&) {}
+  __device__ float apply(const OptimArgs& a, int64_t i, float p, float g) const {
+    float* const momentum_slot = a.slot[kCentered ? 2 : 1];
+    float sq = a.slot[0][i];
+    float ga = kCentered ? a.slot[1][i] : 0.f;
+    const float held = kMomentum ? momentum_slot[i] : 0.f;
+    sq = sq * a.alpha + a.unalpha * (g * g);                         // mul_().addcmul_(), rmsprop.py:316
+    float avg;
+    if (kCentered) {
+      ga = ga + a.unalpha * (g - ga);                                // lerp_, :322
+      avg = sqrtf(sq - ga * ga) + a.eps;                             // addcmul(value = -1).sqrt_(), add_(eps), :323-330
+    } else {
+      avg = sqrtf(sq) + a.eps;                                       // :325-330
+    }
+    a.slot[0][i] = sq;
+    if (kCentered) a.slot[1][i] = ga;
+    if (kMomentum) {
+      const float buf = held * a.momentum + g / avg;                 // mul_().addcdiv_(), :336
+      momentum_slot[i] = buf;
+      return p - a.lr * buf;                                         // :337
+    }
+    return p - a.lr * (g / avg);                                     // addcdiv_(value = -lr), :339
+  }
+};
+
+template <typename Rule>
+__global__ __launch_bounds__(256) void optimizer_kernel(OptimPair pair) {
+  const OptimArgs& a = blockIdx.y == 0 ? pair.net[0] : pair.net[1];
   if (a.polyak_target != nullptr && (int)blockIdx.x >= a.adam_blocks) {
     // the target entries OUTSIDE this optimizer block: their online values are final already
     const int64_t first = (int64_t)((int)blockIdx.x - a.adam_blocks) * blockDim.x + threadIdx.x;
@@ -120,153 +181,18 @@ __global__ __launch_bounds__(256) void adam_kernel(AdamPair pair) {
     return;
   }
   if (a.skip != nullptr && *a.skip != 0) return;
-  const int64_t grid = a.polyak_target != nullptr ? a.adam_blocks : (int64_t)gridDim.x;
-  if ((int64_t)blockIdx.x >= grid) return;         // (pairs: the shorter network's spare blocks)
-  const bool all_zero = a.stats_kind == 1 && a.adv_stats != nullptr && a.adv_stats[2] != 0.f;  // actors.py:71
-  const int step = a.state[0] + 1;
-  if (!all_zero) {
-    const double bias1 = 1.0 - pow(a.beta1_d, (double)step);
-    const double bias2 = 1.0 - pow(a.beta2_d, (double)step);
-    const float step_size = (float)(a.lr_d / bias1);                 // adam.py:533
-    const float bias2_sqrt = (float)sqrt(bias2);                     // adam.py:535
-    const float w1 = (float)(1.0 - a.beta1_d), w2 = (float)(1.0 - a.beta2_d);
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += grid * blockDim.x) {
-      const float g = a.grad_sums[i] * a.grad_scale;
-      float m = a.exp_avg[i], v = a.exp_avg_sq[i];
-      m = m + w1 * (g - m);                                          // lerp_, adam.py:457
-      v = v * a.beta2 + w2 * (g * g);                                // mul_().addcmul_(), :476
-      const float denom = sqrtf(v) / bias2_sqrt + a.eps;             // :545
-      const float p = a.params[i] - step_size * (m / denom);         // addcdiv_, :547
-      a.params[i] = p;
-      a.exp_avg[i] = m;
-      a.exp_avg_sq[i] = v;
-      if (a.polyak_target != nullptr) {                               // this entry's target, same thread
-        float* t = a.polyak_target + a.polyak_offset + i;
-        *t = polyak(*t, p, a.polyak_keep, a.polyak_mix);
-      }
-    }
-  }
-  last_arrival_finalizes(a, grid);
-}
-
-// ---- the optimizer family: Adam with weight decay / amsgrad / maximize, AdamW, SGD, RMSprop ----
-// The single-tensor CPU paths of torch/optim/adam.py:395-547, sgd.py:343-380 and rmsprop.py:287-339 on one flat
-// block, launched, skipped, counted and finalised exactly like adam_kernel (same grid, same arrival counter, the
-// same adam_finalize); plain Adam stays on adam_kernel.  WHICH float32 expression each rule is, operation by
-// operation, is tests/optim_family_ref.py; tests/test_gpu_optim_family.py holds the kernels to it bit for bit.
-// Bytes of HBM traffic per parameter (p and g read, p written = 12, + 8 per state buffer): Adam / AdamW 28, with
-// amsgrad 36; SGD 12, with momentum 20; RMSprop 20, + 8 centered, + 8 with momentum.
-struct FamilyArgs {
-  AdamArgs a;                 // params, sums, state, n, lr, eps, beta2, the float64 betas, statistics, skip, polyak
-  float* slot[3];             // the rule's state buffers (tonic_optimizer_state_slots' order)
-  int decoupled, nesterov, maximize;
-  float weight_decay;         // 0: no `g += wd * p` (adam.py:429, sgd.py:356, rmsprop.py:308)
-  float decay_keep;           // AdamW: F32(1 - lr * wd) (adam.py:419)
-  float momentum, undamped;   // SGD / RMSprop: mu; SGD: F32(1 - dampening)
-  float alpha, unalpha;       // RMSprop: alpha, F32(1 - alpha)
-};
-
-// The rules as types: what is known at compile time decides which state buffers an instantiation streams.  Every
-// rule LOADS all of its state before it stores any of it: the buffers may alias as far as the compiler knows, so a
-// load behind a store waits for it, and each thread walks ~n / 32 768 elements one after the other.  With one
-// round trip per element instead of one per buffer, at n = 4 194 304: SGD with momentum 75.0 -> 49.7 us, centered
-// RMSprop with momentum 114.9 -> 66.3 us (profiles/optim_family_timing.json, DESIGN.md 4.4).
-template <bool kAmsgrad>
-struct AdamRule {
-  float step_size, bias2_sqrt, w1, w2;
-  __device__ void prepare(const FamilyArgs& f) {
-    const AdamArgs& a = f.a;
-    const int step = a.state[0] + 1;
-    const double bias1 = 1.0 - pow(a.beta1_d, (double)step);
-    const double bias2 = 1.0 - pow(a.beta2_d, (double)step);
-    step_size = (float)(a.lr_d / bias1);                             // adam.py:534
-    bias2_sqrt = (float)sqrt(bias2);                                 // :536
-    w1 = (float)(1.0 - a.beta1_d); w2 = (float)(1.0 - a.beta2_d);
-  }
-  __device__ float apply(const FamilyArgs& f, int64_t i, float p, float g) const {
-    float m = f.slot[0][i], v = f.slot[1][i];
-    const float seen = kAmsgrad ? f.slot[2][i] : 0.f;
-    if (f.decoupled) p = p * f.decay_keep;                           // AdamW: param.mul_(1 - lr * wd), :419
-    m = m + w1 * (g - m);                                            // lerp_, :457
-    v = v * f.a.beta2 + w2 * (g * g);                                // mul_().addcmul_(), :476
-    float root = v;
-    if (kAmsgrad) root = (v > seen || v != v) ? v : seen;            // torch.maximum (NaN propagates), :540
-    const float denom = sqrtf(root) / bias2_sqrt + f.a.eps;          // :543 / :545
-    f.slot[0][i] = m;
-    f.slot[1][i] = v;
-    if (kAmsgrad) f.slot[2][i] = root;
-    return p - step_size * (m / denom);                              // addcdiv_, :547
-  }
-};
-
-template <bool kMomentum>
-struct SgdRule {
-  bool first;
-  __device__ void prepare(const FamilyArgs& f) { first = f.a.state[0] == 0; }     // no step taken yet
-  __device__ float apply(const FamilyArgs& f, int64_t i, float p, float g) const {
-    float d = g;
-    if (kMomentum) {
-      const float kept = f.slot[0][i] * f.momentum + f.undamped * g; // mul_().add_(alpha = 1 - dampening), sgd.py:365
-      const float buf = first ? g : kept;                            // buf = grad.clone(), :361-363 (a select: what
-      f.slot[0][i] = buf;                                            //  the buffer held before the first step is unused)
-      d = f.nesterov ? g + f.momentum * buf : buf;                   // :367-370
-    }
-    return p - f.a.lr * d;                                           // param.add_(grad, alpha = -lr), :380
-  }
-};
-
-template <bool kCentered, bool kMomentum>
-struct RmspropRule {
-  __device__ void prepare(const FamilyArgs&) {}
-  __device__ float apply(const FamilyArgs& f, int64_t i, float p, float g) const {
-    float* const momentum_slot = f.slot[kCentered ? 2 : 1];
-    float sq = f.slot[0][i];
-    float ga = kCentered ? f.slot[1][i] : 0.f;
-    const float held = kMomentum ? momentum_slot[i] : 0.f;
-    sq = sq * f.alpha + f.unalpha * (g * g);                         // mul_().addcmul_(), rmsprop.py:316
-    float avg;
-    if (kCentered) {
-      ga = ga + f.unalpha * (g - ga);                                // lerp_, :322
-      avg = sqrtf(sq - ga * ga) + f.a.eps;                           // addcmul(value = -1).sqrt_(), add_(eps), :323-330
-    } else {
-      avg = sqrtf(sq) + f.a.eps;                                     // :325-330
-    }
-    f.slot[0][i] = sq;
-    if (kCentered) f.slot[1][i] = ga;
-    if (kMomentum) {
-      const float buf = held * f.momentum + g / avg;                 // mul_().addcdiv_(), :336
-      momentum_slot[i] = buf;
-      return p - f.a.lr * buf;                                       // :337
-    }
-    return p - f.a.lr * (g / avg);                                   // addcdiv_(value = -lr), :339
-  }
-};
-
-template <typename Rule>
-__global__ __launch_bounds__(256) void family_kernel(FamilyArgs f) {
-  const AdamArgs& a = f.a;
-  if (a.polyak_target != nullptr && (int)blockIdx.x >= a.adam_blocks) {
-    // the target entries OUTSIDE this optimizer block, as in adam_kernel
-    const int64_t first = (int64_t)((int)blockIdx.x - a.adam_blocks) * blockDim.x + threadIdx.x;
-    const int64_t stride = (int64_t)((int)gridDim.x - a.adam_blocks) * blockDim.x;
-    for (int64_t i = first; i < a.polyak_total; i += stride) {
-      if (i >= a.polyak_offset && i < a.polyak_offset + a.n) continue;
-      a.polyak_target[i] = polyak(a.polyak_target[i], a.polyak_online[i], a.polyak_keep, a.polyak_mix);
-    }
-    return;
-  }
-  if (a.skip != nullptr && *a.skip != 0) return;
+  // (pairs: the shorter network's spare workgroups walk nothing and arrive like the others)
   const int64_t grid = a.polyak_target != nullptr ? a.adam_blocks : (int64_t)gridDim.x;
   const bool all_zero = a.stats_kind == 1 && a.adv_stats != nullptr && a.adv_stats[2] != 0.f;  // actors.py:71
   if (!all_zero) {
     Rule rule;
-    rule.prepare(f);
+    rule.prepare(a);
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += grid * blockDim.x) {
       const float before = a.params[i];
       float g = a.grad_sums[i] * a.grad_scale;
-      if (f.maximize) g = -g;                                        // adam.py:397, sgd.py:344, rmsprop.py:302
-      if (f.weight_decay != 0.f && !f.decoupled) g = g + f.weight_decay * before;   // grad.add(param, alpha = wd)
-      const float p = rule.apply(f, i, before, g);
+      if (a.maximize) g = -g;                                        // adam.py:397, sgd.py:344, rmsprop.py:302
+      if (a.weight_decay != 0.f && !a.decoupled) g = g + a.weight_decay * before;   // grad.add(param, alpha = wd)
+      const float p = rule.apply(a, i, before, g);
       a.params[i] = p;
       if (a.polyak_target != nullptr) {                               // this entry's target, same thread
         float* t = a.polyak_target + a.polyak_offset + i;
@@ -343,68 +269,12 @@ using namespace tonic;
 
 namespace {
 
-int adam_fill(AdamArgs& a, const char* what, float* d_params, const float* d_grad_sums,
-              float* d_exp_avg, float* d_exp_avg_sq, int32_t* d_state, int64_t param_count,
-              double grad_scale, double lr, double beta1, double beta2, double eps,
-              int32_t stats_kind, double kl_threshold, double entropy_coeff,
-              const float* d_adv_stats, float* d_info_row, const int32_t* d_skip_flag) {
-  TONIC_REQUIRE(d_params && d_grad_sums && d_exp_avg && d_exp_avg_sq && d_state &&
-                    param_count > 0,
-                TONIC_ERR_INVALID_ARGUMENT, "%s: bad argument", what);
-  TONIC_REQUIRE(stats_kind >= 0 && stats_kind <= 4, TONIC_ERR_INVALID_ARGUMENT,
-                "%s: stats_kind %d", what, stats_kind);
-  a = AdamArgs{};
-  a.params = d_params; a.grad_sums = d_grad_sums; a.exp_avg = d_exp_avg;
-  a.exp_avg_sq = d_exp_avg_sq; a.state = d_state; a.n = param_count;
-  // Hyper-parameters are Python floats in the reference: bias corrections and step size are
-  // formed in float64 and only then rounded to float32 (adam.py:530-547).
-  a.grad_scale = (float)grad_scale; a.lr = (float)lr; a.beta1 = (float)beta1;
-  a.beta2 = (float)beta2; a.eps = (float)eps;
-  a.beta1_d = beta1; a.beta2_d = beta2; a.lr_d = lr;
-  a.stats_kind = stats_kind; a.kl_threshold = (float)kl_threshold;
-  a.entropy_coeff = (float)entropy_coeff;
-  a.adv_stats = d_adv_stats; a.info_row = d_info_row; a.skip = d_skip_flag;
-  return TONIC_OK;
-}
-
 // Few, fat workgroups: every optimizer workgroup ends with one agent-scope atomic on the same
 // counter (the last arriver finalises), and those serialise at ~10 ns each — 760 of them cost more
 // than the finalisation launch they replaced (11.8 vs 10.3 us at 200 k parameters).
 int adam_blocks_for(int64_t param_count) {
   const int64_t blocks = (param_count + 255) / 256;
   return (int)(blocks > 128 ? 128 : blocks);
-}
-
-int adam_launch(float* d_params, const float* d_grad_sums, float* d_exp_avg, float* d_exp_avg_sq,
-                int32_t* d_state, int64_t param_count, double grad_scale, double lr, double beta1,
-                double beta2, double eps, int32_t stats_kind, double kl_threshold,
-                double entropy_coeff, const float* d_adv_stats, float* d_info_row,
-                const int32_t* d_skip_flag, float* d_target, const float* d_online,
-                int64_t total, int64_t offset, double coeff, void* stream, const char* what) {
-  AdamPair pair{};
-  AdamArgs& a = pair.net[0];
-  if (int rc = adam_fill(a, what, d_params, d_grad_sums, d_exp_avg, d_exp_avg_sq, d_state,
-                         param_count, grad_scale, lr, beta1, beta2, eps, stats_kind, kl_threshold,
-                         entropy_coeff, d_adv_stats, d_info_row, d_skip_flag))
-    return rc;
-  const int blocks = adam_blocks_for(param_count);
-  int64_t extra = 0;
-  if (d_target != nullptr) {
-    a.polyak_target = d_target; a.polyak_online = d_online; a.polyak_total = total;
-    a.polyak_offset = offset; a.polyak_keep = (float)(1.0 - coeff); a.polyak_mix = (float)coeff;
-    a.adam_blocks = blocks;
-    extra = (total - param_count + 255) / 256;
-    if (extra > 2048) extra = 2048;
-  }
-  hipStream_t st = as_stream(stream);
-  hipLaunchKernelGGL(adam_kernel, dim3((unsigned)(blocks + extra)), dim3(256), 0, st, pair);
-  TONIC_CHECK_LAUNCH(what);
-  return TONIC_OK;
-}
-
-template <typename Rule>
-void family_launch(const FamilyArgs& f, unsigned blocks, hipStream_t st) {
-  hipLaunchKernelGGL(family_kernel<Rule>, dim3(blocks), dim3(256), 0, st, f);
 }
 
 bool family_rule_valid(const tonic_optimizer_t* rule) {
@@ -418,16 +288,121 @@ bool family_rule_valid(const tonic_optimizer_t* rule) {
   return rule->lr >= 0.0 && rule->weight_decay >= 0.0 && rule->momentum >= 0.0;
 }
 
+int state_slots(const tonic_optimizer_t& rule) {
+  switch (rule.kind) {
+    case TONIC_OPT_SGD: return rule.momentum != 0.0 ? 1 : 0;
+    case TONIC_OPT_RMSPROP:
+      return 1 + ((rule.flags & TONIC_OPT_CENTERED) ? 1 : 0) + (rule.momentum > 0.0 ? 1 : 0);
+    default: return (rule.flags & TONIC_OPT_AMSGRAD) ? 3 : 2;
+  }
+}
+
+// What tonic_adam_step* take as four numbers: torch.optim.Adam without weight decay / amsgrad / maximize.
+tonic_optimizer_t plain_adam(double lr, double beta1, double beta2, double eps) {
+  tonic_optimizer_t rule{};
+  rule.kind = TONIC_OPT_ADAM;
+  rule.lr = lr; rule.beta1 = beta1; rule.beta2 = beta2; rule.eps = eps;
+  return rule;
+}
+
+// The optional target-network update of a step: `d_params` is the block [offset, offset + n) of `online`.
+struct PolyakTail {
+  float* target;
+  const float* online;
+  int64_t total, offset;
+  double coeff;
+};
+
+// Validates and fills ONE network's arguments (`what`: the entry, for the messages); -> `blocks`: the
+// workgroups its launch needs, the polyak tail's included.
+int optim_fill(OptimArgs& a, unsigned& blocks, const char* what, float* d_params, const float* d_grad_sums,
+               float* const slot[3], int32_t* d_state, int64_t param_count, double grad_scale,
+               const tonic_optimizer_t& rule, int32_t stats_kind, double kl_threshold, double entropy_coeff,
+               const float* d_adv_stats, float* d_info_row, const int32_t* d_skip_flag,
+               const PolyakTail& tail = PolyakTail{}) {
+  const int slots = state_slots(rule);
+  bool held = true;
+  for (int k = 0; k < slots; ++k) held = held && slot[k] != nullptr;
+  TONIC_REQUIRE(d_params && d_grad_sums && held && d_state && param_count > 0, TONIC_ERR_INVALID_ARGUMENT,
+                "%s: bad argument", what);
+  TONIC_REQUIRE(stats_kind >= 0 && stats_kind <= 4, TONIC_ERR_INVALID_ARGUMENT,
+                "%s: stats_kind %d", what, stats_kind);
+  a = OptimArgs{};
+  a.params = d_params; a.grad_sums = d_grad_sums; a.state = d_state; a.n = param_count;
+  for (int k = 0; k < slots; ++k) a.slot[k] = slot[k];
+  // Hyper-parameters are Python floats in the reference: bias corrections and step size are
+  // formed in float64 and only then rounded to float32 (adam.py:530-547).
+  a.grad_scale = (float)grad_scale; a.lr = (float)rule.lr; a.beta2 = (float)rule.beta2; a.eps = (float)rule.eps;
+  a.beta1_d = rule.beta1; a.beta2_d = rule.beta2; a.lr_d = rule.lr;
+  a.stats_kind = stats_kind; a.kl_threshold = (float)kl_threshold;
+  a.entropy_coeff = (float)entropy_coeff;
+  a.adv_stats = d_adv_stats; a.info_row = d_info_row; a.skip = d_skip_flag;
+  a.decoupled = rule.kind == TONIC_OPT_ADAMW && rule.weight_decay != 0.0;
+  a.nesterov = (rule.flags & TONIC_OPT_NESTEROV) != 0;
+  a.maximize = (rule.flags & TONIC_OPT_MAXIMIZE) != 0;
+  a.weight_decay = (float)rule.weight_decay;
+  a.decay_keep = (float)(1.0 - rule.lr * rule.weight_decay);
+  a.momentum = (float)rule.momentum; a.undamped = (float)(1.0 - rule.dampening);
+  a.alpha = (float)rule.alpha; a.unalpha = (float)(1.0 - rule.alpha);
+  a.adam_blocks = adam_blocks_for(param_count);
+  int64_t extra = 0;
+  if (tail.target != nullptr) {
+    TONIC_REQUIRE(tail.online && tail.offset >= 0 && tail.offset + param_count <= tail.total &&
+                      d_params == tail.online + tail.offset,
+                  TONIC_ERR_INVALID_ARGUMENT, "%s: block [%lld, +%lld) of %lld", what,
+                  (long long)tail.offset, (long long)param_count, (long long)tail.total);
+    a.polyak_target = tail.target; a.polyak_online = tail.online; a.polyak_total = tail.total;
+    a.polyak_offset = tail.offset; a.polyak_keep = (float)(1.0 - tail.coeff); a.polyak_mix = (float)tail.coeff;
+    extra = (tail.total - param_count + 255) / 256;
+    if (extra > 2048) extra = 2048;
+  }
+  blocks = (unsigned)(a.adam_blocks + extra);
+  return TONIC_OK;
+}
+
+template <typename Rule>
+void launch_as(const OptimPair& pair, dim3 grid, hipStream_t st) {
+  hipLaunchKernelGGL(optimizer_kernel<Rule>, grid, dim3(256), 0, st, pair);
+}
+
+int optim_launch(const tonic_optimizer_t& rule, const OptimPair& pair, dim3 grid, void* stream, const char* what) {
+  hipStream_t st = as_stream(stream);
+  const bool momentum = rule.momentum != 0.0, centered = (rule.flags & TONIC_OPT_CENTERED) != 0;
+  if (rule.kind == TONIC_OPT_SGD) {
+    if (momentum) launch_as<SgdRule<true>>(pair, grid, st);
+    else launch_as<SgdRule<false>>(pair, grid, st);
+  } else if (rule.kind == TONIC_OPT_RMSPROP) {
+    if (centered && momentum) launch_as<RmspropRule<true, true>>(pair, grid, st);
+    else if (centered) launch_as<RmspropRule<true, false>>(pair, grid, st);
+    else if (momentum) launch_as<RmspropRule<false, true>>(pair, grid, st);
+    else launch_as<RmspropRule<false, false>>(pair, grid, st);
+  } else if (rule.flags & TONIC_OPT_AMSGRAD) {
+    launch_as<AdamRule<true>>(pair, grid, st);
+  } else {
+    launch_as<AdamRule<false>>(pair, grid, st);
+  }
+  TONIC_CHECK_LAUNCH(what);
+  return TONIC_OK;
+}
+
+// One network's step: fill, launch.
+int optim_step(const char* what, float* d_params, const float* d_grad_sums, float* const slot[3],
+               int32_t* d_state, int64_t param_count, double grad_scale, const tonic_optimizer_t& rule,
+               int32_t stats_kind, double kl_threshold, double entropy_coeff, const float* d_adv_stats,
+               float* d_info_row, const int32_t* d_skip_flag, const PolyakTail& tail, void* stream) {
+  OptimPair pair{};
+  unsigned blocks = 0;
+  if (int rc = optim_fill(pair.net[0], blocks, what, d_params, d_grad_sums, slot, d_state, param_count,
+                          grad_scale, rule, stats_kind, kl_threshold, entropy_coeff, d_adv_stats, d_info_row,
+                          d_skip_flag, tail))
+    return rc;
+  return optim_launch(rule, pair, dim3(blocks), stream, what);
+}
+
 }  // namespace
 
 extern "C" int32_t tonic_optimizer_state_slots(const tonic_optimizer_t* rule) {
-  if (!family_rule_valid(rule)) return -1;
-  switch (rule->kind) {
-    case TONIC_OPT_SGD: return rule->momentum != 0.0 ? 1 : 0;
-    case TONIC_OPT_RMSPROP:
-      return 1 + ((rule->flags & TONIC_OPT_CENTERED) ? 1 : 0) + (rule->momentum > 0.0 ? 1 : 0);
-    default: return (rule->flags & TONIC_OPT_AMSGRAD) ? 3 : 2;
-  }
+  return family_rule_valid(rule) ? state_slots(*rule) : -1;
 }
 
 extern "C" int tonic_optimizer_step(float* d_params, const float* d_grad_sums, float* d_slots,
@@ -441,58 +416,11 @@ extern "C" int tonic_optimizer_step(float* d_params, const float* d_grad_sums, f
   TONIC_REQUIRE(slots >= 0, TONIC_ERR_INVALID_ARGUMENT,
                 "tonic_optimizer_step: not a rule of the family (kind %d, flags %d)",
                 rule ? rule->kind : -1, rule ? rule->flags : -1);
-  TONIC_REQUIRE(d_params && d_grad_sums && d_state && param_count > 0 && (d_slots || slots == 0),
-                TONIC_ERR_INVALID_ARGUMENT, "tonic_optimizer_step: bad argument");
-  TONIC_REQUIRE(stats_kind >= 0 && stats_kind <= 4, TONIC_ERR_INVALID_ARGUMENT,
-                "tonic_optimizer_step: stats_kind %d", stats_kind);
-  FamilyArgs f{};
-  AdamArgs& a = f.a;
-  a.params = d_params; a.grad_sums = d_grad_sums; a.state = d_state; a.n = param_count;
-  a.grad_scale = (float)grad_scale; a.lr = (float)rule->lr; a.beta1 = (float)rule->beta1;
-  a.beta2 = (float)rule->beta2; a.eps = (float)rule->eps;
-  a.beta1_d = rule->beta1; a.beta2_d = rule->beta2; a.lr_d = rule->lr;
-  a.stats_kind = stats_kind; a.kl_threshold = (float)kl_threshold;
-  a.entropy_coeff = (float)entropy_coeff;
-  a.adv_stats = d_adv_stats; a.info_row = d_info_row; a.skip = d_skip_flag;
-  for (int k = 0; k < slots; ++k) f.slot[k] = d_slots + (int64_t)k * param_count;
-  f.decoupled = rule->kind == TONIC_OPT_ADAMW && rule->weight_decay != 0.0;
-  f.nesterov = (rule->flags & TONIC_OPT_NESTEROV) != 0;
-  f.maximize = (rule->flags & TONIC_OPT_MAXIMIZE) != 0;
-  f.weight_decay = (float)rule->weight_decay;
-  f.decay_keep = (float)(1.0 - rule->lr * rule->weight_decay);
-  f.momentum = (float)rule->momentum; f.undamped = (float)(1.0 - rule->dampening);
-  f.alpha = (float)rule->alpha; f.unalpha = (float)(1.0 - rule->alpha);
-  const int blocks = adam_blocks_for(param_count);
-  int64_t extra = 0;
-  if (d_target != nullptr) {
-    TONIC_REQUIRE(d_online && block_offset >= 0 && block_offset + param_count <= total_count &&
-                      d_params == d_online + block_offset,
-                  TONIC_ERR_INVALID_ARGUMENT, "tonic_optimizer_step: block [%lld, +%lld) of %lld",
-                  (long long)block_offset, (long long)param_count, (long long)total_count);
-    a.polyak_target = d_target; a.polyak_online = d_online; a.polyak_total = total_count;
-    a.polyak_offset = block_offset; a.polyak_keep = (float)(1.0 - coeff); a.polyak_mix = (float)coeff;
-    a.adam_blocks = blocks;
-    extra = (total_count - param_count + 255) / 256;
-    if (extra > 2048) extra = 2048;
-  }
-  const unsigned grid = (unsigned)(blocks + extra);
-  hipStream_t st = as_stream(stream);
-  const bool momentum = rule->momentum != 0.0, centered = (rule->flags & TONIC_OPT_CENTERED) != 0;
-  if (rule->kind == TONIC_OPT_SGD) {
-    if (momentum) family_launch<SgdRule<true>>(f, grid, st);
-    else family_launch<SgdRule<false>>(f, grid, st);
-  } else if (rule->kind == TONIC_OPT_RMSPROP) {
-    if (centered && momentum) family_launch<RmspropRule<true, true>>(f, grid, st);
-    else if (centered) family_launch<RmspropRule<true, false>>(f, grid, st);
-    else if (momentum) family_launch<RmspropRule<false, true>>(f, grid, st);
-    else family_launch<RmspropRule<false, false>>(f, grid, st);
-  } else if (rule->flags & TONIC_OPT_AMSGRAD) {
-    family_launch<AdamRule<true>>(f, grid, st);
-  } else {
-    family_launch<AdamRule<false>>(f, grid, st);
-  }
-  TONIC_CHECK_LAUNCH("tonic_optimizer_step");
-  return TONIC_OK;
+  float* slot[3] = {nullptr, nullptr, nullptr};
+  for (int k = 0; k < slots && d_slots != nullptr; ++k) slot[k] = d_slots + (int64_t)k * param_count;
+  return optim_step("tonic_optimizer_step", d_params, d_grad_sums, slot, d_state, param_count, grad_scale, *rule,
+                    stats_kind, kl_threshold, entropy_coeff, d_adv_stats, d_info_row, d_skip_flag,
+                    PolyakTail{d_target, d_online, total_count, block_offset, coeff}, stream);
 }
 
 extern "C" int tonic_adam_step_pair(
@@ -504,21 +432,21 @@ extern "C" int tonic_adam_step_pair(
     int32_t* d_state_b, int64_t param_count_b, double lr_b, int32_t stats_kind_b,
     float* d_info_row_b,
     double grad_scale, double beta1, double beta2, double eps, void* stream) {
-  AdamPair pair{};
-  if (int rc = adam_fill(pair.net[0], "tonic_adam_step_pair (first)", d_params_a, d_grad_sums_a,
-                         d_exp_avg_a, d_exp_avg_sq_a, d_state_a, param_count_a, grad_scale, lr_a,
-                         beta1, beta2, eps, stats_kind_a, kl_threshold, entropy_coeff, d_adv_stats,
-                         d_info_row_a, d_skip_flag_a))
+  OptimPair pair{};
+  unsigned blocks_a = 0, blocks_b = 0;
+  float* const slot_a[3] = {d_exp_avg_a, d_exp_avg_sq_a, nullptr};
+  float* const slot_b[3] = {d_exp_avg_b, d_exp_avg_sq_b, nullptr};
+  const tonic_optimizer_t rule_a = plain_adam(lr_a, beta1, beta2, eps);
+  if (int rc = optim_fill(pair.net[0], blocks_a, "tonic_adam_step_pair (first)", d_params_a, d_grad_sums_a,
+                          slot_a, d_state_a, param_count_a, grad_scale, rule_a, stats_kind_a, kl_threshold,
+                          entropy_coeff, d_adv_stats, d_info_row_a, d_skip_flag_a))
     return rc;
-  if (int rc = adam_fill(pair.net[1], "tonic_adam_step_pair (second)", d_params_b, d_grad_sums_b,
-                         d_exp_avg_b, d_exp_avg_sq_b, d_state_b, param_count_b, grad_scale, lr_b,
-                         beta1, beta2, eps, stats_kind_b, 0.0, 0.0, nullptr, d_info_row_b, nullptr))
+  if (int rc = optim_fill(pair.net[1], blocks_b, "tonic_adam_step_pair (second)", d_params_b, d_grad_sums_b,
+                          slot_b, d_state_b, param_count_b, grad_scale, plain_adam(lr_b, beta1, beta2, eps),
+                          stats_kind_b, 0.0, 0.0, nullptr, d_info_row_b, nullptr))
     return rc;
-  const int blocks = adam_blocks_for(param_count_a > param_count_b ? param_count_a : param_count_b);
-  hipStream_t st = as_stream(stream);
-  hipLaunchKernelGGL(adam_kernel, dim3(blocks, 2), dim3(256), 0, st, pair);
-  TONIC_CHECK_LAUNCH("tonic_adam_step_pair");
-  return TONIC_OK;
+  return optim_launch(rule_a, pair, dim3(blocks_a > blocks_b ? blocks_a : blocks_b, 2), stream,
+                      "tonic_adam_step_pair");
 }
 
 extern "C" int tonic_adam_step(float* d_params, const float* d_grad_sums, float* d_exp_avg,
@@ -528,10 +456,10 @@ extern "C" int tonic_adam_step(float* d_params, const float* d_grad_sums, float*
                                double entropy_coeff,
                                const float* d_adv_stats, float* d_info_row,
                                const int32_t* d_skip_flag, void* stream) {
-  return adam_launch(d_params, d_grad_sums, d_exp_avg, d_exp_avg_sq, d_state, param_count,
-                     grad_scale, lr, beta1, beta2, eps, stats_kind, kl_threshold, entropy_coeff,
-                     d_adv_stats, d_info_row, d_skip_flag, nullptr, nullptr, 0, 0, 0.0, stream,
-                     "tonic_adam_step");
+  float* const slot[3] = {d_exp_avg, d_exp_avg_sq, nullptr};
+  return optim_step("tonic_adam_step", d_params, d_grad_sums, slot, d_state, param_count, grad_scale,
+                    plain_adam(lr, beta1, beta2, eps), stats_kind, kl_threshold, entropy_coeff, d_adv_stats,
+                    d_info_row, d_skip_flag, PolyakTail{}, stream);
 }
 
 extern "C" int tonic_adam_polyak_step(float* d_online, const float* d_grad_sums, float* d_exp_avg,
@@ -544,10 +472,10 @@ extern "C" int tonic_adam_polyak_step(float* d_online, const float* d_grad_sums,
                     block_offset + param_count <= total_count,
                 TONIC_ERR_INVALID_ARGUMENT, "tonic_adam_polyak_step: block [%lld, +%lld) of %lld",
                 (long long)block_offset, (long long)param_count, (long long)total_count);
-  return adam_launch(d_online + block_offset, d_grad_sums, d_exp_avg, d_exp_avg_sq, d_state,
-                     param_count, grad_scale, lr, beta1, beta2, eps, stats_kind, 0.0, 0.0, nullptr,
-                     d_info_row, nullptr, d_target, d_online, total_count, block_offset, coeff,
-                     stream, "tonic_adam_polyak_step");
+  float* const slot[3] = {d_exp_avg, d_exp_avg_sq, nullptr};
+  return optim_step("tonic_adam_polyak_step", d_online + block_offset, d_grad_sums, slot, d_state, param_count,
+                    grad_scale, plain_adam(lr, beta1, beta2, eps), stats_kind, 0.0, 0.0, nullptr, d_info_row,
+                    nullptr, PolyakTail{d_target, d_online, total_count, block_offset, coeff}, stream);
 }
 
 extern "C" int64_t tonic_clip_workspace_bytes(int64_t n) {

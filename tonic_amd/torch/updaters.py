@@ -7,7 +7,7 @@ stream, with no host synchronisation:
 
     tonic_ppo_actor_grad / tonic_value_regression_grad   fused forward + loss + backward
     [all-reduce of the flat gradient-sum buffer over RCCL when world_size > 1]
-    tonic_adam_step                                       flat Adam + logged statistics
+    tonic_optimizer_step                                  flat optimizer step + logged statistics
 
 The PPO agent drives them through ``enqueue`` for all 80 iterations and reads the
 statistics back once; ``__call__`` (enqueue + read back) exists for drop-in compatibility.
@@ -45,8 +45,8 @@ _FAMILY = {torch.optim.Adam: 'adam', torch.optim.AdamW: 'adamw', torch.optim.SGD
 def optimizer_hyperparameters(factory, default_lr):
     """The rule behind the reference-style ``optimizer=lambda params: torch.optim.X(params, ...)`` factory
     (actors.py:58-59), probed like `adam_hyperparameters`: Adam (with weight_decay / amsgrad / maximize), AdamW, SGD
-    (momentum, dampening, nesterov) and RMSprop (centered, momentum) run on the HIP engine (tonic_optimizer_step;
-    plain Adam on tonic_adam_step*).  -> dict(kind=, lr=, weight_decay=, maximize=, ...) with the rule's own keys,
+    (momentum, dampening, nesterov) and RMSprop (centered, momentum) run on the HIP engine (tonic_optimizer_step).
+    -> dict(kind=, lr=, weight_decay=, maximize=, ...) with the rule's own keys,
     every number a Python float (float64) as torch keeps it.  Anything else is rejected by name."""
     if factory is None:
         return dict(kind='adam', lr=float(default_lr), betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
@@ -75,8 +75,9 @@ def optimizer_hyperparameters(factory, default_lr):
 
 
 def plain_adam(rule):
-    """The rule `adam_hyperparameters` accepts: what tonic_adam_step*, tonic_adam_polyak_step and the fused
-    off-policy iteration compute (AdamW without decay is the same arithmetic)."""
+    """The rule `adam_hyperparameters` accepts: what tonic_adam_step_pair and the fused off-policy iteration
+    compute (AdamW without decay is the same arithmetic).  Every rule, this one included, steps through
+    tonic_optimizer_step otherwise."""
     return rule['kind'] in ('adam', 'adamw') and rule.get('weight_decay', 0.0) == 0 and \
         not rule.get('amsgrad', False) and not rule.get('maximize', False)
 
@@ -141,6 +142,36 @@ def optimizer_slots(lib, rule, count, device):
     if slots < 0:
         raise NotImplementedError(f'{rule}: {lib.tonic_last_error().decode() or "not a rule of the family"}')
     return packed, (torch.zeros(slots * count, dtype=torch.float32, device=device) if slots else None)
+
+
+class _OptimizerState:
+    """One flat block's optimizer on the device: `rule`, the packed tonic_optimizer_t; `slots`, its state buffers as
+    ONE tensor of slots x count floats (None for a rule without state); `state`, the int32 words {step, stop, -,
+    arrivals}.  For Adam and AdamW `exp_avg` / `exp_avg_sq` are views of the first two slots (what
+    tonic_adam_step_pair and the fused off-policy iteration take); None for SGD and RMSprop."""
+
+    def __init__(self, lib, hyper, count, device):
+        self.lib, self.count = lib, count
+        self.rule, self.slots = optimizer_slots(lib, hyper, count, device)
+        self.state = torch.zeros(4, dtype=torch.int32, device=device)
+        self.exp_avg = self.exp_avg_sq = None
+        if hyper['kind'] in ('adam', 'adamw'):
+            self.exp_avg, self.exp_avg_sq = self.slots[:count], self.slots[count:2 * count]
+
+    def enqueue(self, params, grad_sums, grad_scale, info_row, stats_kind=0, kl_threshold=0.0, entropy_coeff=0.0,
+                adv_stats=None, skip=None, targets=None, what='tonic_optimizer_step'):
+        """The step of `params` (the block's `count` floats) from `grad_sums`.  `targets` = (flat target buffer,
+        flat online buffer, offset of this block in them, coeff): the polyak update of ALL targets rides in the
+        same launch."""
+        polyak = (None, None, 0, 0, 0.0)
+        if targets is not None:
+            target, online, offset, coeff = targets
+            assert online.data_ptr() + 4 * offset == params.data_ptr()
+            polyak = (_lib.ptr(target), _lib.ptr(online), online.numel(), offset, float(coeff))
+        _lib.check(self.lib.tonic_optimizer_step(
+            _lib.ptr(params), _lib.ptr(grad_sums), _lib.ptr(self.slots), _lib.ptr(self.state), self.count,
+            grad_scale, ctypes.byref(self.rule), stats_kind, float(kl_threshold), float(entropy_coeff),
+            _lib.ptr(adv_stats), _lib.ptr(info_row), skip, *polyak, _lib.current_stream()), what)
 
 
 def fused_ppo_torso(torso):
@@ -226,15 +257,10 @@ class _FlatUpdater(_StockTorch):
         device = flat.flat.device
         self.count = flat.count
         self.grad_sums = torch.zeros(self.count + INFO_WIDTH, dtype=torch.float32, device=device)
-        # plain Adam: the two moments tonic_adam_step* take; any other rule: tonic_optimizer_t and its state slots
-        self.plain = plain_adam(hyper)
-        self.rule = self.slots = self.exp_avg = self.exp_avg_sq = None
-        if self.plain:
-            self.exp_avg = torch.zeros(self.count, dtype=torch.float32, device=device)
-            self.exp_avg_sq = torch.zeros(self.count, dtype=torch.float32, device=device)
-        else:
-            self.rule, self.slots = optimizer_slots(self.lib, hyper, self.count, device)
-        self.state = torch.zeros(4, dtype=torch.int32, device=device)   # {step, stop, -, -}
+        self.plain = plain_adam(hyper)      # the pair launch and the fused off-policy iteration serve this rule only
+        self.optim = _OptimizerState(self.lib, hyper, self.count, device)
+        self.rule, self.slots, self.state = self.optim.rule, self.optim.slots, self.optim.state
+        self.exp_avg, self.exp_avg_sq = self.optim.exp_avg, self.optim.exp_avg_sq
         self.steps_enqueued = 0     # host mirror of state[0] (off-policy: every enqueued step is taken)
         self.workspace = None
         self.scratch_info = torch.zeros(INFO_WIDTH, dtype=torch.float32, device=device)
@@ -302,35 +328,8 @@ class _FlatUpdater(_StockTorch):
             else:
                 torch.distributed.all_reduce(self.grad_sums)     # RCCL sum over xGMI
         self.enqueue_clip(n_global, skip)
-        h = self.hyper
-        if not self.plain:
-            polyak = (None, None, 0, 0, 0.0)
-            if targets is not None:
-                target, online, offset, coeff = targets
-                assert online.data_ptr() + 4 * offset == self.flat.flat.data_ptr()
-                polyak = (_lib.ptr(target), _lib.ptr(online), online.numel(), offset, float(coeff))
-            _lib.check(self.lib.tonic_optimizer_step(
-                _lib.ptr(self.flat.flat), _lib.ptr(self.grad_sums), _lib.ptr(self.slots), _lib.ptr(self.state),
-                self.count, 1.0 / n_global, ctypes.byref(self.rule), self.stats_kind, float(kl_threshold),
-                float(entropy_coeff), _lib.ptr(adv_stats), _lib.ptr(info_row), skip, *polyak,
-                _lib.current_stream()), 'tonic_optimizer_step')
-            return
-        if targets is not None:
-            target, online, offset, coeff = targets
-            assert online.data_ptr() + 4 * offset == self.flat.flat.data_ptr()
-            _lib.check(self.lib.tonic_adam_polyak_step(
-                _lib.ptr(online), _lib.ptr(self.grad_sums), _lib.ptr(self.exp_avg),
-                _lib.ptr(self.exp_avg_sq), _lib.ptr(self.state), offset, self.count,
-                online.numel(), 1.0 / n_global, h['lr'], h['betas'][0], h['betas'][1], h['eps'],
-                self.stats_kind, _lib.ptr(info_row), _lib.ptr(target), float(coeff),
-                _lib.current_stream()), 'tonic_adam_polyak_step')
-            return
-        _lib.check(self.lib.tonic_adam_step(
-            _lib.ptr(self.flat.flat), _lib.ptr(self.grad_sums), _lib.ptr(self.exp_avg),
-            _lib.ptr(self.exp_avg_sq), _lib.ptr(self.state), self.count, 1.0 / n_global,
-            h['lr'], h['betas'][0], h['betas'][1], h['eps'], self.stats_kind,
-            float(kl_threshold), float(entropy_coeff), _lib.ptr(adv_stats),
-            _lib.ptr(info_row), skip, _lib.current_stream()), 'tonic_adam_step')
+        self.optim.enqueue(self.flat.flat, self.grad_sums, 1.0 / n_global, info_row, self.stats_kind, kl_threshold,
+                           entropy_coeff, adv_stats, skip, targets)
 
 
 def adam_step_constants(hyper, step):
@@ -1465,13 +1464,9 @@ class MaximumAPosterioriPolicyOptimization(_ActorQGradient):
             [self.initial_log_alpha_std] * A + [self.initial_log_temperature]
         self.duals = torch.tensor(duals, dtype=torch.float32, device=device)
         self.dual_grads = torch.zeros(2 * A + 2 + INFO_WIDTH, dtype=torch.float32, device=device)
-        self.dual_rule = self.dual_slots = self.dual_exp_avg = self.dual_exp_avg_sq = None
-        if plain_adam(self.dual_hyper):
-            self.dual_exp_avg = torch.zeros(2 * A + 2, dtype=torch.float32, device=device)
-            self.dual_exp_avg_sq = torch.zeros(2 * A + 2, dtype=torch.float32, device=device)
-        else:
-            self.dual_rule, self.dual_slots = optimizer_slots(self.lib, self.dual_hyper, 2 * A + 2, device)
-        self.dual_state = torch.zeros(4, dtype=torch.int32, device=device)
+        self.dual_optim = _OptimizerState(self.lib, self.dual_hyper, 2 * A + 2, device)
+        self.dual_slots, self.dual_state = self.dual_optim.slots, self.dual_optim.state
+        self.dual_exp_avg, self.dual_exp_avg_sq = self.dual_optim.exp_avg, self.dual_optim.exp_avg_sq
         self.mpo_stats = torch.zeros(9 + 2 * A, dtype=torch.float32, device=device)
         self.dual_info = torch.zeros(INFO_WIDTH, dtype=torch.float32, device=device)
         self.column_sums = torch.zeros(6 + 2 * A, dtype=torch.float64, device=device)
@@ -1529,7 +1524,6 @@ class MaximumAPosterioriPolicyOptimization(_ActorQGradient):
                 int(bool(self.action_penalization)), p(ws), ws.numel(), _lib.current_stream()),
                 'tonic_mpo_actor_grad')
         self._step(n_global or B, info_row, targets=targets)
-        h = self.dual_hyper
         if self.gradient_clip > 0:
             # actors.py:441-445 clips the dual variables' gradient norm as well (the penalty
             # temperature's entry is zero without action penalisation, so it does not count)
@@ -1537,17 +1531,8 @@ class MaximumAPosterioriPolicyOptimization(_ActorQGradient):
                 p(self.dual_grads), self.duals.numel(), 1.0, self.gradient_clip, None,
                 p(self.dual_clip_workspace), self.dual_clip_workspace.numel(),
                 _lib.current_stream()), 'tonic_clip_grad_norm (duals)')
-        if self.dual_rule is not None:
-            _lib.check(self.lib.tonic_optimizer_step(
-                p(self.duals), p(self.dual_grads), p(self.dual_slots), p(self.dual_state), self.duals.numel(), 1.0,
-                ctypes.byref(self.dual_rule), 0, 0.0, 0.0, None, p(self.dual_info), None, None, None, 0, 0, 0.0,
-                _lib.current_stream()), 'tonic_optimizer_step (duals)')
-            return
-        _lib.check(self.lib.tonic_adam_step(
-            p(self.duals), p(self.dual_grads), p(self.dual_exp_avg), p(self.dual_exp_avg_sq),
-            p(self.dual_state), self.duals.numel(), 1.0, h['lr'], h['betas'][0], h['betas'][1],
-            h['eps'], 0, 0.0, 0.0, None, p(self.dual_info), None, _lib.current_stream()),
-            'tonic_adam_step (duals)')
+        self.dual_optim.enqueue(self.duals, self.dual_grads, 1.0, self.dual_info,
+                                what='tonic_optimizer_step (duals)')
 
     def enqueue_empty(self, info_row, n_global, targets=None, stats_row=None):
         """This rank drew none of the global batch: zero sums, the same dual and actor steps."""
