@@ -59,10 +59,12 @@ const char* tonic_last_error(void);
  * 1 .. 4 layer torsos for every off-policy entry, the D4PG / MPO entries take tonic_mlp_hidden codes,
  * 14 = the tonic_trpo_* entries, 15 = tonic_optimizer_step / tonic_optimizer_state_slots,
  * 16 = tonic_critic_loss_t: tonic_critic_loss_check, tonic_twin_q_grad_loss, tonic_expected_sarsa_grad_loss,
- * tonic_q_iteration_t.critic_loss)
+ * tonic_q_iteration_t.critic_loss), 17 = the tonic_mpo_*_joint entries (`joint_kl`: one alpha pair on the KLs
+ * summed over the action dimensions); the MPO entries take 1 .. 256 samples per state (additive: every earlier
+ * entry keeps its signature)
  * and the gfx target the kernels were built for.  TONIC_ABI_VERSION is what a binding was compiled against:
  * tonic_amd/_fastcall (csrc/fastcall.c) and tonic_amd/_lib.py compare it with the loaded library's answer. */
-#define TONIC_ABI_VERSION 16
+#define TONIC_ABI_VERSION 17
 int32_t tonic_abi_version(void);
 const char* tonic_target_arch(void);
 
@@ -972,7 +974,8 @@ int tonic_distributional_actor_grad(const float* d_actor_params, const float* d_
 
 /* ---- MPO (tonic/torch/agents/mpo.py): Gaussian policy head with a tanh loc and
  *   sigma = clamp(softplus(.), 1e-4, 1) (models/actors.py:69-98, two heads), ONE critic with
- *   targets (layouts as for DDPG / SAC); S <= 64 sampled actions per state, tiled like
+ *   targets (layouts as for DDPG / SAC); 1 <= S <= 256 sampled actions per state (four register slots per
+ *   lane of the state's wave in the E-step; anything else is TONIC_ERR_INVALID_ARGUMENT), tiled like
  *   updaters.tile + merge_first_two_dims (row s * B + m); d_eps = the standard-normal draws
  *   [S, B, A] in the order Normal.rsample / Normal.sample consume them.
  *   tonic_policy_forward kind 2 acts with this head (a = loc + sigma * eps; eps NULL = loc).
@@ -1041,6 +1044,32 @@ int tonic_mpo_dual_step(const double* d_column_sums, float* d_duals, double min_
                         int32_t A, int32_t S, double epsilon, double epsilon_penalty,
                         double epsilon_mean, double epsilon_std, int32_t action_penalization,
                         void* stream);
+/* The three entries above with `joint_kl` (0: exactly the entries above; 1: per_dim_constraining=False,
+ * actors.py:305, 415-426 — ONE log_alpha_mean and ONE log_alpha_std constrain the KLs of the Independent normals,
+ * i.e. the per-dimension KLs summed over the action dimensions).  With K = joint_kl ? 1 : A: d_duals [2 K + 2] =
+ * {log_temperature, log_alpha_mean[K], log_alpha_std[K], log_penalty_temperature}, d_dual_grads [2 K + 2 + 8] and
+ * d_stats [9 + 2 K] in the order above with K in place of A.  d_column_sums stays [6 + 2 A]: the per-dimension KL
+ * columns are what the ranks exchange, the dual step sums them over the dimensions (in float64, ascending). */
+int tonic_mpo_actor_grad_joint(const float* d_actor_params, const float* d_target_actor,
+                               const float* d_target_critic, float* d_duals, double min_log_dual,
+                               const float* d_norm_mean, const float* d_norm_std, double norm_clip,
+                               const float* d_observations, const float* d_eps, float* d_grad_sums,
+                               float* d_dual_grads, float* d_stats, int32_t B, int32_t O, int32_t H,
+                               int32_t A, int32_t S, double epsilon, double epsilon_penalty,
+                               double epsilon_mean, double epsilon_std, int32_t action_penalization,
+                               int32_t joint_kl, void* d_workspace, int64_t workspace_bytes, void* stream);
+int tonic_mpo_actor_grad_shard_joint(const float* d_actor_params, const float* d_target_actor,
+                                     const float* d_target_critic, float* d_duals, double min_log_dual,
+                                     const float* d_norm_mean, const float* d_norm_std, double norm_clip,
+                                     const float* d_observations, const float* d_eps, float* d_grad_sums,
+                                     double* d_column_sums, int32_t B, int32_t O, int32_t H, int32_t A,
+                                     int32_t S, int32_t action_penalization, int32_t joint_kl,
+                                     void* d_workspace, int64_t workspace_bytes, void* stream);
+int tonic_mpo_dual_step_joint(const double* d_column_sums, float* d_duals, double min_log_dual,
+                              float* d_dual_grads, float* d_stats, float* d_actor_stats, int32_t B,
+                              int32_t B_global, int32_t A, int32_t S, double epsilon,
+                              double epsilon_penalty, double epsilon_mean, double epsilon_std,
+                              int32_t action_penalization, int32_t joint_kl, void* stream);
 
 #ifdef __cplusplus
 }

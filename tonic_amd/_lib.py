@@ -182,6 +182,13 @@ SIGNATURES = {
                                    [c_i32] * 6 + [c_vp, c_i64, c_vp]),
     'tonic_mpo_dual_step': (ctypes.c_int, [c_vp] * 2 + [c_f64] + [c_vp] * 3 + [c_i32] * 4 + [c_f64] * 4 +
                             [c_i32, c_vp]),
+    # ... with `joint_kl` after `action_penalization` (ABI 17)
+    'tonic_mpo_actor_grad_joint': (ctypes.c_int, [c_vp] * 4 + [c_f64] + [c_vp] * 2 + [c_f64] + [c_vp] * 5 +
+                                   [c_i32] * 5 + [c_f64] * 4 + [c_i32] * 2 + [c_vp, c_i64, c_vp]),
+    'tonic_mpo_actor_grad_shard_joint': (ctypes.c_int, [c_vp] * 4 + [c_f64] + [c_vp] * 2 + [c_f64] + [c_vp] * 4 +
+                                         [c_i32] * 7 + [c_vp, c_i64, c_vp]),
+    'tonic_mpo_dual_step_joint': (ctypes.c_int, [c_vp] * 2 + [c_f64] + [c_vp] * 3 + [c_i32] * 4 + [c_f64] * 4 +
+                                  [c_i32, c_i32, c_vp]),
     'tonic_collector_block_bytes': (c_i64, [c_i64, c_i32, c_i32]),
     'tonic_collector_block_init': (ctypes.c_int, [c_vp, c_i64, c_i64, c_i32, c_i32, c_i32]),
     'tonic_collector_block_offset': (c_i64, [c_vp, c_i32]),
@@ -224,7 +231,7 @@ SIGNATURES = {
 }
 
 
-ABI_VERSION = 16       # include/tonic_hip.h: tonic_abi_version()
+ABI_VERSION = 17       # include/tonic_hip.h: tonic_abi_version()
 
 
 class TonicHipError(RuntimeError):

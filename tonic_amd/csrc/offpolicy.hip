@@ -385,11 +385,15 @@ __global__ void sample_mean_kernel(const float* q, float* out, int B, int S) {
   out[m] = sum / (float)S;
 }
 
-constexpr int kMpoMaxSamples = 64;
+// E-step samples per state: lane l of the state's wave holds samples l, l + 64, ... in kMpoMaxSlots register
+// slots (a condition of mpo_state_kernel's layout, not a tuned figure)
+constexpr int kMpoMaxSlots = 4;
+constexpr int kMpoMaxSamples = 64 * kMpoMaxSlots;
 constexpr int kMpoStats = 16;    // per-state partials: see mpo_state_kernel
 
-// duals [2 A + 2] = {log_temperature, log_alpha_mean[A], log_alpha_std[A], log_penalty_temperature}
-// (actors.py:300-316, per_dim_constraining); value = softplus(log) + 1e-8 (actors.py:378-383)
+// duals [2 K + 2] = {log_temperature, log_alpha_mean[K], log_alpha_std[K], log_penalty_temperature}, K = A
+// (per_dim_constraining) or K = 1 (joint_kl: one alpha pair on the KLs of the Independent normals, actors.py:300-316);
+// value = softplus(log) + 1e-8 (actors.py:378-383)
 __device__ __forceinline__ float dual_value(float log_dual) { return softplus_f(log_dual) + 1e-8f; }
 
 // E-step weights and the M-step gradients at the head outputs, one WAVE per state: lane = sample for
@@ -399,48 +403,74 @@ __device__ __forceinline__ float dual_value(float log_dual) { return softplus_f(
 //   d/d sigma = -sum_s W_s ((a_s - loc_t)^2 / sigma^3 - 1 / sigma) + alpha_std (1 / sigma - sigma_t^2 / sigma^3)
 // with W = softmax_s(q / T) + softmax_s(bound cost / T_penalty).  part[m][.] = {policy_mean, policy_std,
 // LSE, LSE - sum_s w q / T, LSE_penalty, LSE_penalty - sum_s w_p cost / T_p}; klm / kls [m][a] = the
-// per-dimension KLs.  The temperatures' gradients need the differences LSE - sum_s w x (the entropy of w, in
+// per-dimension KLs (joint_kl: the dual kernel sums them over a; every dimension reads the one alpha pair).
+// The temperatures' gradients need the differences LSE - sum_s w x (the entropy of w, in
 // [0, log S]): they are formed here in the max-shifted frame, log(sum) - sum_s w (x - max), because at a cold
 // temperature LSE and sum_s w x are each of the order of |x| (~1e7 for a penalty temperature on the dual floor)
 // and their difference would be lost to float32 rounding.
+// SLOTS = ceil(S / 64): lane l holds samples l + 64 k in slot k (arrays indexed by unrolled constants only, so
+// they stay in registers); a reduction runs over the lane's slots in ascending k, then across the wave.
+// SLOTS = 1 is the one-sample-per-lane kernel operation for operation.
+template <int SLOTS>
 __global__ __launch_bounds__(256) void mpo_state_kernel(
     const float* q, const float* act, const float* loc_t, const float* spre_t, const float* loc,
-    const float* spre, int ldh, const float* duals, float floor, int penalize, float* dloc, float* dspre,
-    float* part, float* klm, float* kls, int B, int A, int S) {
+    const float* spre, int ldh, const float* duals, float floor, int penalize, int joint_kl, float* dloc,
+    float* dspre, float* part, float* klm, float* kls, int B, int A, int S) {
   const int lane = threadIdx.x & 63;
   const int m = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (m >= B) return;
+  const int K = joint_kl ? 1 : A;
   // (every log-dual is read through the floor the reference clamps it to, in place, at the head of its call —
   //  actors.py:347-356; mpo_dual_kernel, the last reader ahead of the duals' optimizer step, writes the
   //  clamped values back)
-  const float T = dual_value(fmaxf(duals[0], floor)), Tp = dual_value(fmaxf(duals[2 * A + 1], floor));
+  const float T = dual_value(fmaxf(duals[0], floor)), Tp = dual_value(fmaxf(duals[2 * K + 1], floor));
+  // softmax over the samples of x (-inf in the slots past S): w[k], LSE and the entropy-like difference
+  auto softmax = [&](const float (&x)[SLOTS], float (&w)[SLOTS], float* lse) {
+    float mx = x[0];
+#pragma unroll
+    for (int k = 1; k < SLOTS; ++k) mx = fmaxf(mx, x[k]);
+    mx = wave_max(mx);
+    float e[SLOTS];
+#pragma unroll
+    for (int k = 0; k < SLOTS; ++k) e[k] = lane + 64 * k < S ? expf(x[k] - mx) : 0.f;
+    float sum = e[0];
+#pragma unroll
+    for (int k = 1; k < SLOTS; ++k) sum += e[k];
+    sum = wave_sum(sum);
+    *lse = mx + logf(sum);
+#pragma unroll
+    for (int k = 0; k < SLOTS; ++k) w[k] = e[k] / sum;
+    float wx = lane < S ? w[0] * (x[0] - mx) : 0.f;
+#pragma unroll
+    for (int k = 1; k < SLOTS; ++k) wx += lane + 64 * k < S ? w[k] * (x[k] - mx) : 0.f;
+    return logf(sum) - wave_sum(wx);
+  };
   // weights_and_temperature_loss (actors.py:325-338): softmax over the samples of q / T
-  const bool sample = lane < S;
-  const float tempered = sample ? q[(int64_t)lane * B + m] / T : -INFINITY;
-  const float mx = wave_max(tempered);
-  const float e = sample ? expf(tempered - mx) : 0.f;
-  const float sum = wave_sum(e);
-  const float lse = mx + logf(sum);
-  float w = e / sum;
-  const float wq = logf(sum) - wave_sum(sample ? w * (tempered - mx) : 0.f);
+  float x[SLOTS], w[SLOTS];
+#pragma unroll
+  for (int k = 0; k < SLOTS; ++k)
+    x[k] = lane + 64 * k < S ? q[(int64_t)(lane + 64 * k) * B + m] / T : -INFINITY;
+  float lse;
+  const float wq = softmax(x, w, &lse);
   float lse_p = 0.f, wc = 0.f;
   if (penalize) {                                              // actors.py:388-398
-    float n2 = 0.f;
-    if (sample) {
-      for (int a = 0; a < A; ++a) {
-        const float v = act[((int64_t)lane * B + m) * A + a];
-        const float d = v - fminf(fmaxf(v, -1.f), 1.f);
-        n2 += d * d;
+    float wp[SLOTS];
+#pragma unroll
+    for (int k = 0; k < SLOTS; ++k) {
+      const int s = lane + 64 * k;
+      float n2 = 0.f;
+      if (s < S) {
+        for (int a = 0; a < A; ++a) {
+          const float v = act[((int64_t)s * B + m) * A + a];
+          const float d = v - fminf(fmaxf(v, -1.f), 1.f);
+          n2 += d * d;
+        }
       }
+      x[k] = s < S ? -sqrtf(n2) / Tp : -INFINITY;
     }
-    const float cost = sample ? -sqrtf(n2) / Tp : -INFINITY;
-    const float mp = wave_max(cost);
-    const float ep = sample ? expf(cost - mp) : 0.f;
-    const float sp = wave_sum(ep);
-    lse_p = mp + logf(sp);
-    const float wp = ep / sp;
-    wc = logf(sp) - wave_sum(sample ? wp * (cost - mp) : 0.f);
-    w += wp;
+    wc = softmax(x, wp, &lse_p);
+#pragma unroll
+    for (int k = 0; k < SLOTS; ++k) w[k] += wp[k];
   }
   // lane = action dimension: the sums over the samples in sample order
   const bool live = lane < A;
@@ -449,15 +479,19 @@ __global__ __launch_bounds__(256) void mpo_state_kernel(
   const float lo = loc[(int64_t)m * ldh + a], pre = spre[(int64_t)m * ldh + a];
   const float sg = gaussian_sigma(pre);
   float pm = 0.f, ps = 0.f, g_loc = 0.f, g_sigma = 0.f;
-  for (int s = 0; s < S; ++s) {
-    const float ws = __shfl(w, s, 64);
-    const float v = act[((int64_t)s * B + m) * A + a];
-    const float d_mean = v - lo, d_std = v - lt;
-    // Normal.log_prob: -(x - mu)^2 / (2 var) - log(sigma) - log(sqrt(2 pi))
-    pm += ws * (-(d_mean * d_mean) / (2.f * (st * st)) - logf(st) - kHalfLog2Pi);
-    ps += ws * (-(d_std * d_std) / (2.f * (sg * sg)) - logf(sg) - kHalfLog2Pi);
-    g_loc -= ws * d_mean / (st * st);
-    g_sigma -= ws * (d_std * d_std / (sg * sg * sg) - 1.f / sg);
+#pragma unroll
+  for (int k = 0; k < SLOTS; ++k) {
+    const int n = min(64, S - 64 * k);
+    for (int j = 0; j < n; ++j) {
+      const float ws = __shfl(w[k], j, 64);
+      const float v = act[((int64_t)(64 * k + j) * B + m) * A + a];
+      const float d_mean = v - lo, d_std = v - lt;
+      // Normal.log_prob: -(x - mu)^2 / (2 var) - log(sigma) - log(sqrt(2 pi))
+      pm += ws * (-(d_mean * d_mean) / (2.f * (st * st)) - logf(st) - kHalfLog2Pi);
+      ps += ws * (-(d_std * d_std) / (2.f * (sg * sg)) - logf(sg) - kHalfLog2Pi);
+      g_loc -= ws * d_mean / (st * st);
+      g_sigma -= ws * (d_std * d_std / (sg * sg * sg) - 1.f / sg);
+    }
   }
   pm = wave_sum(live ? pm : 0.f);
   ps = wave_sum(live ? ps : 0.f);
@@ -466,8 +500,9 @@ __global__ __launch_bounds__(256) void mpo_state_kernel(
     const float ratio = st / sg;
     klm[(int64_t)m * A + a] = 0.5f * ((lt - lo) / st) * ((lt - lo) / st);
     kls[(int64_t)m * A + a] = 0.5f * (ratio * ratio - 1.f - logf(ratio * ratio));
-    const float alpha_mean = dual_value(fmaxf(duals[1 + a], floor)),
-                alpha_std = dual_value(fmaxf(duals[1 + A + a], floor));
+    const int k = joint_kl ? 0 : a;
+    const float alpha_mean = dual_value(fmaxf(duals[1 + k], floor)),
+                alpha_std = dual_value(fmaxf(duals[1 + K + k], floor));
     g_loc += alpha_mean * (lo - lt) / (st * st);
     g_sigma += alpha_std * (1.f / sg - st * st / (sg * sg * sg));
     const float raw = softplus_f(pre);
@@ -482,16 +517,18 @@ __global__ __launch_bounds__(256) void mpo_state_kernel(
 }
 
 // Batch means -> the logged losses, the dual variables' values and their gradients (one workgroup).
-// stats [7 + 2 A + 2] = {policy_mean_loss, policy_std_loss, kl_mean_loss, kl_std_loss, alpha_mean_loss,
-// alpha_std_loss, temperature_loss, temperature, alpha_mean[A], alpha_std[A], penalty_temperature};
-// dual_grads [2 A + 2 + 8]: d loss / d log-duals + the statistics slot of the optimizer step.
+// stats [7 + 2 K + 2] = {policy_mean_loss, policy_std_loss, kl_mean_loss, kl_std_loss, alpha_mean_loss,
+// alpha_std_loss, temperature_loss, temperature, alpha_mean[K], alpha_std[K], penalty_temperature};
+// dual_grads [2 K + 2 + 8]: d loss / d log-duals + the statistics slot of the optimizer step.  K = A, or 1 with
+// joint_kl: the one alpha pair constrains the KLs summed over the action dimensions (actors.py:319-323 on KLs of
+// shape [B] with an alpha of shape [1]).
 //
 // Several ranks (each holds B of the B_norm states of the global batch): everything below is a
 // function of the column MEANS, so the kernel runs in two halves around one all-reduce —
 // out_sums != null: only the local column sums [6 + 2 A] (float64) are written; in_sums != null: the
 // columns are taken from there (the all-reduced sums) instead of the per-state arrays.
 __global__ void mpo_dual_kernel(const float* part, const float* klm, const float* kls,
-                                float* duals, float floor, int penalize, float epsilon,
+                                float* duals, float floor, int penalize, int joint_kl, float epsilon,
                                 float epsilon_penalty, float epsilon_mean, float epsilon_std,
                                 float* dual_grads, float* stats, float* actor_stats, int B, int A,
                                 int S, const double* in_sums, double* out_sums, int B_norm) {
@@ -517,24 +554,32 @@ __global__ void mpo_dual_kernel(const float* part, const float* klm, const float
   }
   if (out_sums != nullptr) return;                    // (uniform)
   __syncthreads();
-  if (tid >= 64) return;                              // wave 0: lane = action dimension
-  const float log_T = fmaxf(duals[0], floor), log_Tp = fmaxf(duals[2 * A + 1], floor);
+  if (tid >= 64) return;                              // wave 0: lane = constraint (action dimension, or the one)
+  const int K = joint_kl ? 1 : A;
+  const float log_T = fmaxf(duals[0], floor), log_Tp = fmaxf(duals[2 * K + 1], floor);
   const float T = dual_value(log_T), Tp = dual_value(log_Tp);
   const float log_S = logf((float)S);
   auto sigmoid = [](float x) { return 1.f / (1.f + expf(-x)); };
   float kl_mean_loss = 0.f, kl_std_loss = 0.f, alpha_mean_loss = 0.f, alpha_std_loss = 0.f;
-  if (tid < A) {
+  if (tid < K) {
     const int a = tid;
-    const float log_am = fmaxf(duals[1 + a], floor), log_as = fmaxf(duals[1 + A + a], floor);
+    const float log_am = fmaxf(duals[1 + a], floor), log_as = fmaxf(duals[1 + K + a], floor);
     const float am = dual_value(log_am), as = dual_value(log_as);
-    const float km = (float)col[6 + a], ks = (float)col[6 + A + a];
+    float km, ks;
+    if (joint_kl) {                                   // the KL of the Independent normals: summed over a
+      double sm = 0, ss = 0;
+      for (int i = 0; i < A; ++i) { sm += col[6 + i]; ss += col[6 + A + i]; }
+      km = (float)sm; ks = (float)ss;
+    } else {
+      km = (float)col[6 + a]; ks = (float)col[6 + A + a];
+    }
     kl_mean_loss = am * km; kl_std_loss = as * ks;                        // actors.py:319-323
     alpha_mean_loss = am * (epsilon_mean - km);
     alpha_std_loss = as * (epsilon_std - ks);
     dual_grads[1 + a] = (epsilon_mean - km) * sigmoid(log_am);
-    dual_grads[1 + A + a] = (epsilon_std - ks) * sigmoid(log_as);
-    duals[1 + a] = log_am; duals[1 + A + a] = log_as;      // the reference's in-place clamp (actors.py:347-356)
-    stats[8 + a] = am; stats[8 + A + a] = as;
+    dual_grads[1 + K + a] = (epsilon_std - ks) * sigmoid(log_as);
+    duals[1 + a] = log_am; duals[1 + K + a] = log_as;      // the reference's in-place clamp (actors.py:347-356)
+    stats[8 + a] = am; stats[8 + K + a] = as;
   }
   kl_mean_loss = wave_sum(kl_mean_loss); kl_std_loss = wave_sum(kl_std_loss);
   alpha_mean_loss = wave_sum(alpha_mean_loss); alpha_std_loss = wave_sum(alpha_std_loss);
@@ -543,17 +588,17 @@ __global__ void mpo_dual_kernel(const float* part, const float* klm, const float
   float temperature_loss = T * (epsilon + (float)col[2] - log_S);
   dual_grads[0] = (epsilon + (float)col[3] - log_S) * sigmoid(log_T);
   duals[0] = log_T;
-  if (penalize) duals[2 * A + 1] = log_Tp;
-  dual_grads[2 * A + 1] = 0.f;
+  if (penalize) duals[2 * K + 1] = log_Tp;
+  dual_grads[2 * K + 1] = 0.f;
   if (penalize) {
     temperature_loss += Tp * (epsilon_penalty + (float)col[4] - log_S);
-    dual_grads[2 * A + 1] =
+    dual_grads[2 * K + 1] =
         (epsilon_penalty + (float)col[5] - log_S) * sigmoid(log_Tp);
   }
-  for (int i = 0; i < 8; ++i) dual_grads[2 * A + 2 + i] = i == 5 ? 1.f : 0.f;
+  for (int i = 0; i < 8; ++i) dual_grads[2 * K + 2 + i] = i == 5 ? 1.f : 0.f;
   stats[0] = -(float)col[0]; stats[1] = -(float)col[1]; stats[2] = kl_mean_loss; stats[3] = kl_std_loss;
   stats[4] = alpha_mean_loss; stats[5] = alpha_std_loss; stats[6] = temperature_loss; stats[7] = T;
-  stats[8 + 2 * A] = Tp;
+  stats[8 + 2 * K] = Tp;
   // the actor's statistics slot {loss_sum = B * (policy losses + KL losses), 0, 0, 0, 0, B, 0, 0}
   actor_stats[0] = (float)B * (stats[0] + stats[1] + kl_mean_loss + kl_std_loss);
   for (int i = 1; i < 8; ++i) actor_stats[i] = i == 5 ? (float)B : 0.f;
@@ -2033,7 +2078,7 @@ extern "C" int tonic_expected_sarsa_grad_loss(
                     d_observations && d_actions && d_next_observations && d_rewards &&
                     d_discounts && d_eps && d_grad_sums && d_workspace && B > 0 && S >= 1 &&
                     S <= kMpoMaxSamples && hidden_known(H),
-                TONIC_ERR_INVALID_ARGUMENT, "tonic_expected_sarsa_grad: bad argument (1 <= samples <= 64)");
+                TONIC_ERR_INVALID_ARGUMENT, "tonic_expected_sarsa_grad: bad argument (1 <= samples <= 256)");
   TONIC_REQUIRE(workspace_bytes >= tonic_mpo_workspace_bytes(B, O, A, H, S), TONIC_ERR_WORKSPACE,
                 "tonic_expected_sarsa_grad: workspace too small");
   hipStream_t st = as_stream(stream);
@@ -2057,18 +2102,38 @@ extern "C" int tonic_expected_sarsa_grad_loss(
 }
 
 namespace {
+static_assert(kMpoMaxSamples == 256, "the messages of the MPO entries name the bound");
+
+// the state kernel on ceil(S / 64) register slots per lane
+void launch_mpo_state(int slots, dim3 grid, hipStream_t st, const float* q, const float* act, const float* loc_t,
+                      const float* spre_t, const float* loc, const float* spre, int ldh, const float* duals,
+                      float floor, int penalize, int joint_kl, float* dloc, float* dspre, float* part, float* klm,
+                      float* kls, int B, int A, int S) {
+#define TONIC_MPO_STATE(SLOTS)                                                                                  \
+  hipLaunchKernelGGL(mpo_state_kernel<SLOTS>, grid, dim3(256), 0, st, q, act, loc_t, spre_t, loc, spre, ldh,   \
+                     duals, floor, penalize, joint_kl, dloc, dspre, part, klm, kls, B, A, S)
+  switch (slots) {
+    case 1: TONIC_MPO_STATE(1); break;
+    case 2: TONIC_MPO_STATE(2); break;
+    case 3: TONIC_MPO_STATE(3); break;
+    default: TONIC_MPO_STATE(4); break;
+  }
+#undef TONIC_MPO_STATE
+}
+
 int mpo_actor_grad(
     const float* d_actor_params, const float* d_target_actor, const float* d_target_critic,
     float* d_duals, double min_log_dual, const float* d_norm_mean, const float* d_norm_std, double norm_clip,
     const float* d_observations, const float* d_eps, float* d_grad_sums, float* d_dual_grads,
     float* d_stats, int32_t B, int32_t O, int32_t H, int32_t A, int32_t S, double epsilon,
     double epsilon_penalty, double epsilon_mean, double epsilon_std, int32_t action_penalization,
-    void* d_workspace, int64_t workspace_bytes, void* stream, double* d_column_sums) {
+    int32_t joint_kl, void* d_workspace, int64_t workspace_bytes, void* stream, double* d_column_sums) {
   TONIC_REQUIRE(d_actor_params && d_target_actor && d_target_critic && d_duals && d_norm_mean &&
                     d_norm_std && d_observations && d_eps && d_grad_sums &&
                     (d_column_sums || (d_dual_grads && d_stats)) &&
-                    d_workspace && B > 0 && S >= 1 && S <= kMpoMaxSamples && A <= 64 && hidden_known(H),
-                TONIC_ERR_INVALID_ARGUMENT, "tonic_mpo_actor_grad: bad argument");
+                    d_workspace && B > 0 && S >= 1 && S <= kMpoMaxSamples && A >= 1 && A <= 64 &&
+                    (joint_kl == 0 || joint_kl == 1) && hidden_known(H),
+                TONIC_ERR_INVALID_ARGUMENT, "tonic_mpo_actor_grad: bad argument (1 <= samples <= 256, A <= 64)");
   TONIC_REQUIRE(workspace_bytes >= tonic_mpo_workspace_bytes(B, O, A, H, S), TONIC_ERR_WORKSPACE,
                 "tonic_mpo_actor_grad: workspace too small");
   hipStream_t st = as_stream(stream);
@@ -2080,11 +2145,11 @@ int mpo_actor_grad(
                          d_observations, d_eps, B, O, H, A, S, w, st));
   TRY(actor_forward(d_actor_params, as, d_observations, B, w.o_h1, w.o_h2, w.loc, w.spre, ldh, true,
                     st));
-  hipLaunchKernelGGL(mpo_state_kernel, dim3((B + 3) / 4), dim3(256), 0, st, w.tq,
-                     w.act, w.loc_t, w.spre_t, w.loc, w.spre, ldh, d_duals, (float)min_log_dual,
-                     action_penalization, w.dloc, w.dspre, w.part, w.klm, w.kls, B, A, S);
+  launch_mpo_state((S + 63) / 64, dim3((B + 3) / 4), st, w.tq, w.act, w.loc_t, w.spre_t, w.loc, w.spre, ldh, d_duals,
+                   (float)min_log_dual, action_penalization, joint_kl, w.dloc, w.dspre, w.part, w.klm, w.kls, B, A,
+                   S);
   hipLaunchKernelGGL(mpo_dual_kernel, dim3(1), dim3(1024), 0, st, w.part, w.klm, w.kls, d_duals,
-                     (float)min_log_dual, action_penalization, (float)epsilon, (float)epsilon_penalty,
+                     (float)min_log_dual, action_penalization, joint_kl, (float)epsilon, (float)epsilon_penalty,
                      (float)epsilon_mean, (float)epsilon_std, d_dual_grads, d_stats,
                      d_grad_sums + actor_count(as), B, A, S, (const double*)nullptr, d_column_sums,
                      B);
@@ -2102,10 +2167,24 @@ extern "C" int tonic_mpo_actor_grad(
     float* d_stats, int32_t B, int32_t O, int32_t H, int32_t A, int32_t S, double epsilon,
     double epsilon_penalty, double epsilon_mean, double epsilon_std, int32_t action_penalization,
     void* d_workspace, int64_t workspace_bytes, void* stream) {
+  return tonic_mpo_actor_grad_joint(d_actor_params, d_target_actor, d_target_critic, d_duals, min_log_dual,
+                                    d_norm_mean, d_norm_std, norm_clip, d_observations, d_eps, d_grad_sums,
+                                    d_dual_grads, d_stats, B, O, H, A, S, epsilon, epsilon_penalty, epsilon_mean,
+                                    epsilon_std, action_penalization, 0, d_workspace, workspace_bytes, stream);
+}
+
+// ... with joint_kl = 1: one alpha pair on the KLs summed over the action dimensions (duals [4], stats [11])
+extern "C" int tonic_mpo_actor_grad_joint(
+    const float* d_actor_params, const float* d_target_actor, const float* d_target_critic,
+    float* d_duals, double min_log_dual, const float* d_norm_mean, const float* d_norm_std, double norm_clip,
+    const float* d_observations, const float* d_eps, float* d_grad_sums, float* d_dual_grads,
+    float* d_stats, int32_t B, int32_t O, int32_t H, int32_t A, int32_t S, double epsilon,
+    double epsilon_penalty, double epsilon_mean, double epsilon_std, int32_t action_penalization,
+    int32_t joint_kl, void* d_workspace, int64_t workspace_bytes, void* stream) {
   return mpo_actor_grad(d_actor_params, d_target_actor, d_target_critic, d_duals, min_log_dual, d_norm_mean,
                         d_norm_std, norm_clip, d_observations, d_eps, d_grad_sums, d_dual_grads,
                         d_stats, B, O, H, A, S, epsilon, epsilon_penalty, epsilon_mean, epsilon_std,
-                        action_penalization, d_workspace, workspace_bytes, stream, nullptr);
+                        action_penalization, joint_kl, d_workspace, workspace_bytes, stream, nullptr);
 }
 
 extern "C" int tonic_mpo_actor_grad_shard(
@@ -2114,11 +2193,23 @@ extern "C" int tonic_mpo_actor_grad_shard(
     const float* d_observations, const float* d_eps, float* d_grad_sums, double* d_column_sums,
     int32_t B, int32_t O, int32_t H, int32_t A, int32_t S, int32_t action_penalization,
     void* d_workspace, int64_t workspace_bytes, void* stream) {
+  return tonic_mpo_actor_grad_shard_joint(d_actor_params, d_target_actor, d_target_critic, d_duals, min_log_dual,
+                                          d_norm_mean, d_norm_std, norm_clip, d_observations, d_eps, d_grad_sums,
+                                          d_column_sums, B, O, H, A, S, action_penalization, 0, d_workspace,
+                                          workspace_bytes, stream);
+}
+
+extern "C" int tonic_mpo_actor_grad_shard_joint(
+    const float* d_actor_params, const float* d_target_actor, const float* d_target_critic,
+    float* d_duals, double min_log_dual, const float* d_norm_mean, const float* d_norm_std, double norm_clip,
+    const float* d_observations, const float* d_eps, float* d_grad_sums, double* d_column_sums,
+    int32_t B, int32_t O, int32_t H, int32_t A, int32_t S, int32_t action_penalization, int32_t joint_kl,
+    void* d_workspace, int64_t workspace_bytes, void* stream) {
   TONIC_REQUIRE(d_column_sums != nullptr, TONIC_ERR_INVALID_ARGUMENT,
                 "tonic_mpo_actor_grad_shard: null column sums");
   return mpo_actor_grad(d_actor_params, d_target_actor, d_target_critic, d_duals, min_log_dual, d_norm_mean,
                         d_norm_std, norm_clip, d_observations, d_eps, d_grad_sums, nullptr, nullptr,
-                        B, O, H, A, S, 0.0, 0.0, 0.0, 0.0, action_penalization, d_workspace,
+                        B, O, H, A, S, 0.0, 0.0, 0.0, 0.0, action_penalization, joint_kl, d_workspace,
                         workspace_bytes, stream, d_column_sums);
 }
 
@@ -2127,12 +2218,24 @@ extern "C" int tonic_mpo_dual_step(const double* d_column_sums, float* d_duals, 
                                    int32_t B, int32_t B_global, int32_t A, int32_t S,
                                    double epsilon, double epsilon_penalty, double epsilon_mean,
                                    double epsilon_std, int32_t action_penalization, void* stream) {
+  return tonic_mpo_dual_step_joint(d_column_sums, d_duals, min_log_dual, d_dual_grads, d_stats, d_actor_stats, B,
+                                   B_global, A, S, epsilon, epsilon_penalty, epsilon_mean, epsilon_std,
+                                   action_penalization, 0, stream);
+}
+
+extern "C" int tonic_mpo_dual_step_joint(const double* d_column_sums, float* d_duals, double min_log_dual,
+                                         float* d_dual_grads, float* d_stats, float* d_actor_stats,
+                                         int32_t B, int32_t B_global, int32_t A, int32_t S,
+                                         double epsilon, double epsilon_penalty, double epsilon_mean,
+                                         double epsilon_std, int32_t action_penalization, int32_t joint_kl,
+                                         void* stream) {
   TONIC_REQUIRE(d_column_sums && d_duals && d_dual_grads && d_stats && d_actor_stats && B >= 0 &&
-                    B_global > 0 && A >= 1 && A <= 64 && S >= 1,
-                TONIC_ERR_INVALID_ARGUMENT, "tonic_mpo_dual_step: bad argument");
+                    B_global > 0 && A >= 1 && A <= 64 && S >= 1 && S <= kMpoMaxSamples &&
+                    (joint_kl == 0 || joint_kl == 1),
+                TONIC_ERR_INVALID_ARGUMENT, "tonic_mpo_dual_step: bad argument (1 <= samples <= 256, A <= 64)");
   hipLaunchKernelGGL(mpo_dual_kernel, dim3(1), dim3(1024), 0, as_stream(stream),
                      (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, d_duals,
-                     (float)min_log_dual, action_penalization, (float)epsilon, (float)epsilon_penalty,
+                     (float)min_log_dual, action_penalization, joint_kl, (float)epsilon, (float)epsilon_penalty,
                      (float)epsilon_mean, (float)epsilon_std, d_dual_grads, d_stats, d_actor_stats,
                      B, A, S, d_column_sums, (double*)nullptr, B_global);
   TONIC_CHECK_LAUNCH("tonic_mpo_dual_step");

@@ -1214,19 +1214,23 @@ def log_ppo_critic_rows(rows):
 
 # ----------------------------------------------------------------- off-policy (SAC / TD3)
 
-def shard_noise(eps, positions, counts, global_batch):
+def shard_noise(eps, positions, counts, global_batch, samples=None):
     """The rows of the GLOBAL noise draws that belong to this rank's part of each batch.
     eps [iterations, draws, S * B, A]: S draws per state of the global batch, sample-major (row
     s * B + m; S = 1 for everything but MPO).  positions[it, :counts[it]] = the batch positions m
     this rank owns.  Returns the same shape with row s * c + j = eps row s * B + positions[j]
-    (c = counts[it]) in front and zeros behind: what the kernels see as a batch of c states."""
+    (c = counts[it]) in front and zeros behind: what the kernels see as a batch of c states.
+    samples: S of each draw when the draws differ (draw d fills its first samples[d] * B rows, MPO with two
+    sample counts); default: every draw fills the rows."""
     local = np.zeros_like(eps)
-    draws, per_sample = eps.shape[1], eps.shape[2] // global_batch
+    draws, width = eps.shape[1], eps.shape[3]
+    if samples is None:
+        samples = (eps.shape[2] // global_batch,) * draws
     for it in range(eps.shape[0]):
         c = counts[it]
-        width = eps.shape[3]
-        kept = eps[it].reshape(draws, per_sample, global_batch, width)[:, :, positions[it, :c]]
-        local[it, :, :per_sample * c] = kept.reshape(draws, per_sample * c, width)   # (c may be 0)
+        for d, per_sample in enumerate(samples):
+            kept = eps[it, d, :per_sample * global_batch].reshape(per_sample, global_batch, width)
+            local[it, d, :per_sample * c] = kept[:, positions[it, :c]].reshape(per_sample * c, width)   # (c may be 0)
     return local
 
 
@@ -1431,7 +1435,7 @@ class DDPG(Agent):
             # gradient SUMS are all-reduced and scaled by 1 / B_global, so the update equals the
             # single-process one on the global buffer.
             indices, positions, counts = self.replay.shard_indices(indices)
-            eps = shard_noise(eps, positions, counts, global_batch)
+            eps = shard_noise(eps, positions, counts, global_batch, self._noise_samples(eps.shape[1]))
         # everything a captured graph bakes in: shapes, the replay's storage, the updaters'
         # hyper-parameters and schedules — a change of any of them re-captures
         key = (iterations, tuple(eps.shape), self.replay.buffers['observations'].data_ptr(),
@@ -1482,7 +1486,7 @@ class DDPG(Agent):
         def enqueue():
             self._infos.zero_()
             draws = self._static_eps.shape[1]
-            per_sample = self._static_eps.shape[2] // global_batch     # (MPO: num_samples rows each)
+            samples = self._noise_samples(draws)       # rows per state of each draw (MPO: its updater's num_samples)
             # the store does not change during an update: the batches of ALL its iterations are
             # gathered by one launch (the rows a rank does not own are padding, never read)
             batches = self.replay.gather_many(self._static_indices)
@@ -1501,12 +1505,12 @@ class DDPG(Agent):
                     self._enqueue_fused(fused, batch, it, self._actor_due(it))
                     continue
                 if c > 0:
-                    self.critic_updater.enqueue(batch, self._static_eps[it, 0, :c * per_sample],
+                    self.critic_updater.enqueue(batch, self._static_eps[it, 0, :c * samples[0]],
                                                 self._infos[0, it], n_global)
                 else:
                     self.critic_updater.enqueue_empty(self._infos[0, it], n_global)
                 if self._actor_due(it):
-                    actor_eps = self._static_eps[it, 1, :c * per_sample] if draws > 1 else None
+                    actor_eps = self._static_eps[it, 1, :c * samples[1]] if draws > 1 else None
                     # update_targets() (ddpg.py:112) rides in the actor's optimizer launch
                     targets = (self.model.flat_target, self.model.flat_online, 0,
                                self.model.target_coeff)
@@ -1688,10 +1692,15 @@ class DDPG(Agent):
                           (rule.kind, rule.param) if rule is not None else None,
                           float(getattr(updater, 'entropy_coeff', 0.0)),
                           float(getattr(updater, 'gradient_clip', 0.0) or 0.0),
+                          int(getattr(updater, 'num_samples', 0)),
                           (noise.scale, noise.clip) if noise is not None else None))
         norm = self.model.observation_normalizer
         return (tuple(parts), float(self.model.target_coeff), getattr(self, 'delay_steps', 1),
                 norm._mean.data_ptr() if norm is not None else 0)
+
+    def _noise_samples(self, draws):
+        """Rows per state in each draw of `_draw_noise`: each updater reads the first c * samples rows of its own."""
+        return (1,) * draws
 
     def _draw_noise(self, iterations):
         # DeterministicQLearning / DeterministicPolicyGradient draw nothing (one unused slot)
@@ -1844,20 +1853,25 @@ class MPO(DDPG):
         self.last_actions = actions.copy()
         return actions
 
+    def _noise_samples(self, draws):
+        return (self.critic_updater.num_samples, self.actor_updater.num_samples)
+
     def _draw_noise(self, iterations):
-        # per iteration: rsample((S,)) of ExpectedSARSA (critics.py:260), then sample((S,)) of the
-        # actor step (actors.py:359) — [S, B, A] standard normals each, kept as [S * B, A]
+        # per iteration: rsample((S_c,)) of ExpectedSARSA (critics.py:260), then sample((S_a,)) of the
+        # actor step (actors.py:359) — [S, B, A] standard normals each, kept as the first S * B rows of a
+        # [max(S_c, S_a) * B, A] block (the rows behind them zero, never read)
         B, A = self.replay.batch_size, self.action_size
-        S_c, S_a = self.critic_updater.num_samples, self.actor_updater.num_samples
-        if S_c != S_a:
-            raise NotImplementedError('ExpectedSARSA and MPO must draw the same number of samples')
-        return np.stack([np.stack([torch.randn(S_c, B, A).numpy().reshape(S_c * B, A),
-                                   torch.randn(S_a, B, A).numpy().reshape(S_a * B, A)])
-                         for _ in range(iterations)])
+        S_c, S_a = self._noise_samples(2)
+        eps = np.zeros((iterations, 2, max(S_c, S_a) * B, A), np.float32)
+        for it in range(iterations):
+            eps[it, 0, :S_c * B] = torch.randn(S_c, B, A).numpy().reshape(S_c * B, A)
+            eps[it, 1, :S_a * B] = torch.randn(S_a, B, A).numpy().reshape(S_a * B, A)
+        return eps
 
     def enqueue_update(self, indices, eps, graph=None):
-        width = 9 + 2 * self.action_size
-        if getattr(self, '_mpo_stats', None) is None or self._mpo_stats.shape[0] != indices.shape[0]:
+        width = 9 + 2 * self.actor_updater.constraints
+        if (getattr(self, '_mpo_stats', None) is None
+                or tuple(self._mpo_stats.shape) != (indices.shape[0], width)):
             self._mpo_stats = torch.zeros(indices.shape[0], width, device=self.device)
             self._graph = None
         return super().enqueue_update(indices, eps, graph)

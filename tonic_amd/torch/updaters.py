@@ -1287,6 +1287,7 @@ class ExpectedSARSA(_TwinCriticQLearning):
     stock_capable = False
 
     def __init__(self, num_samples=20, loss=None, optimizer=None, gradient_clip=0):
+        _check_num_samples('ExpectedSARSA', num_samples)
         self.loss = loss
         self.num_samples = num_samples
         self.optimizer = optimizer
@@ -1426,15 +1427,26 @@ class DistributionalDeterministicPolicyGradient(_ActorQGradient):
         self._step(n_global or B * self.world_size, info_row, targets=targets)
 
 
+MPO_MAX_SAMPLES = 256      # csrc/offpolicy.hip kMpoMaxSamples: four register slots per lane in the E-step
+
+
+def _check_num_samples(name, num_samples):
+    if not 1 <= int(num_samples) <= MPO_MAX_SAMPLES:
+        raise NotImplementedError(
+            f'{name}(num_samples={num_samples}): the MPO kernels hold 1 <= num_samples <= {MPO_MAX_SAMPLES} '
+            'samples per state')
+
+
 MPO_INFO = ('policy_mean_loss', 'policy_std_loss', 'kl_mean_loss', 'kl_std_loss', 'alpha_mean_loss',
             'alpha_std_loss', 'temperature_loss', 'temperature')
 
 
 class MaximumAPosterioriPolicyOptimization(_ActorQGradient):
-    """actors.py:270-464 with per-dimension KL constraints (tonic_mpo_actor_grad): the actor step
-    and the step of the dual variables {log_temperature, log_alpha_mean[A], log_alpha_std[A],
-    log_penalty_temperature} — one flat device vector with its own Adam state (actors.py:289-316;
-    like the reference, the dual optimizer is Adam(lr=1e-2) unless `actor_optimizer` is given)."""
+    """actors.py:270-464 (tonic_mpo_actor_grad_joint): the actor step and the step of the dual variables
+    {log_temperature, log_alpha_mean[K], log_alpha_std[K], log_penalty_temperature} — K = A with per-dimension
+    KL constraints, K = 1 with `per_dim_constraining=False` (one alpha pair on the KLs summed over the action
+    dimensions) — one flat device vector with its own Adam state (actors.py:289-316; like the reference, the
+    dual optimizer is Adam(lr=1e-2) unless `actor_optimizer` is given)."""
     default_lr = 3e-4
     stock_capable = False
 
@@ -1443,9 +1455,9 @@ class MaximumAPosterioriPolicyOptimization(_ActorQGradient):
                  initial_log_alpha_std=10., min_log_dual=-18., per_dim_constraining=True,
                  action_penalization=True, actor_optimizer=None, dual_optimizer=None,
                  gradient_clip=0):
-        if not per_dim_constraining:
-            raise NotImplementedError('only per-dimension KL constraints are fused')
+        _check_num_samples('MaximumAPosterioriPolicyOptimization', num_samples)
         self.num_samples = num_samples
+        self.per_dim_constraining = per_dim_constraining
         self.epsilon, self.epsilon_penalty = epsilon, epsilon_penalty
         self.epsilon_mean, self.epsilon_std = epsilon_mean, epsilon_std
         self.initial_log_temperature = initial_log_temperature
@@ -1460,18 +1472,19 @@ class MaximumAPosterioriPolicyOptimization(_ActorQGradient):
     def initialize(self, model, action_space=None):
         super().initialize(model)
         A, device = self.action_size, self.grad_sums.device
-        duals = [self.initial_log_temperature] + [self.initial_log_alpha_mean] * A + \
-            [self.initial_log_alpha_std] * A + [self.initial_log_temperature]
+        K = self.constraints = A if self.per_dim_constraining else 1        # actors.py:300-311
+        duals = [self.initial_log_temperature] + [self.initial_log_alpha_mean] * K + \
+            [self.initial_log_alpha_std] * K + [self.initial_log_temperature]
         self.duals = torch.tensor(duals, dtype=torch.float32, device=device)
-        self.dual_grads = torch.zeros(2 * A + 2 + INFO_WIDTH, dtype=torch.float32, device=device)
-        self.dual_optim = _OptimizerState(self.lib, self.dual_hyper, 2 * A + 2, device)
+        self.dual_grads = torch.zeros(2 * K + 2 + INFO_WIDTH, dtype=torch.float32, device=device)
+        self.dual_optim = _OptimizerState(self.lib, self.dual_hyper, 2 * K + 2, device)
         self.dual_slots, self.dual_state = self.dual_optim.slots, self.dual_optim.state
         self.dual_exp_avg, self.dual_exp_avg_sq = self.dual_optim.exp_avg, self.dual_optim.exp_avg_sq
-        self.mpo_stats = torch.zeros(9 + 2 * A, dtype=torch.float32, device=device)
+        self.mpo_stats = torch.zeros(9 + 2 * K, dtype=torch.float32, device=device)
         self.dual_info = torch.zeros(INFO_WIDTH, dtype=torch.float32, device=device)
         self.column_sums = torch.zeros(6 + 2 * A, dtype=torch.float64, device=device)
         self.dual_clip_workspace = torch.zeros(
-            self.lib.tonic_clip_workspace_bytes(2 * A + 2), dtype=torch.uint8, device=device)
+            self.lib.tonic_clip_workspace_bytes(2 * K + 2), dtype=torch.uint8, device=device)
 
     def _offpolicy_workspace(self, batch):
         need = self.lib.tonic_mpo_workspace_bytes(batch, self.observation_size, self.action_size,
@@ -1485,44 +1498,45 @@ class MaximumAPosterioriPolicyOptimization(_ActorQGradient):
         p = _lib.ptr
         # (actors.py:347-356 floors the log-duals in place at the head of the call: the kernels read them
         #  through the floor and write the floored values back ahead of the duals' optimizer step)
-        floor = float(self.min_log_dual)
+        floor, joint = float(self.min_log_dual), int(not self.per_dim_constraining)
         stats = stats_row if stats_row is not None else self.mpo_stats
         B = 0 if observations is None else observations.shape[0]
         if parallel.exchanging():
             # this rank's part of the global batch (possibly nothing): the actor's gradient sums and
-            # the column sums of the per-state terms; the dual step needs their GLOBAL means
+            # the column sums of the per-state terms (per-dimension KLs, whatever the constraint); the dual
+            # step needs their GLOBAL means
             if B > 0:
                 ws = self._offpolicy_workspace(B)
                 mean, std = self.norm_tensors()
-                _lib.check(self.lib.tonic_mpo_actor_grad_shard(
+                _lib.check(self.lib.tonic_mpo_actor_grad_shard_joint(
                     p(self.flat.flat), p(self.model.flat_target_actor.flat),
                     p(self.model.flat_target_critics.flat), p(self.duals), floor, p(mean), p(std),
                     self.norm_clip(), p(observations), p(eps), p(self.grad_sums),
                     p(self.column_sums), B, self.observation_size, self.hidden, self.action_size,
-                    self.num_samples, int(bool(self.action_penalization)), p(ws), ws.numel(),
-                    _lib.current_stream()), 'tonic_mpo_actor_grad_shard')
+                    self.num_samples, int(bool(self.action_penalization)), joint, p(ws), ws.numel(),
+                    _lib.current_stream()), 'tonic_mpo_actor_grad_shard_joint')
             else:
                 self.grad_sums.zero_()
                 self.column_sums.zero_()
             torch.distributed.all_reduce(self.column_sums)
-            _lib.check(self.lib.tonic_mpo_dual_step(
+            _lib.check(self.lib.tonic_mpo_dual_step_joint(
                 p(self.column_sums), p(self.duals), floor, p(self.dual_grads), p(stats),
                 p(self.grad_sums[self.count:]), B, n_global, self.action_size, self.num_samples,
                 float(self.epsilon), float(self.epsilon_penalty), float(self.epsilon_mean),
-                float(self.epsilon_std), int(bool(self.action_penalization)),
-                _lib.current_stream()), 'tonic_mpo_dual_step')
+                float(self.epsilon_std), int(bool(self.action_penalization)), joint,
+                _lib.current_stream()), 'tonic_mpo_dual_step_joint')
         else:
             ws = self._offpolicy_workspace(B)
             mean, std = self.norm_tensors()
-            _lib.check(self.lib.tonic_mpo_actor_grad(
+            _lib.check(self.lib.tonic_mpo_actor_grad_joint(
                 p(self.flat.flat), p(self.model.flat_target_actor.flat),
                 p(self.model.flat_target_critics.flat), p(self.duals), floor, p(mean), p(std),
                 self.norm_clip(), p(observations), p(eps), p(self.grad_sums), p(self.dual_grads),
                 p(stats), B, self.observation_size, self.hidden, self.action_size,
                 self.num_samples, float(self.epsilon), float(self.epsilon_penalty),
                 float(self.epsilon_mean), float(self.epsilon_std),
-                int(bool(self.action_penalization)), p(ws), ws.numel(), _lib.current_stream()),
-                'tonic_mpo_actor_grad')
+                int(bool(self.action_penalization)), joint, p(ws), ws.numel(), _lib.current_stream()),
+                'tonic_mpo_actor_grad_joint')
         self._step(n_global or B, info_row, targets=targets)
         if self.gradient_clip > 0:
             # actors.py:441-445 clips the dual variables' gradient norm as well (the penalty
@@ -1540,12 +1554,12 @@ class MaximumAPosterioriPolicyOptimization(_ActorQGradient):
 
     def infos(self, stats):
         """The reference's return dict (actors.py:449-464) from one statistics row (host array)."""
-        A = self.action_size
+        K = self.constraints
         out = {k: stats[i] for i, k in enumerate(MPO_INFO)}
-        out['alpha_mean'] = stats[8:8 + A]
-        out['alpha_std'] = stats[8 + A:8 + 2 * A]
+        out['alpha_mean'] = stats[8:8 + K]
+        out['alpha_std'] = stats[8 + K:8 + 2 * K]
         if self.action_penalization:
-            out['penalty_temperature'] = stats[8 + 2 * A]
+            out['penalty_temperature'] = stats[8 + 2 * K]
         return out
 
     def __call__(self, observations):
