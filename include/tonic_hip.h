@@ -60,11 +60,12 @@ const char* tonic_last_error(void);
  * 14 = the tonic_trpo_* entries, 15 = tonic_optimizer_step / tonic_optimizer_state_slots,
  * 16 = tonic_critic_loss_t: tonic_critic_loss_check, tonic_twin_q_grad_loss, tonic_expected_sarsa_grad_loss,
  * tonic_q_iteration_t.critic_loss), 17 = the tonic_mpo_*_joint entries (`joint_kl`: one alpha pair on the KLs
- * summed over the action dimensions); the MPO entries take 1 .. 256 samples per state (additive: every earlier
- * entry keeps its signature)
+ * summed over the action dimensions); the MPO entries take 1 .. 256 samples per state, 18 = tonic_twin_q_grad_ranged /
+ * tonic_actor_q_grad_ranged (the Return normaliser's value head on the off-policy split entries) (additive: every
+ * earlier entry keeps its signature)
  * and the gfx target the kernels were built for.  TONIC_ABI_VERSION is what a binding was compiled against:
  * tonic_amd/_fastcall (csrc/fastcall.c) and tonic_amd/_lib.py compare it with the loaded library's answer. */
-#define TONIC_ABI_VERSION 17
+#define TONIC_ABI_VERSION 18
 int32_t tonic_abi_version(void);
 const char* tonic_target_arch(void);
 
@@ -279,8 +280,8 @@ int tonic_trpo_evaluate(int32_t layers, const int32_t* sizes, int32_t activation
  * d_value_low / d_value_high: float32 scalars on the device, the normaliser's `_low` / `_high` parameters
  *   (read by the kernels: graph-safe, no host sync).  Both NULL = the plain head, the same bits as the entry
  *   without the suffix; exactly one NULL = TONIC_ERR_INVALID_ARGUMENT.  The squashed head is served by the
- *   shipped grad chain only (grad_variant 4, tonic_hip_dev.h).  Off-policy critics (Q heads) have no
- *   squashed form.
+ *   shipped grad chain only (grad_variant 4, tonic_hip_dev.h).  The off-policy critics' (Q heads')
+ *   squashed form: tonic_twin_q_grad_ranged / tonic_actor_q_grad_ranged below.
  */
 int tonic_value_forward_ranged(const float* d_critic_params, const float* d_norm_mean,
                                const float* d_norm_std, double norm_clip, const float* d_observations,
@@ -817,6 +818,36 @@ int tonic_actor_q_grad(int32_t kind, const float* d_actor_params, const float* d
                        const float* d_observations, const float* d_eps, float* d_grad_sums,
                        int32_t B, int32_t O, int32_t H, int32_t A, double entropy_coeff,
                        void* d_workspace, int64_t workspace_bytes, void* stream);
+
+/* ---- the Return normaliser (off-policy critics: DDPG, TD3, SAC on the split entries) -------
+ * tonic_twin_q_grad_loss / tonic_actor_q_grad for a model built with ActorCriticWithTargets /
+ *   ActorTwinCriticWithTargets(..., return_normalizer=Return(discount_factor)): every critic's value head,
+ *   online and target, publishes v = low + sigmoid(z) (high - low) (tonic/torch/models/critics.py:17-19 +
+ *   normalizers/returns.py:19-21; s = 1 / (1 + exp(-z)), t = high - low, m = s * t, v = low + m, separate float32
+ *   operations, as in "the Return normaliser" above).  TD target, twin minimum, the critic's loss, the actor's
+ *   objective and the logged sums are those of v; a gradient dv that enters a head becomes
+ *   dz = ((dv * t) * (1 - s)) * s (torch's sigmoid_backward order) with s recomputed from the published value,
+ *   s = (v - low) / t.  Served by every path of the two entries: the fused float32 passes, the fp16x2 weight-image
+ *   passes and the layer-by-layer torsos.
+ * d_value_low / d_value_high: float32 scalars on the device, the normaliser's `_low` / `_high` (read by the
+ *   kernels: a captured graph follows a moved range, no host sync).  Both NULL = the same launches and bits as
+ *   the entry without the suffix; exactly one NULL = TONIC_ERR_INVALID_ARGUMENT, checked before anything touches
+ *   the device.  tonic_q_iteration has no squashed form: an agent with a Return normaliser takes these entries. */
+int tonic_twin_q_grad_ranged(int32_t kind, const float* d_policy_params, const float* d_target_critics,
+                             const float* d_critics, const float* d_norm_mean, const float* d_norm_std,
+                             double norm_clip, const float* d_observations, const float* d_actions,
+                             const float* d_next_observations, const float* d_rewards,
+                             const float* d_discounts, const float* d_eps, float* d_grad_sums, int32_t B,
+                             int32_t O, int32_t H, int32_t A, double entropy_coeff, double noise_scale,
+                             double noise_clip, const tonic_critic_loss_t* loss, const float* d_value_low,
+                             const float* d_value_high, void* d_workspace, int64_t workspace_bytes,
+                             void* stream);
+int tonic_actor_q_grad_ranged(int32_t kind, const float* d_actor_params, const float* d_critics,
+                              const float* d_norm_mean, const float* d_norm_std, double norm_clip,
+                              const float* d_observations, const float* d_eps, float* d_grad_sums,
+                              int32_t B, int32_t O, int32_t H, int32_t A, double entropy_coeff,
+                              const float* d_value_low, const float* d_value_high, void* d_workspace,
+                              int64_t workspace_bytes, void* stream);
 
 /* ---- one whole learner iteration of DDPG / TD3 / SAC in 8 launches (4 when the actor is not due).
  * replaces: the body of DDPG._update's loop (tonic/torch/agents/ddpg.py:95-112; td3.py:38-55 with

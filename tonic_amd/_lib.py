@@ -166,6 +166,11 @@ SIGNATURES = {
     'tonic_actor_q_grad': (ctypes.c_int, [c_i32] + [c_vp] * 4 + [c_f64] + [c_vp] * 3 + [c_i32] * 4 +
                            [c_f64] +
                            [c_vp, c_i64, c_vp]),
+    # ... with the Return normaliser's `_low` / `_high` ahead of the workspace (ABI 18)
+    'tonic_twin_q_grad_ranged': (ctypes.c_int, [c_i32] + [c_vp] * 5 + [c_f64] + [c_vp] * 7 + [c_i32] * 4 +
+                                 [c_f64] * 3 + [c_vp] * 3 + [c_vp, c_i64, c_vp]),
+    'tonic_actor_q_grad_ranged': (ctypes.c_int, [c_i32] + [c_vp] * 4 + [c_f64] + [c_vp] * 3 + [c_i32] * 4 +
+                                  [c_f64] + [c_vp] * 2 + [c_vp, c_i64, c_vp]),
     'tonic_distributional_workspace_bytes': (c_i64, [c_i32] * 5),
     'tonic_distributional_q_grad': (ctypes.c_int, [c_vp] * 5 + [c_f64] + [c_vp] * 7 + [c_i32] * 5 +
                                     [c_vp, c_i64, c_vp]),
@@ -231,7 +236,7 @@ SIGNATURES = {
 }
 
 
-ABI_VERSION = 17       # include/tonic_hip.h: tonic_abi_version()
+ABI_VERSION = 18       # include/tonic_hip.h: tonic_abi_version()
 
 
 class TonicHipError(RuntimeError):

@@ -47,6 +47,11 @@ struct GemmArgs {
   ImgTarget img;         // TN + optimizer epilogue: the tensor's fp16x2 weight images (mlpimg.h; null pointers: none)
 };
 
+// The Return normaliser's `_low` / `_high` (float32 scalars on the device) for a launch whose value head squashes
+// (value_squash, mlpfwd.h).  It travels BESIDE the argument structs, as an argument of kernels of its own: the structs
+// and every kernel that existed before the squashed head keep their layout and their code.  Null / null: no squash.
+struct ValueRangeArg { const float* low; const float* high; };
+
 extern std::atomic<unsigned long long*> g_forward_stamps;    // developer probe, see tonic_debug_forward_stamps
 
 constexpr int kGemmGroupMax = 4;
@@ -100,7 +105,10 @@ struct GemmGroupWide {
   AdamFold adam;
 };
 
-int launch_gemm(char mode_a, char mode_b, const GemmArgs& g, int batch, hipStream_t stream);
+// value.low != null ('c', 'c' only): the layer-by-layer critic's head GEMM — after bias and `act` every output goes
+// through value_squash (gemm16_value_head_kernel).
+int launch_gemm(char mode_a, char mode_b, const GemmArgs& g, int batch, hipStream_t stream,
+                ValueRangeArg value = ValueRangeArg{nullptr, nullptr});
 // `count` (<= kGemmGroupMax; the plain TN weight-gradient form: <= kGemmGroupWide) GEMMs of the same layout and
 // K in one launch (see gemm16.hip).
 int launch_gemm_group(char mode_a, char mode_b, const GemmArgs* list, int count, int batch,

@@ -1,5 +1,6 @@
 // gemm16: see gemm16.h.  gfx950, v_mfma_f32_16x16x4_f32, one wave per 16 x 32 output tile.
 #include "gemm16.h"
+#include "mlpfwd.h"      // value_squash: the Return normaliser's value head
 #include "optim_rule.h"
 
 namespace tonic {
@@ -41,8 +42,9 @@ __device__ __forceinline__ void load_operand(const float* __restrict__ P, int ld
 constexpr int kGemmGroup = 4;                      // chunks in flight per wave
 constexpr int kGemmMaxWaves = 16;
 
-template <bool A_KC, bool B_KC>
-__device__ __forceinline__ void gemm16_tiles(const GemmArgs& g, int block_index, float* part) {
+template <bool A_KC, bool B_KC, bool SQ = false>
+__device__ __forceinline__ void gemm16_tiles(const GemmArgs& g, int block_index, float* part,
+                                             ValueRangeArg value = ValueRangeArg{nullptr, nullptr}) {
   const int lane = threadIdx.x, part_of = threadIdx.y, S = blockDim.y;
   const int i = lane & 15, kg = lane >> 4;
   const int tiles_n = (g.N + 31) / 32, tiles_m = (g.M + 15) / 16;
@@ -113,6 +115,7 @@ __device__ __forceinline__ void gemm16_tiles(const GemmArgs& g, int block_index,
 
   const float* bias = g.bias ? g.bias + z * g.strideBias : nullptr;
   const float* mask = g.mask ? g.mask + z * g.strideMask : nullptr;
+  const ValueRange vrange = SQ ? value_range(value.low, value.high) : ValueRange{0.f, 0.f, false};   // (scalar loads)
 #pragma unroll
   for (int half = 0; half < 2; ++half) {
     const int n = n0 + 16 * half + i;
@@ -126,6 +129,7 @@ __device__ __forceinline__ void gemm16_tiles(const GemmArgs& g, int block_index,
       if (g.act == ACT_RELU) v = fmaxf(v, 0.f);
       else if (g.act == ACT_TANH) v = tanhf(v);
       else if (g.act == ACT_ELU) v = v > 0.f ? v : expm1f(v);       // torch.nn.ELU, alpha = 1
+      if constexpr (SQ) v = value_squash(v, vrange);
       if (mask != nullptr) {
         const float a = mask[(int64_t)m * g.ldmask + n];
         if (g.mask_act == ACT_TANH) v = v * (1.f - a * a);
@@ -142,6 +146,13 @@ template <bool A_KC, bool B_KC>
 __global__ __launch_bounds__(64 * kGemmMaxWaves) void gemm16_kernel(GemmArgs g) {
   extern __shared__ float part[];                  // [waves][64][9] when S > 1
   gemm16_tiles<A_KC, B_KC>(g, blockIdx.x, part);
+}
+
+// The value head of a layer-by-layer critic under the Return normaliser (NT; GemmArgs as gemm16_kernel's): the
+// epilogue squashes after bias — a kernel of its own, so that gemm16_kernel stays what it was.
+__global__ __launch_bounds__(64 * kGemmMaxWaves) void gemm16_value_head_kernel(GemmArgs g, ValueRangeArg value) {
+  extern __shared__ float part[];
+  gemm16_tiles<true, true, true>(g, blockIdx.x, part, value);
 }
 
 // Several independent GEMMs of the same operand layout and contraction length in ONE launch (the
@@ -711,9 +722,11 @@ int launch_build_images(const ImgBuild& b, hipStream_t stream) {
   return TONIC_OK;
 }
 
-int launch_gemm(char mode_a, char mode_b, const GemmArgs& g, int batch, hipStream_t stream) {
+int launch_gemm(char mode_a, char mode_b, const GemmArgs& g, int batch, hipStream_t stream, ValueRangeArg value) {
   TONIC_REQUIRE(g.A && g.B && g.C && g.M > 0 && g.N > 0 && g.K > 0 && batch > 0,
                 TONIC_ERR_INVALID_ARGUMENT, "gemm: bad argument (M=%d N=%d K=%d)", g.M, g.N, g.K);
+  TONIC_REQUIRE(value.low == nullptr || (value.high != nullptr && mode_a == 'c' && mode_b == 'c' && !g.mask),
+                TONIC_ERR_INVALID_ARGUMENT, "gemm: the squashed value head is the 'cc' form without a mask");
   if (mode_a == 's' && mode_b == 's' && !g.bias && !g.mask && g.act == ACT_NONE)
     return launch_gemm_group(mode_a, mode_b, &g, 1, batch, stream);
   const int tiles = ((g.M + 15) / 16) * ((g.N + 31) / 32);
@@ -723,7 +736,8 @@ int launch_gemm(char mode_a, char mode_b, const GemmArgs& g, int batch, hipStrea
   const size_t lds = S > 1 ? (size_t)per_block * S * 64 * 9 * sizeof(float) : 0;
 #define TONIC_GEMM_LAUNCH(AKC, BKC) \
   hipLaunchKernelGGL((gemm16_kernel<AKC, BKC>), grid, block, lds, stream, g)
-  if (mode_a == 'c' && mode_b == 'c') TONIC_GEMM_LAUNCH(true, true);
+  if (value.low != nullptr) hipLaunchKernelGGL(gemm16_value_head_kernel, grid, block, lds, stream, g, value);
+  else if (mode_a == 'c' && mode_b == 'c') TONIC_GEMM_LAUNCH(true, true);
   else if (mode_a == 'c' && mode_b == 's') TONIC_GEMM_LAUNCH(true, false);
   else if (mode_a == 's' && mode_b == 's') TONIC_GEMM_LAUNCH(false, false);
   else {

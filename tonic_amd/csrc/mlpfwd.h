@@ -297,6 +297,37 @@ inline CriticLoss critic_loss_rule(const tonic_critic_loss_t* loss) {
   return loss == nullptr ? CriticLoss{TONIC_LOSS_MSE, 0.f} : CriticLoss{loss->kind, (float)loss->param};
 }
 
+// ---- the Return normaliser's value head (tonic/torch/models/critics.py:17-19 + normalizers/returns.py:19-21):
+// v = low + sigmoid(z) (high - low) in the separate float32 operations torch forms (include/tonic_hip.h, "the
+// Return normaliser").  A property of the value HEAD: every forward body publishes v where it published z, and
+// every place a gradient enters the head multiplies it by dv/dz — these two functions are the only statements
+// of either.  `low` / `high` are float32 scalars on the device (ValueRangeArg, gemm16.h), read once per kernel
+// (wave-uniform); only the kernels instantiated for a squashed head (RANGED / SQ) contain any of this.
+struct ValueRange {
+  float low, high; bool on;
+};
+__device__ __forceinline__ ValueRange value_range(const float* low, const float* high) {
+  return low != nullptr ? ValueRange{*low, *high, true} : ValueRange{0.f, 0.f, false};
+}
+__device__ __forceinline__ float value_squash(float z, ValueRange r) {
+  if (!r.on) return z;
+  const float s = 1.f / (1.f + expf(-z));
+  const float t = r.high - r.low;
+  const float m = s * t;
+  return r.low + m;
+}
+// The gradient at z from the gradient `dv` at v: ((dv t) (1 - s)) s — torch's backward of `s * t`, then
+// sigmoid_backward (grad (1 - s) s, left to right).  s is recomputed from the published v, s = (v - low) / t: no
+// second buffer and no second exchange line.  Return keeps min_reward <= -1 <= 1 <= max_reward, so |low|, |high|
+// <= t and the rounding of v moves s by ~1e-7 absolute: visible only where s (1 - s) is small against the batch's
+// largest (tests/test_gpu_offpolicy_return.py holds the gradient sums to 1e-5 of each tensor's largest element).
+__device__ __forceinline__ float value_squash_dz(float dv, float v, ValueRange r) {
+  if (!r.on) return dv;
+  const float t = r.high - r.low;
+  const float s = (v - r.low) / t;
+  return ((dv * t) * (1.f - s)) * s;
+}
+
 // d (actor objective) / d q_z of one sample (shared by actor_loss_kernel and the folded form)
 __device__ __forceinline__ float actor_dq(const float* q, int m, ValueLines at, int twin, int z,
                                           unsigned* coherent = nullptr) {
@@ -371,7 +402,13 @@ bool mlp_forward_supported(int H, int NH, int heads);
 bool mlp_policy_tail_supported(int H, int NH);
 extern std::atomic<int> g_policy_tail;      // tuning key "policy_tail": 0 keeps sampling / noise / copy in their own launches
 bool mlp_backward_supported(int H, int NH, int heads, int xa_count);
-int launch_mlp_backward(const MlpBwdArgs& a, int nets, hipStream_t stream);
-int launch_mlp_forward(const MlpFwdArgs& a, int nets, hipStream_t stream);
+// value.low != null: the launch's value heads (heads = 1, NH = 1, ACT_NONE) publish value_squash(z) in out[] — the
+// backward (loss != LOSS_GIVEN) then reads squashed values from l_q / l_tq and forms dq at the head's
+// pre-activation, value_squash_dz(dq, v).  Kernels of their own (mlp_*_ranged_kernel): the plain and the chained
+// kernels are what they were.  The chained launches (tonic_q_iteration) have no squashed form.
+int launch_mlp_backward(const MlpBwdArgs& a, int nets, hipStream_t stream,
+                        ValueRangeArg value = ValueRangeArg{nullptr, nullptr});
+int launch_mlp_forward(const MlpFwdArgs& a, int nets, hipStream_t stream,
+                       ValueRangeArg value = ValueRangeArg{nullptr, nullptr});
 
 }  // namespace tonic

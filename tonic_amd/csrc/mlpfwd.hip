@@ -333,8 +333,11 @@ __device__ __forceinline__ void policy_tail(const MlpFwdArgs& a, const bool seco
 
 // The pass of workgroup (bx, net): 16 batch rows of one network.  A kernel of its own
 // (mlp_forward_kernel) or one stage of q_chain_kernel.
+// RANGED (mlp_forward_ranged_kernel only): the value head publishes value_squash(z) with `value`'s range; every other
+// instantiation — the plain kernel, the chained launches — holds none of it and is what it was.
+template <bool RANGED = false>
 __device__ __forceinline__ void mlp_forward_body(const MlpFwdArgs& a, const int net, const int bx,
-                                                 float* lds) {
+                                                 float* lds, ValueRangeArg value = ValueRangeArg{nullptr, nullptr}) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);        // scalar: uniform branches
   const int m = lane & 15, kg = lane >> 4;            // A operand row / D column; k group
@@ -397,6 +400,7 @@ __device__ __forceinline__ void mlp_forward_body(const MlpFwdArgs& a, const int 
   // A single output (the value of a critic) is no MFMA tile: it is folded into the epilogue of
   // the second layer as a dot product (below).
   const bool value_head = a.heads == 1 && a.NH == 1 && a.act[0] == ACT_NONE;       // scalar
+  const ValueRange vrange = RANGED ? value_range(value.low, value.high) : ValueRange{0.f, 0.f, false};      // (scalar loads, once; null: the plain head)
   const bool head_wave = !value_head && wave < a.heads * tiles_per_head;
   const int head = head_wave ? wave / tiles_per_head : 0;
   const int head_tile = head_wave ? wave - head * tiles_per_head : 0;
@@ -490,7 +494,9 @@ __device__ __forceinline__ void mlp_forward_body(const MlpFwdArgs& a, const int 
   if (value_head) {
     if (wave == 0 && kg == 0 && row_ok) {
       float* out_base = a.out[0];
-      const float q = ((partial[m] + partial[16 + m]) + (partial[32 + m] + partial[48 + m])) + hbias[0];
+      // (RANGED: the Return normaliser's head publishes v = value_squash(z); the chained launches, the only ones with
+      //  exchange lines, are never RANGED)
+      const float q = value_squash(((partial[m] + partial[16 + m]) + (partial[32 + m] + partial[48 + m])) + hbias[0], vrange);
       out_base[net * a.stride_out + (int64_t)(r0 + m) * a.ldo] = q;
       if (a.xq != nullptr) {       // read by other workgroups of the same launch (ValueLines)
         const int slot = net < a.split ? 32 * net : 32 * (2 + net - a.split);     // one line per writer
@@ -591,8 +597,9 @@ __device__ __forceinline__ void mlp_loss_stats(const MlpBwdArgs& a) {
 // target's q, the twin's q, the critics' action-column gradients — is read (exchange_read) AFTER
 // everything that does not depend on them (ReLU masks, the first weight operands, the head
 // backward's own operands) has been requested: the hand-over's latency runs under those loads.
+template <bool RANGED = false>      // (RANGED, value: see mlp_forward_body; the gradient that enters the head)
 __device__ __forceinline__ void mlp_backward_body(const MlpBwdArgs& a, const int net, const int bx,
-                                                  float* lds) {
+                                                  float* lds, ValueRangeArg value = ValueRangeArg{nullptr, nullptr}) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int m = lane & 15, kg = lane >> 4;
@@ -719,6 +726,7 @@ __device__ __forceinline__ void mlp_backward_body(const MlpBwdArgs& a, const int
 #pragma unroll
   for (int j = 0; j < kMaxTiles; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
   if (a.heads == 0) {                                 // critic: dq[row] * w3[feature]
+    const ValueRange vrange = RANGED ? value_range(value.low, value.high) : ValueRange{0.f, 0.f, false};     // (scalar; null: the plain head)
     float dq;
     if (a.loss == LOSS_GIVEN) {
       dq = a.dq[net * a.stride_dq + row];
@@ -726,9 +734,11 @@ __device__ __forceinline__ void mlp_backward_body(const MlpBwdArgs& a, const int
       if (a.loss == LOSS_TD) {
         const float y = td_target(a.l_rewards, a.l_discounts, a.l_tq, a.l_logp, a.l_alpha, row,
                                   a.l_tq_at, a.l_nets, co);
-        dq = critic_loss_dq(load_shared(a.l_q + a.l_q_at.index(net, row), co) - y, a.l_kind, a.l_param);
+        const float q = load_shared(a.l_q + a.l_q_at.index(net, row), co);
+        dq = value_squash_dz(critic_loss_dq(q - y, a.l_kind, a.l_param), q, vrange);
       } else {
         dq = actor_dq(a.l_q, row, a.l_q_at, a.l_nets == 2, net, co);
+        if (vrange.on) dq = value_squash_dz(dq, load_shared(a.l_q + a.l_q_at.index(net, row), co), vrange);
       }
       if (row_ok && wave == 0 && kg == 0)             // for the weight-gradient GEMM (dw3, db3)
         const_cast<float*>(a.dq)[net * a.stride_dq + row] = dq;
@@ -909,6 +919,24 @@ __global__ __launch_bounds__(256) void mlp_backward_kernel(MlpBwdArgs a) {
   else mlp_backward_body(a, blockIdx.y, blockIdx.x, lds);
 }
 
+// The same passes for value heads under the Return normaliser (launch_mlp_forward / launch_mlp_backward with a range):
+// kernels of their own, the range beside the argument struct — no collector step, no store role.
+template <bool IMG>
+__global__ __launch_bounds__(256) void mlp_forward_ranged_kernel(MlpFwdArgs a, ValueRangeArg value) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  kernarg_prefetch<sizeof(MlpFwdArgs)>();
+  if constexpr (IMG) mlp_forward_body_img<true>(a, blockIdx.y, blockIdx.x, lds, value);
+  else mlp_forward_body<true>(a, blockIdx.y, blockIdx.x, lds, value);
+}
+
+template <bool IMG>
+__global__ __launch_bounds__(256) void mlp_backward_ranged_kernel(MlpBwdArgs a, ValueRangeArg value) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  kernarg_prefetch<sizeof(MlpBwdArgs)>();
+  if constexpr (IMG) mlp_backward_body_img<true>(a, blockIdx.y, blockIdx.x, lds, 0, value);
+  else mlp_backward_body<true>(a, blockIdx.y, blockIdx.x, lds, value);
+}
+
 // ------------------------------------------------------------------ chained passes (mlpfwd.h)
 // The launch's LAST workgroup is nobody's tile: it forms the logged sums of the step's loss from the
 // exchanged values (waiting for each as it goes) while the other workgroups run their chains — in a
@@ -1028,7 +1056,7 @@ static int allow_image_lds(Kernel kernel, const char* what) {
   return TONIC_OK;
 }
 
-int launch_mlp_forward(const MlpFwdArgs& a, int nets, hipStream_t stream) {
+int launch_mlp_forward(const MlpFwdArgs& a, int nets, hipStream_t stream, ValueRangeArg value) {
   TONIC_REQUIRE(mlp_forward_supported(a.H, a.NH, a.heads) && a.B > 0 && a.K1 > 0 && nets > 0,
                 TONIC_ERR_INVALID_ARGUMENT, "mlp_forward: H=%d NH=%d heads=%d B=%d K1=%d", a.H,
                 a.NH, a.heads, a.B, a.K1);
@@ -1056,6 +1084,11 @@ int launch_mlp_forward(const MlpFwdArgs& a, int nets, hipStream_t stream) {
                 a.post, a.heads, a.NH, a.H);
   TONIC_REQUIRE(a.split >= nets || a.X2 != nullptr, TONIC_ERR_INVALID_ARGUMENT,
                 "mlp_forward: split=%d of %d networks without a second input", a.split, nets);
+  const bool ranged = value.low != nullptr;
+  TONIC_REQUIRE(!ranged || (value.high != nullptr && a.heads == 1 && a.NH == 1 && a.act[0] == ACT_NONE &&
+                            a.post == POST_NONE && a.done_flags == nullptr && a.store_on == 0 && a.xq == nullptr),
+                TONIC_ERR_INVALID_ARGUMENT, "mlp_forward: a value range needs plain value heads (heads=%d NH=%d)",
+                a.heads, a.NH);
   size_t lds = (2 * (size_t)kRows * (a.H + 4) + 4 * kRows) * sizeof(float);
   MlpFwdArgs launch = a;
   launch.tail_offset = 0;
@@ -1076,14 +1109,21 @@ int launch_mlp_forward(const MlpFwdArgs& a, int nets, hipStream_t stream) {
     launch.lds_floats = L.total / 4;
     TONIC_REQUIRE(a.store_on == 0 || (nets == 1 && a.done_flags != nullptr && a.store.O <= L.total / 4),
                   TONIC_ERR_INVALID_ARGUMENT, "mlp_forward: a store role needs a single-network collector step");
-    const int status = allow_image_lds(mlp_forward_kernel<true>, "mlp_forward_kernel");
+    const int status = ranged ? allow_image_lds(mlp_forward_ranged_kernel<true>, "mlp_forward_ranged_kernel")
+                              : allow_image_lds(mlp_forward_kernel<true>, "mlp_forward_kernel");
     if (status != TONIC_OK) return status;
-    hipLaunchKernelGGL(mlp_forward_kernel<true>, dim3((a.B + kRows - 1) / kRows + (a.store_on != 0 ? 1 : 0), nets),
+    if (ranged)
+      hipLaunchKernelGGL(mlp_forward_ranged_kernel<true>, dim3((a.B + kRows - 1) / kRows, nets), dim3(256), L.total,
+                         stream, launch, value);
+    else hipLaunchKernelGGL(mlp_forward_kernel<true>, dim3((a.B + kRows - 1) / kRows + (a.store_on != 0 ? 1 : 0), nets),
                        dim3(256), L.total, stream, launch);
   } else {
     TONIC_REQUIRE(a.store_on == 0, TONIC_ERR_INVALID_ARGUMENT, "mlp_forward: the store role rides on the image pass");
-    hipLaunchKernelGGL(mlp_forward_kernel<false>, dim3((a.B + kRows - 1) / kRows, nets), dim3(256), lds,
-                       stream, launch);
+    if (ranged)
+      hipLaunchKernelGGL(mlp_forward_ranged_kernel<false>, dim3((a.B + kRows - 1) / kRows, nets), dim3(256), lds,
+                         stream, launch, value);
+    else hipLaunchKernelGGL(mlp_forward_kernel<false>, dim3((a.B + kRows - 1) / kRows, nets), dim3(256), lds,
+                            stream, launch);
   }
   TONIC_CHECK_LAUNCH("mlp_forward_kernel");
   return TONIC_OK;
@@ -1094,7 +1134,7 @@ bool mlp_backward_supported(int H, int NH, int heads, int xa_count) {
          (heads == 0 || (NH >= 1 && NH <= 64)) && xa_count >= 0 && xa_count <= 64;
 }
 
-int launch_mlp_backward(const MlpBwdArgs& a, int nets, hipStream_t stream) {
+int launch_mlp_backward(const MlpBwdArgs& a, int nets, hipStream_t stream, ValueRangeArg value) {
   TONIC_REQUIRE(mlp_backward_supported(a.H, a.NH, a.heads, a.xa_count) && a.B > 0 && nets > 0,
                 TONIC_ERR_INVALID_ARGUMENT, "mlp_backward: H=%d NH=%d heads=%d B=%d", a.H, a.NH,
                 a.heads, a.B);
@@ -1106,15 +1146,25 @@ int launch_mlp_backward(const MlpBwdArgs& a, int nets, hipStream_t stream) {
                      (!a.hb_sac || (a.heads == 2 && a.hb_eps && a.hb_sigma && a.hb_spre && a.dhead[1]))),
                 TONIC_ERR_INVALID_ARGUMENT, "mlp_backward: folded head backward (heads=%d NH=%d)",
                 a.heads, a.NH);
+  const bool ranged = value.low != nullptr;
+  TONIC_REQUIRE(!ranged || (value.high != nullptr && a.heads == 0 && a.loss != LOSS_GIVEN && a.exchange_failed == nullptr),
+                TONIC_ERR_INVALID_ARGUMENT, "mlp_backward: a value range needs a critic's chain with its loss folded in");
   const size_t lds = (2 * (size_t)kRows * (a.H + 4) +
                       (a.hb_dxa0 != nullptr ? 2 * (size_t)kRows * kHeadPitch : 0)) * sizeof(float);
   if (a.img.block != nullptr) {
     TONIC_REQUIRE(image_pass_supported(0, a.H), TONIC_ERR_INVALID_ARGUMENT,
                   "mlp_backward: H=%d outside the image pass", a.H);
-    const int status = allow_image_lds(mlp_backward_kernel<true>, "mlp_backward_kernel");
+    const int status = ranged ? allow_image_lds(mlp_backward_ranged_kernel<true>, "mlp_backward_ranged_kernel")
+                              : allow_image_lds(mlp_backward_kernel<true>, "mlp_backward_kernel");
     if (status != TONIC_OK) return status;
-    hipLaunchKernelGGL(mlp_backward_kernel<true>, dim3((a.B + kRows - 1) / kRows, nets), dim3(256),
-                       img_lds(0, a.H).total, stream, a);
+    if (ranged)
+      hipLaunchKernelGGL(mlp_backward_ranged_kernel<true>, dim3((a.B + kRows - 1) / kRows, nets), dim3(256),
+                         img_lds(0, a.H).total, stream, a, value);
+    else hipLaunchKernelGGL(mlp_backward_kernel<true>, dim3((a.B + kRows - 1) / kRows, nets), dim3(256),
+                            img_lds(0, a.H).total, stream, a);
+  } else if (ranged) {
+    hipLaunchKernelGGL(mlp_backward_ranged_kernel<false>, dim3((a.B + kRows - 1) / kRows, nets), dim3(256), lds,
+                       stream, a, value);
   } else {
     hipLaunchKernelGGL(mlp_backward_kernel<false>, dim3((a.B + kRows - 1) / kRows, nets), dim3(256), lds,
                        stream, a);

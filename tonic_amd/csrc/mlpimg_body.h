@@ -177,8 +177,10 @@ __device__ __forceinline__ void img_publish(const ImgPublish& p, const float (&v
 }
 
 // ------------------------------------------------------------------------------------------- forward
+template <bool RANGED = false>      // (RANGED, value: see mlp_forward_body)
 __device__ __forceinline__ void mlp_forward_body_img(const MlpFwdArgs& a, const int net, const int bx,
-                                                     float* lds_f) {
+                                                     float* lds_f,
+                                                     ValueRangeArg value = ValueRangeArg{nullptr, nullptr}) {
   char* lds = reinterpret_cast<char*>(lds_f);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -257,6 +259,7 @@ __device__ __forceinline__ void mlp_forward_body_img(const MlpFwdArgs& a, const 
   }
   const int tiles_per_head = (a.NH + 15) / 16;
   const bool value_head = a.heads == 1 && a.NH == 1 && a.act[0] == ACT_NONE;       // scalar
+  const ValueRange vrange = RANGED ? value_range(value.low, value.high) : ValueRange{0.f, 0.f, false};      // (scalar loads, once; null: the plain head)
   const bool head_wave = !value_head && wave < a.heads * tiles_per_head;
   const int head = head_wave ? wave / tiles_per_head : 0;
   const int head_tile = head_wave ? wave - head * tiles_per_head : 0;
@@ -389,7 +392,9 @@ __device__ __forceinline__ void mlp_forward_body_img(const MlpFwdArgs& a, const 
     __syncthreads();
     if (wave == 0 && g == 0 && row_ok) {
       float* out_base = a.out[0];
-      const float q = ((partial[m] + partial[16 + m]) + (partial[32 + m] + partial[48 + m])) + hbias[0];
+      // (RANGED: the Return normaliser's head publishes v = value_squash(z); the chained launches, the only ones with
+      //  exchange lines, are never RANGED)
+      const float q = value_squash(((partial[m] + partial[16 + m]) + (partial[32 + m] + partial[48 + m])) + hbias[0], vrange);
       out_base[net * a.stride_out + (int64_t)(r0 + m) * a.ldo] = q;
       if (a.xq != nullptr) {       // read by other workgroups of the same launch (ValueLines)
         const int slot = net < a.split ? 32 * net : 32 * (2 + net - a.split);     // one line per writer
@@ -441,8 +446,10 @@ __device__ __forceinline__ void mlp_forward_body_img(const MlpFwdArgs& a, const 
 }
 
 // ------------------------------------------------------------------------------------------ backward
+template <bool RANGED = false>
 __device__ __forceinline__ void mlp_backward_body_img(const MlpBwdArgs& a, const int net, const int bx,
-                                                      float* lds_f, const int K1_lds) {
+                                                      float* lds_f, const int K1_lds,
+                                                      ValueRangeArg value = ValueRangeArg{nullptr, nullptr}) {
   char* lds = reinterpret_cast<char*>(lds_f);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -549,6 +556,7 @@ __device__ __forceinline__ void mlp_backward_body_img(const MlpBwdArgs& a, const
   const ImgPublish pub{rowmax, desc, wave, m, g, tiles, H, r0, row_ok, tile_of};
   float d2[kMaxTiles][4];
   if (a.heads == 0) {                                 // critic: dq[row] * w3[feature], fp32
+    const ValueRange vrange = RANGED ? value_range(value.low, value.high) : ValueRange{0.f, 0.f, false};     // (scalar; null: the plain head)
     float dq;
     if (a.loss == LOSS_GIVEN) {
       dq = a.dq[net * a.stride_dq + row];
@@ -556,9 +564,11 @@ __device__ __forceinline__ void mlp_backward_body_img(const MlpBwdArgs& a, const
       if (a.loss == LOSS_TD) {
         const float y = td_target(a.l_rewards, a.l_discounts, a.l_tq, a.l_logp, a.l_alpha, row, a.l_tq_at,
                                   a.l_nets, co);
-        dq = critic_loss_dq(load_shared(a.l_q + a.l_q_at.index(net, row), co) - y, a.l_kind, a.l_param);
+        const float q = load_shared(a.l_q + a.l_q_at.index(net, row), co);
+        dq = value_squash_dz(critic_loss_dq(q - y, a.l_kind, a.l_param), q, vrange);
       } else {
         dq = actor_dq(a.l_q, row, a.l_q_at, a.l_nets == 2, net, co);
+        if (vrange.on) dq = value_squash_dz(dq, load_shared(a.l_q + a.l_q_at.index(net, row), co), vrange);
       }
       if (row_ok && wave == 0 && g == 0)              // for the weight-gradient GEMM (dw3, db3)
         const_cast<float*>(a.dq)[net * a.stride_dq + row] = dq;

@@ -208,20 +208,21 @@ __global__ void copy_actions_kernel(const float* loc, int ld, float* act, int B,
 __global__ void critic_loss_kernel(const float* rewards, const float* discounts,
                                    const float* tq, const float* logp_next, float alpha,
                                    const float* q, float* dq, float* stats, int B, int Bp,
-                                   int nets, CriticLoss loss) {
+                                   int nets, CriticLoss loss, const float* v_low, const float* v_high) {
+  const ValueRange vrange = value_range(v_low, v_high);     // the Return normaliser's head: q / tq are squashed values
   float s_loss = 0.f, s_q1 = 0.f, s_q2 = 0.f;
   for (int m = threadIdx.x; m < B; m += blockDim.x) {
     const float y = td_target(rewards, discounts, tq, logp_next, alpha, m, ValueLines{Bp, 16}, nets);
     if (nets == 1) {
       const float e1 = q[m] - y;
-      dq[m] = critic_loss_dq(e1, loss.kind, loss.param);
+      dq[m] = value_squash_dz(critic_loss_dq(e1, loss.kind, loss.param), q[m], vrange);
       s_loss += critic_loss_term(e1, loss.kind, loss.param);
       s_q1 += q[m];
       continue;
     }
     const float e1 = q[m] - y, e2 = q[Bp + m] - y;
-    dq[m] = critic_loss_dq(e1, loss.kind, loss.param);
-    dq[Bp + m] = critic_loss_dq(e2, loss.kind, loss.param);
+    dq[m] = value_squash_dz(critic_loss_dq(e1, loss.kind, loss.param), q[m], vrange);
+    dq[Bp + m] = value_squash_dz(critic_loss_dq(e2, loss.kind, loss.param), q[Bp + m], vrange);
     s_loss += critic_loss_term(e1, loss.kind, loss.param) + critic_loss_term(e2, loss.kind, loss.param);
     s_q1 += q[m];
     s_q2 += q[Bp + m];
@@ -238,13 +239,15 @@ __global__ void critic_loss_kernel(const float* rewards, const float* discounts,
 //                  TD3  loss = -mean(q1)                          (actors.py:177-179)
 // d loss / d q_z (unscaled by 1/B): -1 on the smaller critic, -1/2 each on ties.
 __global__ void actor_loss_kernel(const float* q, const float* logp, float alpha, int twin,
-                                  float* dq, float* stats, int B, int Bp) {
+                                  float* dq, float* stats, int B, int Bp, const float* v_low,
+                                  const float* v_high) {
+  const ValueRange vrange = value_range(v_low, v_high);     // the Return normaliser's head: q holds squashed values
   float s = 0.f;
   for (int m = threadIdx.x; m < B; m += blockDim.x) {
     const float q1 = q[m];
-    dq[m] = actor_dq(q, m, ValueLines{Bp, 16}, twin, 0);
+    dq[m] = value_squash_dz(actor_dq(q, m, ValueLines{Bp, 16}, twin, 0), q1, vrange);
     if (twin) {
-      dq[Bp + m] = actor_dq(q, m, ValueLines{Bp, 16}, twin, 1);
+      dq[Bp + m] = value_squash_dz(actor_dq(q, m, ValueLines{Bp, 16}, twin, 1), q[Bp + m], vrange);
       s += alpha * logp[m] - fminf(q1, q[Bp + m]);
     } else {
       s += -q1;
@@ -938,7 +941,8 @@ MlpFwdArgs critics_forward_args(const float* params, CriticShape s, int nets, co
 int critics_forward(const float* params, CriticShape s, int nets, const float* X, int ldx, int B,
                     int Bp, float* h1, float* h2, float* q, hipStream_t st,
                     const float* params2 = nullptr, const float* X2 = nullptr,
-                    const CriticImg* img = nullptr) {
+                    const CriticImg* img = nullptr, const float* v_low = nullptr,
+                    const float* v_high = nullptr) {      // (v_low / v_high: the Return normaliser's head, ValueRangeArg)
   const CriticOffsets o(s);
   const int in = s.O + s.A;
   const int HP = s.hp();
@@ -948,12 +952,12 @@ int critics_forward(const float* params, CriticShape s, int nets, const float* X
     MlpFwdArgs f = critics_forward_args(params, s, nets, X, ldx, B, Bp, h1, h2, q, params2,
                                         X2, &launch_nets, img);
     if (params2 != nullptr) f.hidden_from = nets;   // (the first set = the targets: forward only)
-    return launch_mlp_forward(f, launch_nets, st);
+    return launch_mlp_forward(f, launch_nets, st, ValueRangeArg{v_low, v_high});
   }
   if (params2 != nullptr) {            // unfused path: one pass per parameter set
-    TRY(critics_forward(params, s, nets, X, ldx, B, Bp, h1, h2, q, st));
+    TRY(critics_forward(params, s, nets, X, ldx, B, Bp, h1, h2, q, st, nullptr, nullptr, nullptr, v_low, v_high));
     return critics_forward(params2, s, nets, X2, ldx, B, Bp, h1 + nets * hs, h2 + nets * hs,
-                           q + (int64_t)nets * Bp, st);
+                           q + (int64_t)nets * Bp, st, nullptr, nullptr, nullptr, v_low, v_high);
   }
   GemmArgs g;
   for (int l = 0; l < s.L; ++l) {
@@ -967,7 +971,7 @@ int critics_forward(const float* params, CriticShape s, int nets, const float* X
   g = gemm(layer_at(h1, h2, s.L - 1), HP, params + o.w3, o.ldO, q, 1, B, 1, s.last());
   g.bias = params + o.b3;
   g.strideA = hs; g.strideB = o.count; g.strideBias = o.count; g.strideC = Bp;
-  TRY(launch_gemm('c', 'c', g, nets, st));
+  TRY(launch_gemm('c', 'c', g, nets, st, ValueRangeArg{v_low, v_high}));
   return TONIC_OK;
 }
 
@@ -983,6 +987,7 @@ struct StepLoss {
   float alpha;
   const float* q; float* stats;
   CriticLoss rule;                            // LOSS_TD: tonic_critic_loss_t (all-zero: MSE)
+  const float* v_low; const float* v_high;    // the Return normaliser's head (q / tq are squashed values); null: plain
 };
 
 // The one-launch chain's arguments (mlp_backward_supported(H, 1, 0, dxa ? A : 0)).
@@ -1057,10 +1062,10 @@ int critics_backward(const float* params, CriticShape s, int nets, const float* 
     if (loss->kind == LOSS_TD) {
       hipLaunchKernelGGL(critic_loss_kernel, dim3(1), dim3(1024), 0, st, loss->rewards,
                          loss->discounts, loss->tq, loss->logp, loss->alpha, loss->q, dq,
-                         loss->stats, B, Bp, nets, loss->rule);
+                         loss->stats, B, Bp, nets, loss->rule, loss->v_low, loss->v_high);
     } else {
       hipLaunchKernelGGL(actor_loss_kernel, dim3(1), dim3(1024), 0, st, loss->q, loss->logp,
-                         loss->alpha, nets == 2 ? 1 : 0, dq, loss->stats, B, Bp);
+                         loss->alpha, nets == 2 ? 1 : 0, dq, loss->stats, B, Bp, loss->v_low, loss->v_high);
     }
   }
   const int HP = s.hp();
@@ -1071,7 +1076,7 @@ int critics_backward(const float* params, CriticShape s, int nets, const float* 
   if (one_launch) {                                               // ... in ONE launch
     MlpBwdArgs b = critics_chain_args(params, s, nets, B, Bp, h1, h2, dq, dh2, dh1, dxa, loss, img);
     b.skip_dz = grads == nullptr ? 1 : 0;          // (a frozen critic's chain: only its action columns are read)
-    TRY(launch_mlp_backward(b, nets, st));
+    TRY(launch_mlp_backward(b, nets, st, loss ? ValueRangeArg{loss->v_low, loss->v_high} : ValueRangeArg{nullptr, nullptr}));
   } else {
     // dz_top = (dq w3) * act'(h_top)   (two layers: dz2, with h2)
     g = gemm(dq, 1, params + o.w3, o.ldO, dh2, HP, B, s.last(), 1);
@@ -1363,6 +1368,30 @@ extern "C" int tonic_twin_q_grad_loss(int32_t kind, const float* d_policy_params
                                       double entropy_coeff, double noise_scale, double noise_clip,
                                       const tonic_critic_loss_t* loss,
                                       void* d_workspace, int64_t workspace_bytes, void* stream) {
+  return tonic_twin_q_grad_ranged(kind, d_policy_params, d_target_critics, d_critics, d_norm_mean, d_norm_std,
+                                  norm_clip, d_observations, d_actions, d_next_observations, d_rewards, d_discounts,
+                                  d_eps, d_grad_sums, B, O, H, A, entropy_coeff, noise_scale, noise_clip, loss,
+                                  nullptr, nullptr, d_workspace, workspace_bytes, stream);
+}
+
+// ... for critics whose value heads squash into the Return normaliser's [low, high] (models/critics.py:17-19):
+// online and target critics publish v, the TD loss, its gradient and the logged sums are those of v.  NULL / NULL:
+// the plain heads, the launches and bits of tonic_twin_q_grad_loss.
+extern "C" int tonic_twin_q_grad_ranged(int32_t kind, const float* d_policy_params,
+                                        const float* d_target_critics, const float* d_critics,
+                                        const float* d_norm_mean, const float* d_norm_std,
+                                        double norm_clip,
+                                        const float* d_observations, const float* d_actions,
+                                        const float* d_next_observations, const float* d_rewards,
+                                        const float* d_discounts, const float* d_eps,
+                                        float* d_grad_sums, int32_t B, int32_t O, int32_t H, int32_t A,
+                                        double entropy_coeff, double noise_scale, double noise_clip,
+                                        const tonic_critic_loss_t* loss,
+                                        const float* d_value_low, const float* d_value_high,
+                                        void* d_workspace, int64_t workspace_bytes, void* stream) {
+  TONIC_REQUIRE((d_value_low == nullptr) == (d_value_high == nullptr), TONIC_ERR_INVALID_ARGUMENT,
+                "tonic_twin_q_grad_ranged: %s is NULL and the other bound is not (both or neither)",
+                d_value_low == nullptr ? "d_value_low" : "d_value_high");
   TRY(tonic_critic_loss_check(loss));
   TONIC_REQUIRE(d_policy_params && d_target_critics && d_critics && d_norm_mean && d_norm_std &&
                     d_observations && d_actions && d_next_observations && d_rewards &&
@@ -1439,9 +1468,10 @@ extern "C" int tonic_twin_q_grad_loss(int32_t kind, const float* d_policy_params
                        clip_bound(norm_clip), X, B, O, A, ldx, d_observations, d_actions, X2);
   }
   TRY(critics_forward(d_target_critics, cs, nets, X, ldx, B, Bp, h1_all, h2_all, q_all, st,
-                      d_critics, X2, im.on ? &im.target_critics : nullptr));
+                      d_critics, X2, im.on ? &im.target_critics : nullptr, d_value_low, d_value_high));
   const StepLoss td{LOSS_TD, d_rewards, d_discounts, tq, kind == 1 ? logp : (const float*)nullptr,
-                    (float)entropy_coeff, q, d_grad_sums + nets * Pc, critic_loss_rule(loss)};
+                    (float)entropy_coeff, q, d_grad_sums + nets * Pc, critic_loss_rule(loss),
+                    d_value_low, d_value_high};
   TRY(critics_backward(d_critics, cs, nets, X2, ldx, B, Bp, c_h1, c_h2, dq, dh2, dh1, d_grad_sums,
                        nullptr, st, &td, nullptr, im.on ? &im.critics : nullptr));
   TONIC_CHECK_LAUNCH("tonic_twin_q_grad");
@@ -2250,6 +2280,24 @@ extern "C" int tonic_actor_q_grad(int32_t kind, const float* d_actor_params,
                                   const float* d_eps, float* d_grad_sums, int32_t B, int32_t O,
                                   int32_t H, int32_t A, double entropy_coeff, void* d_workspace,
                                   int64_t workspace_bytes, void* stream) {
+  return tonic_actor_q_grad_ranged(kind, d_actor_params, d_critics, d_norm_mean, d_norm_std, norm_clip,
+                                   d_observations, d_eps, d_grad_sums, B, O, H, A, entropy_coeff, nullptr, nullptr,
+                                   d_workspace, workspace_bytes, stream);
+}
+
+// ... through critics whose value heads squash (tonic_twin_q_grad_ranged): the objective and its logged sum are
+// those of v, the gradient that enters each head is multiplied by dv/dz.  NULL / NULL: tonic_actor_q_grad.
+extern "C" int tonic_actor_q_grad_ranged(int32_t kind, const float* d_actor_params,
+                                         const float* d_critics, const float* d_norm_mean,
+                                         const float* d_norm_std, double norm_clip,
+                                         const float* d_observations,
+                                         const float* d_eps, float* d_grad_sums, int32_t B, int32_t O,
+                                         int32_t H, int32_t A, double entropy_coeff,
+                                         const float* d_value_low, const float* d_value_high,
+                                         void* d_workspace, int64_t workspace_bytes, void* stream) {
+  TONIC_REQUIRE((d_value_low == nullptr) == (d_value_high == nullptr), TONIC_ERR_INVALID_ARGUMENT,
+                "tonic_actor_q_grad_ranged: %s is NULL and the other bound is not (both or neither)",
+                d_value_low == nullptr ? "d_value_low" : "d_value_high");
   TONIC_REQUIRE(d_actor_params && d_critics && d_norm_mean && d_norm_std && d_observations &&
                     d_grad_sums && d_workspace && B > 0 && (kind == 0 || d_eps) && hidden_known(H),
                 TONIC_ERR_INVALID_ARGUMENT, "tonic_actor_q_grad: bad argument");
@@ -2311,9 +2359,9 @@ extern "C" int tonic_actor_q_grad(int32_t kind, const float* d_actor_params,
                        B, O, A, ldx);
   }
   TRY(critics_forward(d_critics, cs, nets, X, ldx, B, Bp, c_h1, c_h2, q, st, nullptr, nullptr,
-                      im.on ? &im.critics : nullptr));
+                      im.on ? &im.critics : nullptr, d_value_low, d_value_high));
   const StepLoss objective{LOSS_ACTOR, nullptr, nullptr, nullptr, logp, (float)entropy_coeff, q,
-                           d_grad_sums + Pa};
+                           d_grad_sums + Pa, CriticLoss{TONIC_LOSS_MSE, 0.f}, d_value_low, d_value_high};
   TRY(critics_backward(d_critics, cs, nets, X, ldx, B, Bp, c_h1, c_h2, dq, dh2, dh1, nullptr, dxa,
                        st, &objective, nullptr, im.on ? &im.critics : nullptr));
   hipLaunchKernelGGL(actor_head_backward_kernel, dim3((B * A + threads - 1) / threads),

@@ -1262,6 +1262,9 @@ class DDPG(Agent):
     on this class like in the reference."""
 
     policy_kind = 0          # tonic_policy_forward kind used by `_policy`
+    # ActorCriticWithTargets(..., return_normalizer=Return(...)): served by the updaters' *_ranged entries (DDPG, TD3,
+    # SAC); an agent whose updaters have no squashed form (MPO) keeps raising at its first update
+    serves_return_normalizer = True
 
     def __init__(self, model=None, replay=None, exploration=None, actor_updater=None,
                  critic_updater=None):
@@ -1386,7 +1389,9 @@ class DDPG(Agent):
         if q is None or not q.store(observations, rewards, self.last_observations):
             self._store_staged(observations, rewards, resets, terminations)
         if self.model.return_normalizer:
-            raise NotImplementedError('return normalisers are not supported')
+            if not self.serves_return_normalizer:
+                raise NotImplementedError('return normalisers are not supported')
+            record_reward_range(self.model.return_normalizer, rewards)      # ddpg.py:69-70
         if self.replay.ready(steps):
             self._q.flush()              # the update samples the reserved transitions too
             self._update(steps)          # (ends with a read-back: the store launches are through)
@@ -1559,6 +1564,8 @@ class DDPG(Agent):
         kind, actor_class = self._FUSED.get(type(critic), (None, None))
         if kind is None or type(actor) is not actor_class or critic.stock or actor.stock:
             return None
+        if self.model.return_normalizer:             # tonic_q_iteration has no squashed value head: the split entries
+            return None
         if not (critic.plain and actor.plain):        # tonic_q_iteration's epilogues are plain Adam: the split entries
             return None
         if os.environ.get('TONIC_AMD_FUSED_ITERATION', '1') == '0':
@@ -1695,8 +1702,11 @@ class DDPG(Agent):
                           int(getattr(updater, 'num_samples', 0)),
                           (noise.scale, noise.clip) if noise is not None else None))
         norm = self.model.observation_normalizer
+        # (the Return normaliser's _low / _high are read through their pointers by the captured launches)
+        value_range = self.model.return_normalizer or None
         return (tuple(parts), float(self.model.target_coeff), getattr(self, 'delay_steps', 1),
-                norm._mean.data_ptr() if norm is not None else 0)
+                norm._mean.data_ptr() if norm is not None else 0,
+                (value_range._low.data_ptr(), value_range._high.data_ptr()) if value_range is not None else None)
 
     def _noise_samples(self, draws):
         """Rows per state in each draw of `_draw_noise`: each updater reads the first c * samples rows of its own."""
@@ -1780,6 +1790,38 @@ class DDPG(Agent):
         self.last_infos = infos
         if self.model.observation_normalizer:
             self.model.observation_normalizer.update()
+        if self.model.return_normalizer:
+            # ddpg.py:102-103 / td3.py:54-55: behind the last iteration (the copies into _low / _high are enqueued
+            # on the stream every graph replay of this update — chunks included — went to, and the infos were
+            # read back above), the ranks' ranges merged first
+            merge_reward_ranges(self.model.return_normalizer)
+            self.model.return_normalizer.update()
+
+
+def record_reward_range(normalizer, rewards):
+    """ddpg.py:69-70 (`return_normalizer.record(rewards)`) as ONE record of the step's [min, max]: Return.record only
+    keeps a running min / max, so the pair does what recording every reward does (the argument of
+    tonic_reward_range, include/tonic_hip.h).  NaN is skipped — the reference's `<` / `>` are false for it — and
+    a step whose rewards are all NaN records nothing; +-inf is kept."""
+    rewards = np.asarray(rewards, np.float32).reshape(-1)
+    rewards = rewards[~np.isnan(rewards)]
+    if rewards.size:
+        normalizer.record(np.array([rewards.min(), rewards.max()], np.float32))
+
+
+def merge_reward_ranges(normalizer):
+    """Several ranks: every rank's Return normaliser ends with the union of the ranks' (min_reward, max_reward) —
+    what one process that saw every worker's rewards holds — as one all_reduce(MAX) of (-min, max), like
+    A2C._range_rewards.  A rank that recorded nothing holds the initial (-1, 1), inside every range."""
+    if not (torch.distributed.is_available() and torch.distributed.is_initialized()) \
+            or torch.distributed.get_world_size() == 1:
+        return
+    pair = torch.tensor([-float(normalizer.min_reward), float(normalizer.max_reward)], dtype=torch.float32)
+    if torch.distributed.get_backend() != 'gloo':
+        pair = pair.to(_device())
+    torch.distributed.all_reduce(pair, op=torch.distributed.ReduceOp.MAX)
+    low, high = pair.cpu().numpy()
+    normalizer.min_reward, normalizer.max_reward = np.float32(-low), np.float32(high)
 
 
 def _check_chain(infos):
@@ -1839,6 +1881,7 @@ class MPO(DDPG):
     and the target update — DDPG's staging, HBM Buffer, hipGraph capture and schedule."""
 
     policy_kind = 2
+    serves_return_normalizer = False     # (ExpectedSARSA and the E-step have no squashed form)
 
     def __init__(self, model=None, replay=None, actor_updater=None, critic_updater=None):
         super().__init__(

@@ -1008,6 +1008,9 @@ class _QUpdater(_FlatUpdater):
         layer = head.loc_layer if self.sac else head.action_layer
         self.action_size = layer[0].out_features
         self.normalizer = model.observation_normalizer
+        # the Return normaliser of the critics' value heads (critics.py:17-19; one module shared by the online and
+        # target critics): the *_ranged entries squash with its _low / _high, read on the device
+        self.return_normalizer = getattr(model, 'return_normalizer', None) or None
         device = model.flat_online.device
         self.atoms = getattr(critic.head, 'num_atoms', 0)
         if self.normalizer is None:
@@ -1056,6 +1059,12 @@ class _QUpdater(_FlatUpdater):
 
     def norm_clip(self):
         return float(getattr(self.normalizer, 'clip', None) or 0.0)
+
+    def range_pointers(self):
+        """Device pointers of the Return normaliser's (_low, _high); (None, None) without one: the plain heads."""
+        if self.return_normalizer is None:
+            return None, None
+        return _lib.ptr(self.return_normalizer._low.data), _lib.ptr(self.return_normalizer._high.data)
 
     def _offpolicy_workspace(self, batch):
         if self.atoms:
@@ -1177,15 +1186,19 @@ class _TwinCriticQLearning(_QUpdater):
         mean, std = self.norm_tensors()
         noise = getattr(self, 'target_action_noise', None)
         p = _lib.ptr
-        _lib.check(self.lib.tonic_twin_q_grad_loss(
+        # (a model without a Return normaliser keeps the entry it had; with one: the squashed heads' entry)
+        entry, value_range = 'tonic_twin_q_grad_loss', ()
+        if self.return_normalizer is not None:
+            entry, value_range = 'tonic_twin_q_grad_ranged', self.range_pointers()
+        _lib.check(getattr(self.lib, entry)(
             self.kind, p(self._policy_params()), p(self.model.flat_target_critics.flat),
             p(self.flat.flat), p(mean), p(std), self.norm_clip(), p(batch['observations']),
             p(batch['actions']),
             p(batch['next_observations']), p(batch['rewards']), p(batch['discounts']), p(eps),
             p(self.grad_sums), B, self.observation_size, self.hidden, self.action_size,
             float(getattr(self, 'entropy_coeff', 0.0)), float(noise.scale if noise else 0.0),
-            float(noise.clip if noise else 0.0), ctypes.addressof(self.loss_rule), p(ws), ws.numel(),
-            _lib.current_stream()), 'tonic_twin_q_grad_loss')
+            float(noise.clip if noise else 0.0), ctypes.addressof(self.loss_rule), *value_range, p(ws), ws.numel(),
+            _lib.current_stream()), entry)
         self._step(n_global or B * self.world_size, info_row)
 
     def __call__(self, observations, actions, next_observations, rewards, discounts):
@@ -1376,11 +1389,14 @@ class _ActorQGradient(_QUpdater):
         ws = self._offpolicy_workspace(B)
         mean, std = self.norm_tensors()
         p = _lib.ptr
-        _lib.check(self.lib.tonic_actor_q_grad(
+        entry, value_range = 'tonic_actor_q_grad', ()
+        if self.return_normalizer is not None:
+            entry, value_range = 'tonic_actor_q_grad_ranged', self.range_pointers()
+        _lib.check(getattr(self.lib, entry)(
             self.kind, p(self.flat.flat), p(self.model.flat_critics.flat), p(mean), p(std),
             self.norm_clip(), p(observations), p(eps), p(self.grad_sums), B, self.observation_size, self.hidden,
-            self.action_size, float(getattr(self, 'entropy_coeff', 0.0)), p(ws), ws.numel(),
-            _lib.current_stream()), 'tonic_actor_q_grad')
+            self.action_size, float(getattr(self, 'entropy_coeff', 0.0)), *value_range, p(ws), ws.numel(),
+            _lib.current_stream()), entry)
         self._step(n_global or B * self.world_size, info_row, targets=targets)
 
     def __call__(self, observations):
