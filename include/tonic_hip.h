@@ -61,11 +61,12 @@ const char* tonic_last_error(void);
  * 16 = tonic_critic_loss_t: tonic_critic_loss_check, tonic_twin_q_grad_loss, tonic_expected_sarsa_grad_loss,
  * tonic_q_iteration_t.critic_loss), 17 = the tonic_mpo_*_joint entries (`joint_kl`: one alpha pair on the KLs
  * summed over the action dimensions); the MPO entries take 1 .. 256 samples per state, 18 = tonic_twin_q_grad_ranged /
- * tonic_actor_q_grad_ranged (the Return normaliser's value head on the off-policy split entries) (additive: every
+ * tonic_actor_q_grad_ranged (the Return normaliser's value head on the off-policy split entries), 19 =
+ * tonic_mlp_torso_head: `H` codes that carry the bounds of a Gaussian policy head's scale (additive: every
  * earlier entry keeps its signature)
  * and the gfx target the kernels were built for.  TONIC_ABI_VERSION is what a binding was compiled against:
  * tonic_amd/_fastcall (csrc/fastcall.c) and tonic_amd/_lib.py compare it with the loaded library's answer. */
-#define TONIC_ABI_VERSION 18
+#define TONIC_ABI_VERSION 19
 int32_t tonic_abi_version(void);
 const char* tonic_target_arch(void);
 
@@ -706,11 +707,16 @@ int tonic_adam_polyak_step(float* d_online, const float* d_grad_sums, float* d_e
  *     - tonic_mlp_hidden(H1, H2, activation): two hidden layers of H1 and H2 units (1 .. 4095: the (400, 300)
  *       class), activation 1 = torch.nn.ReLU, 2 = Tanh, 3 = ELU (bit 30 set, bit 29 clear);
  *     - tonic_mlp_torso(layers, sizes, activation) for 1, 3 or 4 layers: a descriptor registered in a process-wide
- *       table of 64 (bits 30 and 29 set, the low bits its index; the same torso always gets the same code; valid in
+ *       table of 256 (bits 30 and 29 set, the low bits its index; the same torso always gets the same code; valid in
  *       the process that registered it).  For two layers tonic_mlp_torso returns what tonic_mlp_hidden does.
+ *     - tonic_mlp_torso_head(layers, sizes, activation, scale_min, scale_max): the torso of an actor whose Gaussian
+ *       head clamps its scale to other bounds than 1e-4 / 1 — a descriptor torso + bounds in the same table, for any
+ *       depth; with the default bounds one of the codes above.  Everything but the scale's clamp reads it as the
+ *       torso's own code.
  *   Layer l is then W_l [H_l, H_(l-1)] b_l [H_l] (H_(-1) = the input), heads / w3 are as wide as the last layer,
  *   same padding rules.  Every torso but the plain one runs layer by layer (csrc/gemm16.hip) instead of in the
- *   fused kernels; tonic_q_iteration* and tonic_mlp_actor_image_bytes serve plain widths only.
+ *   fused kernels; tonic_q_iteration* and tonic_mlp_actor_image_bytes serve plain widths only (with or without
+ *   bounds).
  */
 int64_t tonic_offpolicy_workspace_bytes(int32_t B, int32_t O, int32_t A, int32_t H);
 int32_t tonic_mlp_weight_stride(int32_t cols);
@@ -718,6 +724,21 @@ int32_t tonic_mlp_hidden(int32_t H1, int32_t H2, int32_t activation);
 /* `H` of MLP(sizes[0 .. layers), activation): layers 1 .. 4, widths 1 .. 4095, activation 1 ReLU / 2 Tanh / 3 ELU.
  * Negative (tonic_last_error set): outside those limits, NULL sizes, or the descriptor table is full. */
 int32_t tonic_mlp_torso(int32_t layers, const int32_t* sizes, int32_t activation);
+/* `H` of an ACTOR on that torso whose Gaussian head clamps its scale to [scale_min, scale_max]
+ * (GaussianPolicyHead(scale_min, scale_max), tonic/torch/models/actors.py:69-98).  With the reference's defaults
+ * ((float)scale_min == 1e-4f, (float)scale_max == 1.0f) this is tonic_mlp_torso's code.  Other bounds register
+ * torso + bounds in the same table (two-layer torsos too: bits 30 and 29 set; the same descriptor, the same code),
+ * and every entry that forms a Gaussian scale from the code's actor — tonic_policy_forward kinds 1 and 2,
+ * tonic_collector_q_act, tonic_twin_q_grad*, tonic_actor_q_grad*, tonic_q_iteration, tonic_expected_sarsa_grad*,
+ * tonic_mpo_actor_grad* — clamps to them: sigma = clamp(softplus(.), scale_min, scale_max), its gradient passing
+ * where softplus(.) lies within the bounds.  A critic, a deterministic head and every size query ignore the bounds:
+ * a code whose torso is plain is served by everything that serves the plain width (the fused kernels, the weight
+ * images, tonic_q_iteration*).  Negative (tonic_last_error names both values): not 0 < scale_min <= scale_max with
+ * both finite as float32; or as tonic_mlp_torso.  Every distinct (torso, bounds) pair takes one of the table's 256
+ * slots for the life of the process, as every 1 / 3 / 4-layer torso does: a sweep over more pairs than that in one
+ * process ends with "distinct torsos registered already" for new descriptors, plain torsos included. */
+int32_t tonic_mlp_torso_head(int32_t layers, const int32_t* sizes, int32_t activation, double scale_min,
+                             double scale_max);
 int64_t tonic_mlp_actor_param_count(int32_t O, int32_t H, int32_t A, int32_t heads);
 int64_t tonic_q_critic_param_count(int32_t O, int32_t A, int32_t H);
 

@@ -152,6 +152,8 @@ SIGNATURES = {
     'tonic_mlp_weight_stride': (c_i32, [c_i32]),
     'tonic_mlp_hidden': (c_i32, [c_i32, c_i32, c_i32]),
     'tonic_mlp_torso': (c_i32, [c_i32, c_vp, c_i32]),
+    # ... with the bounds of the actor's Gaussian scale head (ABI 19)
+    'tonic_mlp_torso_head': (c_i32, [c_i32, c_vp, c_i32, c_f64, c_f64]),
     'tonic_mlp_actor_param_count': (c_i64, [c_i32] * 4),
     'tonic_q_critic_param_count': (c_i64, [c_i32] * 3),
     'tonic_buffer_store': (ctypes.c_int, [c_vp] * 14 + [c_i64, c_i64, c_i32, c_i32, c_f64, c_vp]),
@@ -236,7 +238,7 @@ SIGNATURES = {
 }
 
 
-ABI_VERSION = 18       # include/tonic_hip.h: tonic_abi_version()
+ABI_VERSION = 19       # include/tonic_hip.h: tonic_abi_version()
 
 
 class TonicHipError(RuntimeError):

@@ -27,15 +27,19 @@ constexpr float kHalfLog2Pi = 0.91893853320467274178f;
 
 __device__ __forceinline__ float softplus_f(float x) { return x > 20.f ? x : log1pf(expf(x)); }
 
+// The bounds of a Gaussian head's scale (GaussianPolicyHead(scale_min, scale_max), actors.py:69-98): wave-uniform
+// kernel arguments, unpacked on the host from the `H` code (tonic_mlp_torso_head); the reference's defaults
+constexpr float kScaleMin = 1e-4f, kScaleMax = 1.0f;
+
 // One action of SquashedMultivariateNormalDiag.rsample_with_log_prob (actors.py:11-16,94-98):
-// sigma = clamp(softplus(spre), 1e-4, 1), u = loc + eps * sigma, a = tanh(u),
+// sigma = clamp(softplus(spre), scale_lo, scale_hi), u = loc + eps * sigma, a = tanh(u),
 // term = N(u; loc, sigma).log_prob - log(1 - a^2 + 1e-6).
 struct SquashedSample { float action, sigma, logp_term; };
 __device__ __forceinline__ SquashedSample squashed_sample(float loc, float spre, float eps,
-                                                          bool has_eps) {
+                                                          bool has_eps, float scale_lo, float scale_hi) {
   SquashedSample r;
   const float raw = softplus_f(spre);
-  r.sigma = fminf(fmaxf(raw, 1e-4f), 1.0f);
+  r.sigma = fminf(fmaxf(raw, scale_lo), scale_hi);
   const float u = has_eps ? loc + eps * r.sigma : loc;             // rsample: loc + eps * scale
   r.action = tanhf(u);
   const float d = u - loc;
@@ -104,6 +108,9 @@ struct MlpFwdArgs {
   //   POST_TARGET_NOISE    (heads = 1, tanh head): actions = noisy_target_action(head, eps)
   //   POST_COPY            (heads = 1): dense actions out of the padded head buffer
   int post;
+  // POST_SQUASHED_SAMPLE: the bounds of the scale, of both tails (they are passes of one policy head): scale_lo here,
+  // scale_hi behind enc_clip — each in the padding ahead of a pointer, so that the argument segment keeps its size
+  float scale_lo = kScaleMin;
   const float* post_eps;     // [B, NH] standard-normal draws (SAMPLE: may be null = greedy)
   float* post_actions;       // [B, NH]
   float* post_sigma;         // [B, NH] or null
@@ -116,6 +123,7 @@ struct MlpFwdArgs {
   const float* enc_obs; const float* enc_obs2; const float* enc_act2;   // [B, enc_O], [B, NH]
   const float* enc_mean; const float* enc_std;                          // [enc_O]
   float enc_clip;                                                       // MeanStd(clip): +inf = none
+  float scale_hi = kScaleMax;                                           // (see scale_lo)
   float* enc_out; float* enc_out2;
   int enc_O, enc_ld;
   float* reset_area; int64_t reset_floats;   // the launch AHEAD of the chained ones: fill with kExchangeEmpty
@@ -200,6 +208,9 @@ struct MlpBwdArgs {
                                 //   written with exchange_write; the word a reader sets when a value never came
   BwdImages img;                // img.block != null: the products run on fp16x2 terms from weight images (mlpimg.h)
   int skip_dz;                  // image pass: dz2 / dz1 stay out of HBM (a frozen network's chain: no weight gradients)
+  // hb_sac: the scale's bounds (the clamp's gradient gate).  (Last: beside hb_alpha they cost mlp_backward_kernel<true>
+  // 36 bytes of scratch per lane.)
+  float hb_scale_lo = kScaleMin, hb_scale_hi = kScaleMax;
 };
 enum MlpBwdLoss : int { LOSS_GIVEN = 0, LOSS_TD = 1, LOSS_ACTOR = 2 };
 

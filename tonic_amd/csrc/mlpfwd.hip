@@ -267,7 +267,7 @@ __device__ __forceinline__ void policy_tail(const MlpFwdArgs& a, const bool seco
         const bool has_eps = post_eps != nullptr;
         const float eps = (has_eps && ok) ? eps4[u] : 0.f;
         const SquashedSample sm =
-            squashed_sample(first, headbuf[(kRows + prow) * kPostPitch + aa], eps, has_eps);
+            squashed_sample(first, headbuf[(kRows + prow) * kPostPitch + aa], eps, has_eps, a.scale_lo, a.scale_hi);
         term4[u] = sm.logp_term;
         if (ok) {
           post_actions[grow * A + aa] = sm.action;
@@ -772,7 +772,7 @@ __device__ __forceinline__ void mlp_backward_body(const MlpBwdArgs& a, const int
             const float dsigma = du * hb_ep[u] - a.hb_alpha / hb_sg[u];
             const float pre = hb_pre[u];
             const float raw = softplus_f(pre);
-            const bool inside = raw >= 1e-4f && raw <= 1.0f;
+            const bool inside = raw >= a.hb_scale_lo && raw <= a.hb_scale_hi;
             dloc = du;
             dspre = inside ? dsigma / (1.f + expf(-pre)) : 0.f;
           }

@@ -601,7 +601,7 @@ __device__ __forceinline__ void mlp_backward_body_img(const MlpBwdArgs& a, const
             const float dsigma = du * hb_ep[u] - a.hb_alpha / hb_sg[u];
             const float pre = hb_pre[u];
             const float raw = softplus_f(pre);
-            const bool inside = raw >= 1e-4f && raw <= 1.0f;
+            const bool inside = raw >= a.hb_scale_lo && raw <= a.hb_scale_hi;
             dloc = du;
             dspre = inside ? dsigma / (1.f + expf(-pre)) : 0.f;
           }

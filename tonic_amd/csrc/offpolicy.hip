@@ -33,6 +33,7 @@ constexpr int kTorsoMaxLayers = 4;
 struct ActorShape {                              // heads: 1 = deterministic (TD3), 2 = loc+scale (SAC)
   int O, H, A, heads; int H2 = 0; int act = ACT_RELU;
   int L = 2; int H3 = 0, H4 = 0;
+  float scale_lo = kScaleMin, scale_hi = kScaleMax;     // heads == 2: the bounds of the Gaussian head's scale
   __host__ __device__ int h2() const { return H2 > 0 ? H2 : H; }
   __host__ __device__ int width(int l) const { return l == 0 ? H : l == 1 ? h2() : l == 2 ? H3 : H4; }
   __host__ __device__ int last() const { return width(L - 1); }              // the heads' input width
@@ -60,11 +61,16 @@ struct CriticShape {
 // The C ABI passes ONE int32 `H`: the width of a plain torso (any width: bit 30 clear), tonic_mlp_hidden(H1, H2,
 // activation) = 1 << 30 | H1 | H2 << 12 | activation << 24 (two layers, widths below 4096; activation: GemmAct), or
 // for 1, 3 or 4 layers a descriptor that tonic_mlp_torso registered: 1 << 30 | 1 << 29 | its index in a small
-// process-wide table.  The codes are unpacked here, on the host; no kernel sees one.
+// process-wide table.  A descriptor also carries the bounds of the actor's Gaussian scale head; a torso of any depth
+// with bounds other than the defaults is registered (tonic_mlp_torso_head), and a critic ignores them.  The codes are
+// unpacked here, on the host; no kernel sees one.
 constexpr int32_t kHiddenPacked = 1 << 30;
 constexpr int32_t kTorsoRegistered = 1 << 29;
-constexpr int kTorsoTableSize = 64;
-struct Torso { int L, width[kTorsoMaxLayers], act; };   // L == 0: not a torso this library knows
+constexpr int kTorsoTableSize = 256;
+struct Torso {                                          // L == 0: not a torso this library knows
+  int L, width[kTorsoMaxLayers], act;
+  float scale_lo = kScaleMin, scale_hi = kScaleMax;
+};
 
 struct TorsoTable {
   std::mutex lock;
@@ -92,7 +98,17 @@ inline Torso unpack_torso(int32_t code) {
 inline ActorShape actor_shape(int O, int32_t code, int A, int heads) {
   const Torso t = unpack_torso(code);
   return ActorShape{O, t.width[0], A, heads, t.L >= 2 && t.width[1] != t.width[0] ? t.width[1] : 0, t.act, t.L,
-                    t.width[2], t.width[3]};
+                    t.width[2], t.width[3], t.scale_lo, t.scale_hi};
+}
+// The torso's own code: a registered two-layer descriptor (one that carries bounds) as the width or the packed code
+// of its torso, so that whatever serves that torso — the fused kernels and weight images of the plain width among
+// them — decides and sizes as it does there.  Every other code is its own.
+inline int32_t torso_code(int32_t code) {
+  if ((code & kHiddenPacked) == 0 || (code & kTorsoRegistered) == 0) return code;
+  const Torso t = unpack_torso(code);
+  if (t.L != 2) return code;
+  return t.width[0] == t.width[1] && t.act == ACT_RELU ? t.width[0]
+                                                       : kHiddenPacked | t.width[0] | (t.width[1] << 12) | (t.act << 24);
 }
 inline CriticShape critic_shape(int O, int A, int32_t code) {
   const Torso t = unpack_torso(code);
@@ -164,12 +180,12 @@ __global__ void encode_kernel(const float* obs, const float* act, const float* m
 }
 
 // SAC: u = loc + sigma * eps, a = tanh(u), logp = sum_a [N(u; loc, sigma) - log(1 - a^2 + 1e-6)]
-// with sigma = clamp(softplus(spre), 1e-4, 1) (actors.py:11-16,94-98).  A group of G = 2^k >= A
+// with sigma = clamp(softplus(spre), scale_lo, scale_hi) (actors.py:11-16,94-98).  A group of G = 2^k >= A
 // lanes (G <= 32; wider heads loop) owns one sample and folds the log-probability terms with a
 // fixed xor tree, so the dozen transcendental calls per action run in parallel, not in a loop.
 __global__ void sac_sample_kernel(const float* loc, const float* spre, const float* eps, int ld,
                                   float* act, float* logp, float* sigma_out, int B, int A,
-                                  int G) {
+                                  int G, float scale_lo, float scale_hi) {
   const int tid = blockIdx.x * blockDim.x + threadIdx.x;
   const int m = tid / G, lane_a = tid - m * G;
   const bool sample_ok = m < B;
@@ -177,7 +193,8 @@ __global__ void sac_sample_kernel(const float* loc, const float* spre, const flo
   for (int a = lane_a; a < A; a += G) {
     if (!sample_ok) break;
     const SquashedSample sm = squashed_sample(loc[(int64_t)m * ld + a], spre[(int64_t)m * ld + a],
-                                              eps ? eps[(int64_t)m * A + a] : 0.f, eps != nullptr);
+                                              eps ? eps[(int64_t)m * A + a] : 0.f, eps != nullptr, scale_lo,
+                                              scale_hi);
     lp += sm.logp_term;
     act[(int64_t)m * A + a] = sm.action;
     if (sigma_out) sigma_out[(int64_t)m * A + a] = sm.sigma;
@@ -343,19 +360,19 @@ __global__ void loss_stats_kernel(const float* loss_m, float* stats, int B) {
 
 // ---- MPO (agents/mpo.py; updaters/critics.py:238-282, updaters/actors.py:270-464)
 // GaussianPolicyHead (models/actors.py:69-98): loc = tanh(.) (applied by the forward), sigma =
-// clamp(softplus(spre), 1e-4, 1).
-__device__ __forceinline__ float gaussian_sigma(float spre) {
-  return fminf(fmaxf(softplus_f(spre), 1e-4f), 1.0f);
+// clamp(softplus(spre), scale_lo, scale_hi).
+__device__ __forceinline__ float gaussian_sigma(float spre, float scale_lo, float scale_hi) {
+  return fminf(fmaxf(softplus_f(spre), scale_lo), scale_hi);
 }
 
 // Normal.sample / rsample: a = loc + sigma * eps (eps == null: the greedy loc, mpo.py:82-85)
 __global__ void gaussian_sample_kernel(const float* loc, const float* spre, const float* eps,
-                                       int ld, float* act, int B, int A) {
+                                       int ld, float* act, int B, int A, float scale_lo, float scale_hi) {
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= B * A) return;
   const int m = idx / A, a = idx - m * A;
   const float l = loc[(int64_t)m * ld + a];
-  act[idx] = eps ? l + gaussian_sigma(spre[(int64_t)m * ld + a]) * eps[idx] : l;
+  act[idx] = eps ? l + gaussian_sigma(spre[(int64_t)m * ld + a], scale_lo, scale_hi) * eps[idx] : l;
 }
 
 // S samples per state, tiled like updaters.tile + merge_first_two_dims (row s * B + m):
@@ -363,7 +380,7 @@ __global__ void gaussian_sample_kernel(const float* loc, const float* spre, cons
 __global__ void gaussian_tile_kernel(const float* obs, const float* loc, const float* spre,
                                      const float* eps, int ldh, const float* mean,
                                      const float* std, float clip, float* act, float* X, int B,
-                                     int O, int A, int S, int ldx) {
+                                     int O, int A, int S, int ldx, float scale_lo, float scale_hi) {
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= (int64_t)S * B * (O + A)) return;
   const int64_t r = idx / (O + A);
@@ -373,7 +390,8 @@ __global__ void gaussian_tile_kernel(const float* obs, const float* loc, const f
     X[r * ldx + c] = __builtin_amdgcn_fmed3f((obs[(int64_t)m * O + c] - mean[c]) / std[c], -clip, clip);
   } else {
     const int a = c - O;
-    const float v = loc[(int64_t)m * ldh + a] + gaussian_sigma(spre[(int64_t)m * ldh + a]) * eps[r * A + a];
+    const float v = loc[(int64_t)m * ldh + a] +
+                    gaussian_sigma(spre[(int64_t)m * ldh + a], scale_lo, scale_hi) * eps[r * A + a];
     act[r * A + a] = v;
     X[r * ldx + c] = v;
   }
@@ -418,7 +436,7 @@ template <int SLOTS>
 __global__ __launch_bounds__(256) void mpo_state_kernel(
     const float* q, const float* act, const float* loc_t, const float* spre_t, const float* loc,
     const float* spre, int ldh, const float* duals, float floor, int penalize, int joint_kl, float* dloc,
-    float* dspre, float* part, float* klm, float* kls, int B, int A, int S) {
+    float* dspre, float* part, float* klm, float* kls, int B, int A, int S, float scale_lo, float scale_hi) {
   const int lane = threadIdx.x & 63;
   const int m = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (m >= B) return;
@@ -478,9 +496,9 @@ __global__ __launch_bounds__(256) void mpo_state_kernel(
   // lane = action dimension: the sums over the samples in sample order
   const bool live = lane < A;
   const int a = live ? lane : A - 1;
-  const float lt = loc_t[(int64_t)m * ldh + a], st = gaussian_sigma(spre_t[(int64_t)m * ldh + a]);
+  const float lt = loc_t[(int64_t)m * ldh + a], st = gaussian_sigma(spre_t[(int64_t)m * ldh + a], scale_lo, scale_hi);
   const float lo = loc[(int64_t)m * ldh + a], pre = spre[(int64_t)m * ldh + a];
-  const float sg = gaussian_sigma(pre);
+  const float sg = gaussian_sigma(pre, scale_lo, scale_hi);
   float pm = 0.f, ps = 0.f, g_loc = 0.f, g_sigma = 0.f;
 #pragma unroll
   for (int k = 0; k < SLOTS; ++k) {
@@ -509,7 +527,7 @@ __global__ __launch_bounds__(256) void mpo_state_kernel(
     g_loc += alpha_mean * (lo - lt) / (st * st);
     g_sigma += alpha_std * (1.f / sg - st * st / (sg * sg * sg));
     const float raw = softplus_f(pre);
-    const bool inside = raw >= 1e-4f && raw <= 1.0f;
+    const bool inside = raw >= scale_lo && raw <= scale_hi;
     dloc[(int64_t)m * ldh + a] = g_loc * (1.f - lo * lo);                  // tanh loc head
     dspre[(int64_t)m * ldh + a] = inside ? g_sigma / (1.f + expf(-pre)) : 0.f;
   }
@@ -618,7 +636,8 @@ __global__ void actor_head_backward_kernel(const float* dxa0, const float* dxa1,
                                            const float* act,
                                            const float* eps, const float* sigma,
                                            const float* spre, int ld, float alpha, int sac,
-                                           float* dloc, float* dspre, int B, int A) {
+                                           float* dloc, float* dspre, int B, int A, float scale_lo,
+                                           float scale_hi) {
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= B * A) return;
   const int m = idx / A, a = idx - m * A;
@@ -636,7 +655,7 @@ __global__ void actor_head_backward_kernel(const float* dxa0, const float* dxa1,
   const float dsigma = du * eps[idx] - alpha / sg;
   const float pre = spre[(int64_t)m * ld + a];
   const float raw = softplus_f(pre);
-  const bool inside = raw >= 1e-4f && raw <= 1.0f;
+  const bool inside = raw >= scale_lo && raw <= scale_hi;
   dloc[(int64_t)m * ld + a] = du;
   dspre[(int64_t)m * ld + a] = inside ? dsigma / (1.f + expf(-pre)) : 0.f;
 }
@@ -876,6 +895,7 @@ int actor_forward(const float* params, ActorShape s, const float* obs, int B, fl
       f.post = tail->post; f.post_eps = tail->eps; f.post_actions = tail->actions;
       f.post_sigma = tail->sigma; f.post_logp = tail->logp;
       f.noise_scale = tail->noise_scale; f.noise_clip = tail->noise_clip;
+      f.scale_lo = s.scale_lo; f.scale_hi = s.scale_hi;
       f.enc_obs = tail->enc_obs; f.enc_obs2 = tail->enc_obs2; f.enc_act2 = tail->enc_act2;
       f.enc_mean = tail->enc_mean; f.enc_std = tail->enc_std; f.enc_clip = tail->enc_clip;
       f.enc_out = tail->enc_out; f.enc_out2 = tail->enc_out2; f.enc_O = s.O; f.enc_ld = tail->enc_ld;
@@ -1151,6 +1171,7 @@ int64_t offpolicy_workspace_floats(int B, int O, int A, int H) {
 using namespace tonic;
 
 extern "C" int64_t tonic_offpolicy_workspace_bytes(int32_t B, int32_t O, int32_t A, int32_t H) {
+  H = torso_code(H);
   return (offpolicy_workspace_floats(B, O, A, H) + 64 * 30) * 4;
 }
 
@@ -1171,29 +1192,31 @@ extern "C" int32_t tonic_mlp_hidden(int32_t H1, int32_t H2, int32_t activation) 
   return kHiddenPacked | H1 | (H2 << 12) | (activation << 24);
 }
 
-// The `H` argument for MLP(sizes[0 .. layers), activation), 1 .. 4 layers: two layers give tonic_mlp_hidden's
-// code; 1, 3 or 4 a descriptor registered in a process-wide table (the same torso: the same code).  Negative:
-// not representable, or the table is full (tonic_last_error says which).
-extern "C" int32_t tonic_mlp_torso(int32_t layers, const int32_t* sizes, int32_t activation) {
+namespace {
+// MLP(sizes[0 .. layers), activation) as a descriptor, or false (tonic_last_error says why)
+bool torso_descriptor(int32_t layers, const int32_t* sizes, int32_t activation, Torso* t) {
   if (layers < 1 || layers > kTorsoMaxLayers || sizes == nullptr || activation < ACT_RELU || activation > ACT_ELU) {
     set_error("tonic_mlp_torso: %d layers, activation %d (1 .. %d layers; 1 ReLU, 2 Tanh, 3 ELU)", layers,
               activation, kTorsoMaxLayers);
-    return -1;
+    return false;
   }
-  Torso t{layers, {0, 0, 0, 0}, activation};
+  *t = Torso{layers, {0, 0, 0, 0}, activation};
   for (int l = 0; l < layers; ++l) {
     if (sizes[l] < 1 || sizes[l] > 4095) {
       set_error("tonic_mlp_torso: layer %d has %d units (1 .. 4095)", l, sizes[l]);
-      return -1;
+      return false;
     }
-    t.width[l] = sizes[l];
+    t->width[l] = sizes[l];
   }
-  if (layers == 2) return tonic_mlp_hidden(sizes[0], sizes[1], activation);
+  return true;
+}
+// the code of a descriptor in the process-wide table: the one it has, or a new one
+int32_t registered_code(const Torso& t) {
   TorsoTable& table = torso_table();
   std::lock_guard<std::mutex> guard(table.lock);
   for (int i = 0; i < table.count; ++i) {
     const Torso& e = table.entry[i];
-    bool same = e.L == t.L && e.act == t.act;
+    bool same = e.L == t.L && e.act == t.act && e.scale_lo == t.scale_lo && e.scale_hi == t.scale_hi;
     for (int l = 0; l < kTorsoMaxLayers; ++l) same = same && e.width[l] == t.width[l];
     if (same) return kHiddenPacked | kTorsoRegistered | i;
   }
@@ -1203,6 +1226,37 @@ extern "C" int32_t tonic_mlp_torso(int32_t layers, const int32_t* sizes, int32_t
   }
   table.entry[table.count] = t;
   return kHiddenPacked | kTorsoRegistered | table.count++;
+}
+}  // namespace
+
+// The `H` argument for MLP(sizes[0 .. layers), activation), 1 .. 4 layers: two layers give tonic_mlp_hidden's
+// code; 1, 3 or 4 a descriptor registered in a process-wide table (the same torso: the same code).  Negative:
+// not representable, or the table is full (tonic_last_error says which).
+extern "C" int32_t tonic_mlp_torso(int32_t layers, const int32_t* sizes, int32_t activation) {
+  Torso t;
+  if (!torso_descriptor(layers, sizes, activation, &t)) return -1;
+  if (layers == 2) return tonic_mlp_hidden(sizes[0], sizes[1], activation);
+  return registered_code(t);
+}
+
+// ... for an ACTOR whose Gaussian head clamps its scale to [scale_min, scale_max] (GaussianPolicyHead, models/
+// actors.py:69-98): the reference's defaults (1e-4, 1 as float32) give tonic_mlp_torso's code; other bounds register
+// torso + bounds — two-layer torsos too — and every entry that forms a Gaussian scale from the code's actor clamps to
+// them.  A critic ignores the bounds of the code it is given.  -1: the torso is not representable, the bounds are
+// not 0 < scale_min <= scale_max (finite, as float32), or the table is full (tonic_last_error says which).
+extern "C" int32_t tonic_mlp_torso_head(int32_t layers, const int32_t* sizes, int32_t activation, double scale_min,
+                                        double scale_max) {
+  const float lo = (float)scale_min, hi = (float)scale_max;              // what the kernels see
+  if (!(lo > 0.f && lo <= hi && hi - hi == 0.f)) {
+    set_error("tonic_mlp_torso_head: scale_min = %g, scale_max = %g (0 < scale_min <= scale_max, both finite)",
+              scale_min, scale_max);
+    return -1;
+  }
+  if (lo == kScaleMin && hi == kScaleMax) return tonic_mlp_torso(layers, sizes, activation);
+  Torso t;
+  if (!torso_descriptor(layers, sizes, activation, &t)) return -1;
+  t.scale_lo = lo; t.scale_hi = hi;
+  return registered_code(t);
 }
 
 // Policy forward for acting / evaluation.  kind: 0 = deterministic tanh head (TD3,
@@ -1221,12 +1275,12 @@ extern "C" int tonic_policy_forward(const float* d_actor_params, const float* d_
   Workspace ws{static_cast<char*>(d_workspace), 0, workspace_bytes};
   float* h1 = ws.take((int64_t)hidden_layers(H) * Bp * HP); float* h2 = h1 + (int64_t)Bp * HP;
   float* head0 = ws.take((int64_t)Bp * ldh); float* head1 = ws.take((int64_t)Bp * ldh);
-  const ActorShape s = actor_shape(O, H, A, kind == 0 ? 1 : 2);
+  const ActorShape s = actor_shape(O, H, A, kind == 0 ? 1 : 2);     // (with the scale's bounds of the code)
   const int threads = 256;
   if (kind == 2) {       // Gaussian head with a tanh loc (MPO, mpo.py:77-85): a = loc + sigma * eps
     TRY(actor_forward(d_actor_params, s, d_observations, B, h1, h2, head0, head1, ldh, true, st));
     hipLaunchKernelGGL(gaussian_sample_kernel, dim3((B * A + threads - 1) / threads), dim3(threads),
-                       0, st, head0, head1, d_eps, ldh, d_actions, B, A);
+                       0, st, head0, head1, d_eps, ldh, d_actions, B, A, s.scale_lo, s.scale_hi);
     TONIC_CHECK_LAUNCH("tonic_policy_forward");
     return TONIC_OK;
   }
@@ -1243,7 +1297,7 @@ extern "C" int tonic_policy_forward(const float* d_actor_params, const float* d_
     hipLaunchKernelGGL(sac_sample_kernel,
                        dim3((B * sample_group(A) + threads - 1) / threads), dim3(threads), 0, st,
                        head0, head1, d_eps, ldh, d_actions, (float*)nullptr, (float*)nullptr, B, A,
-                       sample_group(A));
+                       sample_group(A), s.scale_lo, s.scale_hi);
   }
   TONIC_CHECK_LAUNCH("tonic_policy_forward");
   return TONIC_OK;
@@ -1259,6 +1313,7 @@ extern "C" int tonic_policy_forward(const float* d_actor_params, const float* d_
 // (the block's own rows are overwritten by then).  replaces: tonic/torch/agents/ddpg.py:45-52,
 // sac.py:40-51 (`_policy` / `_greedy_actions`) for observations that live in a collector block.
 extern "C" int64_t tonic_mlp_actor_image_bytes(int32_t O, int32_t H, int32_t A, int32_t heads) {
+  H = torso_code(H);
   if (!hidden_plain(H) || heads < 1 || heads > 2 || !images_serve(O, A, H) || !mlp_forward_supported(H, A, heads))
     return 0;
   return round_up(actor_images(O, H, A, heads).bytes, 256);
@@ -1276,6 +1331,7 @@ extern "C" int tonic_collector_q_act(tonic_collector_t* collector, const float* 
   int64_t W; int O, A;
   collector_shape(collector, &W, &O, &A);      // (shapes first: nothing is opened before the arguments are known good)
   const ActorShape s = actor_shape(O, H, A, kind == 0 ? 1 : 2);
+  H = torso_code(H);                           // (the bounds are in s; what follows sizes by the torso)
   TONIC_REQUIRE(tonic_mlp_actor_image_bytes(O, H, A, s.heads) > 0 && mlp_policy_tail_supported(s.H, s.A) &&
                     g_policy_tail != 0 && mlp_image_pass_supported(O, s.H),
                 TONIC_ERR_UNSUPPORTED_SHAPE, "tonic_collector_q_act: O=%d H=%d A=%d outside the fused forward", O, H, A);
@@ -1401,6 +1457,8 @@ extern "C" int tonic_twin_q_grad_ranged(int32_t kind, const float* d_policy_para
   TONIC_REQUIRE(workspace_bytes >= tonic_offpolicy_workspace_bytes(B, O, A, H),
                 TONIC_ERR_WORKSPACE, "tonic_twin_q_grad: workspace too small");
   hipStream_t st = as_stream(stream);
+  const ActorShape as = actor_shape(O, H, A, kind == 1 ? 2 : 1);
+  H = torso_code(H);                           // (the bounds are in `as`; what follows sizes by the torso)
   const int Bp = pad16(B), ldx = pitch16(O + A), ldh = pad16(A), threads = 256, HP = hidden_pitch(H);
   const CriticShape cs = critic_shape(O, A, H);
   const int64_t Pc = critic_count(cs);
@@ -1421,7 +1479,6 @@ extern "C" int tonic_twin_q_grad_ranged(int32_t kind, const float* d_policy_para
   float* dh2 = ws.take(layers * 2 * hs); float* dh1 = dh2 + 2 * hs;
 
   // ---- targets (no grad)
-  const ActorShape as = actor_shape(O, H, A, kind == 1 ? 2 : 1);
   // the fused passes' weight images (mlpimg.h), formed from the float32 parameters by THIS call: the policy's,
   // the target critics' and the critics' — the same conversion as the fused iteration's, so the same bits
   ImageSet im = take_images(ws, O, A, H, as.heads, hidden_plain(H) && images_serve(O, A, H) &&
@@ -1458,7 +1515,7 @@ extern "C" int tonic_twin_q_grad_ranged(int32_t kind, const float* d_policy_para
     hipLaunchKernelGGL(sac_sample_kernel,
                        dim3((B * sample_group(A) + threads - 1) / threads), dim3(threads), 0, st,
                        head0, head1, d_eps, ldh, next_act, logp, (float*)nullptr, B, A,
-                       sample_group(A));
+                       sample_group(A), as.scale_lo, as.scale_hi);
   }
   // ---- inputs of the targets (s', a') and of the online critics (s, a): one launch each for
   //      the encoding and for the four-network forward
@@ -1503,6 +1560,7 @@ MlpBwdArgs actor_chain_args(const float* params, ActorShape as, int B, const flo
     b.hb_dxa0 = head_fold->hb_dxa0; b.hb_dxa1 = head_fold->hb_dxa1; b.hb_ldxa = head_fold->hb_ldxa;
     b.hb_act = head_fold->hb_act; b.hb_eps = head_fold->hb_eps; b.hb_sigma = head_fold->hb_sigma;
     b.hb_spre = head_fold->hb_spre; b.hb_sac = head_fold->hb_sac; b.hb_alpha = head_fold->hb_alpha;
+    b.hb_scale_lo = as.scale_lo; b.hb_scale_hi = as.scale_hi;
   }
   if (img != nullptr && img->block != nullptr && b.xa_count == 0)     // (no image of W1^T's columns for actors)
     b.img = BwdImages{img->block, img->v.t2, {img->v.th[0], img->v.th[as.heads - 1]}, ImgView{}, 0};
@@ -1632,18 +1690,21 @@ int64_t q_iteration_floats(int B, int O, int A, int H) {
 }  // namespace
 
 extern "C" int64_t tonic_q_iteration_workspace_bytes(int32_t B, int32_t O, int32_t A, int32_t H) {
+  H = torso_code(H);
   return (q_iteration_floats(B, O, A, H) + 64 * 64) * 4;       // (+ the 256-byte rounding of every take)
 }
 
 extern "C" int tonic_q_iteration_ahead_supported(int32_t B, int32_t O, int32_t H, int32_t A, int32_t nets,
                                                  int32_t passes) {
   if (B <= 0 || nets < 1 || nets > 2 || passes < 1 || passes > 2) return 0;
+  H = torso_code(H);
   if (g_q_chain.load() == 0 || !hidden_plain(H) || !images_serve(O, A, H) || !mlp_image_pass_supported(O, H)) return 0;
   const int tiles = (B + 15) / 16;
   return tiles * (2 * nets + passes) + 1 <= 256;      // one workgroup per compute unit: all of them at once
 }
 
 extern "C" int tonic_q_iteration_supported(int32_t O, int32_t H, int32_t A, int32_t heads) {
+  H = torso_code(H);
   return hidden_plain(H) && mlp_forward_supported(H, A, heads) && mlp_policy_tail_supported(H, A) &&
          mlp_forward_supported(H, 1, 1) && mlp_backward_supported(H, 1, 0, A) &&
          mlp_backward_supported(H, A, heads, 0) && O > 0 ? 1 : 0;
@@ -1653,7 +1714,7 @@ extern "C" int tonic_q_iteration(const tonic_q_iteration_t* it, void* stream) {
   TONIC_REQUIRE(it != nullptr, TONIC_ERR_INVALID_ARGUMENT, "tonic_q_iteration: null arguments");
   const tonic_q_iteration_t& a = *it;
   TRY(tonic_critic_loss_check(&a.critic_loss));
-  const int kind = a.kind, B = a.B, O = a.O, H = a.H, A = a.A;
+  const int kind = a.kind, B = a.B, O = a.O, H = torso_code(a.H), A = a.A;     // (a.H: also the scale's bounds)
   const bool due = a.actor_due != 0;
   const int phase = a.phase;                 // 0 whole iteration | 1 critic half | 2 actor half (sums only)
   TONIC_REQUIRE(phase >= 0 && phase <= 2 && (phase != 2 || due), TONIC_ERR_INVALID_ARGUMENT,
@@ -1663,7 +1724,7 @@ extern "C" int tonic_q_iteration(const tonic_q_iteration_t* it, void* stream) {
                 TONIC_ERR_INVALID_ARGUMENT, "tonic_q_iteration: stage %d, slot %d (phase %d)", stage, slot, phase);
   const tonic_q_iteration_t* next = a.ahead;           // the iteration whose policy passes ride in this critic step
   TONIC_REQUIRE(next == nullptr ||
-                    (phase == 0 && !due && next->kind == kind && next->B == B && next->O == O && next->H == H &&
+                    (phase == 0 && !due && next->kind == kind && next->B == B && next->O == O && next->H == a.H &&
                      next->A == A && next->slot == (slot ^ 1) && next->d_workspace == a.d_workspace &&
                      next->d_actor == a.d_actor && next->d_target_actor == a.d_target_actor &&
                      next->d_next_observations && next->d_observations && next->d_actions &&
@@ -1687,7 +1748,7 @@ extern "C" int tonic_q_iteration(const tonic_q_iteration_t* it, void* stream) {
   const int Bp = pad16(B), ldx = pitch16(O + A), ldh = pad16(A), HP = weight_ld(H);
   const int nets = kind == 2 ? 1 : 2;                  // critics
   const CriticShape cs{O, A, H};
-  const ActorShape as{O, H, A, heads};
+  const ActorShape as = actor_shape(O, a.H, A, heads);
   const int64_t Pc = critic_count(cs), Pa = actor_count(as), hs = (int64_t)Bp * HP;
   Workspace ws{static_cast<char*>(a.d_workspace), 0, a.workspace_bytes};
   // (one failure word per set: the passes that run ahead clear THEIR iteration's word while this one's launches may set theirs)
@@ -1763,6 +1824,7 @@ extern "C" int tonic_q_iteration(const tonic_q_iteration_t* it, void* stream) {
     f.post_eps = it.d_eps_critic; f.post_actions = t.next_act;
     f.post_logp = kind == 1 ? t.logp_next : nullptr;
     f.noise_scale = (float)it.noise_scale; f.noise_clip = (float)it.noise_clip;
+    f.scale_lo = as.scale_lo; f.scale_hi = as.scale_hi;
     f.enc_obs = it.d_next_observations; f.enc_obs2 = it.d_observations; f.enc_act2 = it.d_actions;
     f.enc_mean = it.d_norm_mean; f.enc_std = it.d_norm_std; f.enc_clip = clip_bound(it.norm_clip);
     f.enc_out = t.X; f.enc_out2 = t.X2; f.enc_O = O; f.enc_ld = ldx;
@@ -2024,7 +2086,7 @@ extern "C" int tonic_distributional_actor_grad(
   hipLaunchKernelGGL(actor_head_backward_kernel, dim3((B * A + threads - 1) / threads),
                      dim3(threads), 0, st, w.dxa, (const float*)nullptr, ldh, w.act,
                      (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, ldh, 0.f,
-                     0, w.dloc, (float*)nullptr, B, A);
+                     0, w.dloc, (float*)nullptr, B, A, as.scale_lo, as.scale_hi);
   TRY(actor_shaped_backward(d_actor_params, as, d_observations, O, B, w.a_h1, w.a_h2, w.dloc,
                             nullptr, ldh, w.da_h2, w.da_h1, d_grad_sums, nullptr, 0, 0, st));
   TONIC_CHECK_LAUNCH("tonic_distributional_actor_grad");
@@ -2071,7 +2133,7 @@ int mpo_sampled_values(const float* d_target_actor, const float* d_target_critic
   const int64_t items = (int64_t)S * B * (O + A);
   hipLaunchKernelGGL(gaussian_tile_kernel, dim3((unsigned)((items + threads - 1) / threads)),
                      dim3(threads), 0, st, d_obs, w.loc_t, w.spre_t, d_eps, ldh, d_norm_mean,
-                     d_norm_std, clip_bound(norm_clip), w.act, w.X, B, O, A, S, ldx);
+                     d_norm_std, clip_bound(norm_clip), w.act, w.X, B, O, A, S, ldx, as.scale_lo, as.scale_hi);
   return critics_forward(d_target_critic, critic_shape(O, A, H), 1, w.X, ldx, S * B, pad16(S * B),
                          w.t_h1, w.t_h2, w.tq, st);
 }
@@ -2138,10 +2200,10 @@ static_assert(kMpoMaxSamples == 256, "the messages of the MPO entries name the b
 void launch_mpo_state(int slots, dim3 grid, hipStream_t st, const float* q, const float* act, const float* loc_t,
                       const float* spre_t, const float* loc, const float* spre, int ldh, const float* duals,
                       float floor, int penalize, int joint_kl, float* dloc, float* dspre, float* part, float* klm,
-                      float* kls, int B, int A, int S) {
+                      float* kls, int B, int A, int S, float scale_lo, float scale_hi) {
 #define TONIC_MPO_STATE(SLOTS)                                                                                  \
   hipLaunchKernelGGL(mpo_state_kernel<SLOTS>, grid, dim3(256), 0, st, q, act, loc_t, spre_t, loc, spre, ldh,   \
-                     duals, floor, penalize, joint_kl, dloc, dspre, part, klm, kls, B, A, S)
+                     duals, floor, penalize, joint_kl, dloc, dspre, part, klm, kls, B, A, S, scale_lo, scale_hi)
   switch (slots) {
     case 1: TONIC_MPO_STATE(1); break;
     case 2: TONIC_MPO_STATE(2); break;
@@ -2177,7 +2239,7 @@ int mpo_actor_grad(
                     st));
   launch_mpo_state((S + 63) / 64, dim3((B + 3) / 4), st, w.tq, w.act, w.loc_t, w.spre_t, w.loc, w.spre, ldh, d_duals,
                    (float)min_log_dual, action_penalization, joint_kl, w.dloc, w.dspre, w.part, w.klm, w.kls, B, A,
-                   S);
+                   S, as.scale_lo, as.scale_hi);
   hipLaunchKernelGGL(mpo_dual_kernel, dim3(1), dim3(1024), 0, st, w.part, w.klm, w.kls, d_duals,
                      (float)min_log_dual, action_penalization, joint_kl, (float)epsilon, (float)epsilon_penalty,
                      (float)epsilon_mean, (float)epsilon_std, d_dual_grads, d_stats,
@@ -2304,10 +2366,11 @@ extern "C" int tonic_actor_q_grad_ranged(int32_t kind, const float* d_actor_para
   TONIC_REQUIRE(workspace_bytes >= tonic_offpolicy_workspace_bytes(B, O, A, H),
                 TONIC_ERR_WORKSPACE, "tonic_actor_q_grad: workspace too small");
   hipStream_t st = as_stream(stream);
+  const ActorShape as = actor_shape(O, H, A, kind == 0 ? 1 : 2);
+  H = torso_code(H);                           // (the bounds are in `as`; what follows sizes by the torso)
   const int Bp = pad16(B), ldx = pitch16(O + A), ldh = pad16(A), threads = 256, HP = hidden_pitch(H);
   const int nets = kind == 0 ? 1 : 2;
   const CriticShape cs = critic_shape(O, A, H);
-  const ActorShape as = actor_shape(O, H, A, kind == 0 ? 1 : 2);
   const int64_t Pa = actor_count(as);
   Workspace ws{static_cast<char*>(d_workspace), 0, workspace_bytes};
   const int64_t hs = (int64_t)Bp * HP, layers = hidden_layers(H);     // (layers: see layer_at)
@@ -2351,7 +2414,7 @@ extern "C" int tonic_actor_q_grad_ranged(int32_t kind, const float* d_actor_para
     hipLaunchKernelGGL(sac_sample_kernel,
                        dim3((B * sample_group(A) + threads - 1) / threads), dim3(threads), 0, st,
                        head0, head1, d_eps, ldh, act, logp, sigma, B, A,
-                       sample_group(A));
+                       sample_group(A), as.scale_lo, as.scale_hi);
   }
   if (!tail_done) {
     hipLaunchKernelGGL(encode_kernel, dim3((B * (O + A) + threads - 1) / threads), dim3(threads),
@@ -2367,7 +2430,7 @@ extern "C" int tonic_actor_q_grad_ranged(int32_t kind, const float* d_actor_para
   hipLaunchKernelGGL(actor_head_backward_kernel, dim3((B * A + threads - 1) / threads),
                      dim3(threads), 0, st, dxa, nets == 2 ? dxa + (int64_t)Bp * ldh : (float*)nullptr,
                      ldh, act, d_eps, sigma, head1, ldh,
-                     (float)entropy_coeff, kind == 1 ? 1 : 0, dloc, dspre, B, A);
+                     (float)entropy_coeff, kind == 1 ? 1 : 0, dloc, dspre, B, A, as.scale_lo, as.scale_hi);
   TRY(actor_shaped_backward(d_actor_params, as, d_observations, O, B, a_h1, a_h2, dloc,
                             kind == 1 ? dspre : nullptr, ldh, da_h2, da_h1, d_grad_sums, nullptr,
                             0, 0, st, nullptr, nullptr, im.on ? &im.actor : nullptr));

@@ -361,6 +361,10 @@ class A2C(Agent):
         self.replay.initialize(seed, device=self.device)
         self.actor_updater.initialize(self.model)
         self.critic_updater.initialize(self.model)
+        # acting (and the kernel updates) run the kernels' head: one they do not compute is refused by name.  A torso on
+        # stock torch operators acts and learns through the module's own forward (`_act`, `_stock_grad`): any head
+        if not getattr(self.actor_updater, 'stock', False):
+            updaters.policy_head_rule(self.model.actor.head, 'on_policy')
         self.observation_size = observation_space.shape[0]
         self.action_size = action_space.shape[0]
         self._replicate([self.model.flat_actor.flat, self.model.flat_critic.flat], own_noise=True)
@@ -1700,6 +1704,7 @@ class DDPG(Agent):
                           float(getattr(updater, 'entropy_coeff', 0.0)),
                           float(getattr(updater, 'gradient_clip', 0.0) or 0.0),
                           int(getattr(updater, 'num_samples', 0)),
+                          tuple(float(v) for v in getattr(updater, 'scale_bounds', None) or ()),
                           (noise.scale, noise.clip) if noise is not None else None))
         norm = self.model.observation_normalizer
         # (the Return normaliser's _low / _high are read through their pointers by the captured launches)

@@ -984,8 +984,78 @@ def _torso_width(torso, generic=False):
                               f'stock torch operators), got {sizes} / {torso.activation}')
 
 
+_DEFAULT_SCALE_BOUNDS = (np.float32(1e-4), np.float32(1.))        # actors.py:39-40, 71-72, as the kernels hold them
+
+# what the kernels of each family compute at the policy's head (the initialisers and log_scale_init stay free)
+_HEAD_RULES = {
+    'sac': ('GaussianPolicyHead', dict(loc_activation='Identity', scale_activation='Softplus',
+                                       distribution='SquashedMultivariateNormalDiag'), 'any'),
+    'mpo': ('GaussianPolicyHead', dict(loc_activation='Tanh', scale_activation='Softplus', distribution='Normal'),
+            'any'),
+    'deterministic': ('DeterministicPolicyHead', dict(activation='Tanh'), None),
+    'on_policy': ('DetachedScaleGaussianPolicyHead', dict(loc_activation='Tanh', distribution='Normal'), 'default'),
+}
+
+
+def policy_head_rule(head, family):
+    """What the HIP kernels of `family` ('sac', 'mpo', 'deterministic', 'on_policy') compute for this policy head, or
+    NotImplementedError naming the argument they do not serve (no device needed).  Served:
+      sac            GaussianPolicyHead(loc_activation=Identity, scale_activation=Softplus,
+                     distribution=SquashedMultivariateNormalDiag), any 0 < scale_min <= scale_max
+      mpo            GaussianPolicyHead(loc_activation=Tanh, scale_activation=Softplus, distribution=Normal), any bounds
+      deterministic  DeterministicPolicyHead(activation=Tanh)                                  (DDPG, TD3, D4PG)
+      on_policy      DetachedScaleGaussianPolicyHead(loc_activation=Tanh, distribution=Normal) with the default
+                     scale_min=1e-4, scale_max=1: the PPO / A2C / TRPO kernels hold those bounds
+    Returns the scale's (scale_min, scale_max) as the float32 the kernels clamp to; None for a deterministic head."""
+    from tonic_amd.torch import models
+    class_name, arguments, bounds = _HEAD_RULES[family]
+    served = f'{class_name}(' + ', '.join(f'{k}={v}' for k, v in arguments.items()) + ')' + \
+        {None: '', 'any': ' with any 0 < scale_min <= scale_max',
+         'default': ' with the default scale_min=1e-4, scale_max=1'}[bounds]
+
+    def refuse(argument, value):
+        raise NotImplementedError(f'the {family} kernels serve {served}; got {argument}={value!r}')
+
+    if type(head) is not getattr(models, class_name):       # (a subclass may compute anything in its forward)
+        refuse('head', type(head).__name__)
+    wanted = dict(Identity=torch.nn.Identity, Softplus=torch.nn.Softplus, Tanh=torch.nn.Tanh,
+                  Normal=torch.distributions.normal.Normal,
+                  SquashedMultivariateNormalDiag=models.SquashedMultivariateNormalDiag)
+    for argument, name in arguments.items():
+        if getattr(head, argument) is not wanted[name]:
+            refuse(argument, getattr(head, argument))
+    if bounds is None:
+        return None
+    low, high = np.float32(head.scale_min), np.float32(head.scale_max)
+    if not (0 < low and np.isfinite(low)):
+        refuse('scale_min', head.scale_min)
+    if not (low <= high and np.isfinite(high)):
+        refuse('scale_max', head.scale_max)
+    if bounds == 'default' and (low, high) != _DEFAULT_SCALE_BOUNDS:
+        refuse('scale_min' if low != _DEFAULT_SCALE_BOUNDS[0] else 'scale_max',
+               head.scale_min if low != _DEFAULT_SCALE_BOUNDS[0] else head.scale_max)
+    return low, high
+
+
+def _actor_code(torso, bounds, generic=False):
+    """The `H` argument wherever an entry runs the actor: the torso's own code (`_torso_width`), or — a Gaussian head
+    with bounds other than the defaults — the code tonic_mlp_torso_head registers for torso + bounds."""
+    code = _torso_width(torso, generic)
+    if bounds is None or tuple(bounds) == _DEFAULT_SCALE_BOUNDS:
+        return code
+    sizes = tuple(int(v) for v in torso.sizes)
+    lib = _lib.load()
+    code = lib.tonic_mlp_torso_head(len(sizes), (ctypes.c_int32 * len(sizes))(*sizes),
+                                    _Q_ACTIVATIONS[torso.activation], float(bounds[0]), float(bounds[1]))
+    if code <= 0:
+        raise NotImplementedError(lib.tonic_last_error().decode())
+    return code
+
+
 class _QUpdater(_FlatUpdater):
     """Shared plumbing of the four off-policy updaters: shapes, normaliser tensors, workspace."""
+
+    head_family = 'deterministic'        # `policy_head_rule`: what this updater's entries compute at the policy's head
 
     # updaters whose stock-torch form exists (`_stock_enqueue`): the others keep raising for torsos
     # outside the fused kernels
@@ -1004,6 +1074,12 @@ class _QUpdater(_FlatUpdater):
                 raise
             self.hidden = None           # any MLP(sizes, activation): stock torch operators
         head = model.actor.head
+        # the torso's own code is the critic's; `hidden`, what every entry is given (each runs the actor), also carries
+        # the bounds of a Gaussian head's scale — a critic ignores them
+        self.torso_code, self.scale_bounds = self.hidden, None
+        if self.hidden is not None:
+            self.scale_bounds = policy_head_rule(head, self.head_family)
+            self.hidden = _actor_code(model.actor.torso, self.scale_bounds, self.stock_capable)
         self.sac = hasattr(head, 'scale_layer')
         layer = head.loc_layer if self.sac else head.action_layer
         self.action_size = layer[0].out_features
@@ -1246,6 +1322,7 @@ class TwinCriticDeterministicQLearning(_TwinCriticQLearning):
 class TwinCriticSoftQLearning(_TwinCriticQLearning):
     """critics.py:185-235 (SAC): online-actor sample and entropy bonus in the target."""
     kind, default_lr = 1, 3e-4
+    head_family = 'sac'
 
     def __init__(self, loss=None, optimizer=None, entropy_coeff=0.2, gradient_clip=0):
         self.loss = loss
@@ -1298,6 +1375,7 @@ class ExpectedSARSA(_TwinCriticQLearning):
     `num_samples` actions drawn from the target actor (tonic_expected_sarsa_grad)."""
     default_lr = 3e-4
     stock_capable = False
+    head_family = 'mpo'
 
     def __init__(self, num_samples=20, loss=None, optimizer=None, gradient_clip=0):
         _check_num_samples('ExpectedSARSA', num_samples)
@@ -1465,6 +1543,7 @@ class MaximumAPosterioriPolicyOptimization(_ActorQGradient):
     dual optimizer is Adam(lr=1e-2) unless `actor_optimizer` is given)."""
     default_lr = 3e-4
     stock_capable = False
+    head_family = 'mpo'
 
     def __init__(self, num_samples=20, epsilon=1e-1, epsilon_penalty=1e-3, epsilon_mean=1e-3,
                  epsilon_std=1e-6, initial_log_temperature=1., initial_log_alpha_mean=1.,
@@ -1589,6 +1668,7 @@ class MaximumAPosterioriPolicyOptimization(_ActorQGradient):
 class TwinCriticSoftDeterministicPolicyGradient(_ActorQGradient):
     """actors.py:226-267 (SAC)."""
     kind, default_lr = 1, 3e-4
+    head_family = 'sac'
 
     def __init__(self, optimizer=None, entropy_coeff=0.2, gradient_clip=0):
         self.optimizer = optimizer
