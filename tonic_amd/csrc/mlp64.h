@@ -84,6 +84,8 @@ struct Torso {
   static Torso standard() { return Torso{2, {64, 64, 0, 0}, 1}; }
 };
 bool torso_supported(const Torso& t);
+// an entry's (layers, sizes, activation) arguments as a Torso, or TONIC_ERR_UNSUPPORTED_SHAPE; `what`: the entry
+int parse_torso(const char* what, int32_t layers, const int32_t* sizes, int32_t activation, Torso& t);
 int64_t torso_param_count(int O, int A, bool actor, const Torso& t);
 bool wide_shape(int O, int A, bool actor);
 bool wide_supported(int O, int A, bool actor);

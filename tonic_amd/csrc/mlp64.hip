@@ -28,6 +28,7 @@
 #include <type_traits>
 
 #include <atomic>
+#include <optional>
 #include <unordered_set>
 
 #include "mlp64.h"
@@ -976,58 +977,78 @@ extern "C" int64_t tonic_ppo_workspace_bytes(int64_t n, int32_t O, int32_t A, in
   return tonic_mlp64_grad_workspace_bytes(n, P);
 }
 
-extern "C" int tonic_ppo_act_wide(const float* d_actor_params, const float* d_observations,
-                                  const float* d_eps, float* d_actions, float* d_log_probs,
-                                  int64_t n, int32_t O, int32_t A, void* d_workspace,
-                                  int64_t workspace_bytes, void* stream) {
-  if (!wide_shape(O, A, true))
-    return tonic_ppo_act(d_actor_params, d_observations, d_eps, d_actions, d_log_probs, n, O, A,
-                         stream);
-  TONIC_REQUIRE(d_actor_params && d_observations && d_actions && n >= 0,
-                TONIC_ERR_INVALID_ARGUMENT, "tonic_ppo_act_wide: bad argument");
-  if (int rc = check_wide(O, A, true)) return rc;
-  if (n == 0) return TONIC_OK;
-  MlpArgs a{};
-  a.params = d_actor_params; a.obs = d_observations; a.eps = d_eps;
-  a.out0 = d_actions; a.out1 = d_log_probs; a.n = n; a.O = O; a.A = A;
-  return wide_act(a, d_workspace, workspace_bytes, as_stream(stream));
+// ---- the on-policy operations: act, value forward, actor grad, value regression grad
+// Each is ONE body (serve_*) that states its checks in order and picks its route once; the entries — plain,
+// *_wide, *_torso, *_ranged — are forwarding statements at the end of this file.  A new per-operation option
+// is an argument of the body and a field of the builder below it; the entries pass it through.
+//
+//   route            taken by                                                        kernels
+//   layer by layer   every *_torso entry (even (64, 64) Tanh), and O > 32 / A > 8    mlpwide.hip
+//                    on an entry that takes a workspace
+//   values16         value forward from kValues16MinRows rows (grad_variant >= 1)    mlp64x16.hip
+//   fused            everything else: O <= 32, A <= 8 on the default torso           here / mlp64x16.hip
+struct TorsoSpec {                 // the first three arguments of a *_torso entry
+  int32_t layers;
+  const int32_t* sizes;
+  int32_t activation;
+};
+
+struct Route {
+  bool layered;
+  Torso torso;
+};
+
+// After an entry's pointer checks: the torso's requirements, then those of the route's kernels.  `has_workspace`:
+// an entry without one serves the fused shapes only.
+static int choose_route(const char* what, const std::optional<TorsoSpec>& spec, bool has_workspace, int32_t O,
+                        int32_t A, bool actor, Route& r) {
+  r.torso = Torso::standard();
+  if (spec)
+    if (int rc = parse_torso(what, spec->layers, spec->sizes, spec->activation, r.torso)) return rc;
+  r.layered = spec || (has_workspace && wide_shape(O, A, actor));
+  return r.layered ? check_wide(O, A, actor) : check_shape(O, A, actor);
 }
 
-extern "C" int tonic_value_forward_wide(const float* d_critic_params, const float* d_norm_mean,
-                                        const float* d_norm_std, double norm_clip,
-                                        const float* d_observations, float* d_values, int64_t n,
-                                        int32_t O, void* d_workspace, int64_t workspace_bytes,
-                                        void* stream) {
-  if (!wide_shape(O, 1, false))
-    return tonic_value_forward(d_critic_params, d_norm_mean, d_norm_std, norm_clip,
-                               d_observations, d_values, n, O, stream);
-  TONIC_REQUIRE(d_critic_params && d_norm_mean && d_norm_std && d_observations && d_values &&
-                    n >= 0,
-                TONIC_ERR_INVALID_ARGUMENT, "tonic_value_forward_wide: bad argument");
-  if (int rc = check_wide(O, 1, false)) return rc;
-  if (n == 0) return TONIC_OK;
+static int fwd_blocks(int64_t n) {
+  const int64_t tiles = (n + 31) / 32;
+  const int64_t blocks = (tiles + kFwdWaves - 1) / kFwdWaves;
+  return blocks > 1024 ? 1024 : (int)blocks;
+}
+
+static MlpArgs actor_args(const float* d_actor_params, const float* d_observations, int64_t n, int32_t O,
+                          int32_t A) {
+  MlpArgs a{};
+  a.params = d_actor_params; a.obs = d_observations; a.n = n; a.O = O; a.A = A;
+  return a;
+}
+
+// (both range pointers NULL: the plain head)
+static MlpArgs value_args(const float* d_critic_params, const float* d_norm_mean, const float* d_norm_std,
+                          double norm_clip, const float* d_observations, int64_t n, int32_t O,
+                          const float* d_value_low, const float* d_value_high) {
   MlpArgs a{};
   a.params = d_critic_params; a.obs = d_observations; a.norm_mean = d_norm_mean;
   a.norm_std = d_norm_std; a.norm_clip = clip_bound(norm_clip);
-  a.out0 = d_values; a.n = n; a.O = O; a.A = 1;
-  return wide_value(a, d_workspace, workspace_bytes, as_stream(stream));
+  a.n = n; a.O = O; a.A = 1;
+  a.set_value_range(d_value_low, d_value_high);
+  return a;
 }
 
-extern "C" int tonic_ppo_act(const float* d_actor_params, const float* d_observations,
-                             const float* d_eps, float* d_actions, float* d_log_probs,
-                             int64_t n, int32_t O, int32_t A, void* stream) {
+static int serve_act(const char* what, const std::optional<TorsoSpec>& spec, bool has_workspace,
+                     const float* d_actor_params, const float* d_observations, const float* d_eps,
+                     float* d_actions, float* d_log_probs, int64_t n, int32_t O, int32_t A,
+                     void* d_workspace, int64_t workspace_bytes, void* stream) {
   TONIC_REQUIRE(d_actor_params && d_observations && d_actions && n >= 0,
-                TONIC_ERR_INVALID_ARGUMENT, "tonic_ppo_act: null pointer or negative n");
-  if (int rc = check_shape(O, A, true)) return rc;
+                TONIC_ERR_INVALID_ARGUMENT, "%s: null pointer or negative n", what);
+  Route r;
+  if (int rc = choose_route(what, spec, has_workspace, O, A, true, r)) return rc;
   if (n == 0) return TONIC_OK;
-  MlpArgs a{};
-  a.params = d_actor_params; a.obs = d_observations; a.eps = d_eps;
-  a.out0 = d_actions; a.out1 = d_log_probs; a.n = n; a.O = O; a.A = A;
-  const int64_t tiles = (n + 31) / 32;
-  int blocks = (int)((tiles + kFwdWaves - 1) / kFwdWaves);
-  if (blocks > 1024) blocks = 1024;
-  const int ap = ap_bucket(A);
+  MlpArgs a = actor_args(d_actor_params, d_observations, n, O, A);
+  a.eps = d_eps; a.out0 = d_actions; a.out1 = d_log_probs;
   hipStream_t st = as_stream(stream);
+  if (r.layered) return wide_act(a, d_workspace, workspace_bytes, st, r.torso);
+  const int blocks = fwd_blocks(n);
+  const int ap = ap_bucket(A);
   return dispatch_ks1(ks1_bucket(O), [&](auto ks) {
     constexpr int KS1 = decltype(ks)::value;
     if (ap == 1) return launch_act<KS1, 1>(blocks, st, a);
@@ -1052,16 +1073,14 @@ extern "C" int tonic_ppo_collect_step(
                 "tonic_ppo_collect_step: row=%lld W=%lld", (long long)row, (long long)W);
   if (int rc = check_shape(O, A, true)) return rc;
   CollectArgs c{};
-  c.act.params = d_actor_params; c.act.obs = d_observations; c.act.eps = d_eps;
-  c.act.out0 = d_actions_out; c.act.n = W; c.act.O = O; c.act.A = A;
+  c.act = actor_args(d_actor_params, d_observations, W, O, A);
+  c.act.eps = d_eps; c.act.out0 = d_actions_out;
   c.next_obs = d_next_observations; c.rewards = d_rewards; c.resets = d_resets;
   c.terminations = d_terminations; c.seg_obs = d_seg_observations; c.seg_act = d_seg_actions;
   c.seg_next = d_seg_next_observations; c.seg_rew = d_seg_rewards; c.seg_rst = d_seg_resets;
   c.seg_term = d_seg_terminations; c.seg_lp = d_seg_log_probs; c.norm_acc = d_norm_acc;
   c.row = row;
-  const int64_t tiles = (W + 31) / 32;
-  int act_blocks = (int)((tiles + kFwdWaves - 1) / kFwdWaves);
-  if (act_blocks > 1024) act_blocks = 1024;
+  const int act_blocks = fwd_blocks(W);
   const int ap = ap_bucket(A);
   hipStream_t st = as_stream(stream);
   return dispatch_ks1(ks1_bucket(O), [&](auto ks) -> int {
@@ -1100,38 +1119,10 @@ extern "C" int tonic_ppo_collect_step(
 
 constexpr int64_t kValues16MinRows = 32768;
 
-extern "C" int tonic_value_forward(const float* d_critic_params, const float* d_norm_mean,
-                                   const float* d_norm_std, double norm_clip,
-                                   const float* d_observations,
-                                   float* d_values, int64_t n, int32_t O, void* stream) {
-  TONIC_REQUIRE(d_critic_params && d_norm_mean && d_norm_std && d_observations && d_values &&
-                    n >= 0, TONIC_ERR_INVALID_ARGUMENT, "tonic_value_forward: bad argument");
-  if (int rc = check_shape(O, 1, false)) return rc;
-  if (n == 0) return TONIC_OK;
-  MlpArgs a{};
-  a.params = d_critic_params; a.obs = d_observations; a.norm_mean = d_norm_mean;
-  a.norm_std = d_norm_std; a.norm_clip = clip_bound(norm_clip);
-  a.out0 = d_values; a.n = n; a.O = O; a.A = 1;
-  hipStream_t st = as_stream(stream);
-  // A whole Segment (a2c.py:92-99 evaluates T x W observations twice per update): the forward half
-  // of the regression kernel — 16-sample MFMA tiles with the inputs prefetched a tile ahead —
-  // instead of the per-step kernel below, which is built around the latency of ONE step's rows.
-  const int variant = g_grad_variant;
-  if (n >= kValues16MinRows && variant >= 1 && grad16_supported(O, 1, false)) {
-    a.out1 = d_values;
-    return launch_values16(grad16_blocks(n), st, a, variant - 1);
-  }
-  const int64_t tiles = (n + 31) / 32;
-  int blocks = (int)((tiles + kFwdWaves - 1) / kFwdWaves);
-  if (blocks > 1024) blocks = 1024;
-  return dispatch_ks1(ks1_bucket(O), [&](auto ks) {
-    return launch_value<decltype(ks)::value>(blocks, st, a);
-  });
-}
-
 // ---- the Return normaliser's head (tonic/torch/normalizers/returns.py): the *_ranged entries
-// Both range pointers NULL: the plain entry itself.  Otherwise the squashed instantiations, which serve the
-// shipped grad chain (grad_variant 4) only — the developer references 0 - 3 have no squashed form.
+// Both range pointers NULL: the plain head, the same launches as the entry without the suffix.  Otherwise the
+// squashed instantiations, which serve the shipped grad chain (grad_variant 4) only — the developer references
+// 0 - 3 have no squashed form.  This check comes first in every body that takes a range.
 static int ranged_arguments(const float* d_value_low, const float* d_value_high, const char* what) {
   TONIC_REQUIRE((d_value_low == nullptr) == (d_value_high == nullptr), TONIC_ERR_INVALID_ARGUMENT,
                 "%s: d_value_low and d_value_high must both be set or both be NULL", what);
@@ -1140,32 +1131,38 @@ static int ranged_arguments(const float* d_value_low, const float* d_value_high,
   return TONIC_OK;
 }
 
-extern "C" int tonic_value_forward_ranged(const float* d_critic_params, const float* d_norm_mean,
-                                          const float* d_norm_std, double norm_clip,
-                                          const float* d_observations, float* d_values, int64_t n,
-                                          int32_t O, const float* d_value_low,
-                                          const float* d_value_high, void* stream) {
-  if (int rc = ranged_arguments(d_value_low, d_value_high, "tonic_value_forward_ranged")) return rc;
-  if (d_value_low == nullptr)
-    return tonic_value_forward(d_critic_params, d_norm_mean, d_norm_std, norm_clip, d_observations,
-                               d_values, n, O, stream);
-  TONIC_REQUIRE(d_critic_params && d_norm_mean && d_norm_std && d_observations && d_values &&
-                    n >= 0, TONIC_ERR_INVALID_ARGUMENT, "tonic_value_forward_ranged: bad argument");
-  if (int rc = check_shape(O, 1, false)) return rc;
+static int serve_value_forward(const char* what, const std::optional<TorsoSpec>& spec, bool has_workspace,
+                               const float* d_critic_params, const float* d_norm_mean,
+                               const float* d_norm_std, double norm_clip, const float* d_observations,
+                               float* d_values, int64_t n, int32_t O, void* d_workspace,
+                               int64_t workspace_bytes, const float* d_value_low, const float* d_value_high,
+                               void* stream) {
+  if (int rc = ranged_arguments(d_value_low, d_value_high, what)) return rc;
+  TONIC_REQUIRE(d_critic_params && d_norm_mean && d_norm_std && d_observations && d_values && n >= 0,
+                TONIC_ERR_INVALID_ARGUMENT, "%s: bad argument", what);
+  Route r;
+  if (int rc = choose_route(what, spec, has_workspace, O, 1, false, r)) return rc;
   if (n == 0) return TONIC_OK;
-  MlpArgs a{};
-  a.params = d_critic_params; a.obs = d_observations; a.norm_mean = d_norm_mean;
-  a.norm_std = d_norm_std; a.norm_clip = clip_bound(norm_clip);
-  a.out0 = d_values; a.n = n; a.O = O; a.A = 1;
-  a.set_value_range(d_value_low, d_value_high);
+  MlpArgs a = value_args(d_critic_params, d_norm_mean, d_norm_std, norm_clip, d_observations, n, O,
+                         d_value_low, d_value_high);
+  a.out0 = d_values;
   hipStream_t st = as_stream(stream);
-  if (n >= kValues16MinRows && grad16_supported(O, 1, false)) {      // as tonic_value_forward
+  if (r.layered) return wide_value(a, d_workspace, workspace_bytes, st, r.torso);
+  const bool squashed = d_value_low != nullptr;
+  // A whole Segment (a2c.py:92-99 evaluates T x W observations twice per update): the forward half
+  // of the regression kernel — 16-sample MFMA tiles with the inputs prefetched a tile ahead —
+  // instead of the per-step kernel below, which is built around the latency of ONE step's rows.
+  const int variant = g_grad_variant;             // (the squashed head: kDefaultGradVariant, ranged_arguments)
+  if (n >= kValues16MinRows && variant >= 1 && grad16_supported(O, 1, false)) {
     a.out1 = d_values;
-    return launch_values16_squashed(grad16_blocks(n), st, a);
+    return squashed ? launch_values16_squashed(grad16_blocks(n), st, a)
+                    : launch_values16(grad16_blocks(n), st, a, variant - 1);
   }
-  const int64_t tiles = (n + 31) / 32;
-  int blocks = (int)((tiles + kFwdWaves - 1) / kFwdWaves);
-  if (blocks > 1024) blocks = 1024;
+  const int blocks = fwd_blocks(n);
+  if (!squashed)
+    return dispatch_ks1(ks1_bucket(O), [&](auto ks) {
+      return launch_value<decltype(ks)::value>(blocks, st, a);
+    });
   return dispatch_ks1(ks1_bucket(O), [&](auto ks) {
     return launch_value<decltype(ks)::value, true>(blocks, st, a);
   });
@@ -1177,6 +1174,7 @@ extern "C" int64_t tonic_mlp64_grad_workspace_bytes(int64_t n, int64_t param_cou
   return (int64_t)blocks * pstride * (int64_t)sizeof(float);
 }
 
+// The fused route of the two grad bodies.
 template <bool ACTOR>
 static int run_grad(MlpArgs a, int64_t P, float* d_grad_sums, float entropy_coeff,
                     int32_t max_workgroups, void* d_workspace, int64_t workspace_bytes,
@@ -1250,139 +1248,69 @@ int tonic::launch_reduce_partials(bool actor, const float* partials, int blocks,
   return TONIC_OK;
 }
 
-extern "C" int tonic_ppo_actor_grad(const float* d_actor_params, const float* d_observations,
-                                    const float* d_actions, const float* d_advantages,
-                                    const float* d_adv_stats, const float* d_old_log_probs,
-                                    float* d_grad_sums, int64_t n, int32_t O, int32_t A,
-                                    double ratio_clip, double entropy_coeff,
-                                    const int32_t* d_skip_flag, int32_t max_workgroups,
-                                    void* d_workspace, int64_t workspace_bytes, void* stream) {
+// (every grad entry takes a workspace; `max_workgroups` reaches the fused route only)
+static int serve_actor_grad(const char* what, const std::optional<TorsoSpec>& spec,
+                            const float* d_actor_params, const float* d_observations, const float* d_actions, const float* d_advantages,
+                            const float* d_adv_stats, const float* d_old_log_probs, float* d_grad_sums,
+                            int64_t n, int32_t O, int32_t A, double ratio_clip, double entropy_coeff,
+                            const int32_t* d_skip_flag, int32_t max_workgroups, void* d_workspace,
+                            int64_t workspace_bytes, void* stream) {
   TONIC_REQUIRE(d_actor_params && d_observations && d_actions && d_advantages && d_adv_stats &&
                     d_old_log_probs && d_grad_sums && n > 0,
-                TONIC_ERR_INVALID_ARGUMENT, "tonic_ppo_actor_grad: bad argument");
-  const bool wide = wide_shape(O, A, true);
-  if (int rc = wide ? check_wide(O, A, true) : check_shape(O, A, true)) return rc;
-  MlpArgs a{};
-  a.params = d_actor_params; a.obs = d_observations; a.actions = d_actions;
-  a.adv = d_advantages; a.adv_stats = d_adv_stats; a.old_logp = d_old_log_probs;
-  a.skip = d_skip_flag; a.n = n; a.O = O; a.A = A;
+                TONIC_ERR_INVALID_ARGUMENT, "%s: bad argument", what);
+  Route r;
+  if (int rc = choose_route(what, spec, true, O, A, true, r)) return rc;
+  MlpArgs a = actor_args(d_actor_params, d_observations, n, O, A);
+  a.actions = d_actions; a.adv = d_advantages; a.adv_stats = d_adv_stats; a.old_logp = d_old_log_probs;
+  a.skip = d_skip_flag;
   a.clip_lo = (float)(1.0 - ratio_clip);     // actors.py:85-86 (f64, then f32 in clamp)
   a.clip_hi = (float)(1.0 + ratio_clip);
   a.plain = ratio_clip < 0 ? 1 : 0;
-  if (wide)
+  if (r.layered)
     return wide_actor_grad(a, d_grad_sums, (float)entropy_coeff, d_workspace, workspace_bytes,
-                           as_stream(stream));
-  return run_grad<true>(a, tonic_ppo_actor_param_count(O, A), d_grad_sums,
-                        (float)entropy_coeff, max_workgroups,
-                        d_workspace, workspace_bytes, stream);
+                           as_stream(stream), r.torso);
+  return run_grad<true>(a, tonic_ppo_actor_param_count(O, A), d_grad_sums, (float)entropy_coeff,
+                        max_workgroups, d_workspace, workspace_bytes, stream);
+}
+
+static int serve_value_grad(const char* what, const std::optional<TorsoSpec>& spec,
+                            const float* d_critic_params, const float* d_norm_mean, const float* d_norm_std, double norm_clip,
+                            const float* d_observations, const float* d_returns, float* d_grad_sums,
+                            int64_t n, int32_t O, int32_t max_workgroups, void* d_workspace,
+                            int64_t workspace_bytes, const float* d_value_low, const float* d_value_high,
+                            void* stream) {
+  if (int rc = ranged_arguments(d_value_low, d_value_high, what)) return rc;
+  TONIC_REQUIRE(d_critic_params && d_norm_mean && d_norm_std && d_observations && d_returns &&
+                    d_grad_sums && n > 0,
+                TONIC_ERR_INVALID_ARGUMENT, "%s: bad argument", what);
+  Route r;
+  if (int rc = choose_route(what, spec, true, O, 1, false, r)) return rc;
+  MlpArgs a = value_args(d_critic_params, d_norm_mean, d_norm_std, norm_clip, d_observations, n, O,
+                         d_value_low, d_value_high);
+  a.returns = d_returns;
+  if (r.layered)
+    return wide_critic_grad(a, d_grad_sums, d_workspace, workspace_bytes, as_stream(stream), r.torso);
+  return run_grad<false>(a, tonic_v_critic_param_count(O), d_grad_sums, 0.f, max_workgroups,
+                         d_workspace, workspace_bytes, stream);
 }
 
 // ---- any MLP(sizes, activation) torso: the layer-by-layer path (mlpwide.hip)
-static int torso_from(int32_t layers, const int32_t* sizes, int32_t activation, Torso& t) {
-  TONIC_REQUIRE(sizes != nullptr && layers >= 1 && layers <= kMaxTorsoLayers, TONIC_ERR_UNSUPPORTED_SHAPE,
-                "torso: %d hidden layers (1 .. %d are served)", layers, kMaxTorsoLayers);
-  t = Torso{layers, {0, 0, 0, 0}, activation};
-  for (int l = 0; l < layers; ++l) t.size[l] = sizes[l];
-  TONIC_REQUIRE(torso_supported(t), TONIC_ERR_UNSUPPORTED_SHAPE,
-                "torso: layers of 4 .. 384 units (multiples of 4), activation 1 (Tanh) or 2 (ReLU)");
-  return TONIC_OK;
-}
-
 extern "C" int64_t tonic_ppo_torso_param_count(int32_t O, int32_t A, int32_t actor, int32_t layers,
                                                const int32_t* sizes) {
   Torso t;
-  if (torso_from(layers, sizes, 1, t) != TONIC_OK || !wide_supported(O, actor ? A : 1, actor != 0)) return -1;
+  if (parse_torso("tonic_ppo_torso_param_count", layers, sizes, 1, t) != TONIC_OK ||
+      !wide_supported(O, actor ? A : 1, actor != 0))
+    return -1;
   return torso_param_count(O, actor ? A : 1, actor != 0, t);
 }
 
 extern "C" int64_t tonic_ppo_torso_workspace_bytes(int64_t n, int32_t O, int32_t A, int32_t actor,
                                                    int32_t layers, const int32_t* sizes) {
   Torso t;
-  if (n <= 0 || torso_from(layers, sizes, 1, t) != TONIC_OK ||
+  if (n <= 0 || parse_torso("tonic_ppo_torso_workspace_bytes", layers, sizes, 1, t) != TONIC_OK ||
       !wide_supported(O, actor ? A : 1, actor != 0))
     return -1;
   return wide_workspace_bytes(n, O, actor ? A : 1, actor != 0, t);
-}
-
-extern "C" int tonic_ppo_act_torso(int32_t layers, const int32_t* sizes, int32_t activation,
-                                   const float* d_actor_params, const float* d_observations,
-                                   const float* d_eps, float* d_actions, float* d_log_probs, int64_t n,
-                                   int32_t O, int32_t A, void* d_workspace, int64_t workspace_bytes,
-                                   void* stream) {
-  TONIC_REQUIRE(d_actor_params && d_observations && d_actions && n >= 0, TONIC_ERR_INVALID_ARGUMENT,
-                "tonic_ppo_act_torso: null argument");
-  Torso t;
-  if (int rc = torso_from(layers, sizes, activation, t)) return rc;
-  if (int rc = check_wide(O, A, true)) return rc;
-  if (n == 0) return TONIC_OK;
-  MlpArgs a{};
-  a.params = d_actor_params; a.obs = d_observations; a.eps = d_eps;
-  a.out0 = d_actions; a.out1 = d_log_probs; a.n = n; a.O = O; a.A = A;
-  return wide_act(a, d_workspace, workspace_bytes, as_stream(stream), t);
-}
-
-extern "C" int tonic_value_forward_torso(int32_t layers, const int32_t* sizes, int32_t activation,
-                                         const float* d_critic_params, const float* d_norm_mean,
-                                         const float* d_norm_std, double norm_clip,
-                                         const float* d_observations, float* d_values, int64_t n,
-                                         int32_t O, void* d_workspace, int64_t workspace_bytes,
-                                         void* stream) {
-  TONIC_REQUIRE(d_critic_params && d_norm_mean && d_norm_std && d_observations && d_values && n >= 0,
-                TONIC_ERR_INVALID_ARGUMENT, "tonic_value_forward_torso: null argument");
-  Torso t;
-  if (int rc = torso_from(layers, sizes, activation, t)) return rc;
-  if (int rc = check_wide(O, 1, false)) return rc;
-  if (n == 0) return TONIC_OK;
-  MlpArgs a{};
-  a.params = d_critic_params; a.obs = d_observations; a.norm_mean = d_norm_mean;
-  a.norm_std = d_norm_std; a.norm_clip = clip_bound(norm_clip);
-  a.out0 = d_values; a.n = n; a.O = O; a.A = 1;
-  return wide_value(a, d_workspace, workspace_bytes, as_stream(stream), t);
-}
-
-extern "C" int tonic_ppo_actor_grad_torso(int32_t layers, const int32_t* sizes, int32_t activation,
-                                          const float* d_actor_params, const float* d_observations,
-                                          const float* d_actions, const float* d_advantages,
-                                          const float* d_adv_stats, const float* d_old_log_probs,
-                                          float* d_grad_sums, int64_t n, int32_t O, int32_t A,
-                                          double ratio_clip, double entropy_coeff,
-                                          const int32_t* d_skip_flag, void* d_workspace,
-                                          int64_t workspace_bytes, void* stream) {
-  TONIC_REQUIRE(d_actor_params && d_observations && d_actions && d_advantages && d_adv_stats &&
-                    d_old_log_probs && d_grad_sums && n > 0,
-                TONIC_ERR_INVALID_ARGUMENT, "tonic_ppo_actor_grad_torso: bad argument");
-  Torso t;
-  if (int rc = torso_from(layers, sizes, activation, t)) return rc;
-  if (int rc = check_wide(O, A, true)) return rc;
-  MlpArgs a{};
-  a.params = d_actor_params; a.obs = d_observations; a.actions = d_actions;
-  a.adv = d_advantages; a.adv_stats = d_adv_stats; a.old_logp = d_old_log_probs;
-  a.skip = d_skip_flag; a.n = n; a.O = O; a.A = A;
-  a.clip_lo = (float)(1.0 - ratio_clip);
-  a.clip_hi = (float)(1.0 + ratio_clip);
-  a.plain = ratio_clip < 0 ? 1 : 0;
-  return wide_actor_grad(a, d_grad_sums, (float)entropy_coeff, d_workspace, workspace_bytes,
-                         as_stream(stream), t);
-}
-
-extern "C" int tonic_value_regression_grad_torso(int32_t layers, const int32_t* sizes,
-                                                 int32_t activation, const float* d_critic_params,
-                                                 const float* d_norm_mean, const float* d_norm_std,
-                                                 double norm_clip, const float* d_observations,
-                                                 const float* d_returns, float* d_grad_sums, int64_t n,
-                                                 int32_t O, void* d_workspace, int64_t workspace_bytes,
-                                                 void* stream) {
-  TONIC_REQUIRE(d_critic_params && d_norm_mean && d_norm_std && d_observations && d_returns &&
-                    d_grad_sums && n > 0,
-                TONIC_ERR_INVALID_ARGUMENT, "tonic_value_regression_grad_torso: bad argument");
-  Torso t;
-  if (int rc = torso_from(layers, sizes, activation, t)) return rc;
-  if (int rc = check_wide(O, 1, false)) return rc;
-  MlpArgs a{};
-  a.params = d_critic_params; a.obs = d_observations; a.returns = d_returns;
-  a.norm_mean = d_norm_mean; a.norm_std = d_norm_std; a.norm_clip = clip_bound(norm_clip);
-  a.n = n; a.O = O; a.A = 1;
-  return wide_critic_grad(a, d_grad_sums, d_workspace, workspace_bytes, as_stream(stream), t);
 }
 
 // Developer tool: per-phase s_memtime totals of the 8 waves of workgroup 0 of the 16x16x4 actor
@@ -1395,10 +1323,9 @@ extern "C" int tonic_debug_grad16_phases(const float* d_actor_params, const floa
                                          void* stream) {
   TONIC_REQUIRE(O == 17 && A == 6 && d_phase_cycles && d_workspace,
                 TONIC_ERR_INVALID_ARGUMENT, "tonic_debug_grad16_phases: unsupported shape");
-  MlpArgs a{};
-  a.params = d_actor_params; a.obs = d_observations; a.actions = d_actions;
-  a.adv = d_advantages; a.adv_stats = d_adv_stats; a.old_logp = d_old_log_probs;
-  a.n = n; a.O = O; a.A = A; a.clip_lo = 0.8f; a.clip_hi = 1.2f;
+  MlpArgs a = actor_args(d_actor_params, d_observations, n, O, A);
+  a.actions = d_actions; a.adv = d_advantages; a.adv_stats = d_adv_stats; a.old_logp = d_old_log_probs;
+  a.clip_lo = 0.8f; a.clip_hi = 1.2f;
   a.out0 = static_cast<float*>(d_workspace);
   a.out1 = reinterpret_cast<float*>(d_phase_cycles);
   a.pstride = (int)round_up(tonic_ppo_actor_param_count(O, A) + kStatSlots, 64);
@@ -1408,25 +1335,71 @@ extern "C" int tonic_debug_grad16_phases(const float* d_actor_params, const floa
   return launch_grad16_probe(grad16_blocks(n), as_stream(stream), a);
 }
 
-extern "C" int tonic_value_regression_grad(const float* d_critic_params,
-                                           const float* d_norm_mean, const float* d_norm_std,
-                                           double norm_clip,
-                                           const float* d_observations, const float* d_returns,
-                                           float* d_grad_sums, int64_t n, int32_t O,
-                                           int32_t max_workgroups, void* d_workspace,
-                                           int64_t workspace_bytes, void* stream) {
-  TONIC_REQUIRE(d_critic_params && d_norm_mean && d_norm_std && d_observations && d_returns &&
-                    d_grad_sums && n > 0,
-                TONIC_ERR_INVALID_ARGUMENT, "tonic_value_regression_grad: bad argument");
-  const bool wide = wide_shape(O, 1, false);
-  if (int rc = wide ? check_wide(O, 1, false) : check_shape(O, 1, false)) return rc;
-  MlpArgs a{};
-  a.params = d_critic_params; a.obs = d_observations; a.returns = d_returns;
-  a.norm_mean = d_norm_mean; a.norm_std = d_norm_std; a.norm_clip = clip_bound(norm_clip);
-  a.n = n; a.O = O; a.A = 1;
-  if (wide) return wide_critic_grad(a, d_grad_sums, d_workspace, workspace_bytes, as_stream(stream));
-  return run_grad<false>(a, tonic_v_critic_param_count(O), d_grad_sums, 0.f, max_workgroups,
-                         d_workspace, workspace_bytes, stream);
+// ---- the entries: each forwards to its operation's body with its own name, its torso (none: the default
+// network), whether it takes a workspace, and its range (none: the plain head)
+
+extern "C" int tonic_ppo_act(const float* d_actor_params, const float* d_observations,
+                             const float* d_eps, float* d_actions, float* d_log_probs,
+                             int64_t n, int32_t O, int32_t A, void* stream) {
+  return serve_act("tonic_ppo_act", std::nullopt, false, d_actor_params, d_observations, d_eps, d_actions,
+                   d_log_probs, n, O, A, nullptr, 0, stream);
+}
+
+extern "C" int tonic_ppo_act_wide(const float* d_actor_params, const float* d_observations,
+                                  const float* d_eps, float* d_actions, float* d_log_probs,
+                                  int64_t n, int32_t O, int32_t A, void* d_workspace,
+                                  int64_t workspace_bytes, void* stream) {
+  return serve_act("tonic_ppo_act_wide", std::nullopt, true, d_actor_params, d_observations, d_eps, d_actions,
+                   d_log_probs, n, O, A, d_workspace, workspace_bytes, stream);
+}
+
+extern "C" int tonic_ppo_act_torso(int32_t layers, const int32_t* sizes, int32_t activation,
+                                   const float* d_actor_params, const float* d_observations,
+                                   const float* d_eps, float* d_actions, float* d_log_probs, int64_t n,
+                                   int32_t O, int32_t A, void* d_workspace, int64_t workspace_bytes,
+                                   void* stream) {
+  return serve_act("tonic_ppo_act_torso", TorsoSpec{layers, sizes, activation}, true, d_actor_params,
+                   d_observations, d_eps, d_actions, d_log_probs, n, O, A, d_workspace, workspace_bytes, stream);
+}
+
+extern "C" int tonic_value_forward(const float* d_critic_params, const float* d_norm_mean,
+                                   const float* d_norm_std, double norm_clip,
+                                   const float* d_observations,
+                                   float* d_values, int64_t n, int32_t O, void* stream) {
+  return serve_value_forward("tonic_value_forward", std::nullopt, false, d_critic_params, d_norm_mean,
+                             d_norm_std, norm_clip, d_observations, d_values, n, O, nullptr, 0, nullptr,
+                             nullptr, stream);
+}
+
+extern "C" int tonic_value_forward_wide(const float* d_critic_params, const float* d_norm_mean,
+                                        const float* d_norm_std, double norm_clip,
+                                        const float* d_observations, float* d_values, int64_t n,
+                                        int32_t O, void* d_workspace, int64_t workspace_bytes,
+                                        void* stream) {
+  return serve_value_forward("tonic_value_forward_wide", std::nullopt, true, d_critic_params, d_norm_mean,
+                             d_norm_std, norm_clip, d_observations, d_values, n, O, d_workspace,
+                             workspace_bytes, nullptr, nullptr, stream);
+}
+
+extern "C" int tonic_value_forward_torso(int32_t layers, const int32_t* sizes, int32_t activation,
+                                         const float* d_critic_params, const float* d_norm_mean,
+                                         const float* d_norm_std, double norm_clip,
+                                         const float* d_observations, float* d_values, int64_t n,
+                                         int32_t O, void* d_workspace, int64_t workspace_bytes,
+                                         void* stream) {
+  return serve_value_forward("tonic_value_forward_torso", TorsoSpec{layers, sizes, activation}, true,
+                             d_critic_params, d_norm_mean, d_norm_std, norm_clip, d_observations, d_values,
+                             n, O, d_workspace, workspace_bytes, nullptr, nullptr, stream);
+}
+
+extern "C" int tonic_value_forward_ranged(const float* d_critic_params, const float* d_norm_mean,
+                                          const float* d_norm_std, double norm_clip,
+                                          const float* d_observations, float* d_values, int64_t n,
+                                          int32_t O, const float* d_value_low,
+                                          const float* d_value_high, void* stream) {
+  return serve_value_forward("tonic_value_forward_ranged", std::nullopt, false, d_critic_params,
+                             d_norm_mean, d_norm_std, norm_clip, d_observations, d_values, n, O, nullptr, 0,
+                             d_value_low, d_value_high, stream);
 }
 
 extern "C" int tonic_value_forward_wide_ranged(const float* d_critic_params, const float* d_norm_mean,
@@ -1435,23 +1408,9 @@ extern "C" int tonic_value_forward_wide_ranged(const float* d_critic_params, con
                                                int32_t O, void* d_workspace, int64_t workspace_bytes,
                                                const float* d_value_low, const float* d_value_high,
                                                void* stream) {
-  if (int rc = ranged_arguments(d_value_low, d_value_high, "tonic_value_forward_wide_ranged")) return rc;
-  if (d_value_low == nullptr)
-    return tonic_value_forward_wide(d_critic_params, d_norm_mean, d_norm_std, norm_clip, d_observations,
-                                    d_values, n, O, d_workspace, workspace_bytes, stream);
-  if (!wide_shape(O, 1, false))
-    return tonic_value_forward_ranged(d_critic_params, d_norm_mean, d_norm_std, norm_clip,
-                                      d_observations, d_values, n, O, d_value_low, d_value_high, stream);
-  TONIC_REQUIRE(d_critic_params && d_norm_mean && d_norm_std && d_observations && d_values && n >= 0,
-                TONIC_ERR_INVALID_ARGUMENT, "tonic_value_forward_wide_ranged: bad argument");
-  if (int rc = check_wide(O, 1, false)) return rc;
-  if (n == 0) return TONIC_OK;
-  MlpArgs a{};
-  a.params = d_critic_params; a.obs = d_observations; a.norm_mean = d_norm_mean;
-  a.norm_std = d_norm_std; a.norm_clip = clip_bound(norm_clip);
-  a.out0 = d_values; a.n = n; a.O = O; a.A = 1;
-  a.set_value_range(d_value_low, d_value_high);
-  return wide_value(a, d_workspace, workspace_bytes, as_stream(stream));
+  return serve_value_forward("tonic_value_forward_wide_ranged", std::nullopt, true, d_critic_params,
+                             d_norm_mean, d_norm_std, norm_clip, d_observations, d_values, n, O,
+                             d_workspace, workspace_bytes, d_value_low, d_value_high, stream);
 }
 
 extern "C" int tonic_value_forward_torso_ranged(int32_t layers, const int32_t* sizes, int32_t activation,
@@ -1461,23 +1420,59 @@ extern "C" int tonic_value_forward_torso_ranged(int32_t layers, const int32_t* s
                                                 int32_t O, void* d_workspace, int64_t workspace_bytes,
                                                 const float* d_value_low, const float* d_value_high,
                                                 void* stream) {
-  if (int rc = ranged_arguments(d_value_low, d_value_high, "tonic_value_forward_torso_ranged")) return rc;
-  if (d_value_low == nullptr)
-    return tonic_value_forward_torso(layers, sizes, activation, d_critic_params, d_norm_mean, d_norm_std,
-                                     norm_clip, d_observations, d_values, n, O, d_workspace,
-                                     workspace_bytes, stream);
-  TONIC_REQUIRE(d_critic_params && d_norm_mean && d_norm_std && d_observations && d_values && n >= 0,
-                TONIC_ERR_INVALID_ARGUMENT, "tonic_value_forward_torso_ranged: null argument");
-  Torso t;
-  if (int rc = torso_from(layers, sizes, activation, t)) return rc;
-  if (int rc = check_wide(O, 1, false)) return rc;
-  if (n == 0) return TONIC_OK;
-  MlpArgs a{};
-  a.params = d_critic_params; a.obs = d_observations; a.norm_mean = d_norm_mean;
-  a.norm_std = d_norm_std; a.norm_clip = clip_bound(norm_clip);
-  a.out0 = d_values; a.n = n; a.O = O; a.A = 1;
-  a.set_value_range(d_value_low, d_value_high);
-  return wide_value(a, d_workspace, workspace_bytes, as_stream(stream), t);
+  return serve_value_forward("tonic_value_forward_torso_ranged", TorsoSpec{layers, sizes, activation}, true,
+                             d_critic_params, d_norm_mean, d_norm_std, norm_clip, d_observations, d_values,
+                             n, O, d_workspace, workspace_bytes, d_value_low, d_value_high, stream);
+}
+
+extern "C" int tonic_ppo_actor_grad(const float* d_actor_params, const float* d_observations,
+                                    const float* d_actions, const float* d_advantages,
+                                    const float* d_adv_stats, const float* d_old_log_probs,
+                                    float* d_grad_sums, int64_t n, int32_t O, int32_t A,
+                                    double ratio_clip, double entropy_coeff,
+                                    const int32_t* d_skip_flag, int32_t max_workgroups,
+                                    void* d_workspace, int64_t workspace_bytes, void* stream) {
+  return serve_actor_grad("tonic_ppo_actor_grad", std::nullopt, d_actor_params, d_observations, d_actions,
+                          d_advantages, d_adv_stats, d_old_log_probs, d_grad_sums, n, O, A, ratio_clip,
+                          entropy_coeff, d_skip_flag, max_workgroups, d_workspace, workspace_bytes, stream);
+}
+
+extern "C" int tonic_ppo_actor_grad_torso(int32_t layers, const int32_t* sizes, int32_t activation,
+                                          const float* d_actor_params, const float* d_observations,
+                                          const float* d_actions, const float* d_advantages,
+                                          const float* d_adv_stats, const float* d_old_log_probs,
+                                          float* d_grad_sums, int64_t n, int32_t O, int32_t A,
+                                          double ratio_clip, double entropy_coeff,
+                                          const int32_t* d_skip_flag, void* d_workspace,
+                                          int64_t workspace_bytes, void* stream) {
+  return serve_actor_grad("tonic_ppo_actor_grad_torso", TorsoSpec{layers, sizes, activation}, d_actor_params,
+                          d_observations, d_actions, d_advantages, d_adv_stats, d_old_log_probs, d_grad_sums,
+                          n, O, A, ratio_clip, entropy_coeff, d_skip_flag, 0, d_workspace, workspace_bytes,
+                          stream);
+}
+
+extern "C" int tonic_value_regression_grad(const float* d_critic_params,
+                                           const float* d_norm_mean, const float* d_norm_std,
+                                           double norm_clip,
+                                           const float* d_observations, const float* d_returns,
+                                           float* d_grad_sums, int64_t n, int32_t O,
+                                           int32_t max_workgroups, void* d_workspace,
+                                           int64_t workspace_bytes, void* stream) {
+  return serve_value_grad("tonic_value_regression_grad", std::nullopt, d_critic_params, d_norm_mean,
+                          d_norm_std, norm_clip, d_observations, d_returns, d_grad_sums, n, O, max_workgroups,
+                          d_workspace, workspace_bytes, nullptr, nullptr, stream);
+}
+
+extern "C" int tonic_value_regression_grad_torso(int32_t layers, const int32_t* sizes,
+                                                 int32_t activation, const float* d_critic_params,
+                                                 const float* d_norm_mean, const float* d_norm_std,
+                                                 double norm_clip, const float* d_observations,
+                                                 const float* d_returns, float* d_grad_sums, int64_t n,
+                                                 int32_t O, void* d_workspace, int64_t workspace_bytes,
+                                                 void* stream) {
+  return serve_value_grad("tonic_value_regression_grad_torso", TorsoSpec{layers, sizes, activation},
+                          d_critic_params, d_norm_mean, d_norm_std, norm_clip, d_observations, d_returns,
+                          d_grad_sums, n, O, 0, d_workspace, workspace_bytes, nullptr, nullptr, stream);
 }
 
 extern "C" int tonic_value_regression_grad_ranged(const float* d_critic_params, const float* d_norm_mean,
@@ -1487,24 +1482,9 @@ extern "C" int tonic_value_regression_grad_ranged(const float* d_critic_params, 
                                                   int32_t max_workgroups, void* d_workspace,
                                                   int64_t workspace_bytes, const float* d_value_low,
                                                   const float* d_value_high, void* stream) {
-  if (int rc = ranged_arguments(d_value_low, d_value_high, "tonic_value_regression_grad_ranged")) return rc;
-  if (d_value_low == nullptr)
-    return tonic_value_regression_grad(d_critic_params, d_norm_mean, d_norm_std, norm_clip, d_observations,
-                                       d_returns, d_grad_sums, n, O, max_workgroups, d_workspace,
-                                       workspace_bytes, stream);
-  TONIC_REQUIRE(d_critic_params && d_norm_mean && d_norm_std && d_observations && d_returns &&
-                    d_grad_sums && n > 0,
-                TONIC_ERR_INVALID_ARGUMENT, "tonic_value_regression_grad_ranged: bad argument");
-  const bool wide = wide_shape(O, 1, false);
-  if (int rc = wide ? check_wide(O, 1, false) : check_shape(O, 1, false)) return rc;
-  MlpArgs a{};
-  a.params = d_critic_params; a.obs = d_observations; a.returns = d_returns;
-  a.norm_mean = d_norm_mean; a.norm_std = d_norm_std; a.norm_clip = clip_bound(norm_clip);
-  a.n = n; a.O = O; a.A = 1;
-  a.set_value_range(d_value_low, d_value_high);
-  if (wide) return wide_critic_grad(a, d_grad_sums, d_workspace, workspace_bytes, as_stream(stream));
-  return run_grad<false>(a, tonic_v_critic_param_count(O), d_grad_sums, 0.f, max_workgroups,
-                         d_workspace, workspace_bytes, stream);
+  return serve_value_grad("tonic_value_regression_grad_ranged", std::nullopt, d_critic_params, d_norm_mean,
+                          d_norm_std, norm_clip, d_observations, d_returns, d_grad_sums, n, O, max_workgroups,
+                          d_workspace, workspace_bytes, d_value_low, d_value_high, stream);
 }
 
 extern "C" int tonic_value_regression_grad_torso_ranged(int32_t layers, const int32_t* sizes,
@@ -1515,22 +1495,8 @@ extern "C" int tonic_value_regression_grad_torso_ranged(int32_t layers, const in
                                                         int32_t O, void* d_workspace, int64_t workspace_bytes,
                                                         const float* d_value_low, const float* d_value_high,
                                                         void* stream) {
-  if (int rc = ranged_arguments(d_value_low, d_value_high, "tonic_value_regression_grad_torso_ranged"))
-    return rc;
-  if (d_value_low == nullptr)
-    return tonic_value_regression_grad_torso(layers, sizes, activation, d_critic_params, d_norm_mean,
-                                             d_norm_std, norm_clip, d_observations, d_returns, d_grad_sums, n,
-                                             O, d_workspace, workspace_bytes, stream);
-  TONIC_REQUIRE(d_critic_params && d_norm_mean && d_norm_std && d_observations && d_returns &&
-                    d_grad_sums && n > 0,
-                TONIC_ERR_INVALID_ARGUMENT, "tonic_value_regression_grad_torso_ranged: bad argument");
-  Torso t;
-  if (int rc = torso_from(layers, sizes, activation, t)) return rc;
-  if (int rc = check_wide(O, 1, false)) return rc;
-  MlpArgs a{};
-  a.params = d_critic_params; a.obs = d_observations; a.returns = d_returns;
-  a.norm_mean = d_norm_mean; a.norm_std = d_norm_std; a.norm_clip = clip_bound(norm_clip);
-  a.n = n; a.O = O; a.A = 1;
-  a.set_value_range(d_value_low, d_value_high);
-  return wide_critic_grad(a, d_grad_sums, d_workspace, workspace_bytes, as_stream(stream), t);
+  return serve_value_grad("tonic_value_regression_grad_torso_ranged", TorsoSpec{layers, sizes, activation},
+                          d_critic_params, d_norm_mean, d_norm_std, norm_clip, d_observations, d_returns,
+                          d_grad_sums, n, O, 0, d_workspace, workspace_bytes, d_value_low, d_value_high,
+                          stream);
 }

@@ -828,6 +828,16 @@ bool torso_supported(const Torso& t) {
   return true;
 }
 
+int parse_torso(const char* what, int32_t layers, const int32_t* sizes, int32_t activation, Torso& t) {
+  TONIC_REQUIRE(sizes != nullptr && layers >= 1 && layers <= kMaxTorsoLayers, TONIC_ERR_UNSUPPORTED_SHAPE,
+                "%s: %d hidden layers (1 .. %d are served)", what, layers, kMaxTorsoLayers);
+  t = Torso{layers, {0, 0, 0, 0}, activation};
+  for (int l = 0; l < layers; ++l) t.size[l] = sizes[l];
+  TONIC_REQUIRE(torso_supported(t), TONIC_ERR_UNSUPPORTED_SHAPE,
+                "%s: layers of 4 .. 384 units (multiples of 4), activation 1 (Tanh) or 2 (ReLU)", what);
+  return TONIC_OK;
+}
+
 int64_t torso_param_count(int O, int A, bool actor, const Torso& t) {
   return WideLayout(1, O, A, actor, t).P;
 }

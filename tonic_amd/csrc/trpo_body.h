@@ -362,12 +362,7 @@ struct TrpoLayout {
 
 int trpo_torso(const char* what, int32_t layers, const int32_t* sizes, int32_t activation, int64_t n,
                int32_t O, int32_t A, Torso& t) {
-  TONIC_REQUIRE(sizes != nullptr && layers >= 1 && layers <= kMaxTorsoLayers, TONIC_ERR_UNSUPPORTED_SHAPE,
-                "%s: %d hidden layers (1 .. %d are served)", what, layers, kMaxTorsoLayers);
-  t = Torso{layers, {0, 0, 0, 0}, activation};
-  for (int l = 0; l < layers; ++l) t.size[l] = sizes[l];
-  TONIC_REQUIRE(torso_supported(t), TONIC_ERR_UNSUPPORTED_SHAPE,
-                "%s: layers of 4 .. 384 units (multiples of 4), activation 1 (Tanh) or 2 (ReLU)", what);
+  if (int rc = parse_torso(what, layers, sizes, activation, t)) return rc;
   TONIC_REQUIRE(wide_supported(O, A, true), TONIC_ERR_UNSUPPORTED_SHAPE,
                 "%s: %d observations / %d actions (1 .. 384 / 1 .. %d are served)", what, O, A, kWideLd);
   TONIC_REQUIRE(n > 0, TONIC_ERR_INVALID_ARGUMENT, "%s: %lld rows", what, (long long)n);

@@ -415,25 +415,19 @@ class A2C(Agent):
         p = _lib.ptr
         torso = getattr(self.actor_updater, 'torso', None)
         if torso is not None:
+            prefix, name = torso, 'tonic_ppo_act_torso'
             need = self.lib.tonic_ppo_torso_workspace_bytes(W, self.observation_size, A, 1, torso[0], torso[1])
         else:
+            prefix, name = (), 'tonic_ppo_act_wide'
             need = self.lib.tonic_ppo_workspace_bytes(W, self.observation_size, A, 1)
         if getattr(self, '_act_workspace', None) is None or self._act_workspace.numel() < need:
             self._act_workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=self.device)
-        if torso is not None:
-            _lib.check(self.lib.tonic_ppo_act_torso(
-                *torso, p(self.model.flat_actor.flat), p(stage_in.device_view('observations')),
-                p(stage_in.device_view('eps')), p(stage_out.device_view('actions')),
-                p(stage_out.device_view('log_probs')) if want_log_probs else None,
-                W, self.observation_size, A, p(self._act_workspace), self._act_workspace.numel(),
-                _lib.current_stream()), 'tonic_ppo_act_torso')
-        else:
-            _lib.check(self.lib.tonic_ppo_act_wide(
-                p(self.model.flat_actor.flat), p(stage_in.device_view('observations')),
-                p(stage_in.device_view('eps')), p(stage_out.device_view('actions')),
-                p(stage_out.device_view('log_probs')) if want_log_probs else None,
-                W, self.observation_size, A, p(self._act_workspace), self._act_workspace.numel(),
-                _lib.current_stream()), 'tonic_ppo_act_wide')
+        _lib.check(getattr(self.lib, name)(
+            *prefix, p(self.model.flat_actor.flat), p(stage_in.device_view('observations')),
+            p(stage_in.device_view('eps')), p(stage_out.device_view('actions')),
+            p(stage_out.device_view('log_probs')) if want_log_probs else None,
+            W, self.observation_size, A, p(self._act_workspace), self._act_workspace.numel(),
+            _lib.current_stream()), name)
         return _read_back_actions(stage_in, stage_out)
 
     def _bind(self, observations):

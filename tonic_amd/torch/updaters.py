@@ -282,13 +282,11 @@ class _FlatUpdater(_StockTorch):
         shapes beyond them (O > 32, A > 8: csrc/mlpwide.hip) also the activations of the
         layer-by-layer passes."""
         actor = self.stats_kind == 1
+        shape = (n, self.observation_size, self.action_size if actor else 1, 1 if actor else 0)
         if self.torso is not None:
-            need = self.lib.tonic_ppo_torso_workspace_bytes(
-                n, self.observation_size, self.action_size if actor else 1, 1 if actor else 0,
-                self.torso[0], self.torso[1])
+            need = self.lib.tonic_ppo_torso_workspace_bytes(*shape, *self.torso[:2])
         else:
-            need = self.lib.tonic_ppo_workspace_bytes(
-                n, self.observation_size, self.action_size if actor else 1, 1 if actor else 0)
+            need = self.lib.tonic_ppo_workspace_bytes(*shape)
         if need < 0:
             raise NotImplementedError(
                 f'PPO networks with {self.observation_size} observations / '
@@ -865,31 +863,14 @@ class VRegression(_FlatUpdater):
             return out
         mean, std = self.norm_tensors()
         p = _lib.ptr
-        ws = self._workspace_for(observations.shape[0])
-        value_range = self.range_tensors()
-        if value_range is not None:
-            low, high = p(value_range[0]), p(value_range[1])
-            if self.torso is not None:
-                _lib.check(self.lib.tonic_value_forward_torso_ranged(
-                    *self.torso, p(self.flat.flat), p(mean), p(std), self.norm_clip(), p(observations),
-                    p(out), observations.shape[0], self.observation_size, p(ws), ws.numel(), low, high,
-                    _lib.current_stream()), 'tonic_value_forward_torso_ranged')
-                return out
-            _lib.check(self.lib.tonic_value_forward_wide_ranged(
-                p(self.flat.flat), p(mean), p(std), self.norm_clip(), p(observations), p(out),
-                observations.shape[0], self.observation_size, p(ws), ws.numel(), low, high,
-                _lib.current_stream()), 'tonic_value_forward_wide_ranged')
-            return out
-        if self.torso is not None:
-            _lib.check(self.lib.tonic_value_forward_torso(
-                *self.torso, p(self.flat.flat), p(mean), p(std), self.norm_clip(), p(observations), p(out),
-                observations.shape[0], self.observation_size, p(ws), ws.numel(),
-                _lib.current_stream()), 'tonic_value_forward_torso')
-            return out
-        _lib.check(self.lib.tonic_value_forward_wide(
-            p(self.flat.flat), p(mean), p(std), self.norm_clip(), p(observations), p(out),
-            observations.shape[0], self.observation_size, p(ws), ws.numel(),
-            _lib.current_stream()), 'tonic_value_forward_wide')
+        n = observations.shape[0]
+        ws = self._workspace_for(n)
+        low, high = map(p, self.range_tensors() or (None, None))         # both NULL: the plain head
+        prefix, name = ((), 'tonic_value_forward_wide_ranged') if self.torso is None else \
+            (self.torso, 'tonic_value_forward_torso_ranged')
+        _lib.check(getattr(self.lib, name)(
+            *prefix, p(self.flat.flat), p(mean), p(std), self.norm_clip(), p(observations), p(out), n,
+            self.observation_size, p(ws), ws.numel(), low, high, _lib.current_stream()), name)
         return out
 
     def enqueue_grad(self, observations, returns, norm=None, value_range=None):
@@ -907,32 +888,17 @@ class VRegression(_FlatUpdater):
         ws = self._workspace_for(n)
         mean, std = norm if norm is not None else self.norm_tensors()
         p = _lib.ptr
-        if value_range is None:
-            value_range = self.range_tensors()
-        if value_range is not None:
-            low, high = p(value_range[0]), p(value_range[1])
-            if self.torso is not None:
-                _lib.check(self.lib.tonic_value_regression_grad_torso_ranged(
-                    *self.torso, p(self.flat.flat), p(mean), p(std), self.norm_clip(), p(observations),
-                    p(returns), p(self.grad_sums), n, self.observation_size, p(ws), ws.numel(), low, high,
-                    _lib.current_stream()), 'tonic_value_regression_grad_torso_ranged')
-                return
-            _lib.check(self.lib.tonic_value_regression_grad_ranged(
-                p(self.flat.flat), p(mean), p(std), self.norm_clip(), p(observations), p(returns),
-                p(self.grad_sums), n, self.observation_size, self.max_workgroups, p(ws), ws.numel(),
-                low, high, _lib.current_stream()), 'tonic_value_regression_grad_ranged')
-            return
+        low, high = map(p, value_range or self.range_tensors() or (None, None))   # both NULL: the plain head
         if self.torso is not None:
-            _lib.check(self.lib.tonic_value_regression_grad_torso(
+            _lib.check(self.lib.tonic_value_regression_grad_torso_ranged(
                 *self.torso, p(self.flat.flat), p(mean), p(std), self.norm_clip(), p(observations),
-                p(returns), p(self.grad_sums), n, self.observation_size, p(ws), ws.numel(),
-                _lib.current_stream()), 'tonic_value_regression_grad_torso')
+                p(returns), p(self.grad_sums), n, self.observation_size, p(ws), ws.numel(), low, high,
+                _lib.current_stream()), 'tonic_value_regression_grad_torso_ranged')
             return
-        _lib.check(self.lib.tonic_value_regression_grad(
+        _lib.check(self.lib.tonic_value_regression_grad_ranged(
             p(self.flat.flat), p(mean), p(std), self.norm_clip(), p(observations), p(returns),
             p(self.grad_sums), n, self.observation_size, self.max_workgroups, p(ws), ws.numel(),
-            _lib.current_stream()),
-            'tonic_value_regression_grad')
+            low, high, _lib.current_stream()), 'tonic_value_regression_grad_ranged')
 
     def enqueue_step(self, n_local, info_row, allreduce=True):
         if self.stock:
