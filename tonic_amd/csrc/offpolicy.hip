@@ -21,6 +21,7 @@
 #include "collector_q.h"
 #include "bufstore.h"
 
+#include <algorithm>
 #include <mutex>
 
 namespace tonic {
@@ -838,11 +839,6 @@ void add_critic_images(ImgBuild& b, const float* params, CriticShape s, int nets
     b.add(p + o.W1, o.ld1, s.H, s.O + s.A, at, v.t1a, true, s.O, s.A);
   }
 }
-int64_t images_floats(int O, int A, int H, int heads) {
-  // [actor | target actor | two critics | two target critics], 256-byte slots
-  return 2 * round_up(actor_images(O, H, A, heads).bytes, 256) / 4 +
-         2 * round_up(2 * critic_images(O, A, H).bytes, 256) / 4;
-}
 bool images_serve(int O, int A, int H) {
   return g_q_images.load() != 0 && H >= 16 && H <= 256 && H % 16 == 0 && A <= 64 &&
          mlp_image_pass_supported(O + A, H);
@@ -865,6 +861,36 @@ struct PolicyTail {
   int enc_ld;
 };
 
+// The fused form's arguments (a plain torso, mlp_forward_supported(H, A, heads)); tail != null: folded into the
+// launch (mlp_policy_tail_supported(H, A)); img: the weight images the products run on (null, or a null block: none).
+MlpFwdArgs actor_forward_args(const float* params, ActorShape s, const float* obs, int ldx, int B, float* h1,
+                              float* h2, float* head0, float* head1, int ldh, bool tanh_head,
+                              const PolicyTail* tail, const ActorImg* img) {
+  const ActorParams p(params, s);
+  MlpFwdArgs f{};
+  f.X = obs; f.ldx = ldx; f.K1 = s.O;
+  f.W1 = p.W1; f.b1 = p.b1; f.W2 = p.W2; f.b2 = p.b2; f.ldw1 = p.ld1; f.ldw2 = p.ldH;
+  f.Wh[0] = p.head_w(0); f.bh[0] = p.head_b(0);
+  f.Wh[1] = p.head_w(s.heads - 1); f.bh[1] = p.head_b(s.heads - 1);
+  f.heads = s.heads; f.NH = s.A;
+  f.h1 = h1; f.h2 = h2; f.ldh = s.hp();
+  f.out[0] = head0; f.out[1] = s.heads == 2 ? head1 : head0; f.ldo = ldh;
+  f.act[0] = tanh_head ? ACT_TANH : ACT_NONE; f.act[1] = ACT_NONE;
+  f.B = B; f.H = s.H; f.split = 1 << 30;
+  if (img != nullptr && img->block != nullptr)
+    f.img = FwdImages{img->block, img->v.f1, img->v.f2, {img->v.fh[0], img->v.fh[s.heads - 1]}, 0, 0};
+  if (tail != nullptr) {
+    f.post = tail->post; f.post_eps = tail->eps; f.post_actions = tail->actions;
+    f.post_sigma = tail->sigma; f.post_logp = tail->logp;
+    f.noise_scale = tail->noise_scale; f.noise_clip = tail->noise_clip;
+    f.scale_lo = s.scale_lo; f.scale_hi = s.scale_hi;
+    f.enc_obs = tail->enc_obs; f.enc_obs2 = tail->enc_obs2; f.enc_act2 = tail->enc_act2;
+    f.enc_mean = tail->enc_mean; f.enc_std = tail->enc_std; f.enc_clip = tail->enc_clip;
+    f.enc_out = tail->enc_out; f.enc_out2 = tail->enc_out2; f.enc_O = s.O; f.enc_ld = tail->enc_ld;
+  }
+  return f;
+}
+
 int actor_forward(const float* params, ActorShape s, const float* obs, int B, float* h1,
                   float* h2, float* head0, float* head1, int ldh, bool tanh_head,
                   hipStream_t st, const PolicyTail* tail = nullptr, bool* tail_done = nullptr,
@@ -875,32 +901,14 @@ int actor_forward(const float* params, ActorShape s, const float* obs, int B, fl
   if (tail_done != nullptr) *tail_done = false;
   const int HP = s.hp();
   if (s.plain() && mlp_forward_supported(s.H, s.A, s.heads)) {      // one launch for torso + heads
-    MlpFwdArgs f{};
-    f.X = obs; f.ldx = ldx; f.K1 = s.O;
-    f.W1 = p.W1; f.b1 = p.b1; f.W2 = p.W2; f.b2 = p.b2; f.ldw1 = p.ld1; f.ldw2 = p.ldH;
-    f.Wh[0] = p.head_w(0); f.bh[0] = p.head_b(0);
-    f.Wh[1] = p.head_w(s.heads - 1); f.bh[1] = p.head_b(s.heads - 1);
-    f.heads = s.heads; f.NH = s.A;
-    f.h1 = h1; f.h2 = h2; f.ldh = HP;
-    f.out[0] = head0; f.out[1] = s.heads == 2 ? head1 : head0; f.ldo = ldh;
-    f.act[0] = tanh_head ? ACT_TANH : ACT_NONE; f.act[1] = ACT_NONE;
-    f.B = B; f.H = s.H; f.split = 1 << 30;
-    if (img != nullptr && img->block != nullptr)
-      f.img = FwdImages{img->block, img->v.f1, img->v.f2, {img->v.fh[0], img->v.fh[s.heads - 1]}, 0, 0};
+    const bool fuse_tail = tail != nullptr && g_policy_tail != 0 && mlp_policy_tail_supported(s.H, s.A);
+    MlpFwdArgs f = actor_forward_args(params, s, obs, ldx, B, h1, h2, head0, head1, ldh, tanh_head,
+                                      fuse_tail ? tail : nullptr, img);
     if (step != nullptr) {       // a step of a collector's block: completion words, the rows' device copy
       f.done_flags = step->done_flags; f.done_seq = step->seq; f.rows_out = rows_out; f.rows_ld = s.O;
       if (store != nullptr) { f.store = *store; f.store_on = 1; }
     }
-    if (tail != nullptr && g_policy_tail != 0 && mlp_policy_tail_supported(s.H, s.A)) {
-      f.post = tail->post; f.post_eps = tail->eps; f.post_actions = tail->actions;
-      f.post_sigma = tail->sigma; f.post_logp = tail->logp;
-      f.noise_scale = tail->noise_scale; f.noise_clip = tail->noise_clip;
-      f.scale_lo = s.scale_lo; f.scale_hi = s.scale_hi;
-      f.enc_obs = tail->enc_obs; f.enc_obs2 = tail->enc_obs2; f.enc_act2 = tail->enc_act2;
-      f.enc_mean = tail->enc_mean; f.enc_std = tail->enc_std; f.enc_clip = tail->enc_clip;
-      f.enc_out = tail->enc_out; f.enc_out2 = tail->enc_out2; f.enc_O = s.O; f.enc_ld = tail->enc_ld;
-      if (tail_done != nullptr) *tail_done = true;
-    }
+    if (tail_done != nullptr) *tail_done = fuse_tail;
     return launch_mlp_forward(f, 1, st);
   }
   // layer by layer: one launch per layer (bias + activation in the epilogue), then one per head
@@ -920,6 +928,35 @@ int actor_forward(const float* params, ActorShape s, const float* obs, int B, fl
     g = gemm(top, HP, p.head_w(1), p.ldO, head1, ldh, B, s.A, s.last());
     g.bias = p.head_b(1);
     TRY(launch_gemm('c', 'c', g, 1, st));
+  }
+  return TONIC_OK;
+}
+
+// One policy pass: the forward with its tail, and — where the tail did not fuse — what the tail says as launches of
+// their own: the stand-alone kernel of tail.post on the head outputs, then the critics' input rows (tail.enc_out; a
+// second pair with tail.enc_out2).  The launch error, if any, is the caller's TONIC_CHECK_LAUNCH to report.
+int policy_pass(const float* params, ActorShape s, const float* obs, int B, float* h1, float* h2, float* head0,
+                float* head1, int ldh, bool tanh_head, hipStream_t st, const PolicyTail& tail,
+                const ActorImg* img = nullptr) {
+  bool tail_done = false;
+  TRY(actor_forward(params, s, obs, B, h1, h2, head0, head1, ldh, tanh_head, st, &tail, &tail_done, 0, img));
+  if (tail_done) return TONIC_OK;
+  const int threads = 256, A = s.A;
+  if (tail.post == POST_TARGET_NOISE) {
+    hipLaunchKernelGGL(td3_target_action_kernel, dim3((B * A + threads - 1) / threads), dim3(threads), 0, st,
+                       head0, ldh, tail.eps, tail.actions, B, A, tail.noise_scale, tail.noise_clip);
+  } else if (tail.post == POST_COPY) {
+    hipLaunchKernelGGL(copy_actions_kernel, dim3((B * A + threads - 1) / threads), dim3(threads), 0, st, head0,
+                       ldh, tail.actions, B, A);
+  } else {
+    hipLaunchKernelGGL(sac_sample_kernel, dim3((B * sample_group(A) + threads - 1) / threads), dim3(threads), 0,
+                       st, head0, head1, tail.eps, ldh, tail.actions, tail.logp, tail.sigma, B, A, sample_group(A),
+                       s.scale_lo, s.scale_hi);
+  }
+  if (tail.enc_out != nullptr) {
+    hipLaunchKernelGGL(encode_kernel, dim3((B * (s.O + A) + threads - 1) / threads, tail.enc_out2 != nullptr ? 2 : 1),
+                       dim3(threads), 0, st, tail.enc_obs, tail.actions, tail.enc_mean, tail.enc_std, tail.enc_clip,
+                       tail.enc_out, B, s.O, A, tail.enc_ld, tail.enc_obs2, tail.enc_act2, tail.enc_out2);
   }
   return TONIC_OK;
 }
@@ -1122,17 +1159,29 @@ int critics_backward(const float* params, CriticShape s, int nets, const float* 
   return TONIC_OK;
 }
 
+// One workspace, one layout type: its constructor performs the takes, in their order, and keeps the pointers.  A
+// size query runs the same constructor over a workspace with a null base (measure) and returns `used`, so that no
+// size is stated twice and no take sequence can outgrow what its query answered.
 struct Workspace {
-  char* base;
-  int64_t used, capacity;
+  char* base;                  // null: a size query — the takes only count
+  int64_t used;
   float* take(int64_t floats) {
-    float* p = reinterpret_cast<float*>(base + used);
+    float* p = base != nullptr ? reinterpret_cast<float*>(base + used) : nullptr;
     used += round_up(floats * 4, 256);
     return p;
   }
 };
+// the second of two arrays taken as one region (null with the region: a size query)
+inline float* behind(float* p, int64_t floats) { return p != nullptr ? p + floats : nullptr; }
+template <typename Layout, typename... Args>
+int64_t measure(Args... args) {
+  Workspace ws{nullptr, 0};
+  const Layout layout(ws, args...);
+  return ws.used;
+}
 
-// The six networks' image blocks, carved from the END of a workspace's takes (so that nothing else moves).
+// The six networks' image blocks [actor | target actor | two critics | two target critics] in 256-byte slots, carved
+// from the END of a workspace's takes (so that nothing else moves).
 struct ImageSet {
   ActorImg actor, target_actor;
   CriticImg critics, target_critics;       // (critics.second / .target = the targets and vice versa, as needed)
@@ -1155,15 +1204,63 @@ ImageSet take_images(Workspace& ws, int O, int A, int H, int heads, bool on) {
   return im;
 }
 
-int64_t offpolicy_workspace_floats(int B, int O, int A, int H) {
-  // (every hidden array below holds hidden_layers(H) layers: HP stands for half of them, two layers' pitch)
-  const int64_t Bp = pad16(B), ldx = pitch16(O + A), ldh = pad16(A), HP = hidden_pitch(H) * hidden_layers(H) / 2;
-  // actor h1,h2 + 2 heads + act + sigma + logp ; X ; critics h1,h2,q,dq,dh2,dh1 (x2) ; dX ; dloc,dspre,dah2,dah1
-  return 2 * Bp * HP + 2 * Bp * ldh + 2 * Bp * A + Bp + Bp * ldx + 2 * (4 * Bp * HP + 2 * Bp) +
-         Bp * ldx + 2 * Bp * ldh + 2 * Bp * HP + 2 * Bp * ldh + 64 * 16 +
-         4 * Bp * HP + Bp * ldx + 4 * Bp +                // second input + four-network forward
-         (hidden_plain(H) ? images_floats(O, A, H, 2) : 0);     // the weight images (mlpimg.h)
-}
+// The layouts of tonic_offpolicy_workspace_bytes' four users.  H: the torso's own code (torso_code).  A network's
+// hidden activations are ONE region of hidden_layers(H) layers (layer_at), hs floats each; `images`: the entry's
+// run-time decision — the query measures with what a plain torso may ask for (a Gaussian policy's images).
+struct PolicyForwardLayout {             // tonic_policy_forward
+  float *h1, *h2, *head0, *head1;
+  PolicyForwardLayout(Workspace& ws, int B, int A, int32_t H) {
+    const int64_t Bp = pad16(B), hs = Bp * hidden_pitch(H);
+    h1 = ws.take(hidden_layers(H) * hs); h2 = behind(h1, hs);
+    head0 = ws.take(Bp * pad16(A)); head1 = ws.take(Bp * pad16(A));
+  }
+};
+struct CollectorActLayout {              // tonic_collector_q_act (the fused forward: a plain torso)
+  float *h1, *h2, *head0, *head1;
+  CollectorActLayout(Workspace& ws, int B, int A, int32_t H) {
+    const int64_t Bp = pad16(B), hs = Bp * hidden_pitch(H);
+    h1 = ws.take(hs); h2 = ws.take(hs);
+    head0 = ws.take(Bp * pad16(A)); head1 = ws.take(Bp * pad16(A));
+  }
+};
+struct TwinQLayout {                     // the critic step (tonic_twin_q_grad*)
+  float *a_h1, *a_h2, *head0, *head1, *next_act, *logp, *X, *X2, *h1_all, *h2_all, *q_all, *dq, *dh2, *dh1;
+  ImageSet im;
+  TwinQLayout(Workspace& ws, int B, int O, int A, int32_t H, int heads, bool images) {
+    const int64_t Bp = pad16(B), ldx = pitch16(O + A), ldh = pad16(A), hs = Bp * hidden_pitch(H), L = hidden_layers(H);
+    a_h1 = ws.take(L * hs); a_h2 = behind(a_h1, hs);
+    head0 = ws.take(Bp * ldh); head1 = ws.take(Bp * ldh);
+    next_act = ws.take(Bp * A); logp = ws.take(Bp);
+    // target critics on (s', a') and online critics on (s, a) share ONE forward launch: inputs X /
+    // X2, activations and values laid out [targets | online]
+    X = ws.take(Bp * ldx); X2 = ws.take(Bp * ldx);
+    h1_all = ws.take(L * 4 * hs); h2_all = behind(h1_all, 4 * hs);
+    q_all = ws.take(4 * Bp);
+    dq = ws.take(2 * Bp);
+    dh2 = ws.take(L * 2 * hs); dh1 = behind(dh2, 2 * hs);
+    im = take_images(ws, O, A, H, heads, images);
+  }
+};
+struct ActorQLayout {                    // the actor step through the critics (tonic_actor_q_grad*)
+  float *a_h1, *a_h2, *head0, *head1, *act, *sigma, *logp, *X, *c_h1, *c_h2, *q, *dq, *dh2, *dh1, *dxa, *dloc,
+      *dspre, *da_h2, *da_h1;
+  ImageSet im;
+  ActorQLayout(Workspace& ws, int B, int O, int A, int32_t H, int heads, bool images) {
+    const int64_t Bp = pad16(B), ldx = pitch16(O + A), ldh = pad16(A), hs = Bp * hidden_pitch(H), L = hidden_layers(H);
+    a_h1 = ws.take(L * hs); a_h2 = behind(a_h1, hs);
+    head0 = ws.take(Bp * ldh); head1 = ws.take(Bp * ldh);
+    act = ws.take(Bp * A); sigma = ws.take(Bp * A);
+    logp = ws.take(Bp);
+    X = ws.take(Bp * ldx);
+    c_h1 = ws.take(L * 2 * hs); c_h2 = behind(c_h1, 2 * hs);
+    q = ws.take(2 * Bp); dq = ws.take(2 * Bp);
+    dh2 = ws.take(L * 2 * hs); dh1 = behind(dh2, 2 * hs);
+    dxa = ws.take(2 * Bp * ldh);                  // action columns of the critics' input gradients
+    dloc = ws.take(Bp * ldh); dspre = ws.take(Bp * ldh);
+    da_h2 = ws.take(L * hs); da_h1 = behind(da_h2, hs);
+    im = take_images(ws, O, A, H, heads, images);
+  }
+};
 
 }  // namespace
 }  // namespace tonic
@@ -1172,7 +1269,11 @@ using namespace tonic;
 
 extern "C" int64_t tonic_offpolicy_workspace_bytes(int32_t B, int32_t O, int32_t A, int32_t H) {
   H = torso_code(H);
-  return (offpolicy_workspace_floats(B, O, A, H) + 64 * 30) * 4;
+  // the largest of its four users' layouts, with the images wherever a torso may have them (a plain one: never by
+  // the run-time switches — a query is a function of its arguments) and a Gaussian policy's two heads
+  const bool images = hidden_plain(H);
+  return std::max({measure<TwinQLayout>(B, O, A, H, 2, images), measure<ActorQLayout>(B, O, A, H, 2, images),
+                   measure<PolicyForwardLayout>(B, A, H), measure<CollectorActLayout>(B, A, H)});
 }
 
 extern "C" int32_t tonic_mlp_weight_stride(int32_t cols) { return weight_ld(cols); }
@@ -1271,34 +1372,21 @@ extern "C" int tonic_policy_forward(const float* d_actor_params, const float* d_
   TONIC_REQUIRE(workspace_bytes >= tonic_offpolicy_workspace_bytes(B, O, A, H),
                 TONIC_ERR_WORKSPACE, "tonic_policy_forward: workspace too small");
   hipStream_t st = as_stream(stream);
-  const int Bp = pad16(B), ldh = pad16(A), HP = hidden_pitch(H);
-  Workspace ws{static_cast<char*>(d_workspace), 0, workspace_bytes};
-  float* h1 = ws.take((int64_t)hidden_layers(H) * Bp * HP); float* h2 = h1 + (int64_t)Bp * HP;
-  float* head0 = ws.take((int64_t)Bp * ldh); float* head1 = ws.take((int64_t)Bp * ldh);
+  const int ldh = pad16(A);
+  Workspace ws{static_cast<char*>(d_workspace), 0};
+  const PolicyForwardLayout w(ws, B, A, H);
   const ActorShape s = actor_shape(O, H, A, kind == 0 ? 1 : 2);     // (with the scale's bounds of the code)
   const int threads = 256;
   if (kind == 2) {       // Gaussian head with a tanh loc (MPO, mpo.py:77-85): a = loc + sigma * eps
-    TRY(actor_forward(d_actor_params, s, d_observations, B, h1, h2, head0, head1, ldh, true, st));
+    TRY(actor_forward(d_actor_params, s, d_observations, B, w.h1, w.h2, w.head0, w.head1, ldh, true, st));
     hipLaunchKernelGGL(gaussian_sample_kernel, dim3((B * A + threads - 1) / threads), dim3(threads),
-                       0, st, head0, head1, d_eps, ldh, d_actions, B, A, s.scale_lo, s.scale_hi);
+                       0, st, w.head0, w.head1, d_eps, ldh, d_actions, B, A, s.scale_lo, s.scale_hi);
     TONIC_CHECK_LAUNCH("tonic_policy_forward");
     return TONIC_OK;
   }
   PolicyTail tail{};
   tail.post = kind == 0 ? POST_COPY : POST_SQUASHED_SAMPLE; tail.eps = d_eps; tail.actions = d_actions;
-  bool tail_done = false;
-  TRY(actor_forward(d_actor_params, s, d_observations, B, h1, h2, head0, head1, ldh, kind == 0, st,
-                    &tail, &tail_done));
-  if (tail_done) {
-  } else if (kind == 0) {
-    hipLaunchKernelGGL(copy_actions_kernel, dim3((B * A + threads - 1) / threads), dim3(threads),
-                       0, st, head0, ldh, d_actions, B, A);
-  } else {
-    hipLaunchKernelGGL(sac_sample_kernel,
-                       dim3((B * sample_group(A) + threads - 1) / threads), dim3(threads), 0, st,
-                       head0, head1, d_eps, ldh, d_actions, (float*)nullptr, (float*)nullptr, B, A,
-                       sample_group(A), s.scale_lo, s.scale_hi);
-  }
+  TRY(policy_pass(d_actor_params, s, d_observations, B, w.h1, w.h2, w.head0, w.head1, ldh, kind == 0, st, tail));
   TONIC_CHECK_LAUNCH("tonic_policy_forward");
   return TONIC_OK;
 }
@@ -1338,10 +1426,9 @@ extern "C" int tonic_collector_q_act(tonic_collector_t* collector, const float* 
   TONIC_REQUIRE(workspace_bytes >= tonic_offpolicy_workspace_bytes((int32_t)W, O, A, H), TONIC_ERR_WORKSPACE,
                 "tonic_collector_q_act: workspace too small");
   hipStream_t st = as_stream(stream);
-  const int B = (int)W, Bp = pad16(B), ldh = pad16(A), HP = hidden_pitch(H);
-  Workspace ws{static_cast<char*>(d_workspace), 0, workspace_bytes};
-  float* h1 = ws.take((int64_t)Bp * HP); float* h2 = ws.take((int64_t)Bp * HP);
-  float* head0 = ws.take((int64_t)Bp * ldh); float* head1 = ws.take((int64_t)Bp * ldh);
+  const int B = (int)W, ldh = pad16(A);
+  Workspace ws{static_cast<char*>(d_workspace), 0};
+  const CollectorActLayout w(ws, B, A, H);
   // the actor's weight images (mlpimg.h): the caller's buffer, rebuilt here when it says the parameters moved
   const ActorImg img{static_cast<char*>(d_actor_images), nullptr, actor_images(O, s.H, A, s.heads)};
   if (rebuild_images != 0) {
@@ -1367,8 +1454,8 @@ extern "C" int tonic_collector_q_act(tonic_collector_t* collector, const float* 
   PolicyTail tail{};
   tail.post = kind == 0 ? POST_COPY : POST_SQUASHED_SAMPLE; tail.eps = step.eps; tail.actions = step.actions_out;
   bool tail_done = false;
-  TRY(actor_forward(d_actor_params, s, step.observations, B, h1, h2, head0, head1, ldh, kind == 0, st, &tail,
-                    &tail_done, 0, &img, &step, d_rows_out, store != nullptr ? &st_args : nullptr));
+  TRY(actor_forward(d_actor_params, s, step.observations, B, w.h1, w.h2, w.head0, w.head1, ldh, kind == 0, st,
+                    &tail, &tail_done, 0, &img, &step, d_rows_out, store != nullptr ? &st_args : nullptr));
   TONIC_REQUIRE(tail_done, TONIC_ERR_UNSUPPORTED_SHAPE, "tonic_collector_q_act: the policy tail did not fuse");
   TONIC_CHECK_LAUNCH("tonic_collector_q_act");
   return TONIC_OK;
@@ -1396,94 +1483,42 @@ extern "C" int tonic_critic_loss_check(const tonic_critic_loss_t* loss) {
   return TONIC_OK;
 }
 
-extern "C" int tonic_twin_q_grad(int32_t kind, const float* d_policy_params,
-                                 const float* d_target_critics, const float* d_critics,
-                                 const float* d_norm_mean, const float* d_norm_std,
-                                 double norm_clip,
-                                 const float* d_observations, const float* d_actions,
-                                 const float* d_next_observations, const float* d_rewards,
-                                 const float* d_discounts, const float* d_eps,
-                                 float* d_grad_sums, int32_t B, int32_t O, int32_t H, int32_t A,
-                                 double entropy_coeff, double noise_scale, double noise_clip,
-                                 void* d_workspace, int64_t workspace_bytes, void* stream) {
-  return tonic_twin_q_grad_loss(kind, d_policy_params, d_target_critics, d_critics, d_norm_mean, d_norm_std,
-                                norm_clip, d_observations, d_actions, d_next_observations, d_rewards, d_discounts,
-                                d_eps, d_grad_sums, B, O, H, A, entropy_coeff, noise_scale, noise_clip, nullptr,
-                                d_workspace, workspace_bytes, stream);
-}
-
-// ... with the critic's loss (`loss=` of the reference's updaters, critics.py:58,142,189): NULL = MSE
-extern "C" int tonic_twin_q_grad_loss(int32_t kind, const float* d_policy_params,
-                                      const float* d_target_critics, const float* d_critics,
-                                      const float* d_norm_mean, const float* d_norm_std,
-                                      double norm_clip,
-                                      const float* d_observations, const float* d_actions,
-                                      const float* d_next_observations, const float* d_rewards,
-                                      const float* d_discounts, const float* d_eps,
-                                      float* d_grad_sums, int32_t B, int32_t O, int32_t H, int32_t A,
-                                      double entropy_coeff, double noise_scale, double noise_clip,
-                                      const tonic_critic_loss_t* loss,
-                                      void* d_workspace, int64_t workspace_bytes, void* stream) {
-  return tonic_twin_q_grad_ranged(kind, d_policy_params, d_target_critics, d_critics, d_norm_mean, d_norm_std,
-                                  norm_clip, d_observations, d_actions, d_next_observations, d_rewards, d_discounts,
-                                  d_eps, d_grad_sums, B, O, H, A, entropy_coeff, noise_scale, noise_clip, loss,
-                                  nullptr, nullptr, d_workspace, workspace_bytes, stream);
-}
-
-// ... for critics whose value heads squash into the Return normaliser's [low, high] (models/critics.py:17-19):
-// online and target critics publish v, the TD loss, its gradient and the logged sums are those of v.  NULL / NULL:
-// the plain heads, the launches and bits of tonic_twin_q_grad_loss.
-extern "C" int tonic_twin_q_grad_ranged(int32_t kind, const float* d_policy_params,
-                                        const float* d_target_critics, const float* d_critics,
-                                        const float* d_norm_mean, const float* d_norm_std,
-                                        double norm_clip,
-                                        const float* d_observations, const float* d_actions,
-                                        const float* d_next_observations, const float* d_rewards,
-                                        const float* d_discounts, const float* d_eps,
-                                        float* d_grad_sums, int32_t B, int32_t O, int32_t H, int32_t A,
-                                        double entropy_coeff, double noise_scale, double noise_clip,
-                                        const tonic_critic_loss_t* loss,
-                                        const float* d_value_low, const float* d_value_high,
-                                        void* d_workspace, int64_t workspace_bytes, void* stream) {
+namespace {
+int twin_q_grad(int32_t kind, const float* d_policy_params, const float* d_target_critics, const float* d_critics,
+                const float* d_norm_mean, const float* d_norm_std, double norm_clip, const float* d_observations,
+                const float* d_actions, const float* d_next_observations, const float* d_rewards,
+                const float* d_discounts, const float* d_eps, float* d_grad_sums, int32_t B, int32_t O, int32_t H,
+                int32_t A, double entropy_coeff, double noise_scale, double noise_clip,
+                const tonic_critic_loss_t* loss, const float* d_value_low, const float* d_value_high,
+                void* d_workspace, int64_t workspace_bytes, void* stream) {
   TONIC_REQUIRE((d_value_low == nullptr) == (d_value_high == nullptr), TONIC_ERR_INVALID_ARGUMENT,
                 "tonic_twin_q_grad_ranged: %s is NULL and the other bound is not (both or neither)",
                 d_value_low == nullptr ? "d_value_low" : "d_value_high");
   TRY(tonic_critic_loss_check(loss));
-  TONIC_REQUIRE(d_policy_params && d_target_critics && d_critics && d_norm_mean && d_norm_std &&
-                    d_observations && d_actions && d_next_observations && d_rewards &&
-                    d_discounts && (d_eps || kind == 2) && d_grad_sums && d_workspace && B > 0 &&
-                    kind >= 0 && kind <= 2 && hidden_known(H),
+  TONIC_REQUIRE(d_policy_params && d_target_critics && d_critics && d_norm_mean && d_norm_std && d_observations &&
+                    d_actions && d_next_observations && d_rewards && d_discounts && (d_eps || kind == 2) &&
+                    d_grad_sums && d_workspace && B > 0 && kind >= 0 && kind <= 2 && hidden_known(H),
                 TONIC_ERR_INVALID_ARGUMENT, "tonic_twin_q_grad: bad argument");
-  TONIC_REQUIRE(workspace_bytes >= tonic_offpolicy_workspace_bytes(B, O, A, H),
-                TONIC_ERR_WORKSPACE, "tonic_twin_q_grad: workspace too small");
+  TONIC_REQUIRE(workspace_bytes >= tonic_offpolicy_workspace_bytes(B, O, A, H), TONIC_ERR_WORKSPACE,
+                "tonic_twin_q_grad: workspace too small");
   hipStream_t st = as_stream(stream);
   const ActorShape as = actor_shape(O, H, A, kind == 1 ? 2 : 1);
   H = torso_code(H);                           // (the bounds are in `as`; what follows sizes by the torso)
-  const int Bp = pad16(B), ldx = pitch16(O + A), ldh = pad16(A), threads = 256, HP = hidden_pitch(H);
+  const int Bp = pad16(B), ldx = pitch16(O + A), ldh = pad16(A);
   const CriticShape cs = critic_shape(O, A, H);
-  const int64_t Pc = critic_count(cs);
-  Workspace ws{static_cast<char*>(d_workspace), 0, workspace_bytes};
-  const int64_t hs = (int64_t)Bp * HP, layers = hidden_layers(H);     // (layers: see layer_at)
-  float* a_h1 = ws.take(layers * hs); float* a_h2 = a_h1 + hs;
-  float* head0 = ws.take((int64_t)Bp * ldh); float* head1 = ws.take((int64_t)Bp * ldh);
-  float* next_act = ws.take((int64_t)Bp * A); float* logp = ws.take(Bp);
+  const int64_t Pc = critic_count(cs), hs = (int64_t)Bp * hidden_pitch(H);
   const int nets = kind == 2 ? 1 : 2;
-  // target critics on (s', a') and online critics on (s, a) share ONE forward launch: inputs X /
-  // X2, activations and values laid out [targets | online]
-  float* X = ws.take((int64_t)Bp * ldx); float* X2 = ws.take((int64_t)Bp * ldx);
-  float* h1_all = ws.take(layers * 4 * hs); float* h2_all = h1_all + 4 * hs;
-  float* q_all = ws.take(4LL * Bp);
-  float* c_h1 = h1_all + nets * hs; float* c_h2 = h2_all + nets * hs;
-  float* tq = q_all; float* q = q_all + (int64_t)nets * Bp;
-  float* dq = ws.take(2LL * Bp);
-  float* dh2 = ws.take(layers * 2 * hs); float* dh1 = dh2 + 2 * hs;
-
-  // ---- targets (no grad)
   // the fused passes' weight images (mlpimg.h), formed from the float32 parameters by THIS call: the policy's,
   // the target critics' and the critics' — the same conversion as the fused iteration's, so the same bits
-  ImageSet im = take_images(ws, O, A, H, as.heads, hidden_plain(H) && images_serve(O, A, H) &&
-                                                    mlp_forward_supported(H, A, as.heads) &&
-                                                    mlp_backward_supported(H, 1, 0, 0));
+  Workspace ws{static_cast<char*>(d_workspace), 0};
+  const TwinQLayout w(ws, B, O, A, H, as.heads,
+                      hidden_plain(H) && images_serve(O, A, H) && mlp_forward_supported(H, A, as.heads) &&
+                          mlp_backward_supported(H, 1, 0, 0));
+  const ImageSet& im = w.im;
+  float* c_h1 = w.h1_all + nets * hs; float* c_h2 = w.h2_all + nets * hs;
+  float* tq = w.q_all; float* q = w.q_all + (int64_t)nets * Bp;
+
+  // ---- targets (no grad)
   if (im.on) {
     ImgBuild build;
     add_actor_images(build, d_policy_params, as, im.actor);
@@ -1495,44 +1530,66 @@ extern "C" int tonic_twin_q_grad_ranged(int32_t kind, const float* d_policy_para
   // stored (s, a) -> X2
   PolicyTail tail{};
   tail.post = kind == 0 ? POST_TARGET_NOISE : kind == 2 ? POST_COPY : POST_SQUASHED_SAMPLE;
-  tail.eps = d_eps; tail.actions = next_act; tail.logp = kind == 1 ? logp : nullptr;
+  tail.eps = d_eps; tail.actions = w.next_act; tail.logp = kind == 1 ? w.logp : nullptr;
   tail.noise_scale = (float)noise_scale; tail.noise_clip = (float)noise_clip;
   tail.enc_obs = d_next_observations; tail.enc_obs2 = d_observations; tail.enc_act2 = d_actions;
   tail.enc_mean = d_norm_mean; tail.enc_std = d_norm_std; tail.enc_clip = clip_bound(norm_clip);
-  tail.enc_out = X; tail.enc_out2 = X2; tail.enc_ld = ldx;
-  bool tail_done = false;
-  TRY(actor_forward(d_policy_params, as, d_next_observations, B, a_h1, a_h2, head0, head1, ldh,
-                    kind != 1, st, &tail, &tail_done, 0, im.on ? &im.actor : nullptr));
-  if (tail_done) {
-  } else if (kind == 0) {
-    hipLaunchKernelGGL(td3_target_action_kernel, dim3((B * A + threads - 1) / threads),
-                       dim3(threads), 0, st, head0, ldh, d_eps, next_act, B, A,
-                       (float)noise_scale, (float)noise_clip);
-  } else if (kind == 2) {
-    hipLaunchKernelGGL(copy_actions_kernel, dim3((B * A + threads - 1) / threads), dim3(threads),
-                       0, st, head0, ldh, next_act, B, A);
-  } else {
-    hipLaunchKernelGGL(sac_sample_kernel,
-                       dim3((B * sample_group(A) + threads - 1) / threads), dim3(threads), 0, st,
-                       head0, head1, d_eps, ldh, next_act, logp, (float*)nullptr, B, A,
-                       sample_group(A), as.scale_lo, as.scale_hi);
-  }
-  // ---- inputs of the targets (s', a') and of the online critics (s, a): one launch each for
-  //      the encoding and for the four-network forward
-  if (!tail_done) {
-    hipLaunchKernelGGL(encode_kernel, dim3((B * (O + A) + threads - 1) / threads, 2),
-                       dim3(threads), 0, st, d_next_observations, next_act, d_norm_mean, d_norm_std,
-                       clip_bound(norm_clip), X, B, O, A, ldx, d_observations, d_actions, X2);
-  }
-  TRY(critics_forward(d_target_critics, cs, nets, X, ldx, B, Bp, h1_all, h2_all, q_all, st,
-                      d_critics, X2, im.on ? &im.target_critics : nullptr, d_value_low, d_value_high));
-  const StepLoss td{LOSS_TD, d_rewards, d_discounts, tq, kind == 1 ? logp : (const float*)nullptr,
+  tail.enc_out = w.X; tail.enc_out2 = w.X2; tail.enc_ld = ldx;
+  TRY(policy_pass(d_policy_params, as, d_next_observations, B, w.a_h1, w.a_h2, w.head0, w.head1, ldh, kind != 1,
+                  st, tail, im.on ? &im.actor : nullptr));
+  // ---- the targets on (s', a') and the online critics on (s, a): one four-network forward
+  TRY(critics_forward(d_target_critics, cs, nets, w.X, ldx, B, Bp, w.h1_all, w.h2_all, w.q_all, st,
+                      d_critics, w.X2, im.on ? &im.target_critics : nullptr, d_value_low, d_value_high));
+  const StepLoss td{LOSS_TD, d_rewards, d_discounts, tq, kind == 1 ? w.logp : (const float*)nullptr,
                     (float)entropy_coeff, q, d_grad_sums + nets * Pc, critic_loss_rule(loss),
                     d_value_low, d_value_high};
-  TRY(critics_backward(d_critics, cs, nets, X2, ldx, B, Bp, c_h1, c_h2, dq, dh2, dh1, d_grad_sums,
+  TRY(critics_backward(d_critics, cs, nets, w.X2, ldx, B, Bp, c_h1, c_h2, w.dq, w.dh2, w.dh1, d_grad_sums,
                        nullptr, st, &td, nullptr, im.on ? &im.critics : nullptr));
   TONIC_CHECK_LAUNCH("tonic_twin_q_grad");
   return TONIC_OK;
+}
+}  // namespace
+
+extern "C" int tonic_twin_q_grad(
+    int32_t kind, const float* d_policy_params, const float* d_target_critics, const float* d_critics,
+    const float* d_norm_mean, const float* d_norm_std, double norm_clip, const float* d_observations,
+    const float* d_actions, const float* d_next_observations, const float* d_rewards, const float* d_discounts,
+    const float* d_eps, float* d_grad_sums, int32_t B, int32_t O, int32_t H, int32_t A, double entropy_coeff,
+    double noise_scale, double noise_clip, void* d_workspace, int64_t workspace_bytes, void* stream) {
+  return twin_q_grad(kind, d_policy_params, d_target_critics, d_critics, d_norm_mean, d_norm_std, norm_clip,
+                     d_observations, d_actions, d_next_observations, d_rewards, d_discounts, d_eps, d_grad_sums, B, O,
+                     H, A, entropy_coeff, noise_scale, noise_clip, nullptr, nullptr, nullptr, d_workspace,
+                     workspace_bytes, stream);
+}
+
+// ... with the critic's loss (`loss=` of the reference's updaters, critics.py:58,142,189): NULL = MSE
+extern "C" int tonic_twin_q_grad_loss(
+    int32_t kind, const float* d_policy_params, const float* d_target_critics, const float* d_critics,
+    const float* d_norm_mean, const float* d_norm_std, double norm_clip, const float* d_observations,
+    const float* d_actions, const float* d_next_observations, const float* d_rewards, const float* d_discounts,
+    const float* d_eps, float* d_grad_sums, int32_t B, int32_t O, int32_t H, int32_t A, double entropy_coeff,
+    double noise_scale, double noise_clip, const tonic_critic_loss_t* loss, void* d_workspace,
+    int64_t workspace_bytes, void* stream) {
+  return twin_q_grad(kind, d_policy_params, d_target_critics, d_critics, d_norm_mean, d_norm_std, norm_clip,
+                     d_observations, d_actions, d_next_observations, d_rewards, d_discounts, d_eps, d_grad_sums, B, O,
+                     H, A, entropy_coeff, noise_scale, noise_clip, loss, nullptr, nullptr, d_workspace,
+                     workspace_bytes, stream);
+}
+
+// ... for critics whose value heads squash into the Return normaliser's [low, high] (models/critics.py:17-19):
+// online and target critics publish v, the TD loss, its gradient and the logged sums are those of v.  NULL / NULL:
+// the plain heads, the launches and bits of tonic_twin_q_grad_loss.
+extern "C" int tonic_twin_q_grad_ranged(
+    int32_t kind, const float* d_policy_params, const float* d_target_critics, const float* d_critics,
+    const float* d_norm_mean, const float* d_norm_std, double norm_clip, const float* d_observations,
+    const float* d_actions, const float* d_next_observations, const float* d_rewards, const float* d_discounts,
+    const float* d_eps, float* d_grad_sums, int32_t B, int32_t O, int32_t H, int32_t A, double entropy_coeff,
+    double noise_scale, double noise_clip, const tonic_critic_loss_t* loss, const float* d_value_low,
+    const float* d_value_high, void* d_workspace, int64_t workspace_bytes, void* stream) {
+  return twin_q_grad(kind, d_policy_params, d_target_critics, d_critics, d_norm_mean, d_norm_std, norm_clip,
+                     d_observations, d_actions, d_next_observations, d_rewards, d_discounts, d_eps, d_grad_sums, B, O,
+                     H, A, entropy_coeff, noise_scale, noise_clip, loss, d_value_low, d_value_high, d_workspace,
+                     workspace_bytes, stream);
 }
 
 namespace {
@@ -1641,10 +1698,87 @@ int actor_shaped_backward(const float* params, ActorShape as, const float* X, in
                                 fold, img);
 }
 
-}  // namespace
-
 // Actor gradient through the (frozen) critics.  kind 0 = DeterministicPolicyGradient on
 // critic_1 only (actors.py:170-189 with td3.py:36), 1 = TwinCriticSoftDeterministicPolicyGradient
+// (actors.py:238-267).  Gradient SUMS for the actor + 8 statistics {loss_sum, 0.., B, ..}.
+int actor_q_grad(int32_t kind, const float* d_actor_params, const float* d_critics, const float* d_norm_mean,
+                 const float* d_norm_std, double norm_clip, const float* d_observations, const float* d_eps,
+                 float* d_grad_sums, int32_t B, int32_t O, int32_t H, int32_t A, double entropy_coeff,
+                 const float* d_value_low, const float* d_value_high, void* d_workspace, int64_t workspace_bytes,
+                 void* stream) {
+  TONIC_REQUIRE((d_value_low == nullptr) == (d_value_high == nullptr), TONIC_ERR_INVALID_ARGUMENT,
+                "tonic_actor_q_grad_ranged: %s is NULL and the other bound is not (both or neither)",
+                d_value_low == nullptr ? "d_value_low" : "d_value_high");
+  TONIC_REQUIRE(d_actor_params && d_critics && d_norm_mean && d_norm_std && d_observations &&
+                    d_grad_sums && d_workspace && B > 0 && (kind == 0 || d_eps) && hidden_known(H),
+                TONIC_ERR_INVALID_ARGUMENT, "tonic_actor_q_grad: bad argument");
+  TONIC_REQUIRE(workspace_bytes >= tonic_offpolicy_workspace_bytes(B, O, A, H),
+                TONIC_ERR_WORKSPACE, "tonic_actor_q_grad: workspace too small");
+  hipStream_t st = as_stream(stream);
+  const ActorShape as = actor_shape(O, H, A, kind == 0 ? 1 : 2);
+  H = torso_code(H);                           // (the bounds are in `as`; what follows sizes by the torso)
+  const int Bp = pad16(B), ldx = pitch16(O + A), ldh = pad16(A), threads = 256;
+  const int nets = kind == 0 ? 1 : 2;
+  const CriticShape cs = critic_shape(O, A, H);
+  const int64_t Pa = actor_count(as);
+  // the weight images of the actor and the critics (mlpimg.h), formed by this call (see twin_q_grad)
+  Workspace ws{static_cast<char*>(d_workspace), 0};
+  const ActorQLayout w(ws, B, O, A, H, as.heads,
+                       hidden_plain(H) && images_serve(O, A, H) && mlp_forward_supported(H, A, as.heads) &&
+                           mlp_backward_supported(H, A, as.heads, 0) && mlp_backward_supported(H, 1, 0, A));
+  const ImageSet& im = w.im;
+  if (im.on) {
+    ImgBuild build;
+    add_actor_images(build, d_actor_params, as, im.actor);
+    add_critic_images(build, d_critics, cs, nets, im.critics.block, im.critics.v);
+    TRY(launch_build_images(build, st));
+  }
+
+  PolicyTail tail{};                             // the tail also encodes the critics' input (s, a)
+  tail.post = kind == 0 ? POST_COPY : POST_SQUASHED_SAMPLE; tail.eps = d_eps; tail.actions = w.act;
+  tail.sigma = kind == 0 ? nullptr : w.sigma; tail.logp = kind == 0 ? nullptr : w.logp;
+  tail.enc_obs = d_observations; tail.enc_mean = d_norm_mean; tail.enc_std = d_norm_std;
+  tail.enc_clip = clip_bound(norm_clip); tail.enc_out = w.X; tail.enc_ld = ldx;
+  TRY(policy_pass(d_actor_params, as, d_observations, B, w.a_h1, w.a_h2, w.head0, w.head1, ldh, kind == 0, st,
+                  tail, im.on ? &im.actor : nullptr));
+  TRY(critics_forward(d_critics, cs, nets, w.X, ldx, B, Bp, w.c_h1, w.c_h2, w.q, st, nullptr, nullptr,
+                      im.on ? &im.critics : nullptr, d_value_low, d_value_high));
+  const StepLoss objective{LOSS_ACTOR, nullptr, nullptr, nullptr, w.logp, (float)entropy_coeff, w.q,
+                           d_grad_sums + Pa, CriticLoss{TONIC_LOSS_MSE, 0.f}, d_value_low, d_value_high};
+  TRY(critics_backward(d_critics, cs, nets, w.X, ldx, B, Bp, w.c_h1, w.c_h2, w.dq, w.dh2, w.dh1, nullptr, w.dxa,
+                       st, &objective, nullptr, im.on ? &im.critics : nullptr));
+  hipLaunchKernelGGL(actor_head_backward_kernel, dim3((B * A + threads - 1) / threads), dim3(threads), 0, st, w.dxa,
+                     nets == 2 ? w.dxa + (int64_t)Bp * ldh : (float*)nullptr, ldh, w.act, d_eps, w.sigma, w.head1, ldh,
+                     (float)entropy_coeff, kind == 1 ? 1 : 0, w.dloc, w.dspre, B, A, as.scale_lo, as.scale_hi);
+  TRY(actor_shaped_backward(d_actor_params, as, d_observations, O, B, w.a_h1, w.a_h2, w.dloc,
+                            kind == 1 ? w.dspre : nullptr, ldh, w.da_h2, w.da_h1, d_grad_sums, nullptr, 0, 0, st,
+                            nullptr, nullptr, im.on ? &im.actor : nullptr));
+  TONIC_CHECK_LAUNCH("tonic_actor_q_grad");
+  return TONIC_OK;
+}
+
+}  // namespace
+
+extern "C" int tonic_actor_q_grad(
+    int32_t kind, const float* d_actor_params, const float* d_critics, const float* d_norm_mean,
+    const float* d_norm_std, double norm_clip, const float* d_observations, const float* d_eps, float* d_grad_sums,
+    int32_t B, int32_t O, int32_t H, int32_t A, double entropy_coeff, void* d_workspace, int64_t workspace_bytes,
+    void* stream) {
+  return actor_q_grad(kind, d_actor_params, d_critics, d_norm_mean, d_norm_std, norm_clip, d_observations, d_eps,
+                      d_grad_sums, B, O, H, A, entropy_coeff, nullptr, nullptr, d_workspace, workspace_bytes, stream);
+}
+
+// ... through critics whose value heads squash (tonic_twin_q_grad_ranged): the objective and its logged sum are
+// those of v, the gradient that enters each head is multiplied by dv/dz.  NULL / NULL: tonic_actor_q_grad.
+extern "C" int tonic_actor_q_grad_ranged(
+    int32_t kind, const float* d_actor_params, const float* d_critics, const float* d_norm_mean,
+    const float* d_norm_std, double norm_clip, const float* d_observations, const float* d_eps, float* d_grad_sums,
+    int32_t B, int32_t O, int32_t H, int32_t A, double entropy_coeff, const float* d_value_low,
+    const float* d_value_high, void* d_workspace, int64_t workspace_bytes, void* stream) {
+  return actor_q_grad(kind, d_actor_params, d_critics, d_norm_mean, d_norm_std, norm_clip, d_observations, d_eps,
+                      d_grad_sums, B, O, H, A, entropy_coeff, d_value_low, d_value_high, d_workspace, workspace_bytes,
+                      stream);
+}
 
 // ------------------------------------------------------------------ one whole learner iteration
 // ddpg.py:95-112 / td3.py:38-55 / sac.py with the launches of the two updaters merged where they do
@@ -1670,28 +1804,63 @@ namespace {
 // workspace, so that it stays where it is whatever batch size the workspace is used with next.
 constexpr int64_t kChainSyncArea = 64;               // floats
 
-int64_t q_iteration_floats(int B, int O, int A, int H) {
-  const int64_t Bp = pad16(B), ldx = pitch16(O + A), ldh = pad16(A), HP = weight_ld(H);
-  // what the policy passes (launch 1) write and the chained launches exchange: two sets (tonic_q_iteration_t.slot)
-  const int64_t set = 2 * (2 * Bp * HP + 2 * Bp * ldh)   // policy passes: h1, h2, two head outputs, x2
-                      + 3 * Bp * A + 2 * Bp              // next actions, new actions, sigma, two log-probs
-                      + 3 * Bp * ldx                     // X (s', a'), X2 (s, a), X3 (s, a_new)
-                      + 2 * Bp * ldh                     // dxa (two critics)
-                      + (Bp / 16) * kExchangeTileFloats; // the chained launches' value lines
-  return 2 * set
-         + 2 * 4 * Bp * HP + 4 * Bp                 // four-critic forward: h1, h2, values
-         + 2 * Bp + 2 * 2 * Bp * HP                 // dq, dz2, dz1 of two critics
-         + 2 * Bp * ldh                             // dloc, dspre
-         + 2 * Bp * HP                              // actor dz2, dz1
-         + kChainSyncArea                           // the chained launches' failure words (first)
-         + images_floats(O, A, H, 2);               // the six networks' weight images (mlpimg.h)
+// Everything launch 1 writes — the chained launches' exchange area (the value lines of the tiles, then the
+// critics' action-column gradients: ONE span, emptied by the policy launch of every iteration), the policy
+// passes' activations and head outputs [net 0 | net 1], the actions / log-probabilities, the critics' input
+// rows — twice: an iteration works on set `slot`, the passes it runs ahead for the next one on the other
+struct PolicySet {
+  float *xq, *dxa, *exchange_end, *p_h1, *p_h2, *head0, *head1, *next_act, *logp_next, *act, *sigma, *logp,
+      *X, *X2, *X3;
+};
+// tonic_q_iteration's workspace (H: a plain width): the failure words first, the images last
+struct QIterationLayout {
+  // (one failure word per set: the passes that run ahead clear THEIR word while this iteration's launches may set its)
+  unsigned* failed_words;
+  PolicySet sets[2];
+  float *h1_all, *h2_all, *q_all, *dq, *dh2, *dh1, *dloc, *dspre, *da_h2, *da_h1;
+  ImageSet im;
+  QIterationLayout(Workspace& ws, int B, int O, int A, int H, int heads, bool images) {
+    const int64_t Bp = pad16(B), ldx = pitch16(O + A), ldh = pad16(A), hs = Bp * weight_ld(H);
+    failed_words = reinterpret_cast<unsigned*>(ws.take(kChainSyncArea));
+    for (PolicySet& t : sets) {
+      t.xq = ws.take((Bp / 16) * kExchangeTileFloats);
+      t.dxa = ws.take(2 * Bp * ldh);
+      t.exchange_end = ws.take(0);
+      t.p_h1 = ws.take(2 * hs); t.p_h2 = ws.take(2 * hs);
+      t.head0 = ws.take(2 * Bp * ldh); t.head1 = ws.take(2 * Bp * ldh);
+      t.next_act = ws.take(Bp * A); t.logp_next = ws.take(Bp);
+      t.act = ws.take(Bp * A); t.sigma = ws.take(Bp * A);
+      t.logp = ws.take(Bp);
+      t.X = ws.take(Bp * ldx); t.X2 = ws.take(Bp * ldx);
+      t.X3 = ws.take(Bp * ldx);
+    }
+    h1_all = ws.take(4 * hs); h2_all = ws.take(4 * hs);
+    q_all = ws.take(4 * Bp);
+    dq = ws.take(2 * Bp);
+    dh2 = ws.take(2 * hs); dh1 = ws.take(2 * hs);
+    dloc = ws.take(Bp * ldh); dspre = ws.take(Bp * ldh);
+    da_h2 = ws.take(hs); da_h1 = ws.take(hs);
+    im = take_images(ws, O, A, H, heads, images);
+  }
+};
+
+// torch.optim.Adam of one block (`n` parameters at `params`) in the epilogue of its weight-gradient launch
+AdamFold adam_fold(const tonic_q_optimizer& o, float* params, int64_t n, float grad_scale, int stats_kind,
+                   const unsigned* skip) {
+  AdamFold f{};
+  f.grads = o.d_grad_sums; f.params = params; f.exp_avg = o.d_exp_avg;
+  f.exp_avg_sq = o.d_exp_avg_sq; f.state = o.d_state; f.n = n;
+  f.grad_scale = grad_scale; f.beta2 = (float)o.beta2; f.eps = (float)o.eps;
+  f.beta1_d = o.beta1; f.beta2_d = o.beta2; f.lr_d = o.lr;
+  f.stats_kind = stats_kind; f.info_row = o.d_info_row; f.consts = o.d_step_constants;
+  f.skip = skip;
+  return f;
 }
 
 }  // namespace
 
 extern "C" int64_t tonic_q_iteration_workspace_bytes(int32_t B, int32_t O, int32_t A, int32_t H) {
-  H = torso_code(H);
-  return (q_iteration_floats(B, O, A, H) + 64 * 64) * 4;       // (+ the 256-byte rounding of every take)
+  return measure<QIterationLayout>(B, O, A, torso_code(H), 2, true);       // (the images: always, a Gaussian policy's)
 }
 
 extern "C" int tonic_q_iteration_ahead_supported(int32_t B, int32_t O, int32_t H, int32_t A, int32_t nets,
@@ -1750,49 +1919,18 @@ extern "C" int tonic_q_iteration(const tonic_q_iteration_t* it, void* stream) {
   const CriticShape cs{O, A, H};
   const ActorShape as = actor_shape(O, a.H, A, heads);
   const int64_t Pc = critic_count(cs), Pa = actor_count(as), hs = (int64_t)Bp * HP;
-  Workspace ws{static_cast<char*>(a.d_workspace), 0, a.workspace_bytes};
-  // (one failure word per set: the passes that run ahead clear THEIR iteration's word while this one's launches may set theirs)
-  unsigned* failed_words = reinterpret_cast<unsigned*>(ws.take(kChainSyncArea));
-  unsigned* failed = failed_words + slot;
-  // Everything launch 1 writes — the chained launches' exchange area (the value lines of the tiles, then the
-  // critics' action-column gradients: ONE span, emptied by the policy launch of every iteration), the policy
-  // passes' activations and head outputs [net 0 | net 1], the actions / log-probabilities, the critics' input
-  // rows — twice: an iteration works on set `slot`, the passes it runs ahead for the next one on the other
-  struct PolicySet {
-    float *xq, *dxa, *exchange_end, *p_h1, *p_h2, *head0, *head1, *next_act, *logp_next, *act, *sigma, *logp,
-        *X, *X2, *X3;
-  } sets[2];
-  for (int set = 0; set < 2; ++set) {
-    PolicySet& t = sets[set];
-    t.xq = ws.take((int64_t)(Bp / 16) * kExchangeTileFloats);
-    t.dxa = ws.take(2LL * Bp * ldh);
-    t.exchange_end = ws.take(0);
-    t.p_h1 = ws.take(2 * hs); t.p_h2 = ws.take(2 * hs);
-    t.head0 = ws.take(2LL * Bp * ldh); t.head1 = ws.take(2LL * Bp * ldh);
-    t.next_act = ws.take((int64_t)Bp * A); t.logp_next = ws.take(Bp);
-    t.act = ws.take((int64_t)Bp * A); t.sigma = ws.take((int64_t)Bp * A);
-    t.logp = ws.take(Bp);
-    t.X = ws.take((int64_t)Bp * ldx); t.X2 = ws.take((int64_t)Bp * ldx);
-    t.X3 = ws.take((int64_t)Bp * ldx);
-  }
-  const PolicySet& mine = sets[slot];
-  float *xq = mine.xq, *dxa = mine.dxa, *p_h1 = mine.p_h1, *p_h2 = mine.p_h2, *head1 = mine.head1,
-        *logp_next = mine.logp_next, *act = mine.act, *sigma = mine.sigma, *logp = mine.logp, *X = mine.X,
-        *X2 = mine.X2, *X3 = mine.X3;
+  Workspace ws{static_cast<char*>(a.d_workspace), 0};
+  const QIterationLayout w(ws, B, O, A, H, heads, images_serve(O, A, H));
+  unsigned* failed = w.failed_words + slot;
+  const PolicySet& mine = w.sets[slot];
   const bool chain = g_q_chain.load() != 0;
-  float* h1_all = ws.take(4 * hs); float* h2_all = ws.take(4 * hs);
-  float* q_all = ws.take(4LL * Bp);
-  float* c_h1 = h1_all + nets * hs; float* c_h2 = h2_all + nets * hs;
-  float* tq = q_all; float* q = q_all + (int64_t)nets * Bp;
-  float* dq = ws.take(2LL * Bp);
-  float* dh2 = ws.take(2 * hs); float* dh1 = ws.take(2 * hs);
-  float* dloc = ws.take((int64_t)Bp * ldh); float* dspre = ws.take((int64_t)Bp * ldh);
-  float* da_h2 = ws.take(hs); float* da_h1 = ws.take(hs);
+  float* c_h1 = w.h1_all + nets * hs; float* c_h2 = w.h2_all + nets * hs;
+  float* tq = w.q_all; float* q = w.q_all + (int64_t)nets * Bp;
   // the weight images of the six networks (mlpimg.h): rebuilt from the float32 parameters when the caller says
   // they may have changed since this workspace last saw them (the first iteration of an update call; every call
   // in phases, where the caller's own optimizer launches step the parameters), kept up to date by the optimizer
   // epilogues of this call otherwise
-  ImageSet im = take_images(ws, O, A, H, heads, images_serve(O, A, H));
+  const ImageSet& im = w.im;
   if (im.on && (a.refresh_images != 0 || phase != 0)) {
     ImgBuild build;
     add_actor_images(build, a.d_actor, as, im.actor);
@@ -1808,26 +1946,17 @@ extern "C" int tonic_q_iteration(const tonic_q_iteration_t* it, void* stream) {
   auto policy_passes = [&](const tonic_q_iteration_t& it, const PolicySet& t, unsigned* failed_word) {
     const bool it_due = it.actor_due != 0;
     const float* policy = kind == 1 ? it.d_actor : it.d_target_actor;
-    ActorParams p(policy, as);
-    MlpFwdArgs f{};
-    f.X = it.d_next_observations; f.ldx = O; f.K1 = O;
-    f.W1 = p.W1; f.b1 = p.b1; f.W2 = p.W2; f.b2 = p.b2; f.ldw1 = p.ld1; f.ldw2 = p.ldH;
-    f.Wh[0] = p.head_w(0); f.bh[0] = p.head_b(0);
-    f.Wh[1] = p.head_w(heads - 1); f.bh[1] = p.head_b(heads - 1);
-    f.heads = heads; f.NH = A;
-    f.h1 = t.p_h1; f.h2 = t.p_h2; f.ldh = HP;
-    f.out[0] = t.head0; f.out[1] = heads == 2 ? t.head1 : t.head0; f.ldo = ldh;
-    f.act[0] = kind != 1 ? ACT_TANH : ACT_NONE; f.act[1] = ACT_NONE;
-    f.B = B; f.H = H; f.split = 1 << 30;
+    PolicyTail tail{};           // net 0: the critic step's policy on s', its tail encodes (s', a') and (s, a)
+    tail.post = kind == 0 ? POST_TARGET_NOISE : kind == 2 ? POST_COPY : POST_SQUASHED_SAMPLE;
+    tail.eps = it.d_eps_critic; tail.actions = t.next_act; tail.logp = kind == 1 ? t.logp_next : nullptr;
+    tail.noise_scale = (float)it.noise_scale; tail.noise_clip = (float)it.noise_clip;
+    tail.enc_obs = it.d_next_observations; tail.enc_obs2 = it.d_observations; tail.enc_act2 = it.d_actions;
+    tail.enc_mean = it.d_norm_mean; tail.enc_std = it.d_norm_std; tail.enc_clip = clip_bound(it.norm_clip);
+    tail.enc_out = t.X; tail.enc_out2 = t.X2; tail.enc_ld = ldx;
+    const ActorImg* pi = !im.on ? nullptr : kind == 1 ? &im.actor : &im.target_actor;
+    MlpFwdArgs f = actor_forward_args(policy, as, it.d_next_observations, O, B, t.p_h1, t.p_h2, t.head0, t.head1,
+                                      ldh, kind != 1, &tail, pi);
     f.stride_hidden = hs; f.stride_out = (int64_t)Bp * ldh;
-    f.post = kind == 0 ? POST_TARGET_NOISE : kind == 2 ? POST_COPY : POST_SQUASHED_SAMPLE;
-    f.post_eps = it.d_eps_critic; f.post_actions = t.next_act;
-    f.post_logp = kind == 1 ? t.logp_next : nullptr;
-    f.noise_scale = (float)it.noise_scale; f.noise_clip = (float)it.noise_clip;
-    f.scale_lo = as.scale_lo; f.scale_hi = as.scale_hi;
-    f.enc_obs = it.d_next_observations; f.enc_obs2 = it.d_observations; f.enc_act2 = it.d_actions;
-    f.enc_mean = it.d_norm_mean; f.enc_std = it.d_norm_std; f.enc_clip = clip_bound(it.norm_clip);
-    f.enc_out = t.X; f.enc_out2 = t.X2; f.enc_O = O; f.enc_ld = ldx;
     // (phases: the failure word is the caller's to clear — it stands for the whole update)
     if (chain) { f.reset_area = t.xq; f.reset_floats = t.exchange_end - t.xq; f.reset_failed = phase == 0 ? failed_word : nullptr; }
     if (it_due) {
@@ -1840,10 +1969,8 @@ extern "C" int tonic_q_iteration(const tonic_q_iteration_t* it, void* stream) {
       f.tail2.logp = kind == 1 ? t.logp : nullptr;
       f.tail2.enc_obs = it.d_observations; f.tail2.enc_out = t.X3;
     }
-    if (im.on) {
-      const ActorImg& pi = kind == 1 ? im.actor : im.target_actor;
-      f.img = FwdImages{pi.block, pi.v.f1, pi.v.f2, {pi.v.fh[0], pi.v.fh[heads - 1]}, 0,
-                        it_due ? im.actor.block - pi.block : 0};
+    if (pi != nullptr) {
+      if (it_due) f.img.second = im.actor.block - pi->block;
       f.hidden_from = 1;             // (net 0, the critic step's policy, has no backward)
     }
     return f;
@@ -1852,19 +1979,13 @@ extern "C" int tonic_q_iteration(const tonic_q_iteration_t* it, void* stream) {
   // ---- 2: targets on (s', a') and online critics on (s, a)
   // ---- 3 + 4: TD loss, backward chain, weight gradients + Adam (+ polyak of the critics)
   const float grad_scale = (float)(1.0 / (a.global_batch > 0 ? a.global_batch : B));
-  AdamFold cf{};
-  cf.grads = a.critic.d_grad_sums; cf.params = a.d_critics; cf.exp_avg = a.critic.d_exp_avg;
-  cf.exp_avg_sq = a.critic.d_exp_avg_sq; cf.state = a.critic.d_state; cf.n = nets * Pc;
-  cf.grad_scale = grad_scale; cf.beta2 = (float)a.critic.beta2; cf.eps = (float)a.critic.eps;
-  cf.beta1_d = a.critic.beta1; cf.beta2_d = a.critic.beta2; cf.lr_d = a.critic.lr;
-  cf.stats_kind = 3; cf.info_row = a.critic.d_info_row; cf.consts = a.critic.d_step_constants;
-  cf.skip = chain ? failed : nullptr;
+  AdamFold cf = adam_fold(a.critic, a.d_critics, nets * Pc, grad_scale, 3, chain ? failed : nullptr);
   if (due) {
     cf.target = a.d_target_critics;
     cf.polyak_keep = (float)(1.0 - a.target_coeff); cf.polyak_mix = (float)a.target_coeff;
   }
   const StepLoss td{LOSS_TD, a.d_rewards, a.d_discounts, tq,
-                    kind == 1 ? logp_next : (const float*)nullptr, (float)a.critic_entropy_coeff, q,
+                    kind == 1 ? mine.logp_next : (const float*)nullptr, (float)a.critic_entropy_coeff, q,
                     a.critic.d_grad_sums + nets * Pc, critic_loss_rule(&a.critic_loss)};
   const AdamFold* critic_fold = phase == 0 ? &cf : nullptr;       // phases: gradient sums only
   if (phase == 2) {
@@ -1874,28 +1995,28 @@ extern "C" int tonic_q_iteration(const tonic_q_iteration_t* it, void* stream) {
     // soon as the targets of their 16 rows have arrived (q_critic_step_kernel)
     QCriticStep step{};
     int launch_nets = 0;
-    step.fwd = critics_forward_args(a.d_target_critics, cs, nets, X, ldx, B, Bp, h1_all, h2_all,
-                                    q_all, a.d_critics, X2, &launch_nets, im.on ? &im.target_critics : nullptr);
-    step.fwd.xq = xq;
+    step.fwd = critics_forward_args(a.d_target_critics, cs, nets, mine.X, ldx, B, Bp, w.h1_all, w.h2_all,
+                                    w.q_all, a.d_critics, mine.X2, &launch_nets, im.on ? &im.target_critics : nullptr);
+    step.fwd.xq = mine.xq;
     step.fwd.hidden_from = nets;     // (the targets: forward only)
-    step.bwd = critics_chain_args(a.d_critics, cs, nets, B, Bp, c_h1, c_h2, dq, dh2, dh1, nullptr, &td,
+    step.bwd = critics_chain_args(a.d_critics, cs, nets, B, Bp, c_h1, c_h2, w.dq, w.dh2, w.dh1, nullptr, &td,
                                   critics_img);
     step.bwd.exchange_failed = failed;   // targets: lines 0, 1 of the tile; the online critics: lines 2, 3
-    step.bwd.l_tq = xq; step.bwd.l_tq_at = ValueLines{32, kExchangeTileFloats};
-    step.bwd.l_q = xq + 64; step.bwd.l_q_at = ValueLines{32, kExchangeTileFloats};
+    step.bwd.l_tq = mine.xq; step.bwd.l_tq_at = ValueLines{32, kExchangeTileFloats};
+    step.bwd.l_q = mine.xq + 64; step.bwd.l_q_at = ValueLines{32, kExchangeTileFloats};
     step.nets = nets;
     if (next != nullptr) {            // the next iteration's policy passes: more workgroups of this launch
-      step.ahead = policy_passes(*next, sets[slot ^ 1], failed_words + (slot ^ 1));
+      step.ahead = policy_passes(*next, w.sets[slot ^ 1], w.failed_words + (slot ^ 1));
       step.ahead_nets = next->actor_due ? 2 : 1;
     }
     TRY(launch_q_critic_step(step, st));
-    TRY(critics_weight_gradients(cs, nets, X2, ldx, B, Bp, c_h1, c_h2, dq, dh2, dh1,
+    TRY(critics_weight_gradients(cs, nets, mine.X2, ldx, B, Bp, c_h1, c_h2, w.dq, w.dh2, w.dh1,
                                  a.critic.d_grad_sums, st, critic_fold, critics_img));
   } else {
     TONIC_REQUIRE(next == nullptr, TONIC_ERR_INVALID_ARGUMENT, "tonic_q_iteration: passes ahead need the chained launches");
-    TRY(critics_forward(a.d_target_critics, cs, nets, X, ldx, B, Bp, h1_all, h2_all, q_all, st,
-                        a.d_critics, X2, im.on ? &im.target_critics : nullptr));
-    TRY(critics_backward(a.d_critics, cs, nets, X2, ldx, B, Bp, c_h1, c_h2, dq, dh2, dh1,
+    TRY(critics_forward(a.d_target_critics, cs, nets, mine.X, ldx, B, Bp, w.h1_all, w.h2_all, w.q_all, st,
+                        a.d_critics, mine.X2, im.on ? &im.target_critics : nullptr));
+    TRY(critics_backward(a.d_critics, cs, nets, mine.X2, ldx, B, Bp, c_h1, c_h2, w.dq, w.dh2, w.dh1,
                          a.critic.d_grad_sums, nullptr, st, &td, critic_fold, critics_img));
   }
   if (!due || phase == 1) {
@@ -1904,21 +2025,15 @@ extern "C" int tonic_q_iteration(const tonic_q_iteration_t* it, void* stream) {
   }
   // ---- 5 + 6: the updated critics on (s, a_new), the actor objective, down to the action columns
   const int used = kind == 1 ? 2 : 1;                  // TD3 / DDPG: critic_1 only (td3.py:36)
-  const StepLoss objective{LOSS_ACTOR, nullptr, nullptr, nullptr, logp,
+  const StepLoss objective{LOSS_ACTOR, nullptr, nullptr, nullptr, mine.logp,
                            (float)a.actor_entropy_coeff, q, a.actor.d_grad_sums + Pa};
   // ---- 7 + 8: head backward + actor chain, weight gradients + Adam + polyak of the actor
   MlpBwdArgs hb{};
-  hb.hb_dxa0 = dxa; hb.hb_dxa1 = used == 2 ? dxa + (int64_t)Bp * ldh : nullptr; hb.hb_ldxa = ldh;
-  hb.hb_act = act; hb.hb_eps = a.d_eps_actor; hb.hb_sigma = sigma;
-  hb.hb_spre = head1 + (int64_t)Bp * ldh;              // net 1's scale head
+  hb.hb_dxa0 = mine.dxa; hb.hb_dxa1 = used == 2 ? mine.dxa + (int64_t)Bp * ldh : nullptr; hb.hb_ldxa = ldh;
+  hb.hb_act = mine.act; hb.hb_eps = a.d_eps_actor; hb.hb_sigma = mine.sigma;
+  hb.hb_spre = mine.head1 + (int64_t)Bp * ldh;              // net 1's scale head
   hb.hb_sac = kind == 1 ? 1 : 0; hb.hb_alpha = (float)a.actor_entropy_coeff;
-  AdamFold af{};
-  af.grads = a.actor.d_grad_sums; af.params = a.d_actor; af.exp_avg = a.actor.d_exp_avg;
-  af.exp_avg_sq = a.actor.d_exp_avg_sq; af.state = a.actor.d_state; af.n = Pa;
-  af.grad_scale = grad_scale; af.beta2 = (float)a.actor.beta2; af.eps = (float)a.actor.eps;
-  af.beta1_d = a.actor.beta1; af.beta2_d = a.actor.beta2; af.lr_d = a.actor.lr;
-  af.stats_kind = 4; af.info_row = a.actor.d_info_row; af.consts = a.actor.d_step_constants;
-  af.skip = chain ? failed : nullptr;
+  AdamFold af = adam_fold(a.actor, a.d_actor, Pa, grad_scale, 4, chain ? failed : nullptr);
   af.target = a.d_target_actor;
   af.polyak_keep = (float)(1.0 - a.target_coeff); af.polyak_mix = (float)a.target_coeff;
   const AdamFold* actor_fold = phase == 0 ? &af : nullptr;
@@ -1927,28 +2042,28 @@ extern "C" int tonic_q_iteration(const tonic_q_iteration_t* it, void* stream) {
     // exchange q) -> their chain to the action columns -> head backward + the actor's chain
     QActorStep step{};
     int launch_nets = 0;
-    step.fwd = critics_forward_args(a.d_critics, cs, used, X3, ldx, B, Bp, c_h1, c_h2, q, nullptr,
+    step.fwd = critics_forward_args(a.d_critics, cs, used, mine.X3, ldx, B, Bp, c_h1, c_h2, q, nullptr,
                                     nullptr, &launch_nets, critics_img);
-    step.fwd.xq = xq + 128;              // the critics' q: lines 4, 5 of the tile
-    step.bwd = critics_chain_args(a.d_critics, cs, used, B, Bp, c_h1, c_h2, dq, dh2, dh1, dxa,
+    step.fwd.xq = mine.xq + 128;              // the critics' q: lines 4, 5 of the tile
+    step.bwd = critics_chain_args(a.d_critics, cs, used, B, Bp, c_h1, c_h2, w.dq, w.dh2, w.dh1, mine.dxa,
                                   &objective, critics_img);
     step.bwd.exchange_failed = failed;
     step.bwd.skip_dz = 1;            // (the critics are frozen in the actor step: only dxa leaves their chain)
-    step.bwd.l_q = xq + 128; step.bwd.l_q_at = ValueLines{32, kExchangeTileFloats};
-    step.actor = actor_chain_args(a.d_actor, as, B, p_h1 + hs, p_h2 + hs, dloc,
-                                  kind == 1 ? dspre : nullptr, ldh, da_h2, da_h1, nullptr, 0, 0, &hb, actor_img);
+    step.bwd.l_q = mine.xq + 128; step.bwd.l_q_at = ValueLines{32, kExchangeTileFloats};
+    step.actor = actor_chain_args(a.d_actor, as, B, mine.p_h1 + hs, mine.p_h2 + hs, w.dloc,
+                                  kind == 1 ? w.dspre : nullptr, ldh, w.da_h2, w.da_h1, nullptr, 0, 0, &hb, actor_img);
     step.actor.exchange_failed = failed;
     step.used = used;
     TRY(launch_q_actor_step(step, st));
-    TRY(actor_weight_gradients(as, a.d_observations, O, B, p_h1 + hs, p_h2 + hs, dloc,
-                               kind == 1 ? dspre : nullptr, ldh, da_h2, da_h1, a.actor.d_grad_sums,
+    TRY(actor_weight_gradients(as, a.d_observations, O, B, mine.p_h1 + hs, mine.p_h2 + hs, w.dloc,
+                               kind == 1 ? w.dspre : nullptr, ldh, w.da_h2, w.da_h1, a.actor.d_grad_sums,
                                st, actor_fold, actor_img));
   } else {
-    TRY(critics_forward(a.d_critics, cs, used, X3, ldx, B, Bp, c_h1, c_h2, q, st, nullptr, nullptr, critics_img));
-    TRY(critics_backward(a.d_critics, cs, used, X3, ldx, B, Bp, c_h1, c_h2, dq, dh2, dh1, nullptr,
-                         dxa, st, &objective, nullptr, critics_img));
-    TRY(actor_shaped_backward(a.d_actor, as, a.d_observations, O, B, p_h1 + hs, p_h2 + hs, dloc,
-                              kind == 1 ? dspre : nullptr, ldh, da_h2, da_h1, a.actor.d_grad_sums,
+    TRY(critics_forward(a.d_critics, cs, used, mine.X3, ldx, B, Bp, c_h1, c_h2, q, st, nullptr, nullptr, critics_img));
+    TRY(critics_backward(a.d_critics, cs, used, mine.X3, ldx, B, Bp, c_h1, c_h2, w.dq, w.dh2, w.dh1, nullptr,
+                         mine.dxa, st, &objective, nullptr, critics_img));
+    TRY(actor_shaped_backward(a.d_actor, as, a.d_observations, O, B, mine.p_h1 + hs, mine.p_h2 + hs, w.dloc,
+                              kind == 1 ? w.dspre : nullptr, ldh, w.da_h2, w.da_h1, a.actor.d_grad_sums,
                               nullptr, 0, 0, st, &hb, actor_fold, actor_img));
   }
   TONIC_CHECK_LAUNCH("tonic_q_iteration");
@@ -1962,28 +2077,22 @@ extern "C" int tonic_q_iteration(const tonic_q_iteration_t* it, void* stream) {
 
 namespace {
 
-// Every (h1, h2) / (dz2, dz1) pair is the first two layers of a region of `layers` (hidden_layers; see layer_at).
+// Every (h1, h2) / (dz2, dz1) pair is the first two layers of a region of hidden_layers(H) layers (see layer_at).
 struct DistributionalBuffers {
   float *a_h1, *a_h2, *head, *act, *X, *X2, *t_h1, *t_h2, *t_logits, *c_h1, *c_h2, *logits,
       *dlogits, *loss_m, *dz2, *dz1, *dxa, *dloc, *da_h2, *da_h1;
-  static int64_t floats(int Bp, int HP, int layers, int ldh, int ldx, int ldl, int A) {
-    const int64_t hid = (int64_t)Bp * HP * layers / 2;          // (two of these: one region)
-    return 2 * hid + (int64_t)Bp * ldh + (int64_t)Bp * A + 2LL * Bp * ldx + 4 * hid +
-           3LL * Bp * ldl + Bp + 2 * hid + 2LL * Bp * ldh + 2 * hid + 64 * 24;
-  }
-  DistributionalBuffers(void* d_workspace, int64_t bytes, int Bp, int HP, int layers, int ldh, int ldx,
-                        int ldl, int A) {
-    Workspace ws{static_cast<char*>(d_workspace), 0, bytes};
-    const int64_t hid = (int64_t)Bp * HP, region = hid * layers;
-    a_h1 = ws.take(region); a_h2 = a_h1 + hid;
-    head = ws.take((int64_t)Bp * ldh); act = ws.take((int64_t)Bp * A);
-    X = ws.take((int64_t)Bp * ldx); X2 = ws.take((int64_t)Bp * ldx);
-    t_h1 = ws.take(region); t_h2 = t_h1 + hid; c_h1 = ws.take(region); c_h2 = c_h1 + hid;
-    t_logits = ws.take((int64_t)Bp * ldl); logits = ws.take((int64_t)Bp * ldl);
-    dlogits = ws.take((int64_t)Bp * ldl); loss_m = ws.take(Bp);
-    dz2 = ws.take(region); dz1 = dz2 + hid;
-    dxa = ws.take((int64_t)Bp * ldh); dloc = ws.take((int64_t)Bp * ldh);
-    da_h2 = ws.take(region); da_h1 = da_h2 + hid;
+  DistributionalBuffers(Workspace& ws, int B, int O, int A, int32_t H, int NA) {
+    const int64_t Bp = pad16(B), ldx = pitch16(O + A), ldh = pad16(A), ldl = pad16(NA);
+    const int64_t hid = Bp * hidden_pitch(H), region = hid * hidden_layers(H);
+    a_h1 = ws.take(region); a_h2 = behind(a_h1, hid);
+    head = ws.take(Bp * ldh); act = ws.take(Bp * A);
+    X = ws.take(Bp * ldx); X2 = ws.take(Bp * ldx);
+    t_h1 = ws.take(region); t_h2 = behind(t_h1, hid); c_h1 = ws.take(region); c_h2 = behind(c_h1, hid);
+    t_logits = ws.take(Bp * ldl); logits = ws.take(Bp * ldl);
+    dlogits = ws.take(Bp * ldl); loss_m = ws.take(Bp);
+    dz2 = ws.take(region); dz1 = behind(dz2, hid);
+    dxa = ws.take(Bp * ldh); dloc = ws.take(Bp * ldh);
+    da_h2 = ws.take(region); da_h1 = behind(da_h2, hid);
   }
 };
 
@@ -1991,8 +2100,7 @@ struct DistributionalBuffers {
 
 extern "C" int64_t tonic_distributional_workspace_bytes(int32_t B, int32_t O, int32_t A, int32_t H,
                                                         int32_t NA) {
-  return DistributionalBuffers::floats(pad16(B), hidden_pitch(H), hidden_layers(H), pad16(A), pitch16(O + A),
-                                       pad16(NA), A) * 4;
+  return measure<DistributionalBuffers>(B, O, A, H, NA);
 }
 
 extern "C" int tonic_distributional_q_grad(
@@ -2010,9 +2118,9 @@ extern "C" int tonic_distributional_q_grad(
   TONIC_REQUIRE(workspace_bytes >= tonic_distributional_workspace_bytes(B, O, A, H, NA),
                 TONIC_ERR_WORKSPACE, "tonic_distributional_q_grad: workspace too small");
   hipStream_t st = as_stream(stream);
-  const int Bp = pad16(B), ldx = pitch16(O + A), ldh = pad16(A), ldl = pad16(NA), threads = 256;
-  const DistributionalBuffers w(d_workspace, workspace_bytes, Bp, hidden_pitch(H), hidden_layers(H), ldh, ldx,
-                                ldl, A);
+  const int ldx = pitch16(O + A), ldh = pad16(A), ldl = pad16(NA);
+  Workspace ws{static_cast<char*>(d_workspace), 0};
+  const DistributionalBuffers w(ws, B, O, A, H, NA);
   const ActorShape as = actor_shape(O, H, A, 1), cs = actor_shape(O + A, H, NA, 1);
   // a' = target_actor(s') (critics.py:104); its tail encodes (s', a') -> X and the stored (s, a) -> X2
   PolicyTail tail{};
@@ -2020,16 +2128,7 @@ extern "C" int tonic_distributional_q_grad(
   tail.enc_obs = d_next_observations; tail.enc_obs2 = d_observations; tail.enc_act2 = d_actions;
   tail.enc_mean = d_norm_mean; tail.enc_std = d_norm_std; tail.enc_clip = clip_bound(norm_clip);
   tail.enc_out = w.X; tail.enc_out2 = w.X2; tail.enc_ld = ldx;
-  bool tail_done = false;
-  TRY(actor_forward(d_target_actor, as, d_next_observations, B, w.a_h1, w.a_h2, w.head, w.head, ldh,
-                    true, st, &tail, &tail_done));
-  if (!tail_done) {
-    hipLaunchKernelGGL(copy_actions_kernel, dim3((B * A + threads - 1) / threads), dim3(threads),
-                       0, st, w.head, ldh, w.act, B, A);
-    hipLaunchKernelGGL(encode_kernel, dim3((B * (O + A) + threads - 1) / threads, 2),
-                       dim3(threads), 0, st, d_next_observations, w.act, d_norm_mean, d_norm_std,
-                       clip_bound(norm_clip), w.X, B, O, A, ldx, d_observations, d_actions, w.X2);
-  }
+  TRY(policy_pass(d_target_actor, as, d_next_observations, B, w.a_h1, w.a_h2, w.head, w.head, ldh, true, st, tail));
   TRY(actor_forward(d_target_critic, cs, w.X, B, w.t_h1, w.t_h2, w.t_logits, w.t_logits, ldl, false,
                     st, nullptr, nullptr, ldx));
   TRY(actor_forward(d_critic, cs, w.X2, B, w.c_h1, w.c_h2, w.logits, w.logits, ldl, false, st,
@@ -2056,24 +2155,15 @@ extern "C" int tonic_distributional_actor_grad(
   TONIC_REQUIRE(workspace_bytes >= tonic_distributional_workspace_bytes(B, O, A, H, NA),
                 TONIC_ERR_WORKSPACE, "tonic_distributional_actor_grad: workspace too small");
   hipStream_t st = as_stream(stream);
-  const int Bp = pad16(B), ldx = pitch16(O + A), ldh = pad16(A), ldl = pad16(NA), threads = 256;
-  const DistributionalBuffers w(d_workspace, workspace_bytes, Bp, hidden_pitch(H), hidden_layers(H), ldh, ldx,
-                                ldl, A);
+  const int ldx = pitch16(O + A), ldh = pad16(A), ldl = pad16(NA), threads = 256;
+  Workspace ws{static_cast<char*>(d_workspace), 0};
+  const DistributionalBuffers w(ws, B, O, A, H, NA);
   const ActorShape as = actor_shape(O, H, A, 1), cs = actor_shape(O + A, H, NA, 1);
   PolicyTail tail{};                              // a = actor(s); the tail encodes (s, a) -> X
   tail.post = POST_COPY; tail.actions = w.act;
   tail.enc_obs = d_observations; tail.enc_mean = d_norm_mean; tail.enc_std = d_norm_std;
   tail.enc_clip = clip_bound(norm_clip); tail.enc_out = w.X; tail.enc_ld = ldx;
-  bool tail_done = false;
-  TRY(actor_forward(d_actor_params, as, d_observations, B, w.a_h1, w.a_h2, w.head, w.head, ldh,
-                    true, st, &tail, &tail_done));
-  if (!tail_done) {
-    hipLaunchKernelGGL(copy_actions_kernel, dim3((B * A + threads - 1) / threads), dim3(threads),
-                       0, st, w.head, ldh, w.act, B, A);
-    hipLaunchKernelGGL(encode_kernel, dim3((B * (O + A) + threads - 1) / threads), dim3(threads),
-                       0, st, d_observations, w.act, d_norm_mean, d_norm_std, clip_bound(norm_clip),
-                       w.X, B, O, A, ldx);
-  }
+  TRY(policy_pass(d_actor_params, as, d_observations, B, w.a_h1, w.a_h2, w.head, w.head, ldh, true, st, tail));
   TRY(actor_forward(d_critic, cs, w.X, B, w.c_h1, w.c_h2, w.logits, w.logits, ldl, false, st,
                     nullptr, nullptr, ldx));
   hipLaunchKernelGGL(distributional_actor_loss_kernel, dim3((B + 3) / 4), dim3(256), 0, st,
@@ -2100,24 +2190,18 @@ namespace {
 struct MpoBuffers {
   float *a_h1, *a_h2, *loc_t, *spre_t, *loc, *spre, *o_h1, *o_h2, *act, *X, *X2, *t_h1, *t_h2, *tq,
       *tq_mean, *c_h1, *c_h2, *q, *dq, *dh2, *dh1, *dloc, *dspre, *da_h2, *da_h1, *part, *klm, *kls;
-  static int64_t floats(int B, int S, int HP, int ldh, int ldx, int A) {    // (HP: see tonic_mpo_workspace_bytes)
-    const int64_t Bp = pad16(B), Rp = pad16(S * B);
-    return 4 * Bp * HP + 4 * Bp * ldh + Rp * A + Rp * ldx + Bp * ldx + 2 * Rp * HP + Rp + Bp +
-           2 * Bp * HP + 2 * Bp + 2 * Bp * HP + 2 * Bp * ldh + 2 * Bp * HP + Bp * kMpoStats +
-           2 * Bp * A + 64 * 32;
-  }
-  // every (h1, h2) / (dh2, dh1) pair: the first two layers of a region of `layers` (hidden_layers; see layer_at)
-  MpoBuffers(void* d_workspace, int64_t bytes, int B, int S, int HP, int layers, int ldh, int ldx, int A) {
-    Workspace ws{static_cast<char*>(d_workspace), 0, bytes};
-    const int64_t Bp = pad16(B), Rp = pad16(S * B), hid = Bp * HP;
-    a_h1 = ws.take(layers * hid); a_h2 = a_h1 + hid; o_h1 = ws.take(layers * hid); o_h2 = o_h1 + hid;
+  // every (h1, h2) / (dh2, dh1) pair: the first two layers of a region of hidden_layers(H) layers (see layer_at)
+  MpoBuffers(Workspace& ws, int B, int O, int A, int32_t H, int S) {
+    const int64_t Bp = pad16(B), Rp = pad16(S * B), HP = hidden_pitch(H), hid = Bp * HP, layers = hidden_layers(H);
+    const int64_t ldh = pad16(A), ldx = pitch16(O + A);
+    a_h1 = ws.take(layers * hid); a_h2 = behind(a_h1, hid); o_h1 = ws.take(layers * hid); o_h2 = behind(o_h1, hid);
     loc_t = ws.take(Bp * ldh); spre_t = ws.take(Bp * ldh); loc = ws.take(Bp * ldh);
     spre = ws.take(Bp * ldh);
     act = ws.take(Rp * A); X = ws.take(Rp * ldx); X2 = ws.take(Bp * ldx);
-    t_h1 = ws.take(layers * Rp * HP); t_h2 = t_h1 + Rp * HP; tq = ws.take(Rp); tq_mean = ws.take(Bp);
-    c_h1 = ws.take(layers * hid); c_h2 = c_h1 + hid; q = ws.take(Bp); dq = ws.take(Bp);
-    dh2 = ws.take(layers * hid); dh1 = dh2 + hid;
-    dloc = ws.take(Bp * ldh); dspre = ws.take(Bp * ldh); da_h2 = ws.take(layers * hid); da_h1 = da_h2 + hid;
+    t_h1 = ws.take(layers * Rp * HP); t_h2 = behind(t_h1, Rp * HP); tq = ws.take(Rp); tq_mean = ws.take(Bp);
+    c_h1 = ws.take(layers * hid); c_h2 = behind(c_h1, hid); q = ws.take(Bp); dq = ws.take(Bp);
+    dh2 = ws.take(layers * hid); dh1 = behind(dh2, hid);
+    dloc = ws.take(Bp * ldh); dspre = ws.take(Bp * ldh); da_h2 = ws.take(layers * hid); da_h1 = behind(da_h2, hid);
     part = ws.take(Bp * kMpoStats); klm = ws.take(Bp * A); kls = ws.take(Bp * A);
   }
 };
@@ -2141,24 +2225,11 @@ int mpo_sampled_values(const float* d_target_actor, const float* d_target_critic
 }  // namespace
 
 extern "C" int64_t tonic_mpo_workspace_bytes(int32_t B, int32_t O, int32_t A, int32_t H, int32_t S) {
-  // (every hidden array holds hidden_layers(H) layers: the floats' HP stands for half of them, two layers' pitch)
-  return MpoBuffers::floats(B, S, hidden_pitch(H) * hidden_layers(H) / 2, pad16(A), pitch16(O + A), A) * 4;
+  return measure<MpoBuffers>(B, O, A, H, S);
 }
 
-extern "C" int tonic_expected_sarsa_grad(
-    const float* d_target_actor, const float* d_target_critic, const float* d_critic,
-    const float* d_norm_mean, const float* d_norm_std, double norm_clip,
-    const float* d_observations, const float* d_actions, const float* d_next_observations,
-    const float* d_rewards, const float* d_discounts, const float* d_eps, float* d_grad_sums,
-    int32_t B, int32_t O, int32_t H, int32_t A, int32_t S, void* d_workspace,
-    int64_t workspace_bytes, void* stream) {
-  return tonic_expected_sarsa_grad_loss(d_target_actor, d_target_critic, d_critic, d_norm_mean, d_norm_std, norm_clip,
-                                        d_observations, d_actions, d_next_observations, d_rewards, d_discounts, d_eps,
-                                        d_grad_sums, B, O, H, A, S, nullptr, d_workspace, workspace_bytes, stream);
-}
-
-// ... with the critic's loss (critics.py:243: `self.loss(returns, values)`, symmetric in the error): NULL = MSE
-extern "C" int tonic_expected_sarsa_grad_loss(
+namespace {
+int expected_sarsa_grad(
     const float* d_target_actor, const float* d_target_critic, const float* d_critic,
     const float* d_norm_mean, const float* d_norm_std, double norm_clip,
     const float* d_observations, const float* d_actions, const float* d_next_observations,
@@ -2175,7 +2246,8 @@ extern "C" int tonic_expected_sarsa_grad_loss(
                 "tonic_expected_sarsa_grad: workspace too small");
   hipStream_t st = as_stream(stream);
   const int Bp = pad16(B), ldx = pitch16(O + A), threads = 256;
-  const MpoBuffers w(d_workspace, workspace_bytes, B, S, hidden_pitch(H), hidden_layers(H), pad16(A), ldx, A);
+  Workspace ws{static_cast<char*>(d_workspace), 0};
+  const MpoBuffers w(ws, B, O, A, H, S);
   const CriticShape cs = critic_shape(O, A, H);
   TRY(mpo_sampled_values(d_target_actor, d_target_critic, d_norm_mean, d_norm_std, norm_clip,
                          d_next_observations, d_eps, B, O, H, A, S, w, st));
@@ -2191,6 +2263,32 @@ extern "C" int tonic_expected_sarsa_grad_loss(
                        d_grad_sums, nullptr, st, &td));
   TONIC_CHECK_LAUNCH("tonic_expected_sarsa_grad");
   return TONIC_OK;
+}
+}  // namespace
+
+extern "C" int tonic_expected_sarsa_grad(
+    const float* d_target_actor, const float* d_target_critic, const float* d_critic,
+    const float* d_norm_mean, const float* d_norm_std, double norm_clip,
+    const float* d_observations, const float* d_actions, const float* d_next_observations,
+    const float* d_rewards, const float* d_discounts, const float* d_eps, float* d_grad_sums,
+    int32_t B, int32_t O, int32_t H, int32_t A, int32_t S, void* d_workspace,
+    int64_t workspace_bytes, void* stream) {
+  return expected_sarsa_grad(d_target_actor, d_target_critic, d_critic, d_norm_mean, d_norm_std, norm_clip,
+                             d_observations, d_actions, d_next_observations, d_rewards, d_discounts, d_eps,
+                             d_grad_sums, B, O, H, A, S, nullptr, d_workspace, workspace_bytes, stream);
+}
+
+// ... with the critic's loss (critics.py:243: `self.loss(returns, values)`, symmetric in the error): NULL = MSE
+extern "C" int tonic_expected_sarsa_grad_loss(
+    const float* d_target_actor, const float* d_target_critic, const float* d_critic,
+    const float* d_norm_mean, const float* d_norm_std, double norm_clip,
+    const float* d_observations, const float* d_actions, const float* d_next_observations,
+    const float* d_rewards, const float* d_discounts, const float* d_eps, float* d_grad_sums,
+    int32_t B, int32_t O, int32_t H, int32_t A, int32_t S, const tonic_critic_loss_t* loss, void* d_workspace,
+    int64_t workspace_bytes, void* stream) {
+  return expected_sarsa_grad(d_target_actor, d_target_critic, d_critic, d_norm_mean, d_norm_std, norm_clip,
+                             d_observations, d_actions, d_next_observations, d_rewards, d_discounts, d_eps,
+                             d_grad_sums, B, O, H, A, S, loss, d_workspace, workspace_bytes, stream);
 }
 
 namespace {
@@ -2219,7 +2317,10 @@ int mpo_actor_grad(
     const float* d_observations, const float* d_eps, float* d_grad_sums, float* d_dual_grads,
     float* d_stats, int32_t B, int32_t O, int32_t H, int32_t A, int32_t S, double epsilon,
     double epsilon_penalty, double epsilon_mean, double epsilon_std, int32_t action_penalization,
-    int32_t joint_kl, void* d_workspace, int64_t workspace_bytes, void* stream, double* d_column_sums) {
+    int32_t joint_kl, void* d_workspace, int64_t workspace_bytes, void* stream, double* d_column_sums, bool shard) {
+  // (a rank's shard of the batch: only the column sums leave, the duals' half follows the all-reduce — mpo_dual_step)
+  TONIC_REQUIRE(!shard || d_column_sums != nullptr, TONIC_ERR_INVALID_ARGUMENT,
+                "tonic_mpo_actor_grad_shard: null column sums");
   TONIC_REQUIRE(d_actor_params && d_target_actor && d_target_critic && d_duals && d_norm_mean &&
                     d_norm_std && d_observations && d_eps && d_grad_sums &&
                     (d_column_sums || (d_dual_grads && d_stats)) &&
@@ -2230,8 +2331,8 @@ int mpo_actor_grad(
                 "tonic_mpo_actor_grad: workspace too small");
   hipStream_t st = as_stream(stream);
   const int ldh = pad16(A);
-  const MpoBuffers w(d_workspace, workspace_bytes, B, S, hidden_pitch(H), hidden_layers(H), ldh, pitch16(O + A),
-                     A);
+  Workspace ws{static_cast<char*>(d_workspace), 0};
+  const MpoBuffers w(ws, B, O, A, H, S);
   const ActorShape as = actor_shape(O, H, A, 2);
   TRY(mpo_sampled_values(d_target_actor, d_target_critic, d_norm_mean, d_norm_std, norm_clip,
                          d_observations, d_eps, B, O, H, A, S, w, st));
@@ -2250,6 +2351,23 @@ int mpo_actor_grad(
   TONIC_CHECK_LAUNCH("tonic_mpo_actor_grad");
   return TONIC_OK;
 }
+
+int mpo_dual_step(const double* d_column_sums, float* d_duals, double min_log_dual, float* d_dual_grads,
+                  float* d_stats, float* d_actor_stats, int32_t B, int32_t B_global, int32_t A, int32_t S,
+                  double epsilon, double epsilon_penalty, double epsilon_mean, double epsilon_std,
+                  int32_t action_penalization, int32_t joint_kl, void* stream) {
+  TONIC_REQUIRE(d_column_sums && d_duals && d_dual_grads && d_stats && d_actor_stats && B >= 0 &&
+                    B_global > 0 && A >= 1 && A <= 64 && S >= 1 && S <= kMpoMaxSamples &&
+                    (joint_kl == 0 || joint_kl == 1),
+                TONIC_ERR_INVALID_ARGUMENT, "tonic_mpo_dual_step: bad argument (1 <= samples <= 256, A <= 64)");
+  hipLaunchKernelGGL(mpo_dual_kernel, dim3(1), dim3(1024), 0, as_stream(stream),
+                     (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, d_duals,
+                     (float)min_log_dual, action_penalization, joint_kl, (float)epsilon, (float)epsilon_penalty,
+                     (float)epsilon_mean, (float)epsilon_std, d_dual_grads, d_stats, d_actor_stats,
+                     B, A, S, d_column_sums, (double*)nullptr, B_global);
+  TONIC_CHECK_LAUNCH("tonic_mpo_dual_step");
+  return TONIC_OK;
+}
 }  // namespace
 
 extern "C" int tonic_mpo_actor_grad(
@@ -2259,10 +2377,10 @@ extern "C" int tonic_mpo_actor_grad(
     float* d_stats, int32_t B, int32_t O, int32_t H, int32_t A, int32_t S, double epsilon,
     double epsilon_penalty, double epsilon_mean, double epsilon_std, int32_t action_penalization,
     void* d_workspace, int64_t workspace_bytes, void* stream) {
-  return tonic_mpo_actor_grad_joint(d_actor_params, d_target_actor, d_target_critic, d_duals, min_log_dual,
-                                    d_norm_mean, d_norm_std, norm_clip, d_observations, d_eps, d_grad_sums,
-                                    d_dual_grads, d_stats, B, O, H, A, S, epsilon, epsilon_penalty, epsilon_mean,
-                                    epsilon_std, action_penalization, 0, d_workspace, workspace_bytes, stream);
+  return mpo_actor_grad(d_actor_params, d_target_actor, d_target_critic, d_duals, min_log_dual, d_norm_mean,
+                        d_norm_std, norm_clip, d_observations, d_eps, d_grad_sums, d_dual_grads,
+                        d_stats, B, O, H, A, S, epsilon, epsilon_penalty, epsilon_mean, epsilon_std,
+                        action_penalization, 0, d_workspace, workspace_bytes, stream, nullptr, false);
 }
 
 // ... with joint_kl = 1: one alpha pair on the KLs summed over the action dimensions (duals [4], stats [11])
@@ -2276,7 +2394,7 @@ extern "C" int tonic_mpo_actor_grad_joint(
   return mpo_actor_grad(d_actor_params, d_target_actor, d_target_critic, d_duals, min_log_dual, d_norm_mean,
                         d_norm_std, norm_clip, d_observations, d_eps, d_grad_sums, d_dual_grads,
                         d_stats, B, O, H, A, S, epsilon, epsilon_penalty, epsilon_mean, epsilon_std,
-                        action_penalization, joint_kl, d_workspace, workspace_bytes, stream, nullptr);
+                        action_penalization, joint_kl, d_workspace, workspace_bytes, stream, nullptr, false);
 }
 
 extern "C" int tonic_mpo_actor_grad_shard(
@@ -2285,10 +2403,10 @@ extern "C" int tonic_mpo_actor_grad_shard(
     const float* d_observations, const float* d_eps, float* d_grad_sums, double* d_column_sums,
     int32_t B, int32_t O, int32_t H, int32_t A, int32_t S, int32_t action_penalization,
     void* d_workspace, int64_t workspace_bytes, void* stream) {
-  return tonic_mpo_actor_grad_shard_joint(d_actor_params, d_target_actor, d_target_critic, d_duals, min_log_dual,
-                                          d_norm_mean, d_norm_std, norm_clip, d_observations, d_eps, d_grad_sums,
-                                          d_column_sums, B, O, H, A, S, action_penalization, 0, d_workspace,
-                                          workspace_bytes, stream);
+  return mpo_actor_grad(d_actor_params, d_target_actor, d_target_critic, d_duals, min_log_dual, d_norm_mean,
+                        d_norm_std, norm_clip, d_observations, d_eps, d_grad_sums, nullptr, nullptr, B, O, H, A, S,
+                        0.0, 0.0, 0.0, 0.0, action_penalization, 0, d_workspace, workspace_bytes, stream, d_column_sums,
+                        true);
 }
 
 extern "C" int tonic_mpo_actor_grad_shard_joint(
@@ -2297,12 +2415,10 @@ extern "C" int tonic_mpo_actor_grad_shard_joint(
     const float* d_observations, const float* d_eps, float* d_grad_sums, double* d_column_sums,
     int32_t B, int32_t O, int32_t H, int32_t A, int32_t S, int32_t action_penalization, int32_t joint_kl,
     void* d_workspace, int64_t workspace_bytes, void* stream) {
-  TONIC_REQUIRE(d_column_sums != nullptr, TONIC_ERR_INVALID_ARGUMENT,
-                "tonic_mpo_actor_grad_shard: null column sums");
   return mpo_actor_grad(d_actor_params, d_target_actor, d_target_critic, d_duals, min_log_dual, d_norm_mean,
-                        d_norm_std, norm_clip, d_observations, d_eps, d_grad_sums, nullptr, nullptr,
-                        B, O, H, A, S, 0.0, 0.0, 0.0, 0.0, action_penalization, joint_kl, d_workspace,
-                        workspace_bytes, stream, d_column_sums);
+                        d_norm_std, norm_clip, d_observations, d_eps, d_grad_sums, nullptr, nullptr, B, O, H, A, S,
+                        0.0, 0.0, 0.0, 0.0, action_penalization, joint_kl, d_workspace, workspace_bytes, stream,
+                        d_column_sums, true);
 }
 
 extern "C" int tonic_mpo_dual_step(const double* d_column_sums, float* d_duals, double min_log_dual,
@@ -2310,9 +2426,8 @@ extern "C" int tonic_mpo_dual_step(const double* d_column_sums, float* d_duals, 
                                    int32_t B, int32_t B_global, int32_t A, int32_t S,
                                    double epsilon, double epsilon_penalty, double epsilon_mean,
                                    double epsilon_std, int32_t action_penalization, void* stream) {
-  return tonic_mpo_dual_step_joint(d_column_sums, d_duals, min_log_dual, d_dual_grads, d_stats, d_actor_stats, B,
-                                   B_global, A, S, epsilon, epsilon_penalty, epsilon_mean, epsilon_std,
-                                   action_penalization, 0, stream);
+  return mpo_dual_step(d_column_sums, d_duals, min_log_dual, d_dual_grads, d_stats, d_actor_stats, B, B_global, A, S,
+                       epsilon, epsilon_penalty, epsilon_mean, epsilon_std, action_penalization, 0, stream);
 }
 
 extern "C" int tonic_mpo_dual_step_joint(const double* d_column_sums, float* d_duals, double min_log_dual,
@@ -2321,121 +2436,8 @@ extern "C" int tonic_mpo_dual_step_joint(const double* d_column_sums, float* d_d
                                          double epsilon, double epsilon_penalty, double epsilon_mean,
                                          double epsilon_std, int32_t action_penalization, int32_t joint_kl,
                                          void* stream) {
-  TONIC_REQUIRE(d_column_sums && d_duals && d_dual_grads && d_stats && d_actor_stats && B >= 0 &&
-                    B_global > 0 && A >= 1 && A <= 64 && S >= 1 && S <= kMpoMaxSamples &&
-                    (joint_kl == 0 || joint_kl == 1),
-                TONIC_ERR_INVALID_ARGUMENT, "tonic_mpo_dual_step: bad argument (1 <= samples <= 256, A <= 64)");
-  hipLaunchKernelGGL(mpo_dual_kernel, dim3(1), dim3(1024), 0, as_stream(stream),
-                     (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, d_duals,
-                     (float)min_log_dual, action_penalization, joint_kl, (float)epsilon, (float)epsilon_penalty,
-                     (float)epsilon_mean, (float)epsilon_std, d_dual_grads, d_stats, d_actor_stats,
-                     B, A, S, d_column_sums, (double*)nullptr, B_global);
-  TONIC_CHECK_LAUNCH("tonic_mpo_dual_step");
-  return TONIC_OK;
-}
-
-// (actors.py:238-267).  Gradient SUMS for the actor + 8 statistics {loss_sum, 0.., B, ..}.
-extern "C" int tonic_actor_q_grad(int32_t kind, const float* d_actor_params,
-                                  const float* d_critics, const float* d_norm_mean,
-                                  const float* d_norm_std, double norm_clip,
-                                  const float* d_observations,
-                                  const float* d_eps, float* d_grad_sums, int32_t B, int32_t O,
-                                  int32_t H, int32_t A, double entropy_coeff, void* d_workspace,
-                                  int64_t workspace_bytes, void* stream) {
-  return tonic_actor_q_grad_ranged(kind, d_actor_params, d_critics, d_norm_mean, d_norm_std, norm_clip,
-                                   d_observations, d_eps, d_grad_sums, B, O, H, A, entropy_coeff, nullptr, nullptr,
-                                   d_workspace, workspace_bytes, stream);
-}
-
-// ... through critics whose value heads squash (tonic_twin_q_grad_ranged): the objective and its logged sum are
-// those of v, the gradient that enters each head is multiplied by dv/dz.  NULL / NULL: tonic_actor_q_grad.
-extern "C" int tonic_actor_q_grad_ranged(int32_t kind, const float* d_actor_params,
-                                         const float* d_critics, const float* d_norm_mean,
-                                         const float* d_norm_std, double norm_clip,
-                                         const float* d_observations,
-                                         const float* d_eps, float* d_grad_sums, int32_t B, int32_t O,
-                                         int32_t H, int32_t A, double entropy_coeff,
-                                         const float* d_value_low, const float* d_value_high,
-                                         void* d_workspace, int64_t workspace_bytes, void* stream) {
-  TONIC_REQUIRE((d_value_low == nullptr) == (d_value_high == nullptr), TONIC_ERR_INVALID_ARGUMENT,
-                "tonic_actor_q_grad_ranged: %s is NULL and the other bound is not (both or neither)",
-                d_value_low == nullptr ? "d_value_low" : "d_value_high");
-  TONIC_REQUIRE(d_actor_params && d_critics && d_norm_mean && d_norm_std && d_observations &&
-                    d_grad_sums && d_workspace && B > 0 && (kind == 0 || d_eps) && hidden_known(H),
-                TONIC_ERR_INVALID_ARGUMENT, "tonic_actor_q_grad: bad argument");
-  TONIC_REQUIRE(workspace_bytes >= tonic_offpolicy_workspace_bytes(B, O, A, H),
-                TONIC_ERR_WORKSPACE, "tonic_actor_q_grad: workspace too small");
-  hipStream_t st = as_stream(stream);
-  const ActorShape as = actor_shape(O, H, A, kind == 0 ? 1 : 2);
-  H = torso_code(H);                           // (the bounds are in `as`; what follows sizes by the torso)
-  const int Bp = pad16(B), ldx = pitch16(O + A), ldh = pad16(A), threads = 256, HP = hidden_pitch(H);
-  const int nets = kind == 0 ? 1 : 2;
-  const CriticShape cs = critic_shape(O, A, H);
-  const int64_t Pa = actor_count(as);
-  Workspace ws{static_cast<char*>(d_workspace), 0, workspace_bytes};
-  const int64_t hs = (int64_t)Bp * HP, layers = hidden_layers(H);     // (layers: see layer_at)
-  float* a_h1 = ws.take(layers * hs); float* a_h2 = a_h1 + hs;
-  float* head0 = ws.take((int64_t)Bp * ldh); float* head1 = ws.take((int64_t)Bp * ldh);
-  float* act = ws.take((int64_t)Bp * A); float* sigma = ws.take((int64_t)Bp * A);
-  float* logp = ws.take(Bp);
-  float* X = ws.take((int64_t)Bp * ldx);
-  float* c_h1 = ws.take(layers * 2 * hs); float* c_h2 = c_h1 + 2 * hs;
-  float* q = ws.take(2LL * Bp); float* dq = ws.take(2LL * Bp);
-  float* dh2 = ws.take(layers * 2 * hs); float* dh1 = dh2 + 2 * hs;
-  float* dxa = ws.take(2LL * Bp * ldh);         // action columns of the critics' input gradients
-  float* dloc = ws.take((int64_t)Bp * ldh); float* dspre = ws.take((int64_t)Bp * ldh);
-  float* da_h2 = ws.take(layers * hs); float* da_h1 = da_h2 + hs;
-  // the weight images of the actor and the critics (mlpimg.h), formed by this call (see tonic_twin_q_grad)
-  ImageSet im = take_images(ws, O, A, H, as.heads, hidden_plain(H) && images_serve(O, A, H) &&
-                                                    mlp_forward_supported(H, A, as.heads) &&
-                                                    mlp_backward_supported(H, A, as.heads, 0) &&
-                                                    mlp_backward_supported(H, 1, 0, A));
-  if (im.on) {
-    ImgBuild build;
-    add_actor_images(build, d_actor_params, as, im.actor);
-    add_critic_images(build, d_critics, cs, nets, im.critics.block, im.critics.v);
-    TRY(launch_build_images(build, st));
-  }
-
-  PolicyTail tail{};                             // the tail also encodes the critics' input (s, a)
-  tail.post = kind == 0 ? POST_COPY : POST_SQUASHED_SAMPLE; tail.eps = d_eps; tail.actions = act;
-  tail.sigma = kind == 0 ? nullptr : sigma; tail.logp = kind == 0 ? nullptr : logp;
-  tail.enc_obs = d_observations; tail.enc_mean = d_norm_mean; tail.enc_std = d_norm_std;
-  tail.enc_clip = clip_bound(norm_clip);
-  tail.enc_out = X; tail.enc_ld = ldx;
-  bool tail_done = false;
-  TRY(actor_forward(d_actor_params, as, d_observations, B, a_h1, a_h2, head0, head1, ldh,
-                    kind == 0, st, &tail, &tail_done, 0, im.on ? &im.actor : nullptr));
-  if (tail_done) {
-  } else if (kind == 0) {
-    hipLaunchKernelGGL(copy_actions_kernel, dim3((B * A + threads - 1) / threads), dim3(threads),
-                       0, st, head0, ldh, act, B, A);
-  } else {
-    hipLaunchKernelGGL(sac_sample_kernel,
-                       dim3((B * sample_group(A) + threads - 1) / threads), dim3(threads), 0, st,
-                       head0, head1, d_eps, ldh, act, logp, sigma, B, A,
-                       sample_group(A), as.scale_lo, as.scale_hi);
-  }
-  if (!tail_done) {
-    hipLaunchKernelGGL(encode_kernel, dim3((B * (O + A) + threads - 1) / threads), dim3(threads),
-                       0, st, d_observations, act, d_norm_mean, d_norm_std, clip_bound(norm_clip), X,
-                       B, O, A, ldx);
-  }
-  TRY(critics_forward(d_critics, cs, nets, X, ldx, B, Bp, c_h1, c_h2, q, st, nullptr, nullptr,
-                      im.on ? &im.critics : nullptr, d_value_low, d_value_high));
-  const StepLoss objective{LOSS_ACTOR, nullptr, nullptr, nullptr, logp, (float)entropy_coeff, q,
-                           d_grad_sums + Pa, CriticLoss{TONIC_LOSS_MSE, 0.f}, d_value_low, d_value_high};
-  TRY(critics_backward(d_critics, cs, nets, X, ldx, B, Bp, c_h1, c_h2, dq, dh2, dh1, nullptr, dxa,
-                       st, &objective, nullptr, im.on ? &im.critics : nullptr));
-  hipLaunchKernelGGL(actor_head_backward_kernel, dim3((B * A + threads - 1) / threads),
-                     dim3(threads), 0, st, dxa, nets == 2 ? dxa + (int64_t)Bp * ldh : (float*)nullptr,
-                     ldh, act, d_eps, sigma, head1, ldh,
-                     (float)entropy_coeff, kind == 1 ? 1 : 0, dloc, dspre, B, A, as.scale_lo, as.scale_hi);
-  TRY(actor_shaped_backward(d_actor_params, as, d_observations, O, B, a_h1, a_h2, dloc,
-                            kind == 1 ? dspre : nullptr, ldh, da_h2, da_h1, d_grad_sums, nullptr,
-                            0, 0, st, nullptr, nullptr, im.on ? &im.actor : nullptr));
-  TONIC_CHECK_LAUNCH("tonic_actor_q_grad");
-  return TONIC_OK;
+  return mpo_dual_step(d_column_sums, d_duals, min_log_dual, d_dual_grads, d_stats, d_actor_stats, B, B_global, A, S,
+                       epsilon, epsilon_penalty, epsilon_mean, epsilon_std, action_penalization, joint_kl, stream);
 }
 
 extern "C" int tonic_buffer_gather(const int64_t* d_indices, const float* d_buf_observations,
