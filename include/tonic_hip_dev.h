@@ -2,7 +2,7 @@
  * Developer entry points of libtonic_hip.so — NOT part of the drop-in boundary (include/tonic_hip.h).
  * They exist for the parity tests and the profiling scripts of this repository: a process-wide
  * tuning switch between kernel variants that compute the same thing, one stand-alone GEMM of the
- * small-batch building block, and a cycle probe of the fused grad kernel.  Nothing in the product
+ * small-batch building block (and the block's batched / grouped launches, for its own tests), and a cycle probe of the fused grad kernel.  Nothing in the product
  * path (the tonic_amd package itself, as opposed to tests, scripts and bench) may depend on the knobs being set.
  */
 #ifndef TONIC_HIP_DEV_H
@@ -56,6 +56,25 @@ int tonic_gemm_f32(const char* mode, const float* d_a, const float* d_b, float* 
                    const float* d_bias, const float* d_mask, float* d_colsum, int32_t M,
                    int32_t N, int32_t K, int32_t lda, int32_t ldb, int32_t ldc, int32_t act,
                    int32_t accumulate, double alpha, void* stream);
+
+/* Developer / test entry: the WHOLE building block — every field of a problem, the batch dimension and the
+ * grouped launches (tests/test_gpu_gemm_block.py).  One problem is
+ *   C[z] = [C[z] +] mask'(act(alpha * op(A[z]) op(B[z]) + bias[z])),   z = 0 .. batch - 1,
+ * with operand X[z] = x + z * stride_x (floats; a stride of 0 shares the operand among the batch), row pitches
+ * lda / ldb / ldc / ldmask (floats), act 0 none, 1 relu, 2 tanh, 3 elu; the mask holds act(z) of another layer and
+ * multiplies by that activation's derivative, chosen by mask_act: 0 / 1 (mask > 0), 2 (1 - mask^2), 3 (mask > 0 ? 1 :
+ * mask + 1).  bias, mask and colsum may be null; colsum[z][m] = sum_k A[z][k][m], mode "TN" only.
+ * count == 1: the single launch; count = 2 .. 4: one grouped launch of problems that share mode and K; count = 5, 6:
+ * the plain "TN" form only (no bias, mask or activation).  Everything else is refused with
+ * TONIC_ERR_INVALID_ARGUMENT before any launch.  No optimizer epilogue, weight images or value range. */
+typedef struct {
+  const float *a, *b; float *c; const float *bias, *mask; float *colsum;
+  int32_t M, N, K, lda, ldb, ldc, ldmask;
+  int64_t stride_a, stride_b, stride_c, stride_bias, stride_mask, stride_colsum;
+  int32_t act, mask_act, accumulate; float alpha;
+} tonic_gemm_problem;
+int tonic_gemm_group_f32(const char* mode, const tonic_gemm_problem* problems,
+                         int32_t count, int32_t batch, void* stream);
 
 /* Test tool: `workgroups` workgroups that each hold a compute unit to themselves (100 KB of LDS:
  * neither a collect nor a grad workgroup fits beside one) and spin for `milliseconds` of the

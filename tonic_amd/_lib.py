@@ -66,6 +66,16 @@ class QIteration(ctypes.Structure):
                 ('critic_loss', CriticLoss)]
 
 
+class GemmProblem(ctypes.Structure):
+    """tonic_gemm_problem of include/tonic_hip_dev.h (field for field; developer / test entry)."""
+    _fields_ = [('a', c_vp), ('b', c_vp), ('c', c_vp), ('bias', c_vp), ('mask', c_vp), ('colsum', c_vp),
+                ('M', c_i32), ('N', c_i32), ('K', c_i32), ('lda', c_i32), ('ldb', c_i32), ('ldc', c_i32),
+                ('ldmask', c_i32),
+                ('stride_a', c_i64), ('stride_b', c_i64), ('stride_c', c_i64), ('stride_bias', c_i64),
+                ('stride_mask', c_i64), ('stride_colsum', c_i64),
+                ('act', c_i32), ('mask_act', c_i32), ('accumulate', c_i32), ('alpha', ctypes.c_float)]
+
+
 # name -> (restype, argtypes); mirrors include/tonic_hip.h one to one.
 SIGNATURES = {
     'tonic_last_error': (ctypes.c_char_p, []),
@@ -235,6 +245,7 @@ SIGNATURES = {
     'tonic_debug_forward_stamps': (ctypes.c_int, [c_vp]),
     'tonic_debug_occupy': (ctypes.c_int, [c_i32, c_f64, c_vp]),
     'tonic_gemm_f32': (ctypes.c_int, [ctypes.c_char_p] + [c_vp] * 6 + [c_i32] * 8 + [c_f64, c_vp]),
+    'tonic_gemm_group_f32': (ctypes.c_int, [ctypes.c_char_p, c_vp, c_i32, c_i32, c_vp]),
 }
 
 

@@ -770,3 +770,29 @@ extern "C" int tonic_gemm_f32(const char* mode, const float* d_a, const float* d
   const char b = mode[1] == 'T' ? 'c' : 's';
   return launch_gemm(a, b, g, 1, as_stream(stream));
 }
+
+// Developer / test entry point: the whole block — every GemmArgs field, the batch dimension and the grouped
+// launches (count == 1: launch_gemm, count >= 2: launch_gemm_group), without optimizer epilogue, weight
+// images or value range.  The argument translation of tonic_gemm_f32 and nothing else.
+extern "C" int tonic_gemm_group_f32(const char* mode, const tonic_gemm_problem* problems, int32_t count,
+                                    int32_t batch, void* stream) {
+  TONIC_REQUIRE(mode != nullptr && mode[0] && mode[1], TONIC_ERR_INVALID_ARGUMENT,
+                "tonic_gemm_group_f32: bad mode");
+  TONIC_REQUIRE(problems != nullptr && count >= 1 && count <= kGemmGroupWide, TONIC_ERR_INVALID_ARGUMENT,
+                "tonic_gemm_group_f32: %d problems", count);
+  GemmArgs list[kGemmGroupWide];
+  for (int p = 0; p < count; ++p) {
+    const tonic_gemm_problem& q = problems[p];
+    GemmArgs g{};
+    g.A = q.a; g.B = q.b; g.C = q.c; g.bias = q.bias; g.mask = q.mask; g.colsum = q.colsum;
+    g.M = q.M; g.N = q.N; g.K = q.K; g.lda = q.lda; g.ldb = q.ldb; g.ldc = q.ldc; g.ldmask = q.ldmask;
+    g.strideA = q.stride_a; g.strideB = q.stride_b; g.strideC = q.stride_c;
+    g.strideBias = q.stride_bias; g.strideMask = q.stride_mask; g.strideColsum = q.stride_colsum;
+    g.act = q.act; g.mask_act = q.mask_act; g.accumulate = q.accumulate; g.alpha = q.alpha;
+    list[p] = g;
+  }
+  const char a = mode[0] == 'N' ? 'c' : 's';
+  const char b = mode[1] == 'T' ? 'c' : 's';
+  if (count == 1) return launch_gemm(a, b, list[0], batch, as_stream(stream));
+  return launch_gemm_group(a, b, list, count, batch, as_stream(stream));
+}
