@@ -18,7 +18,6 @@ runs with equal seeds follow the reference's trajectory up to float32 rounding. 
 step t+1 is made while the GPU works on step t; ``test_step`` (which draws from the same
 generator, a2c.py:87-90) first rewinds the generator to where the reference would be.
 """
-import ctypes
 import os
 import random
 import time
@@ -30,6 +29,7 @@ import torch
 from tonic_amd import _lib, agents, explorations, logger, parallel, replays
 from tonic_amd.collector import Block, Collector
 from tonic_amd.q_block import QBlocks
+from tonic_amd.q_update import QUpdate, _check_chain, chunk_size, shard_noise      # noqa: F401 (for their importers)
 from tonic_amd.torch import models, normalizers, updaters
 
 
@@ -1212,26 +1212,6 @@ def log_ppo_critic_rows(rows):
 
 # ----------------------------------------------------------------- off-policy (SAC / TD3)
 
-def shard_noise(eps, positions, counts, global_batch, samples=None):
-    """The rows of the GLOBAL noise draws that belong to this rank's part of each batch.
-    eps [iterations, draws, S * B, A]: S draws per state of the global batch, sample-major (row
-    s * B + m; S = 1 for everything but MPO).  positions[it, :counts[it]] = the batch positions m
-    this rank owns.  Returns the same shape with row s * c + j = eps row s * B + positions[j]
-    (c = counts[it]) in front and zeros behind: what the kernels see as a batch of c states.
-    samples: S of each draw when the draws differ (draw d fills its first samples[d] * B rows, MPO with two
-    sample counts); default: every draw fills the rows."""
-    local = np.zeros_like(eps)
-    draws, width = eps.shape[1], eps.shape[3]
-    if samples is None:
-        samples = (eps.shape[2] // global_batch,) * draws
-    for it in range(eps.shape[0]):
-        c = counts[it]
-        for d, per_sample in enumerate(samples):
-            kept = eps[it, d, :per_sample * global_batch].reshape(per_sample, global_batch, width)
-            local[it, d, :per_sample * c] = kept[:, positions[it, :c]].reshape(per_sample * c, width)   # (c may be 0)
-    return local
-
-
 def _twin_model(head):
     return models.ActorTwinCriticWithTargets(
         actor=models.Actor(
@@ -1295,8 +1275,7 @@ class DDPG(Agent):
         self._workers = None
         self._policy_io = {}
         self._q = QBlocks(self)      # acting / storing on the environments' own blocks (tonic_amd.q_block)
-        self._graph, self._static_key = None, None       # a re-initialised agent re-captures
-        self._slots, self._slot_index = {}, 0
+        self._u = QUpdate(self)      # how an update call reaches the GPU (tonic_amd.q_update); anew: re-captures
 
     def close(self):
         """Stores what is still deferred and lets go of the environments' blocks; gives back what the agent holds
@@ -1427,126 +1406,8 @@ class DDPG(Agent):
         standard-normal draws in the order the reference consumes them.  With `graph` (default:
         on unless TONIC_AMD_NO_GRAPH=1) the launch sequence — gather, the fused forward / backward /
         grouped weight-gradient launches, Adam + polyak: 13 per SAC iteration — is captured once into a hipGraph
-        reading fixed index / noise buffers and replayed on later calls."""
-        iterations, global_batch = indices.shape
-        self._q.parameters_changed()
-        world = self.critic_updater.world_size
-        counts = None
-        if world > 1:
-            # SURVEY §8e: every rank draws the same GLOBAL index / noise stream and keeps the
-            # samples whose worker column lives in its shard (binomial split, mean B / world);
-            # gradient SUMS are all-reduced and scaled by 1 / B_global, so the update equals the
-            # single-process one on the global buffer.
-            indices, positions, counts = self.replay.shard_indices(indices)
-            eps = shard_noise(eps, positions, counts, global_batch, self._noise_samples(eps.shape[1]))
-        # everything a captured graph bakes in: shapes, the replay's storage, the updaters'
-        # hyper-parameters and schedules — a change of any of them re-captures
-        key = (iterations, tuple(eps.shape), self.replay.buffers['observations'].data_ptr(),
-               self.replay.max_size, self._graph_signature())
-        if getattr(self, '_static_key', None) != key:
-            self._static_key = key
-            self._static_indices = torch.zeros(indices.shape, dtype=torch.int64, device=self.device)
-            self._static_eps = torch.zeros(eps.shape, dtype=torch.float32, device=self.device)
-            self._infos = torch.zeros(2, iterations, updaters.INFO_WIDTH, device=self.device)
-            self._graph = None
-        self._static_indices.copy_(torch.as_tensor(indices), non_blocking=True)
-        self._static_eps.copy_(torch.as_tensor(eps), non_blocking=True)
-        if graph is None:
-            graph = os.environ.get('TONIC_AMD_NO_GRAPH', '0') != '1'
-
-        fused = self._fused_kind()
-        # Several ranks / gradient clipping need the complete gradient sums between gradients and step: the
-        # same chained launches in two halves around the exchange (tonic_q_iteration_t.phase), the steps
-        # through the updaters' own `_step` (all-reduce, clip, Adam [+ polyak]) like the split entry points
-        phased = fused is not None and self._fused_in_phases()
-        self._phased_update = phased
-        if phased:
-            self._fused_workspace_for(max(indices.shape[1], 1))[:4].zero_()   # the update's failure word
-        if fused is not None and not phased:
-            # the optimizer steps' float64 constants, formed here like the reference's Python
-            # floats: [iteration, {critic, actor}, {step_size, bias_correction2_sqrt}]
-            table = np.zeros((iterations, 2, 2), np.float32)
-            critic, actor = self.critic_updater, self.actor_updater
-            if not getattr(self, '_step_mirror_valid', False):
-                # the host mirrors of the device's step counters are only kept by THIS path: after
-                # an update on the split entry points (whose captured graphs step the device counter
-                # on every replay), an exception on the way to the launches or a skipped step, the
-                # counters on the device are the authority (one read-back, then none again)
-                critic.steps_enqueued = int(critic.state[0])
-                actor.steps_enqueued = int(actor.state[0])
-            self._step_mirror_valid = False          # until this update's launches are out
-            for it in range(iterations):
-                critic.steps_enqueued += 1
-                table[it, 0] = updaters.adam_step_constants(critic.hyper, critic.steps_enqueued)
-                if self._actor_due(it):
-                    actor.steps_enqueued += 1
-                    table[it, 1] = updaters.adam_step_constants(actor.hyper, actor.steps_enqueued)
-            if getattr(self, '_static_adam', None) is None or self._static_adam.shape != table.shape:
-                self._static_adam = torch.zeros(table.shape, device=self.device)
-                self._graph = None
-            self._static_adam.copy_(torch.as_tensor(table), non_blocking=True)
-
-        def enqueue():
-            self._infos.zero_()
-            draws = self._static_eps.shape[1]
-            samples = self._noise_samples(draws)       # rows per state of each draw (MPO: its updater's num_samples)
-            # the store does not change during an update: the batches of ALL its iterations are
-            # gathered by one launch (the rows a rank does not own are padding, never read)
-            batches = self.replay.gather_many(self._static_indices)
-            if fused is not None and not phased and counts is None:
-                self._enqueue_fused_iterations(fused, batches, iterations)
-                return
-            for it in range(iterations):
-                c = global_batch if counts is None else int(counts[it])
-                n_global = None if counts is None else global_batch
-                if c > 0:
-                    batch = {k: v[it, :c] for k, v in batches.items()}
-                if phased:
-                    self._enqueue_phased(fused, batch if c > 0 else None, it, self._actor_due(it), n_global)
-                    continue
-                if fused is not None:
-                    self._enqueue_fused(fused, batch, it, self._actor_due(it))
-                    continue
-                if c > 0:
-                    self.critic_updater.enqueue(batch, self._static_eps[it, 0, :c * samples[0]],
-                                                self._infos[0, it], n_global)
-                else:
-                    self.critic_updater.enqueue_empty(self._infos[0, it], n_global)
-                if self._actor_due(it):
-                    actor_eps = self._static_eps[it, 1, :c * samples[1]] if draws > 1 else None
-                    # update_targets() (ddpg.py:112) rides in the actor's optimizer launch
-                    targets = (self.model.flat_target, self.model.flat_online, 0,
-                               self.model.target_coeff)
-                    if c > 0:
-                        self._enqueue_actor(batch['observations'], actor_eps, it, n_global, targets)
-                    else:
-                        self._enqueue_actor(None, None, it, n_global, targets)
-
-        stock = self.critic_updater.stock or self.actor_updater.stock    # (autograd: no capture)
-        if not graph or stock or parallel.exchanging():      # collectives sit between the kernels
-            enqueue()
-            self._step_mirror_valid = fused is not None and not phased
-            return self._infos
-        if self._graph is None:
-            batch_size = indices.shape[1]
-            self.critic_updater._offpolicy_workspace(batch_size)    # allocate outside the capture
-            self.actor_updater._offpolicy_workspace(batch_size)
-            self.replay.gather_many(self._static_indices)
-            if fused is not None:
-                self._fused_workspace_for(batch_size)
-            torch.cuda.synchronize()
-            self._graph = torch.cuda.CUDAGraph()
-            with _lib.capturing(self._graph):
-                enqueue()
-        self._graph.replay()
-        self._step_mirror_valid = fused is not None and not phased
-        return self._infos
-
-    def _enqueue_actor(self, observations, eps, iteration, n_global, targets):
-        if observations is None:                    # this rank drew none of the global batch
-            self.actor_updater.enqueue_empty(self._infos[1, iteration], n_global, targets)
-            return
-        self.actor_updater.enqueue(observations, eps, self._infos[1, iteration], n_global, targets)
+        reading fixed index / noise buffers and replayed on later calls (tonic_amd.q_update)."""
+        return self._u.enqueue(indices, eps, graph)
 
     # -- the whole iteration through tonic_q_iteration (5 launches instead of 13)
     _FUSED = {updaters.DeterministicQLearning: (2, updaters.DeterministicPolicyGradient),
@@ -1554,138 +1415,23 @@ class DDPG(Agent):
               updaters.TwinCriticSoftQLearning: (1, updaters.TwinCriticSoftDeterministicPolicyGradient)}
 
     def _fused_kind(self):
-        """The `kind` of tonic_q_iteration when it serves this agent: the plain DDPG / TD3 / SAC
-        updaters, one rank (several ranks all-reduce between gradients and step), no gradient
-        clipping (needs the whole gradient before the step), shapes inside the fused kernels.
-        TONIC_AMD_FUSED_ITERATION=0 keeps the split entry points (the tests compare the two)."""
-        critic, actor = self.critic_updater, self.actor_updater
-        kind, actor_class = self._FUSED.get(type(critic), (None, None))
-        if kind is None or type(actor) is not actor_class or critic.stock or actor.stock:
-            return None
-        if self.model.return_normalizer:             # tonic_q_iteration has no squashed value head: the split entries
-            return None
-        if not (critic.plain and actor.plain):        # tonic_q_iteration's epilogues are plain Adam: the split entries
-            return None
-        if os.environ.get('TONIC_AMD_FUSED_ITERATION', '1') == '0':
-            return None
-        if not self.lib.tonic_q_iteration_supported(self.observation_size, self.hidden,
-                                                    self.action_size, 2 if kind == 1 else 1):
-            return None
-        needs_phases = parallel.exchanging() or critic.world_size > 1 or critic.gradient_clip > 0 \
-            or actor.gradient_clip > 0
-        if needs_phases and os.environ.get('TONIC_AMD_FUSED_PHASES', '1') == '0':
-            return None
-        return kind
+        """The `kind` of tonic_q_iteration when it serves this agent (QUpdate.route), else None."""
+        return self._u.route().fused_kind
 
     def _fused_in_phases(self):
-        """The fused iteration in two halves, gradient sums only (tonic_q_iteration_t.phase 1 / 2): whenever
-        something has to see the complete sums before the step — the exchange between ranks, a gradient-norm
-        clip.  TONIC_AMD_FUSED_PHASES=0: the split entry points there, as before round 5."""
-        critic, actor = self.critic_updater, self.actor_updater
-        needed = parallel.exchanging() or critic.world_size > 1 or critic.gradient_clip > 0 \
-            or actor.gradient_clip > 0
-        return needed and os.environ.get('TONIC_AMD_FUSED_PHASES', '1') != '0'
+        """The fused iteration in two halves around what has to see the complete gradient sums (QUpdate.route)."""
+        return self._u.route().in_phases
 
-    def _fused_workspace_for(self, batch_size):
-        need = self.lib.tonic_q_iteration_workspace_bytes(batch_size, self.observation_size,
-                                                          self.action_size, self.hidden)
-        ws = getattr(self, '_fused_workspace', None)
-        if ws is None or ws.numel() < need:
-            # (zero-filled: its head holds the arrival words of the chained launches)
-            self._fused_workspace = ws = torch.zeros(need, dtype=torch.uint8, device=self.device)
-        return ws
+    # read-only, under the names other code knows: the last update's route and the current Slot's graph, noise
+    # buffer and statistics rows
+    _phased_update = property(lambda self: self._u.phased)
+    _graph = property(lambda self: self._u.slot.graph)
+    _static_eps = property(lambda self: self._u.slot.eps)
+    _mpo_stats = property(lambda self: self._u.slot.stats)
 
-    def _enqueue_phased(self, kind, batch, iteration, actor_due, n_global):
-        """One iteration as [policy passes + critic step + critics' weight gradients] -> exchange / clip + Adam
-        -> [actor step + actor's weight gradients] -> exchange / clip + Adam + polyak: 3 + 1 + 2 + 1 launches
-        around the two exchanges instead of the split entry points' 4 + 1 + 5 + 1."""
-        critic, actor, model = self.critic_updater, self.actor_updater, self.model
-        targets = (model.flat_target, model.flat_online, 0, model.target_coeff)
-        if batch is None:                           # this rank drew none of the global batch
-            critic.enqueue_empty(self._infos[0, iteration], n_global)
-            if actor_due:
-                self._enqueue_actor(None, None, iteration, n_global, targets)
-            return
-        B = batch['observations'].shape[0]
-        n = n_global or B * critic.world_size
-        self._enqueue_fused(kind, batch, iteration, actor_due, phase=1)
-        critic._step(n, self._infos[0, iteration])
-        if actor_due:
-            self._enqueue_fused(kind, batch, iteration, actor_due, phase=2)
-            actor._step(n, self._infos[1, iteration], targets=targets)
-
-    def _enqueue_fused_iterations(self, kind, batches, iterations):
-        """The fused iterations of one update call.  With delayed actor updates (td3.py:43-46) the policy passes
-        (launch 1) of iteration k + 1 — they read the actor, the target actor, ITS batch and noise, none of which a
-        critic step writes — ride as more workgroups in the critic-step launch of an iteration k that does not step
-        the actor (tonic_q_iteration_t.ahead: the workspace's other set of launch-1 outputs; iteration k + 1 then
-        starts behind them, stage 2).  At B = 100 a launch fills a ninth of the chip: one launch and its dispatch
-        less per pair of iterations.  Same kernels' code on the same inputs: the same bits
-        (TONIC_AMD_POLICY_AHEAD=0: every iteration by itself; the tests compare)."""
-        due = [bool(self._actor_due(it)) for it in range(iterations)]
-        B = batches['observations'].shape[1]
-        nets = 1 if kind == 2 else 2
-        ahead_on = os.environ.get('TONIC_AMD_POLICY_AHEAD', '1') != '0' and not all(due)
-        args, rides = [], []             # rides[it]: iteration it + 1's policy passes run in it's critic step
-        slot = 0
-        for it in range(iterations):
-            args.append(self._fused_arguments(kind, {k: v[it] for k, v in batches.items()}, it, due[it],
-                                              stage=2 if it and rides[it - 1] else 0, slot=slot))
-            rides.append(ahead_on and not due[it] and it + 1 < iterations and bool(
-                self.lib.tonic_q_iteration_ahead_supported(B, self.observation_size, self.hidden, self.action_size,
-                                                           nets, 2 if due[it + 1] else 1)))
-            if rides[it]:
-                slot ^= 1                # (the passes ahead write the other set: the next iteration's)
-        for it in range(iterations):
-            if rides[it]:
-                args[it].ahead = ctypes.addressof(args[it + 1])      # (read during this call only; `args` lives on)
-            _lib.check(self.lib.tonic_q_iteration(ctypes.byref(args[it]), _lib.current_stream()),
-                       'tonic_q_iteration')
-
-    def _enqueue_fused(self, kind, batch, iteration, actor_due, phase=0):
-        _lib.check(self.lib.tonic_q_iteration(
-            ctypes.byref(self._fused_arguments(kind, batch, iteration, actor_due, phase)), _lib.current_stream()),
-            'tonic_q_iteration')
-
-    def _fused_arguments(self, kind, batch, iteration, actor_due, phase=0, stage=0, slot=0):
-        critic, actor, model, p = self.critic_updater, self.actor_updater, self.model, _lib.ptr
-        B = batch['observations'].shape[0]
-        ws = self._fused_workspace_for(B)
-        mean, std = critic.norm_tensors()
-        noise = getattr(critic, 'target_action_noise', None)
-        eps = self._static_eps
-
-        def optimizer(updater, info_row, constants):
-            h = updater.hyper
-            return _lib.QOptimizer(p(updater.grad_sums), p(updater.exp_avg), p(updater.exp_avg_sq),
-                                   p(updater.state), p(info_row), p(constants), h['lr'],
-                                   h['betas'][0], h['betas'][1], h['eps'])
-        return _lib.QIteration(
-            kind=kind, actor_due=int(bool(actor_due)), B=B, O=self.observation_size, H=self.hidden,
-            A=self.action_size, global_batch=B,
-            d_actor=p(model.flat_actor.flat), d_critics=p(model.flat_critics.flat),
-            d_target_actor=p(model.flat_target_actor.flat),
-            d_target_critics=p(model.flat_target_critics.flat),
-            d_norm_mean=p(mean), d_norm_std=p(std), norm_clip=critic.norm_clip(),
-            d_observations=p(batch['observations']), d_actions=p(batch['actions']),
-            d_next_observations=p(batch['next_observations']), d_rewards=p(batch['rewards']),
-            d_discounts=p(batch['discounts']),
-            d_eps_critic=p(eps[iteration, 0]) if kind != 2 else None,
-            d_eps_actor=p(eps[iteration, 1]) if kind == 1 else None,
-            critic_entropy_coeff=float(getattr(critic, 'entropy_coeff', 0.0)),
-            actor_entropy_coeff=float(getattr(actor, 'entropy_coeff', 0.0)),
-            noise_scale=float(noise.scale if noise else 0.0),
-            noise_clip=float(noise.clip if noise else 0.0),
-            target_coeff=float(model.target_coeff),
-            critic=optimizer(critic, self._infos[0, iteration],
-                             self._static_adam[iteration, 0] if phase == 0 else None),
-            actor=optimizer(actor, self._infos[1, iteration],
-                            self._static_adam[iteration, 1] if phase == 0 else None),
-            d_workspace=p(ws), workspace_bytes=ws.numel(), phase=phase, stage=stage, slot=slot,
-            critic_loss=critic.loss_rule,
-            # the workspace's fp16x2 weight images follow the optimizer epilogues INSIDE an update call; between
-            # calls anybody may have written parameters (load_state_dict, another path): rebuilt on iteration 0
-            refresh_images=int(iteration == 0 or phase != 0))
+    def _stats_width(self):
+        """Floats per iteration the actor updater writes besides its statistics row (Slot.stats)."""
+        return 0
 
     def _graph_signature(self):
         parts = []
@@ -1715,67 +1461,26 @@ class DDPG(Agent):
         # DeterministicQLearning / DeterministicPolicyGradient draw nothing (one unused slot)
         return np.zeros((iterations, 1, self.replay.batch_size, self.action_size), np.float32)
 
-    # -- an update call in chunks: the host draws chunk k + 1's index and noise streams while the GPU runs chunk k
-    _SLOT_FIELDS = ('_static_key', '_static_indices', '_static_eps', '_infos', '_graph', '_static_adam')
-
-    def _select_slot(self, index):
-        """Two sets of everything a captured update graph reads (index / noise / step-constant buffers, the
-        statistics rows, the graph itself): one is being replayed while the host fills the other."""
-        current = getattr(self, '_slot_index', 0)
-        if index == current:
-            return
-        slots = self.__dict__.setdefault('_slots', {})
-        slots[current] = {f: getattr(self, f, None) for f in self._SLOT_FIELDS}
-        chosen = slots.get(index, {})
-        for f in self._SLOT_FIELDS:
-            setattr(self, f, chosen.get(f))
-        self._slot_index = index
-
-    def _update_chunk(self, iterations):
-        """How many iterations one graph of a chunked update holds (0: one graph for the whole call).  The streams
-        are drawn in the reference's order either way (indices: the Buffer's RandomState, noise: torch's CPU
-        generator, both only consumed by this call while it runs) — chunking only moves WHEN the host draws them:
-        7.6 -> ~6 ms per SAC update call of 50 iterations, whose 2 ms of host draws ran in front of 5.4 ms of GPU
-        work (profiles/r06_offpolicy_pmc.md).  Needs the fused iteration in a hipGraph on one rank; chunks hold a
-        whole number of actor delays.  TONIC_AMD_UPDATE_CHUNK=0: off; =n: n iterations per chunk."""
-        chunk = int(os.environ.get('TONIC_AMD_UPDATE_CHUNK', '10'))
-        delay = int(getattr(self, 'delay_steps', 1) or 1)
-        if (chunk <= 0 or iterations < 2 * chunk or iterations % chunk or chunk % delay
-                or type(self)._update is not DDPG._update or type(self).enqueue_update is not DDPG.enqueue_update
-                or os.environ.get('TONIC_AMD_NO_GRAPH', '0') == '1' or parallel.exchanging()
-                or self.critic_updater.world_size > 1 or self._fused_kind() is None or self._fused_in_phases()):
-            return 0
-        return chunk
+    def _update_chunk(self, iterations, route=None):
+        """Iterations per graph of an update call in chunks, 0: one graph (q_update.chunk_size).  A subclass with
+        an enqueue_update or _update of its own gets none."""
+        overridden = type(self)._update is not DDPG._update or type(self).enqueue_update is not DDPG.enqueue_update
+        return chunk_size(iterations, int(getattr(self, 'delay_steps', 1) or 1), route or self._u.route(), overridden)
 
     def _update(self, steps):
-        replay = self.replay
-        chunk = self._update_chunk(replay.batch_iterations)
-        if chunk:
-            parts = []
-            for k in range(replay.batch_iterations // chunk):
-                indices = replay.sample_indices(chunk)         # (host: while the GPU runs the chunk before)
-                eps = self._draw_noise(chunk)
-                self._select_slot(k & 1)
-                parts.append(self.enqueue_update(indices, eps).clone())
-            self._select_slot(0)
-            infos = torch.cat(parts, dim=1).cpu().numpy()
-        else:
-            indices = replay.sample_indices()
-            eps = self._draw_noise(indices.shape[0])
-            infos = self.enqueue_update(indices, eps).cpu().numpy()
-        parallel.check_one_shot()
-        if getattr(self, '_phased_update', False) and int(self._fused_workspace[:4].view(torch.int32)[0]):
-            # (in phases the steps are the updaters' own launches: nothing held them back)
-            raise _lib.TonicHipError(
-                'a chained launch of this update gave up waiting for a peer workgroup (250 ms): its gradient '
-                'sums were incomplete and have been stepped on — the parameters are no longer valid '
-                '(TONIC_AMD_TUNING=q_chain=0 runs one launch per pass)')
-        try:
-            _check_chain(infos)
-        except _lib.TonicHipError:
-            self._step_mirror_valid = False          # skipped steps: the device's counters decide
-            raise
-        replay.last_steps = steps
+        infos, stats = self._u.run()
+        self.replay.last_steps = steps
+        self._log_update(infos, stats)
+        if self.model.observation_normalizer:
+            self.model.observation_normalizer.update()
+        if self.model.return_normalizer and self.serves_return_normalizer:
+            # ddpg.py:102-103 / td3.py:54-55: behind the last iteration (the copies into _low / _high are enqueued
+            # on the stream every graph replay of this update — chunks included — went to, and the infos were
+            # read back above), the ranks' ranges merged first
+            merge_reward_ranges(self.model.return_normalizer)
+            self.model.return_normalizer.update()
+
+    def _log_update(self, infos, stats):
         twin = hasattr(self.model, 'critic_2')
         for row in infos[0]:
             logger.store('critic/loss', row[0])
@@ -1787,14 +1492,6 @@ class DDPG(Agent):
         for row in infos[1][infos[1][:, 6] > 0]:
             logger.store('actor/loss', row[0])
         self.last_infos = infos
-        if self.model.observation_normalizer:
-            self.model.observation_normalizer.update()
-        if self.model.return_normalizer:
-            # ddpg.py:102-103 / td3.py:54-55: behind the last iteration (the copies into _low / _high are enqueued
-            # on the stream every graph replay of this update — chunks included — went to, and the infos were
-            # read back above), the ranks' ranges merged first
-            merge_reward_ranges(self.model.return_normalizer)
-            self.model.return_normalizer.update()
 
 
 def record_reward_range(normalizer, rewards):
@@ -1821,20 +1518,6 @@ def merge_reward_ranges(normalizer):
     torch.distributed.all_reduce(pair, op=torch.distributed.ReduceOp.MAX)
     low, high = pair.cpu().numpy()
     normalizer.min_reward, normalizer.max_reward = np.float32(-low), np.float32(high)
-
-
-def _check_chain(infos):
-    """A chained launch whose workgroups waited 250 ms for a value of a peer that never came (a GPU
-    shared with something that starves the launch, a lost workgroup) does not hang and does not step:
-    the iteration's optimizer epilogues wrote nothing and marked their statistic rows (slot 7).  The
-    parameters are intact; the update is incomplete, which is an error and not a log line."""
-    gave_up = np.argwhere(infos[..., 7] > 0)
-    if len(gave_up):
-        raise _lib.TonicHipError(
-            f'{len(gave_up)} optimizer steps of this update were skipped: a chained launch gave up '
-            f'waiting for a peer workgroup (first: updater {gave_up[0][0]}, iteration '
-            f'{gave_up[0][1]}); parameters, moments and targets are those of the last complete '
-            'iteration (TONIC_AMD_TUNING=q_chain=0 runs one launch per pass)')
 
 
 def _d4pg_model():
@@ -1910,38 +1593,16 @@ class MPO(DDPG):
             eps[it, 1, :S_a * B] = torch.randn(S_a, B, A).numpy().reshape(S_a * B, A)
         return eps
 
-    def enqueue_update(self, indices, eps, graph=None):
-        width = 9 + 2 * self.actor_updater.constraints
-        if (getattr(self, '_mpo_stats', None) is None
-                or tuple(self._mpo_stats.shape) != (indices.shape[0], width)):
-            self._mpo_stats = torch.zeros(indices.shape[0], width, device=self.device)
-            self._graph = None
-        return super().enqueue_update(indices, eps, graph)
+    def _stats_width(self):
+        return 9 + 2 * self.actor_updater.constraints
 
-    def _enqueue_actor(self, observations, eps, iteration, n_global, targets):
-        if observations is None:                    # this rank drew none of the global batch
-            self.actor_updater.enqueue_empty(self._infos[1, iteration], n_global, targets,
-                                             stats_row=self._mpo_stats[iteration])
-            return
-        self.actor_updater.enqueue(observations, eps, self._infos[1, iteration], n_global, targets,
-                                   stats_row=self._mpo_stats[iteration])
-
-    def _update(self, steps):
-        replay = self.replay
-        indices = replay.sample_indices()
-        eps = self._draw_noise(indices.shape[0])
-        infos = self.enqueue_update(indices, eps).cpu().numpy()
-        stats = self._mpo_stats.cpu().numpy()
-        parallel.check_one_shot()
-        replay.last_steps = steps
+    def _log_update(self, infos, stats):
         for row, actor_row in zip(infos[0], stats):                 # mpo.py:92-97
             logger.store('critic/loss', row[0])
             logger.store('critic/q', row[1])
             for key, value in self.actor_updater.infos(actor_row).items():
                 logger.store('actor/' + key, value)
         self.last_infos, self.last_actor_infos = infos, stats
-        if self.model.observation_normalizer:
-            self.model.observation_normalizer.update()
 
 
 class TD3(DDPG):
