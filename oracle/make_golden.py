@@ -189,6 +189,66 @@ def golden_buffer_nstep(tonic):
     save('buffer_nstep', source='tonic/replays/buffers.py:33-79', **out)
 
 
+def golden_buffer_nstep_edges(tonic):
+    """tonic/replays/buffers.py:33-79 at the value edges of accumulate_n_steps (same keys as buffer_nstep, plus
+    `discount`): return_steps - 1 >= max_size (the chain runs the full circle and ends on the row just written,
+    down to max_size == 1), rewards of either zero sign, an infinite reward behind a cut chain (0 * inf: the cut
+    rows turn NaN, nothing selects them away), a NaN next observation, discount factors 1 and 0."""
+    out = {}
+    #         workers size steps discount stores edge
+    cases = [(2, 4, 3, 0.99, 9, None),            # max_size 2 == return_steps - 1
+             (3, 9, 9, 0.99, 11, None),           # max_size 3 < return_steps - 1
+             (3, 3, 2, 0.99, 5, None),            # max_size 1: every chain is the row itself
+             (4, 20, 3, 0.99, 13, 'zeros'),
+             (4, 20, 5, 1.0, 9, 'inf'),             # (row 5 is still there at the end)
+             (2, 12, 3, 0.99, 10, 'nan'),
+             (3, 15, 4, 0.0, 9, 'inf')]
+    for case, (workers, size, steps, discount, n_store, edge) in enumerate(cases):
+        rng = np.random.RandomState(60 + case)
+        buf = tonic.replays.Buffer(size=size, return_steps=steps, discount_factor=discount)
+        buf.initialize(seed=case)
+        pre = f'n{case}_'
+        names = ('observations', 'actions', 'next_observations', 'rewards', 'resets',
+                 'terminations')
+        stored = {k: [] for k in names}
+        for t in range(n_store):
+            kw = dict(observations=rng.normal(size=(workers, 3)).astype(np.float32),
+                      actions=rng.uniform(-1, 1, size=(workers, 2)).astype(np.float32),
+                      next_observations=rng.normal(size=(workers, 3)).astype(np.float32),
+                      rewards=rng.normal(size=workers).astype(np.float32),
+                      resets=rng.uniform(size=workers) < 0.25,
+                      terminations=rng.uniform(size=workers) < 0.15)
+            if edge == 'zeros':
+                kw['rewards'] = rng.choice(np.array([-0.0, 0.0, 1.0, -1.0], np.float32), size=workers)
+                kw['resets'][1] = t % 2 == 1                       # a worker that resets on every second step
+                kw['resets'][2] = False
+            if edge == 'inf':
+                kw['resets'][0] = t == 5                           # worker 0: the chain is cut behind row 5 ...
+                kw['resets'][1] = False
+                if t == 6:                                         # ... and the next reward is infinite
+                    kw['rewards'][:2] = np.inf
+                    kw['rewards'][2] = -np.inf
+            if edge == 'nan':
+                kw['resets'][1] = t == 3
+                kw['resets'][0] = False
+                if t == 4:
+                    kw['next_observations'][:, 1] = np.nan
+            for k in names:
+                stored[k].append(kw[k])
+            with np.errstate(invalid='ignore'):                    # (0 * inf, on purpose)
+                buf.store(**kw)
+            if t == 3:
+                for k, v in buf.buffers.items():
+                    out[pre + 'early_' + k] = v.copy()
+        for k in names:
+            out[pre + 'in_' + k] = np.array(stored[k])
+        for k, v in buf.buffers.items():
+            out[pre + 'buf_' + k] = v.copy()
+        out[pre + 'cfg'] = np.array([workers, size, steps, buf.index, buf.size], np.int64)
+        out[pre + 'discount'] = np.float64(discount)
+    save('buffer_nstep_edges', source='tonic/replays/buffers.py:33-79', n_cases=len(cases), **out)
+
+
 def golden_segment_minibatches(tonic):
     """tonic/replays/segments.py:50-65 with batch_size set (index stream)."""
     seg = tonic.replays.Segment(size=6, batch_iterations=3, batch_size=7)
@@ -594,6 +654,7 @@ def main():
                 globals()['golden_' + name](tonic)
         return
     golden_buffer_nstep(tonic)
+    golden_buffer_nstep_edges(tonic)
     golden_lambda_returns(tonic)
     golden_meanstd(tonic)
     golden_buffer(tonic)

@@ -1032,10 +1032,12 @@ def test_agent_drop_in_trajectory(golden, lib):
                                g['post0/observation_normalizer._std'], rtol=0, atol=1e-7)
 
 
-@pytest.mark.parametrize('O,A,W', [(17, 6, 256), (3, 1, 5), (28, 8, 70)])
+@pytest.mark.parametrize('O,A,W', [(17, 6, 256), (3, 1, 5), (28, 8, 70), (28, 8, 1500)])
 def test_fused_collect_step_equals_act_plus_store(lib, O, A, W):
     """tonic_ppo_collect_step == tonic_ppo_act + tonic_segment_store, bit for bit, and the
-    hipGraph replay of the collect loop equals its eager execution."""
+    hipGraph replay of the collect loop equals its eager execution.  (W = 1500: W * O is more than any record tile
+    the launch can have — `record_floats` of csrc/mlp64.hip is its dynamic LDS, 160 KiB at the most —, so the
+    record of the fused step runs over several chunks.)"""
     import tonic_amd
     import tonic_amd.torch
     from tonic_amd.environments import Box

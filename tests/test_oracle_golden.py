@@ -208,6 +208,19 @@ def nstep_cases(g):
         yield pre, workers, size, steps, index, filled, rows
 
 
+def nstep_golden_cases(g):
+    """Every case of an n-step golden (buffer_nstep: three, discount factor 0.99; buffer_nstep_edges: `n_cases`, each
+    with its own): (prefix, workers, size, return_steps, final index, final size, discount factor, stored rows)."""
+    for case in range(int(g['n_cases']) if 'n_cases' in g.files else 3):
+        pre = f'n{case}_'
+        workers, size, steps, index, filled = (int(x) for x in g[pre + 'cfg'])
+        discount = float(g[pre + 'discount']) if pre + 'discount' in g.files else 0.99
+        rows = [{k: g[pre + 'in_' + k][t] for k in (
+            'observations', 'actions', 'next_observations', 'rewards', 'resets', 'terminations')}
+            for t in range(g[pre + 'in_rewards'].shape[0])]
+        yield pre, workers, size, steps, index, filled, discount, rows
+
+
 def test_buffer_n_step_accumulation_bit_exact(golden):
     """Buffer(return_steps > 1): store + accumulate_n_steps (buffers.py:33-79)."""
     g = golden('buffer_nstep')
@@ -221,6 +234,42 @@ def test_buffer_n_step_accumulation_bit_exact(golden):
         assert (buf.index, buf.size) == (index, filled)
         for k in buf.KEYS:
             assert np.array_equal(buf.buffers[k], g[pre + 'buf_' + k], equal_nan=True), k
+
+
+def _buffer_port_equals_golden(g):
+    """The helper and assertions of test_buffer_n_step_accumulation_bit_exact for any n-step golden, plus the sign of
+    every zero."""
+    for pre, workers, size, steps, index, filled, discount, rows in nstep_golden_cases(g):
+        buf = port.BufferPort(size, workers, return_steps=steps, discount_factor=discount)
+        for t, row in enumerate(rows):
+            with np.errstate(invalid='ignore'):                # (the edge cases multiply 0 by inf, as recorded)
+                buf.store(**row)
+            if t == 3:
+                for k in buf.KEYS:
+                    assert np.array_equal(buf.buffers[k], g[pre + 'early_' + k], equal_nan=True), (pre, k)
+        assert (buf.index, buf.size) == (index, filled)
+        for k in buf.KEYS:
+            assert np.array_equal(buf.buffers[k], g[pre + 'buf_' + k], equal_nan=True), (pre, k)
+            held = ~np.isnan(g[pre + 'buf_' + k])               # (array_equal takes -0.0 for 0.0)
+            assert np.array_equal(np.signbit(buf.buffers[k])[held], np.signbit(g[pre + 'buf_' + k])[held]), (pre, k)
+
+
+def test_buffer_n_step_value_edges_bit_exact(golden):
+    """The same at the value edges recorded from the reference in buffer_nstep_edges.npz: return_steps - 1 >=
+    max_size (the chain ends on the row just written), signed zero rewards, an infinite reward behind a cut chain
+    (0 * inf is NaN exactly where the reference's is), a NaN next observation, discount factors 1 and 0."""
+    g = golden('buffer_nstep_edges')
+    cases = list(nstep_golden_cases(g))
+    assert len(cases) == 7
+    assert any(steps - 1 >= size // workers for _, workers, size, steps, *_ in cases)
+    assert any(size // workers == 1 for _, workers, size, *_ in cases)
+    rewards = np.concatenate([g[pre + 'in_rewards'].ravel() for pre, *_ in cases])
+    assert (np.signbit(rewards) & (rewards == 0)).any() and (~np.signbit(rewards) & (rewards == 0)).any()
+    assert np.isinf(rewards).any()
+    assert any(np.isnan(g[pre + 'in_next_observations']).any() for pre, *_ in cases)
+    # the edges reach the stored rows: a NaN reward where a chain was cut before the infinite one, a zero of each sign
+    assert any(np.isnan(g[pre + 'buf_rewards'][:filled]).any() for pre, _, _, _, _, filled, *_ in cases)
+    _buffer_port_equals_golden(g)
 
 
 def test_segment_minibatch_indices_bit_exact(golden):

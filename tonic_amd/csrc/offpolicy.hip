@@ -2450,7 +2450,7 @@ extern "C" int tonic_buffer_gather(const int64_t* d_indices, const float* d_buf_
                                    void* stream) {
   TONIC_REQUIRE(d_indices && d_buf_observations && d_buf_actions && d_buf_next_observations &&
                     d_buf_rewards && d_buf_discounts && d_observations && d_actions &&
-                    d_next_observations && d_rewards && d_discounts && W > 0 && B > 0,
+                    d_next_observations && d_rewards && d_discounts && W > 0 && B > 0 && O > 0 && A > 0,
                 TONIC_ERR_INVALID_ARGUMENT, "tonic_buffer_gather: bad argument");
   GatherArgs g{d_indices, d_buf_observations, d_buf_actions, d_buf_next_observations,
                d_buf_rewards, d_buf_discounts, d_observations, d_actions, d_next_observations,
