@@ -63,10 +63,10 @@ const char* tonic_last_error(void);
  * summed over the action dimensions); the MPO entries take 1 .. 256 samples per state, 18 = tonic_twin_q_grad_ranged /
  * tonic_actor_q_grad_ranged (the Return normaliser's value head on the off-policy split entries), 19 =
  * tonic_mlp_torso_head: `H` codes that carry the bounds of a Gaussian policy head's scale (additive: every
- * earlier entry keeps its signature)
+ * earlier entry keeps its signature), 20 = tonic_twin_distributional_q_grad / _workspace_bytes (TD4; additive)
  * and the gfx target the kernels were built for.  TONIC_ABI_VERSION is what a binding was compiled against:
  * tonic_amd/_fastcall (csrc/fastcall.c) and tonic_amd/_lib.py compare it with the loaded library's answer. */
-#define TONIC_ABI_VERSION 19
+#define TONIC_ABI_VERSION 20
 int32_t tonic_abi_version(void);
 const char* tonic_target_arch(void);
 
@@ -1023,6 +1023,39 @@ int tonic_distributional_actor_grad(const float* d_actor_params, const float* d_
                                     const float* d_values, float* d_grad_sums, int32_t B,
                                     int32_t O, int32_t H, int32_t A, int32_t NA,
                                     void* d_workspace, int64_t workspace_bytes, void* stream);
+
+/* ---- TD4: twin distributional critics (tonic/tensorflow/agents/td4.py, tensorflow/updaters/critics.py:279-336,
+ *   TwinCriticDistributionalDeterministicQLearning — the one agent of the library without a torch form).  TD3's
+ *   twin critics, clipped target-action noise and delayed actor steps on D4PG's categorical critic.
+ *   d_target_critics / d_critics: two blocks [critic_1 | critic_2], each in the D4PG critic's layout
+ *   (tonic_mlp_actor_param_count(O + A, H, NA, 1)); d_values: the ONE support of all four heads, float32 [NA],
+ *   ascending, 2 <= NA <= 64; d_eps [B, A]: one standard-normal draw; `H`: an `H` code as above.
+ *
+ * tonic_twin_distributional_q_grad — the critic step up to the optimizer step, per row of the batch:
+ *     a'      = clamp(target_actor(s') + clamp(noise_scale * eps, -noise_clip, noise_clip), -1, 1)
+ *     p_k     = softmax(target_critic_k(s', a')), mu_k = sum_i p_k,i z_i                    (k = 1, 2)
+ *     T       = project(r + discount * z, p_2 if mu_2 < mu_1 else p_1)   — the first critic on a tie or a NaN mean;
+ *               the projection of tonic_distributional_q_grad, run once
+ *     loss_k  = -sum_i T_i log_softmax(critic_k(s, a))_i ; loss = mean(loss_1) + mean(loss_2)
+ *   Passes: 1 the target actor (its tail adds the noise and encodes (s', a') and (s, a)), 2 the two target critics,
+ *   3 the two online critics, 4 the loss kernel (one wave per row, lane = atom), 5 the statistics (float64, fixed
+ *   order), 6 one backward per online critic into its own block of the sums.
+ *   Output: gradient SUMS of [critic_1 | critic_2] + 8 statistics {sum loss_1 + loss_2, sum q1, sum q2, 0, 0, B, 0, 0}
+ *   with q_k = sum_i softmax(critic_k(s, a))_i z_i, the ONLINE critics' means (the row tonic_twin_q_grad leaves).
+ *   -1: a NULL pointer, B <= 0, NA outside 2 .. 64, an unknown `H`, a negative or non-finite noise parameter;
+ *   -4: a workspace below tonic_twin_distributional_workspace_bytes (never below
+ *   tonic_distributional_workspace_bytes of the same shape: such a workspace serves the actor step too).
+ *   The actor step is tonic_distributional_actor_grad on d_critics: it reads the first block, critic_1. */
+int64_t tonic_twin_distributional_workspace_bytes(int32_t B, int32_t O, int32_t A, int32_t H, int32_t NA);
+int tonic_twin_distributional_q_grad(const float* d_target_actor, const float* d_target_critics,
+                                     const float* d_critics, const float* d_norm_mean,
+                                     const float* d_norm_std, double norm_clip,
+                                     const float* d_observations, const float* d_actions,
+                                     const float* d_next_observations, const float* d_rewards,
+                                     const float* d_discounts, const float* d_eps, const float* d_values,
+                                     float* d_grad_sums, int32_t B, int32_t O, int32_t H, int32_t A,
+                                     int32_t NA, double noise_scale, double noise_clip, void* d_workspace,
+                                     int64_t workspace_bytes, void* stream);
 
 /* ---- MPO (tonic/torch/agents/mpo.py): Gaussian policy head with a tanh loc and
  *   sigma = clamp(softplus(.), 1e-4, 1) (models/actors.py:69-98, two heads), ONE critic with

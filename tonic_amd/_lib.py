@@ -188,6 +188,9 @@ SIGNATURES = {
                                     [c_vp, c_i64, c_vp]),
     'tonic_distributional_actor_grad': (ctypes.c_int, [c_vp] * 4 + [c_f64] + [c_vp] * 3 +
                                         [c_i32] * 5 + [c_vp, c_i64, c_vp]),
+    'tonic_twin_distributional_workspace_bytes': (c_i64, [c_i32] * 5),
+    'tonic_twin_distributional_q_grad': (ctypes.c_int, [c_vp] * 5 + [c_f64] + [c_vp] * 8 + [c_i32] * 5 +
+                                         [c_f64] * 2 + [c_vp, c_i64, c_vp]),
     'tonic_mpo_workspace_bytes': (c_i64, [c_i32] * 5),
     'tonic_expected_sarsa_grad': (ctypes.c_int, [c_vp] * 5 + [c_f64] + [c_vp] * 7 + [c_i32] * 5 +
                                   [c_vp, c_i64, c_vp]),
@@ -249,7 +252,7 @@ SIGNATURES = {
 }
 
 
-ABI_VERSION = 19       # include/tonic_hip.h: tonic_abi_version()
+ABI_VERSION = 20      # include/tonic_hip.h: tonic_abi_version()
 
 
 class TonicHipError(RuntimeError):

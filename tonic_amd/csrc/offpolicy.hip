@@ -331,6 +331,65 @@ __global__ __launch_bounds__(256) void distributional_critic_loss_kernel(
   if (lane == 0) loss_m[m] = loss;
 }
 
+// TD4 (the library's TwinCriticDistributionalDeterministicQLearning): two target critics and two online critics over
+// ONE support.  p_k = softmax(target_logits_k), mu_k = sum_i p_k,i z_i; the row's target distribution is that of the
+// target critic with the smaller mean — critic 2 only when mu_2 < mu_1, so a tie and a NaN mean select critic 1 —
+// projected as above.  The triangular weights depend on the returns and the support alone, so the loop runs once, on
+// the selected p_next.  Each online critic takes the cross-entropy against the same target:
+//   d loss_k / d logits_k,i = softmax_k,i sum(T) - T_i ;  sample_m [3][Bp] = {loss_1 + loss_2, q1, q2} per sample,
+// q_k = sum_i softmax(logits_k)_i z_i the ONLINE critics' means (the logged critic/q1, critic/q2).
+__global__ __launch_bounds__(256) void twin_distributional_critic_loss_kernel(
+    const float* target_logits_1, const float* target_logits_2, const float* logits_1, const float* logits_2, int ld,
+    const float* rewards, const float* discounts, const float* values, int NA, float* dlogits_1, float* dlogits_2,
+    float* sample_m, int B, int Bp) {
+  const int lane = threadIdx.x & 63;
+  const int m = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (m >= B) return;
+  const bool live = lane < NA;
+  const int i = live ? lane : NA - 1;
+  const float z = values[i], vmin = values[0], vmax = values[NA - 1];
+  const float p1 = wave_softmax(target_logits_1[(int64_t)m * ld + i], live, nullptr);
+  const float p2 = wave_softmax(target_logits_2[(int64_t)m * ld + i], live, nullptr);
+  const float mu1 = wave_sum(live ? p1 * z : 0.f), mu2 = wave_sum(live ? p2 * z : 0.f);
+  const float p_next = mu2 < mu1 ? p2 : p1;                          // (wave-uniform: every lane holds both sums)
+  const float ret = rewards[m] + discounts[m] * z;
+  const float clipped = fminf(fmaxf(ret, vmin), vmax);
+  const float d_pos = (i + 1 < NA ? values[i + 1] : vmin) - z;
+  const float d_neg = z - (i > 0 ? values[i - 1] : vmax);
+  float target = 0.f;
+  for (int j = 0; j < NA; ++j) {
+    const float delta = __shfl(clipped, j, 64) - z;
+    const float sign = delta >= 0.f ? 1.f : 0.f;
+    const float hat = (sign * delta / d_pos) - ((1.f - sign) * delta / d_neg);
+    target += fminf(fmaxf(1.f - hat, 0.f), 1.f) * __shfl(p_next, j, 64);
+  }
+  if (!live) target = 0.f;
+  const float total = wave_sum(target);
+  float log_norm_1, log_norm_2;
+  const float logit_1 = logits_1[(int64_t)m * ld + i], logit_2 = logits_2[(int64_t)m * ld + i];
+  const float q1p = wave_softmax(logit_1, live, &log_norm_1), q2p = wave_softmax(logit_2, live, &log_norm_2);
+  const float loss_1 = -wave_sum(live ? target * (logit_1 - log_norm_1) : 0.f);
+  const float loss_2 = -wave_sum(live ? target * (logit_2 - log_norm_2) : 0.f);
+  const float q1 = wave_sum(live ? q1p * z : 0.f), q2 = wave_sum(live ? q2p * z : 0.f);
+  if (lane < ld) {
+    dlogits_1[(int64_t)m * ld + lane] = live ? q1p * total - target : 0.f;
+    dlogits_2[(int64_t)m * ld + lane] = live ? q2p * total - target : 0.f;
+  }
+  if (lane == 0) { sample_m[m] = loss_1 + loss_2; sample_m[Bp + m] = q1; sample_m[2 * Bp + m] = q2; }
+}
+
+// the 8 statistics {sum loss_1 + loss_2, sum q1, sum q2, 0, 0, B, 0, 0} (the stats_kind 3 row) from the per-sample
+// values sample_m [3][Bp] (fixed order, float64)
+__global__ void twin_loss_stats_kernel(const float* sample_m, float* stats, int B, int Bp) {
+  double a = 0, b = 0, c = 0;
+  for (int m = threadIdx.x; m < B; m += blockDim.x) { a += sample_m[m]; b += sample_m[Bp + m]; c += sample_m[2 * Bp + m]; }
+  block_sum3(a, b, c);
+  if (threadIdx.x == 0) {
+    stats[0] = (float)a; stats[1] = (float)b; stats[2] = (float)c; stats[3] = 0.f;
+    stats[4] = 0.f; stats[5] = (float)B; stats[6] = 0.f; stats[7] = 0.f;
+  }
+}
+
 // DistributionalDeterministicPolicyGradient (actors.py:203-224): value = sum_i softmax(logits)_i z_i,
 // loss = -mean(value): d(-value) / d logits_i = -p_i (z_i - value).
 __global__ __launch_bounds__(256) void distributional_actor_loss_kernel(
@@ -2180,6 +2239,92 @@ extern "C" int tonic_distributional_actor_grad(
   TRY(actor_shaped_backward(d_actor_params, as, d_observations, O, B, w.a_h1, w.a_h2, w.dloc,
                             nullptr, ldh, w.da_h2, w.da_h1, d_grad_sums, nullptr, 0, 0, st));
   TONIC_CHECK_LAUNCH("tonic_distributional_actor_grad");
+  return TONIC_OK;
+}
+
+// ------------------------------------------------------------------ TD4 (twin distributional critics)
+// TD3's twin critics, clipped target-action noise and delayed actor steps on D4PG's categorical critic: the critic
+// step of both online critics in one entry.  The actor step is tonic_distributional_actor_grad on the first block of
+// the flat critics, critic_1.
+
+namespace {
+
+// D4PG's arrays — a workspace of this size serves tonic_distributional_actor_grad as well — and the second critic's:
+// `one` holds the policy pass, X / X2, critic 1 (target and online) and the chain's (dz2, dz1), which the two
+// backward passes use one after the other.
+struct TwinDistributionalBuffers {
+  DistributionalBuffers one;
+  float *t_h1, *t_h2, *t_logits, *c_h1, *c_h2, *logits, *dlogits, *sample_m;
+  TwinDistributionalBuffers(Workspace& ws, int B, int O, int A, int32_t H, int NA) : one(ws, B, O, A, H, NA) {
+    const int64_t Bp = pad16(B), ldl = pad16(NA);
+    const int64_t hid = Bp * hidden_pitch(H), region = hid * hidden_layers(H);
+    t_h1 = ws.take(region); t_h2 = behind(t_h1, hid); c_h1 = ws.take(region); c_h2 = behind(c_h1, hid);
+    t_logits = ws.take(Bp * ldl); logits = ws.take(Bp * ldl); dlogits = ws.take(Bp * ldl);
+    sample_m = ws.take(3 * Bp);
+  }
+};
+
+}  // namespace
+
+extern "C" int64_t tonic_twin_distributional_workspace_bytes(int32_t B, int32_t O, int32_t A, int32_t H,
+                                                             int32_t NA) {
+  return measure<TwinDistributionalBuffers>(B, O, A, H, NA);
+}
+
+extern "C" int tonic_twin_distributional_q_grad(
+    const float* d_target_actor, const float* d_target_critics, const float* d_critics,
+    const float* d_norm_mean, const float* d_norm_std, double norm_clip,
+    const float* d_observations, const float* d_actions, const float* d_next_observations,
+    const float* d_rewards, const float* d_discounts, const float* d_eps, const float* d_values,
+    float* d_grad_sums, int32_t B, int32_t O, int32_t H, int32_t A, int32_t NA, double noise_scale,
+    double noise_clip, void* d_workspace, int64_t workspace_bytes, void* stream) {
+  TONIC_REQUIRE(d_target_actor && d_target_critics && d_critics && d_norm_mean && d_norm_std &&
+                    d_observations && d_actions && d_next_observations && d_rewards &&
+                    d_discounts && d_eps && d_values && d_grad_sums && d_workspace && B > 0 && NA >= 2 &&
+                    NA <= 64 && hidden_known(H),
+                TONIC_ERR_INVALID_ARGUMENT, "tonic_twin_distributional_q_grad: bad argument (2 <= atoms <= 64)");
+  TONIC_REQUIRE(std::isfinite(noise_scale) && std::isfinite(noise_clip) && noise_scale >= 0 && noise_clip >= 0,
+                TONIC_ERR_INVALID_ARGUMENT,
+                "tonic_twin_distributional_q_grad: noise scale %g, clip %g (finite and >= 0)", noise_scale, noise_clip);
+  TONIC_REQUIRE(workspace_bytes >= tonic_twin_distributional_workspace_bytes(B, O, A, H, NA),
+                TONIC_ERR_WORKSPACE, "tonic_twin_distributional_q_grad: workspace too small");
+  hipStream_t st = as_stream(stream);
+  const int Bp = pad16(B), ldx = pitch16(O + A), ldh = pad16(A), ldl = pad16(NA);
+  Workspace ws{static_cast<char*>(d_workspace), 0};
+  const TwinDistributionalBuffers w(ws, B, O, A, H, NA);
+  const DistributionalBuffers& w1 = w.one;
+  const ActorShape as = actor_shape(O, H, A, 1), cs = actor_shape(O + A, H, NA, 1);
+  const int64_t Pc = actor_count(cs);               // the flat blocks: [critic_1 | critic_2]
+  // 1  a' = clamp(target_actor(s') + clamp(scale eps, -clip, clip), -1, 1); the tail encodes (s', a') -> X and the
+  //    stored (s, a) -> X2
+  PolicyTail tail{};
+  tail.post = POST_TARGET_NOISE; tail.eps = d_eps; tail.actions = w1.act;
+  tail.noise_scale = (float)noise_scale; tail.noise_clip = (float)noise_clip;
+  tail.enc_obs = d_next_observations; tail.enc_obs2 = d_observations; tail.enc_act2 = d_actions;
+  tail.enc_mean = d_norm_mean; tail.enc_std = d_norm_std; tail.enc_clip = clip_bound(norm_clip);
+  tail.enc_out = w1.X; tail.enc_out2 = w1.X2; tail.enc_ld = ldx;
+  TRY(policy_pass(d_target_actor, as, d_next_observations, B, w1.a_h1, w1.a_h2, w1.head, w1.head, ldh, true, st, tail));
+  // 2  the two target critics on (s', a')
+  TRY(actor_forward(d_target_critics, cs, w1.X, B, w1.t_h1, w1.t_h2, w1.t_logits, w1.t_logits, ldl, false, st,
+                    nullptr, nullptr, ldx));
+  TRY(actor_forward(d_target_critics + Pc, cs, w1.X, B, w.t_h1, w.t_h2, w.t_logits, w.t_logits, ldl, false, st,
+                    nullptr, nullptr, ldx));
+  // 3  the two online critics on (s, a)
+  TRY(actor_forward(d_critics, cs, w1.X2, B, w1.c_h1, w1.c_h2, w1.logits, w1.logits, ldl, false, st, nullptr,
+                    nullptr, ldx));
+  TRY(actor_forward(d_critics + Pc, cs, w1.X2, B, w.c_h1, w.c_h2, w.logits, w.logits, ldl, false, st, nullptr,
+                    nullptr, ldx));
+  // 4 + 5  the loss on the target distribution of the smaller mean, and the statistics behind both gradient blocks
+  hipLaunchKernelGGL(twin_distributional_critic_loss_kernel, dim3((B + 3) / 4), dim3(256), 0, st, w1.t_logits,
+                     w.t_logits, w1.logits, w.logits, ldl, d_rewards, d_discounts, d_values, NA, w1.dlogits, w.dlogits,
+                     w.sample_m, B, Bp);
+  hipLaunchKernelGGL(twin_loss_stats_kernel, dim3(1), dim3(1024), 0, st, w.sample_m, d_grad_sums + 2 * Pc, B, Bp);
+  // 6  each online critic's backward into its own block of the sums
+  TRY(actor_shaped_backward(d_critics, cs, w1.X2, ldx, B, w1.c_h1, w1.c_h2, w1.dlogits, nullptr, ldl, w1.dz2, w1.dz1,
+                            d_grad_sums, nullptr, 0, 0, st));
+  TRY(actor_shaped_backward(d_critics + Pc, cs, w1.X2, ldx, B, w.c_h1, w.c_h2, w.dlogits, nullptr, ldl, w1.dz2,
+                            w1.dz1, d_grad_sums + Pc, nullptr, 0, 0, st));
+  TONIC_CHECK_LAUNCH("tonic_twin_distributional_q_grad");
   return TONIC_OK;
 }
 

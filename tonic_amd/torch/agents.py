@@ -1212,14 +1212,14 @@ def log_ppo_critic_rows(rows):
 
 # ----------------------------------------------------------------- off-policy (SAC / TD3)
 
-def _twin_model(head):
+def _twin_model(head, critic_head=None):
     return models.ActorTwinCriticWithTargets(
         actor=models.Actor(
             encoder=models.ObservationEncoder(),
             torso=models.MLP((256, 256), torch.nn.ReLU), head=head),
         critic=models.Critic(
             encoder=models.ObservationActionEncoder(),
-            torso=models.MLP((256, 256), torch.nn.ReLU), head=models.ValueHead()),
+            torso=models.MLP((256, 256), torch.nn.ReLU), head=critic_head or models.ValueHead()),
         observation_normalizer=normalizers.MeanStd())
 
 
@@ -1627,6 +1627,22 @@ class TD3(DDPG):
         # TargetActionNoise: one torch.randn_like(actions) per critic update (critics.py:131)
         B, A = self.replay.batch_size, self.action_size
         return np.stack([torch.randn(B, A).numpy()[None] for _ in range(iterations)])
+
+
+class TD4(TD3):
+    """tonic/tensorflow/agents/td4.py:5-32, the one agent of the library without a torch form: TD3 — twin critics,
+    clipped target-action noise, delayed actor and target updates — on D4PG's categorical critics and 5-step
+    returns.  The actor ascends critic_1's mean (`model.critic`, the alias TD3 sets)."""
+
+    def __init__(self, model=None, replay=None, exploration=None, actor_updater=None,
+                 critic_updater=None, delay_steps=2):
+        super().__init__(
+            model=model or _twin_model(models.DeterministicPolicyHead(),
+                                       models.DistributionalValueHead(-150., 150., 51)),
+            replay=replay or replays.Buffer(return_steps=5), exploration=exploration,
+            actor_updater=actor_updater or updaters.DistributionalDeterministicPolicyGradient(),
+            critic_updater=critic_updater or updaters.TwinCriticDistributionalDeterministicQLearning(),
+            delay_steps=delay_steps)
 
 
 class SAC(DDPG):

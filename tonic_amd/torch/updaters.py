@@ -1336,6 +1336,61 @@ class DistributionalDeterministicQLearning(_TwinCriticQLearning):
         return self._info(lambda row: self.enqueue(batch, None, row), ('loss',))
 
 
+class TwinCriticDistributionalDeterministicQLearning(_TwinCriticQLearning):
+    """TD4's critic step (the library's tensorflow/updaters/critics.py:279-336, which has no torch form): TD3's
+    clipped target-action noise and twin critics on D4PG's categorical critic.  Per row, the target distribution is
+    that of the target critic with the smaller mean (the first on a tie), projected onto the support at
+    r + discount * z; both online critics take the cross-entropy against it (tonic_twin_distributional_q_grad).
+    Logs the row of TD3 and SAC: loss, and the online critics' mean values q1, q2."""
+    stock_capable = False
+    stats_kind = 3          # {loss, q1 mean, q2 mean}
+
+    def __init__(self, optimizer=None, target_action_noise=None, gradient_clip=0):
+        self.optimizer = optimizer
+        self.gradient_clip = gradient_clip
+        self.target_action_noise = target_action_noise or TargetActionNoise(scale=0.2, clip=0.5)
+
+    def initialize(self, model):
+        name = type(self).__name__
+        if not hasattr(model, 'critic_2'):
+            raise NotImplementedError(f'{name} needs a model with twin critics (ActorTwinCriticWithTargets)')
+        critics = (model.critic_1, model.critic_2, model.target_critic_1, model.target_critic_2)
+        if not all(getattr(critic.head, 'num_atoms', 0) for critic in critics):
+            raise NotImplementedError(f'{name} needs critics with a DistributionalValueHead')
+        support = critics[0].head.values
+        for critic in critics[1:]:
+            # one support for the projection, the target means and the logged values (the targets are copies made
+            # at construction: unequal only when somebody changed one head afterwards)
+            if critic.head.values.shape != support.shape or not torch.equal(critic.head.values.cpu(), support.cpu()):
+                raise NotImplementedError(f'{name} needs the same support in all four critics\' heads')
+        super().initialize(model)
+
+    def _policy_params(self):
+        return self.model.flat_target_actor.flat
+
+    def _offpolicy_workspace(self, batch):
+        need = self.lib.tonic_twin_distributional_workspace_bytes(
+            batch, self.observation_size, self.action_size, self.hidden, self.atoms)
+        if self.workspace is None or self.workspace.numel() < need:
+            self.workspace = torch.empty(need, dtype=torch.uint8, device=self.grad_sums.device)
+        return self.workspace
+
+    def enqueue(self, batch, eps, info_row, n_global=None):
+        """eps: the [B, A] standard-normal draw of the target-action noise."""
+        B = batch['observations'].shape[0]
+        ws = self._offpolicy_workspace(B)
+        mean, std = self.norm_tensors()
+        noise = self.target_action_noise
+        p = _lib.ptr
+        _lib.check(self.lib.tonic_twin_distributional_q_grad(
+            p(self._policy_params()), p(self.model.flat_target_critics.flat), p(self.flat.flat), p(mean), p(std),
+            self.norm_clip(), p(batch['observations']), p(batch['actions']), p(batch['next_observations']),
+            p(batch['rewards']), p(batch['discounts']), p(eps), p(self.values), p(self.grad_sums), B,
+            self.observation_size, self.hidden, self.action_size, self.atoms, float(noise.scale), float(noise.clip),
+            p(ws), ws.numel(), _lib.current_stream()), 'tonic_twin_distributional_q_grad')
+        self._step(n_global or B * self.world_size, info_row)
+
+
 class ExpectedSARSA(_TwinCriticQLearning):
     """critics.py:238-282 (MPO): one critic regressed on r + discount * the mean target value of
     `num_samples` actions drawn from the target actor (tonic_expected_sarsa_grad)."""
