@@ -63,10 +63,11 @@ const char* tonic_last_error(void);
  * summed over the action dimensions); the MPO entries take 1 .. 256 samples per state, 18 = tonic_twin_q_grad_ranged /
  * tonic_actor_q_grad_ranged (the Return normaliser's value head on the off-policy split entries), 19 =
  * tonic_mlp_torso_head: `H` codes that carry the bounds of a Gaussian policy head's scale (additive: every
- * earlier entry keeps its signature), 20 = tonic_twin_distributional_q_grad / _workspace_bytes (TD4; additive)
+ * earlier entry keeps its signature), 20 = tonic_twin_distributional_q_grad / _workspace_bytes (TD4; additive),
+ * 21 = tonic_q_regression_grad / tonic_q_regression_workspace_bytes (QRegression; additive)
  * and the gfx target the kernels were built for.  TONIC_ABI_VERSION is what a binding was compiled against:
  * tonic_amd/_fastcall (csrc/fastcall.c) and tonic_amd/_lib.py compare it with the loaded library's answer. */
-#define TONIC_ABI_VERSION 20
+#define TONIC_ABI_VERSION 21
 int32_t tonic_abi_version(void);
 const char* tonic_target_arch(void);
 
@@ -869,6 +870,36 @@ int tonic_actor_q_grad_ranged(int32_t kind, const float* d_actor_params, const f
                               int32_t B, int32_t O, int32_t H, int32_t A, double entropy_coeff,
                               const float* d_value_low, const float* d_value_high, void* d_workspace,
                               int64_t workspace_bytes, void* stream);
+
+/* ---- regression of one critic on returns the caller computed (ABI 21) ---------------------
+ * replaces: QRegression.__call__ (tonic/torch/updaters/critics.py:31-53): values = model.critic(observations,
+ *   actions); loss = self.loss(values, returns); backward — for Monte-Carlo, n-step or lambda-returns of the
+ *   caller's own.  One call encodes (s, a) once (encoders.py:28-31 with MeanStd and its clip), runs the ONLINE
+ *   critic's forward and its backward under the step loss y = returns[m]: no policy pass, no target network, no
+ *   next observations, weight images of this critic only.
+ * d_critic: ONE critic in the padded off-policy layout, tonic_q_critic_param_count floats.  `H`: any `H` code
+ *   of the off-policy entries (a head code's bounds are ignored, as a critic ignores them everywhere).  `loss`:
+ *   tonic_critic_loss_t as above, NULL = MSE.  d_value_low / d_value_high: both NULL = plain heads; both given = the
+ *   Return normaliser's squashed head, read on the device as in the *_ranged entries (exactly one NULL =
+ *   TONIC_ERR_INVALID_ARGUMENT).  d_returns [B] is read as given: neither rewards, discounts nor target values
+ *   enter.
+ * Output: gradient SUMS over the batch for the critic + 8 statistics {loss_term_sum, q_sum, 0, 0, 0, B, 0, 0} (with
+ *   a squashed head: of v) — what tonic_optimizer_step with stats_kind 3 expects, grad_scale = 1 / B.
+ * Routes, as the critic step chooses between them: fp16x2 weight images + one-launch forward and backward where
+ *   the images serve the shape; the float32 one-launch passes for any other plain torso the fused kernels hold;
+ *   layer by layer (one launch per layer, the loss as a launch of its own) for every other torso.  On each route
+ *   the sums and statistics are bit-identical to the DDPG critic step (kind 2) with rewards = returns and
+ *   discounts = 0 on finite target networks.
+ * Workspace: a layout of its own, never above tonic_offpolicy_workspace_bytes for the same shape.  Checked
+ *   before anything touches the device, in this order: the low / high pair, `loss`, the pointers with B > 0 and a
+ *   known `H`, the workspace size. */
+int64_t tonic_q_regression_workspace_bytes(int32_t B, int32_t O, int32_t A, int32_t H);
+int tonic_q_regression_grad(const float* d_critic, const float* d_norm_mean, const float* d_norm_std,
+                            double norm_clip, const float* d_observations, const float* d_actions,
+                            const float* d_returns, float* d_grad_sums, int32_t B, int32_t O, int32_t H,
+                            int32_t A, const tonic_critic_loss_t* loss, const float* d_value_low,
+                            const float* d_value_high, void* d_workspace, int64_t workspace_bytes,
+                            void* stream);
 
 /* ---- one whole learner iteration of DDPG / TD3 / SAC in 8 launches (4 when the actor is not due).
  * replaces: the body of DDPG._update's loop (tonic/torch/agents/ddpg.py:95-112; td3.py:38-55 with

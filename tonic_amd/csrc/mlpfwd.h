@@ -188,6 +188,9 @@ struct MlpBwdArgs {
   //               (critics.py:72-79, 166-175, 219-227; MSE: 2 (q_z - y)); stats {loss_term_sum, q1_sum, q2_sum, 0, 0, B, 0, 0}
   //   LOSS_ACTOR  SAC: alpha * logp - min(q1, q2); TD3 / DDPG: -q1 (actors.py:177-179, 254-257);
   //               dq_z = -1 on the smaller critic (-1/2 each on ties); stats {loss_sum, 0, ..., B, ..}
+  //   LOSS_REGRESSION  y = returns[m] as given (critics.py:31-53, QRegression): one critic, dq = loss'(q - y), stats
+  //               {loss_term_sum, q_sum, 0, 0, 0, B, 0, 0}.  Kernels of their own (mlp_backward_regression_kernel), which
+  //               take `returns` beside this struct: none of the l_rewards / l_discounts / l_tq / l_logp is read.
   int loss;
   const float* l_rewards; const float* l_discounts; const float* l_tq; const float* l_logp;
   const float* l_q; float* l_stats;
@@ -212,7 +215,7 @@ struct MlpBwdArgs {
   // 36 bytes of scratch per lane.)
   float hb_scale_lo = kScaleMin, hb_scale_hi = kScaleMax;
 };
-enum MlpBwdLoss : int { LOSS_GIVEN = 0, LOSS_TD = 1, LOSS_ACTOR = 2 };
+enum MlpBwdLoss : int { LOSS_GIVEN = 0, LOSS_TD = 1, LOSS_ACTOR = 2, LOSS_REGRESSION = 3 };
 
 // The TD target and the errors of one sample (shared by critic_loss_kernel and the folded form)
 // ---- hand-over between the workgroups of a chained launch: "the data is its own flag"
@@ -285,7 +288,8 @@ __device__ __forceinline__ float td_target(const float* rewards, const float* di
 // The critic's loss on one error e = q - y (tonic_critic_loss_t: torch.nn.functional.{mse,l1,smooth_l1,huber}_loss
 // and their backward, float32; `param` = beta / delta rounded once by the host).  The ONLY two places that know
 // what the TD loss is: critic_loss_kernel, mlp_loss_stats and the LOSS_TD branches of both backward bodies call
-// them, so the split entries and the fused iteration keep the same bits.  `kind` / `param` are kernel arguments
+// them, so the split entries and the fused iteration keep the same bits — and so do regression_loss_kernel and the
+// bodies' REGRESS branches, whose error is q - returns[m] (LOSS_REGRESSION).  `kind` / `param` are kernel arguments
 // (wave-uniform: the branch is scalar).  A NaN error: every term is NaN; the gradient is NaN except where the
 // rule is the sign alone (L1, smooth-L1 with beta = 0), which gives 0 — as torch does.
 struct CriticLoss { int kind; float param; };
@@ -417,8 +421,10 @@ bool mlp_backward_supported(int H, int NH, int heads, int xa_count);
 // backward (loss != LOSS_GIVEN) then reads squashed values from l_q / l_tq and forms dq at the head's
 // pre-activation, value_squash_dz(dq, v).  Kernels of their own (mlp_*_ranged_kernel): the plain and the chained
 // kernels are what they were.  The chained launches (tonic_q_iteration) have no squashed form.
+// a.loss == LOSS_REGRESSION (one critic, with or without a range): `returns` [B] is the target, read by kernels of
+// their own again (mlp_backward_regression_kernel); null for every other loss.
 int launch_mlp_backward(const MlpBwdArgs& a, int nets, hipStream_t stream,
-                        ValueRangeArg value = ValueRangeArg{nullptr, nullptr});
+                        ValueRangeArg value = ValueRangeArg{nullptr, nullptr}, const float* returns = nullptr);
 int launch_mlp_forward(const MlpFwdArgs& a, int nets, hipStream_t stream,
                        ValueRangeArg value = ValueRangeArg{nullptr, nullptr});
 

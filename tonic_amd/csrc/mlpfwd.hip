@@ -558,12 +558,19 @@ __device__ __forceinline__ float load_shared(const float* p, unsigned* exchange_
 }
 
 // The logged sums of the step's loss over the whole batch (one workgroup; result -> l_stats)
-__device__ __forceinline__ void mlp_loss_stats(const MlpBwdArgs& a) {
+// REGRESS (the regression kernels only): LOSS_REGRESSION, the target of row r is returns[r]
+template <bool REGRESS = false>
+__device__ __forceinline__ void mlp_loss_stats(const MlpBwdArgs& a, const float* returns = nullptr) {
   const int tid = threadIdx.x;
   unsigned* co = a.exchange_failed;                   // null: plain loads
   double s0 = 0, s1 = 0, s2 = 0;
   for (int r = tid; r < a.B; r += blockDim.x) {
-    if (a.loss == LOSS_TD) {
+    if constexpr (REGRESS) {
+      const float q1 = a.l_q[a.l_q_at.index(0, r)];
+      const float sq = critic_loss_term(q1 - returns[r], a.l_kind, a.l_param);
+      s1 += q1;
+      s0 += sq;
+    } else if (a.loss == LOSS_TD) {
       const float y = td_target(a.l_rewards, a.l_discounts, a.l_tq, a.l_logp, a.l_alpha, r, a.l_tq_at,
                                 a.l_nets, co);
       const float q1 = load_shared(a.l_q + a.l_q_at.index(0, r), co);
@@ -597,9 +604,11 @@ __device__ __forceinline__ void mlp_loss_stats(const MlpBwdArgs& a) {
 // target's q, the twin's q, the critics' action-column gradients — is read (exchange_read) AFTER
 // everything that does not depend on them (ReLU masks, the first weight operands, the head
 // backward's own operands) has been requested: the hand-over's latency runs under those loads.
-template <bool RANGED = false>      // (RANGED, value: see mlp_forward_body; the gradient that enters the head)
+// REGRESS (mlp_backward_regression_kernel only): the critic's dq is formed from `returns` (LOSS_REGRESSION).
+template <bool RANGED = false, bool REGRESS = false>      // (RANGED, value: see mlp_forward_body; the gradient that enters the head)
 __device__ __forceinline__ void mlp_backward_body(const MlpBwdArgs& a, const int net, const int bx,
-                                                  float* lds, ValueRangeArg value = ValueRangeArg{nullptr, nullptr}) {
+                                                  float* lds, ValueRangeArg value = ValueRangeArg{nullptr, nullptr},
+                                                  const float* returns = nullptr) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int m = lane & 15, kg = lane >> 4;
@@ -728,7 +737,12 @@ __device__ __forceinline__ void mlp_backward_body(const MlpBwdArgs& a, const int
   if (a.heads == 0) {                                 // critic: dq[row] * w3[feature]
     const ValueRange vrange = RANGED ? value_range(value.low, value.high) : ValueRange{0.f, 0.f, false};     // (scalar; null: the plain head)
     float dq;
-    if (a.loss == LOSS_GIVEN) {
+    if constexpr (REGRESS) {                          // regression on the given returns: nothing else is read
+      const float q = a.l_q[a.l_q_at.index(net, row)];
+      dq = value_squash_dz(critic_loss_dq(q - returns[row], a.l_kind, a.l_param), q, vrange);
+      if (row_ok && wave == 0 && kg == 0)             // for the weight-gradient GEMM (dw3, db3)
+        const_cast<float*>(a.dq)[net * a.stride_dq + row] = dq;
+    } else if (a.loss == LOSS_GIVEN) {
       dq = a.dq[net * a.stride_dq + row];
     } else {                                          // the step's loss, folded into this launch
       if (a.loss == LOSS_TD) {
@@ -874,7 +888,7 @@ __device__ __forceinline__ void mlp_backward_body(const MlpBwdArgs& a, const int
     }
   }
   // the logged sums (uniform); a chain launch leaves them to its last workgroup
-  if (a.loss != LOSS_GIVEN && co == nullptr && bx == 0 && net == 0) mlp_loss_stats(a);
+  if (a.loss != LOSS_GIVEN && co == nullptr && bx == 0 && net == 0) mlp_loss_stats<REGRESS>(a, returns);
 }
 
 
@@ -935,6 +949,17 @@ __global__ __launch_bounds__(256) void mlp_backward_ranged_kernel(MlpBwdArgs a, 
   kernarg_prefetch<sizeof(MlpBwdArgs)>();
   if constexpr (IMG) mlp_backward_body_img<true>(a, blockIdx.y, blockIdx.x, lds, 0, value);
   else mlp_backward_body<true>(a, blockIdx.y, blockIdx.x, lds, value);
+}
+
+// A critic's chain with LOSS_REGRESSION folded in (launch_mlp_backward with `returns`), plain and squashed heads:
+// kernels of their own once more, the target beside the argument struct — the kernels above hold none of it.
+template <bool IMG, bool RANGED>
+__global__ __launch_bounds__(256) void mlp_backward_regression_kernel(MlpBwdArgs a, ValueRangeArg value,
+                                                                      const float* returns) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  kernarg_prefetch<sizeof(MlpBwdArgs)>();
+  if constexpr (IMG) mlp_backward_body_img<RANGED, true>(a, blockIdx.y, blockIdx.x, lds, 0, value, returns);
+  else mlp_backward_body<RANGED, true>(a, blockIdx.y, blockIdx.x, lds, value, returns);
 }
 
 // ------------------------------------------------------------------ chained passes (mlpfwd.h)
@@ -1134,7 +1159,20 @@ bool mlp_backward_supported(int H, int NH, int heads, int xa_count) {
          (heads == 0 || (NH >= 1 && NH <= 64)) && xa_count >= 0 && xa_count <= 64;
 }
 
-int launch_mlp_backward(const MlpBwdArgs& a, int nets, hipStream_t stream, ValueRangeArg value) {
+template <bool IMG, bool RANGED>
+static int launch_backward_regression(const MlpBwdArgs& a, size_t lds, hipStream_t stream, ValueRangeArg value,
+                                      const float* returns) {
+  if constexpr (IMG) {
+    const int status = allow_image_lds(mlp_backward_regression_kernel<IMG, RANGED>, "mlp_backward_regression_kernel");
+    if (status != TONIC_OK) return status;
+  }
+  hipLaunchKernelGGL((mlp_backward_regression_kernel<IMG, RANGED>), dim3((a.B + kRows - 1) / kRows, 1), dim3(256), lds,
+                     stream, a, value, returns);
+  TONIC_CHECK_LAUNCH("mlp_backward_regression_kernel");
+  return TONIC_OK;
+}
+
+int launch_mlp_backward(const MlpBwdArgs& a, int nets, hipStream_t stream, ValueRangeArg value, const float* returns) {
   TONIC_REQUIRE(mlp_backward_supported(a.H, a.NH, a.heads, a.xa_count) && a.B > 0 && nets > 0,
                 TONIC_ERR_INVALID_ARGUMENT, "mlp_backward: H=%d NH=%d heads=%d B=%d", a.H, a.NH,
                 a.heads, a.B);
@@ -1151,6 +1189,23 @@ int launch_mlp_backward(const MlpBwdArgs& a, int nets, hipStream_t stream, Value
                 TONIC_ERR_INVALID_ARGUMENT, "mlp_backward: a value range needs a critic's chain with its loss folded in");
   const size_t lds = (2 * (size_t)kRows * (a.H + 4) +
                       (a.hb_dxa0 != nullptr ? 2 * (size_t)kRows * kHeadPitch : 0)) * sizeof(float);
+  const bool regression = a.loss == LOSS_REGRESSION;
+  TONIC_REQUIRE(regression == (returns != nullptr) &&
+                    (!regression || (a.heads == 0 && nets == 1 && a.l_nets == 1 && a.l_q != nullptr && a.l_stats != nullptr &&
+                                     a.exchange_failed == nullptr)),
+                TONIC_ERR_INVALID_ARGUMENT, "mlp_backward: regression on given returns is one critic's chain (loss=%d nets=%d)",
+                a.loss, nets);
+  if (regression) {                                   // kernels of their own; what follows is what it was
+    if (a.img.block != nullptr) {
+      TONIC_REQUIRE(image_pass_supported(0, a.H), TONIC_ERR_INVALID_ARGUMENT,
+                    "mlp_backward: H=%d outside the image pass", a.H);
+      const size_t img_bytes = img_lds(0, a.H).total;
+      return ranged ? launch_backward_regression<true, true>(a, img_bytes, stream, value, returns)
+                    : launch_backward_regression<true, false>(a, img_bytes, stream, value, returns);
+    }
+    return ranged ? launch_backward_regression<false, true>(a, lds, stream, value, returns)
+                  : launch_backward_regression<false, false>(a, lds, stream, value, returns);
+  }
   if (a.img.block != nullptr) {
     TONIC_REQUIRE(image_pass_supported(0, a.H), TONIC_ERR_INVALID_ARGUMENT,
                   "mlp_backward: H=%d outside the image pass", a.H);

@@ -446,10 +446,11 @@ __device__ __forceinline__ void mlp_forward_body_img(const MlpFwdArgs& a, const 
 }
 
 // ------------------------------------------------------------------------------------------ backward
-template <bool RANGED = false>
+template <bool RANGED = false, bool REGRESS = false>      // (REGRESS, returns: see mlp_backward_body)
 __device__ __forceinline__ void mlp_backward_body_img(const MlpBwdArgs& a, const int net, const int bx,
                                                       float* lds_f, const int K1_lds,
-                                                      ValueRangeArg value = ValueRangeArg{nullptr, nullptr}) {
+                                                      ValueRangeArg value = ValueRangeArg{nullptr, nullptr},
+                                                      const float* returns = nullptr) {
   char* lds = reinterpret_cast<char*>(lds_f);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -558,7 +559,12 @@ __device__ __forceinline__ void mlp_backward_body_img(const MlpBwdArgs& a, const
   if (a.heads == 0) {                                 // critic: dq[row] * w3[feature], fp32
     const ValueRange vrange = RANGED ? value_range(value.low, value.high) : ValueRange{0.f, 0.f, false};     // (scalar; null: the plain head)
     float dq;
-    if (a.loss == LOSS_GIVEN) {
+    if constexpr (REGRESS) {                          // regression on the given returns: nothing else is read
+      const float q = a.l_q[a.l_q_at.index(net, row)];
+      dq = value_squash_dz(critic_loss_dq(q - returns[row], a.l_kind, a.l_param), q, vrange);
+      if (row_ok && wave == 0 && g == 0)              // for the weight-gradient GEMM (dw3, db3)
+        const_cast<float*>(a.dq)[net * a.stride_dq + row] = dq;
+    } else if (a.loss == LOSS_GIVEN) {
       dq = a.dq[net * a.stride_dq + row];
     } else {                                          // the step's loss, folded into this launch
       if (a.loss == LOSS_TD) {
@@ -729,5 +735,5 @@ __device__ __forceinline__ void mlp_backward_body_img(const MlpBwdArgs& a, const
     }
   }
   // the logged sums (uniform); a chain launch leaves them to its last workgroup
-  if (a.loss != LOSS_GIVEN && co == nullptr && bx == 0 && net == 0) mlp_loss_stats(a);
+  if (a.loss != LOSS_GIVEN && co == nullptr && bx == 0 && net == 0) mlp_loss_stats<REGRESS>(a, returns);
 }

@@ -1,7 +1,7 @@
 // Off-policy learner path (SAC / TD3 / DDPG / D4PG / MPO), gfx950.
 //
 // Restates (paths relative to the reference checkout):
-//   tonic/torch/updaters/critics.py:125-134 (TargetActionNoise), :156-182
+//   tonic/torch/updaters/critics.py:31-53 (QRegression), :125-134 (TargetActionNoise), :156-182
 //     (TwinCriticDeterministicQLearning), :202-235 (TwinCriticSoftQLearning),
 //   tonic/torch/updaters/actors.py:170-189 (DeterministicPolicyGradient), :238-267
 //     (TwinCriticSoftDeterministicPolicyGradient),
@@ -250,6 +250,26 @@ __global__ void critic_loss_kernel(const float* rewards, const float* discounts,
   if (threadIdx.x == 0) {
     stats[0] = (float)a; stats[1] = (float)b; stats[2] = (float)c; stats[3] = 0.f;
     stats[4] = 0.f; stats[5] = (float)B; stats[6] = 0.f; stats[7] = 0.f;
+  }
+}
+
+// QRegression (critics.py:31-53): y = returns[m] as given, one critic — dq = loss'(q - y) at the head's
+// pre-activation and the statistics row critic_loss_kernel writes for one critic (LOSS_REGRESSION, mlpfwd.h).
+__global__ void regression_loss_kernel(const float* returns, const float* q, float* dq, float* stats, int B,
+                                       CriticLoss loss, const float* v_low, const float* v_high) {
+  const ValueRange vrange = value_range(v_low, v_high);     // the Return normaliser's head: q holds squashed values
+  float s_loss = 0.f, s_q = 0.f;
+  for (int m = threadIdx.x; m < B; m += blockDim.x) {
+    const float e = q[m] - returns[m];
+    dq[m] = value_squash_dz(critic_loss_dq(e, loss.kind, loss.param), q[m], vrange);
+    s_loss += critic_loss_term(e, loss.kind, loss.param);
+    s_q += q[m];
+  }
+  double a = s_loss, b = s_q, unused = 0;
+  block_sum3(a, b, unused);
+  if (threadIdx.x == 0) {
+    stats[0] = (float)a; stats[1] = (float)b;
+    for (int i = 2; i < 8; ++i) stats[i] = i == 5 ? (float)B : 0.f;
   }
 }
 
@@ -1095,15 +1115,16 @@ int critics_forward(const float* params, CriticShape s, int nets, const float* X
 // the flat layout (stride = critic param count).  dxa != null: the ACTION columns of the input
 // gradient, [nets][Bp][pad16(A)] (all the actor step needs of dX; the caller adds the critics).
 // loss != null: dq is not given but FORMED from the forward outputs by the step's loss (LOSS_TD /
-// LOSS_ACTOR, mlpfwd.h) and written to `dq`, the logged sums to loss->stats — inside the backward
+// LOSS_ACTOR / LOSS_REGRESSION, mlpfwd.h) and written to `dq`, the logged sums to loss->stats — inside the backward
 // launch when the one-launch chain applies, by the stand-alone loss kernel otherwise.
 struct StepLoss {
-  int kind;                                   // LOSS_TD | LOSS_ACTOR
+  int kind;                                   // LOSS_TD | LOSS_ACTOR | LOSS_REGRESSION
   const float* rewards; const float* discounts; const float* tq; const float* logp;
   float alpha;
   const float* q; float* stats;
-  CriticLoss rule;                            // LOSS_TD: tonic_critic_loss_t (all-zero: MSE)
+  CriticLoss rule;                            // LOSS_TD, LOSS_REGRESSION: tonic_critic_loss_t (all-zero: MSE)
   const float* v_low; const float* v_high;    // the Return normaliser's head (q / tq are squashed values); null: plain
+  const float* returns;                       // LOSS_REGRESSION: the targets [B] (one critic; all it reads beside q)
 };
 
 // The one-launch chain's arguments (mlp_backward_supported(H, 1, 0, dxa ? A : 0)).
@@ -1175,7 +1196,10 @@ int critics_backward(const float* params, CriticShape s, int nets, const float* 
   const CriticOffsets o(s);
   const bool one_launch = s.plain() && mlp_backward_supported(s.H, 1, 0, dxa ? s.A : 0);
   if (loss && !one_launch) {
-    if (loss->kind == LOSS_TD) {
+    if (loss->kind == LOSS_REGRESSION) {
+      hipLaunchKernelGGL(regression_loss_kernel, dim3(1), dim3(1024), 0, st, loss->returns, loss->q, dq, loss->stats,
+                         B, loss->rule, loss->v_low, loss->v_high);
+    } else if (loss->kind == LOSS_TD) {
       hipLaunchKernelGGL(critic_loss_kernel, dim3(1), dim3(1024), 0, st, loss->rewards,
                          loss->discounts, loss->tq, loss->logp, loss->alpha, loss->q, dq,
                          loss->stats, B, Bp, nets, loss->rule, loss->v_low, loss->v_high);
@@ -1192,7 +1216,8 @@ int critics_backward(const float* params, CriticShape s, int nets, const float* 
   if (one_launch) {                                               // ... in ONE launch
     MlpBwdArgs b = critics_chain_args(params, s, nets, B, Bp, h1, h2, dq, dh2, dh1, dxa, loss, img);
     b.skip_dz = grads == nullptr ? 1 : 0;          // (a frozen critic's chain: only its action columns are read)
-    TRY(launch_mlp_backward(b, nets, st, loss ? ValueRangeArg{loss->v_low, loss->v_high} : ValueRangeArg{nullptr, nullptr}));
+    TRY(launch_mlp_backward(b, nets, st, loss ? ValueRangeArg{loss->v_low, loss->v_high} : ValueRangeArg{nullptr, nullptr},
+                            loss ? loss->returns : nullptr));
   } else {
     // dz_top = (dq w3) * act'(h_top)   (two layers: dz2, with h2)
     g = gemm(dq, 1, params + o.w3, o.ldO, dh2, HP, B, s.last(), 1);
@@ -1318,6 +1343,25 @@ struct ActorQLayout {                    // the actor step through the critics (
     dloc = ws.take(Bp * ldh); dspre = ws.take(Bp * ldh);
     da_h2 = ws.take(L * hs); da_h1 = behind(da_h2, hs);
     im = take_images(ws, O, A, H, heads, images);
+  }
+};
+// Regression of one critic on given returns (tonic_q_regression_grad): the critic's input, one network's activations,
+// values and chain, and — `images` — this critic's weight images alone.  A query of its own
+// (tonic_q_regression_workspace_bytes): every take is one TwinQLayout makes as well, at least as large.
+struct QRegressionLayout {
+  float *X, *h1, *h2, *q, *dq, *dh2, *dh1;
+  CriticImg img;                         // block null: the float32 passes
+  QRegressionLayout(Workspace& ws, int B, int O, int A, int32_t H, bool images) {
+    const int64_t Bp = pad16(B), ldx = pitch16(O + A), hs = Bp * hidden_pitch(H), L = hidden_layers(H);
+    X = ws.take(Bp * ldx);
+    h1 = ws.take(L * hs); h2 = behind(h1, hs);
+    q = ws.take(Bp); dq = ws.take(Bp);
+    dh2 = ws.take(L * hs); dh1 = behind(dh2, hs);
+    img = CriticImg{};
+    if (images) {
+      const CriticImages cv = critic_images(O, A, H);
+      img = CriticImg{reinterpret_cast<char*>(ws.take(round_up(cv.bytes, 256) / 4)), nullptr, nullptr, cv};
+    }
   }
 };
 
@@ -1649,6 +1693,59 @@ extern "C" int tonic_twin_q_grad_ranged(
                      d_observations, d_actions, d_next_observations, d_rewards, d_discounts, d_eps, d_grad_sums, B, O,
                      H, A, entropy_coeff, noise_scale, noise_clip, loss, d_value_low, d_value_high, d_workspace,
                      workspace_bytes, stream);
+}
+
+// QRegression.__call__ (tonic/torch/updaters/critics.py:31-53): values = critic(s, a), loss(values, returns) on
+// returns the caller computed — the encoder, the online critic's forward and its backward with LOSS_REGRESSION.
+// No policy pass, no target network, no next observations; weight images of this critic only.  The routes are
+// twin_q_grad's: images where images_serve says so, the float32 one-launch passes for any other plain torso, layer
+// by layer otherwise.
+extern "C" int64_t tonic_q_regression_workspace_bytes(int32_t B, int32_t O, int32_t A, int32_t H) {
+  H = torso_code(H);
+  return measure<QRegressionLayout>(B, O, A, H, hidden_plain(H));      // (a function of its arguments, as above)
+}
+
+extern "C" int tonic_q_regression_grad(
+    const float* d_critic, const float* d_norm_mean, const float* d_norm_std, double norm_clip,
+    const float* d_observations, const float* d_actions, const float* d_returns, float* d_grad_sums, int32_t B,
+    int32_t O, int32_t H, int32_t A, const tonic_critic_loss_t* loss, const float* d_value_low,
+    const float* d_value_high, void* d_workspace, int64_t workspace_bytes, void* stream) {
+  TONIC_REQUIRE((d_value_low == nullptr) == (d_value_high == nullptr), TONIC_ERR_INVALID_ARGUMENT,
+                "tonic_q_regression_grad: %s is NULL and the other bound is not (both or neither)",
+                d_value_low == nullptr ? "d_value_low" : "d_value_high");
+  TRY(tonic_critic_loss_check(loss));
+  TONIC_REQUIRE(d_critic && d_norm_mean && d_norm_std && d_observations && d_actions && d_returns && d_grad_sums &&
+                    d_workspace && B > 0 && hidden_known(H),
+                TONIC_ERR_INVALID_ARGUMENT, "tonic_q_regression_grad: bad argument");
+  TONIC_REQUIRE(workspace_bytes >= tonic_q_regression_workspace_bytes(B, O, A, H), TONIC_ERR_WORKSPACE,
+                "tonic_q_regression_grad: workspace too small");
+  hipStream_t st = as_stream(stream);
+  H = torso_code(H);                           // (a head code's bounds: a critic ignores them)
+  const int Bp = pad16(B), ldx = pitch16(O + A);
+  const CriticShape cs = critic_shape(O, A, H);
+  const int64_t Pc = critic_count(cs);
+  Workspace ws{static_cast<char*>(d_workspace), 0};
+  const QRegressionLayout w(ws, B, O, A, H,
+                            hidden_plain(H) && images_serve(O, A, H) && mlp_forward_supported(H, 1, 1) &&
+                                mlp_backward_supported(H, 1, 0, 0));
+  const CriticImg* img = w.img.block != nullptr ? &w.img : nullptr;
+  if (img != nullptr) {
+    ImgBuild build;
+    add_critic_images(build, d_critic, cs, 1, w.img.block, w.img.v);
+    TRY(launch_build_images(build, st));
+  }
+  const int threads = 256;
+  hipLaunchKernelGGL(encode_kernel, dim3((B * (O + A) + threads - 1) / threads), dim3(threads), 0, st, d_observations,
+                     d_actions, d_norm_mean, d_norm_std, clip_bound(norm_clip), w.X, B, O, A, ldx, nullptr, nullptr,
+                     nullptr);
+  TRY(critics_forward(d_critic, cs, 1, w.X, ldx, B, Bp, w.h1, w.h2, w.q, st, nullptr, nullptr, img, d_value_low,
+                      d_value_high));
+  const StepLoss regression{LOSS_REGRESSION, nullptr, nullptr, nullptr, nullptr, 0.f, w.q, d_grad_sums + Pc,
+                            critic_loss_rule(loss), d_value_low, d_value_high, d_returns};
+  TRY(critics_backward(d_critic, cs, 1, w.X, ldx, B, Bp, w.h1, w.h2, w.dq, w.dh2, w.dh1, d_grad_sums, nullptr, st,
+                       &regression, nullptr, img));
+  TONIC_CHECK_LAUNCH("tonic_q_regression_grad");
+  return TONIC_OK;
 }
 
 namespace {

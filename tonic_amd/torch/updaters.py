@@ -1180,7 +1180,6 @@ class _TwinCriticQLearning(_QUpdater):
         `eps` are the standard-normal draws the reference makes inside (target-action noise /
         the next action's rsample), in its order.  Losses are formed as SUMS over this rank's part
         of the batch divided by the global batch size, so that several ranks add up to the mean."""
-        from tonic_amd import parallel
         model, B = self.model, batch['observations'].shape[0]
         n = float(n_global or B)
         twin = hasattr(model, 'critic_1')
@@ -1202,8 +1201,14 @@ class _TwinCriticQLearning(_QUpdater):
             if self.kind == 1:
                 next_values = next_values - self.entropy_coeff * log_probs
             returns = batch['rewards'] + batch['discounts'] * next_values
-        self.torch_optimizer.zero_grad()
         critics = (model.critic_1, model.critic_2) if twin else (model.critic,)
+        self._stock_regress(critics, batch, returns, n, info_row)
+
+    def _stock_regress(self, critics, batch, returns, n, info_row):
+        """`loss = self.loss(values, returns)` of every critic on (observations, actions), backward, the ranks'
+        exchange, clip, step and the logged row {loss, mean q of each critic}."""
+        from tonic_amd import parallel
+        self.torch_optimizer.zero_grad()
         values = [critic(batch['observations'], batch['actions']) for critic in critics]
         loss = sum(critic_loss_sum(self.loss_rule, v, returns) for v in values) / n
         loss.backward()
@@ -1269,6 +1274,104 @@ class DeterministicQLearning(_TwinCriticQLearning):
                      next_observations=next_observations, rewards=rewards, discounts=discounts)
         out = self._info(lambda row: self.enqueue(batch, None, row), ('loss', 'q'))
         return out
+
+
+class QRegression(_TwinCriticQLearning):
+    """critics.py:31-53: ``model.critic(observations, actions)`` regressed on returns the caller computed
+    (Monte-Carlo, n-step or lambda-returns of its own) — tonic_q_regression_grad + tonic_optimizer_step.  No policy
+    pass and no target network: the shapes are the critic's alone, so an actor on another torso or with another head
+    does not leave the HIP path, and a model needs no targets to take the stock route.
+
+    A critic in the padded off-policy layout (``ActorCriticWithTargets.pack``) on a torso the kernels serve
+    (`_torso_width`) runs the HIP entry; any other single-critic model — a torso outside the envelope,
+    TONIC_AMD_TORSO_STOCK=1, a plain ``ActorCritic`` whose critic has an ObservationActionEncoder — runs the same
+    arithmetic as stock torch operators.  ``__call__`` returns dict(loss=, q=) with `q` the batch mean, as
+    `DeterministicQLearning` here does."""
+    default_lr = 1e-3
+
+    def __init__(self, loss=None, optimizer=None, gradient_clip=0):
+        self.loss = loss
+        self.optimizer = optimizer
+        self.gradient_clip = gradient_clip
+
+    def _shapes(self, model):
+        from tonic_amd.torch import models
+        self.model = model
+        if hasattr(model, 'critic_1'):
+            raise NotImplementedError('QRegression regresses model.critic (critics.py:40,45): a model with critic_1 / '
+                                      'critic_2 is not served, twin regression is no updater of the reference')
+        critic = model.critic
+        if isinstance(critic.head, models.DistributionalValueHead) or getattr(critic.head, 'num_atoms', 0):
+            raise NotImplementedError('QRegression on a DistributionalValueHead is not served: the loss of '
+                                      'critics.py:46 cannot take a distribution for its values')
+        self.observation_size = model.actor.torso.model[0].in_features
+        self.action_size = critic.torso.model[0].in_features - self.observation_size
+        self.normalizer = model.observation_normalizer
+        self.return_normalizer = getattr(model, 'return_normalizer', None) or None
+        self.atoms, self.scale_bounds = 0, None
+        # the critic's own flat block: [critic] behind the actor in the padded off-policy layout, or the unpadded
+        # block of ActorCritic.pack, which only the stock route reads
+        flat = getattr(model, 'flat_critics', None)
+        self.hidden = None
+        if flat is not None and type(critic.encoder) is models.ObservationActionEncoder and self.action_size > 0:
+            try:
+                self.hidden = _torso_width(critic.torso, True)
+            except NotImplementedError:
+                pass                         # any MLP(sizes, activation): stock torch operators
+            if self.hidden is not None and flat.count != _lib.load().tonic_q_critic_param_count(
+                    self.observation_size, self.action_size, self.hidden):
+                self.hidden = None           # (not the packed layout the entry walks)
+        if flat is None:
+            flat = getattr(model, 'flat_critic', None)
+        if flat is None:
+            raise NotImplementedError('QRegression needs a packed model (model.pack(device)): the critic\'s '
+                                      'parameters are stepped in their flat block')
+        self.torso_code = self.hidden
+        device = flat.flat.device
+        if self.normalizer is None:
+            self._unit = (torch.zeros(self.observation_size, device=device),
+                          torch.ones(self.observation_size, device=device))
+        return flat
+
+    def initialize(self, model):
+        flat = self._shapes(model)
+        self._setup(flat, optimizer_hyperparameters(self.optimizer, self.default_lr))
+        self.variables = flat.params
+        if self.hidden is None:
+            self._stock_setup(self.optimizer, self.default_lr)
+
+    def _offpolicy_workspace(self, batch):
+        need = self.lib.tonic_q_regression_workspace_bytes(batch, self.observation_size, self.action_size,
+                                                           self.hidden)
+        if self.workspace is None or self.workspace.numel() < need:
+            self.workspace = torch.empty(need, dtype=torch.uint8, device=self.grad_sums.device)
+        return self.workspace
+
+    def _stock_enqueue(self, batch, info_row, n_global):
+        """critics.py:43-53 as stock torch operators; the loss is the SUM over this rank's part of the batch divided
+        by the global batch size, so that several ranks add up to the mean (`_stock_regress`)."""
+        n = float(n_global or batch['observations'].shape[0])
+        self._stock_regress((self.model.critic,), batch, batch['returns'], n, info_row)
+
+    def enqueue(self, batch, info_row, n_global=None):
+        """`batch`: observations [B, O], actions [B, A], returns [B] on the device.  Asynchronous; safe under a
+        captured graph (the Return normaliser's range is read on the device)."""
+        if self.stock:
+            return self._stock_enqueue(batch, info_row, n_global)
+        B = batch['observations'].shape[0]
+        ws = self._offpolicy_workspace(B)
+        mean, std = self.norm_tensors()
+        p = _lib.ptr
+        _lib.check(self.lib.tonic_q_regression_grad(
+            p(self.flat.flat), p(mean), p(std), self.norm_clip(), p(batch['observations']), p(batch['actions']),
+            p(batch['returns']), p(self.grad_sums), B, self.observation_size, self.hidden, self.action_size,
+            ctypes.addressof(self.loss_rule), *self.range_pointers(), p(ws), ws.numel(), _lib.current_stream()),
+            'tonic_q_regression_grad')
+        self._step(n_global or B * self.world_size, info_row)
+
+    def __call__(self, observations, actions, returns):
+        batch = dict(observations=observations, actions=actions, returns=returns)
+        return self._info(lambda row: self.enqueue(batch, row), ('loss', 'q'))
 
 
 class TwinCriticDeterministicQLearning(_TwinCriticQLearning):
