@@ -25,6 +25,27 @@ CODES = {'tanh': 1, 'relu': 2}
 SHAPES = [(17, 6, 1), (17, 6, 63), (17, 6, 65), (3, 1, 777), (111, 8, 4099), (9, 21, 1500), (384, 32, 300),
           (17, 6, 66003)]
 CASES = [(*shape, 'default') for shape in SHAPES] + [(17, 6, 1000, name) for name in TORSOS]
+# The launch edges of the layer-by-layer kernels (DESIGN.md §4.6 / §4.7 map each path to its case), name ->
+# (sizes, activation, (O, A, n)); n = 333 is 6 slabs of 56 rows, the last one ragged (53 rows).
+#   min4     K = 1 non-vec first layer, NOUT = 4, the head on K = 4 (one partial 16-column group), A = 1 backward
+#   steps    O = 65: non-vec, two chunks (KS = 17); dense / tangent at TN = 2, 4 (three tiles), 4 and a 64-output
+#            slice + a 4-wide remainder; wgrad_kernel<2> (20 <- 65) and <1> (the head on K = 68, tk = 5),
+#            wgrad_rows<4,4> / <1,4>; A = 5: scalar stores
+#   k116     112 <- 116: wgrad_kernel<4> just past wgrad_rows<4,7>; the head on K = 112: wgrad_kernel<1>; A = 4: the
+#            vec backward through the head (ldx = 32); tangent with two chunks
+#   wide256  tangent at K = 256: four 64-output slices, four chunks, the 131 072 B LDS request (kTangentMaxLds)
+#   wide384  K = 4 vec first layer; tangent at K = 384: 32-output slices (96 KB), 260 = eight of them + a 4-wide
+#            one; the head on K = 260 (KS = 68); A = 32
+#   stride   2048 * 64 + 17 rows: the first two waves take a second tile and the last tile holds one row — the
+#            tile stride with a two-chunk K (4 <- 68) in dense_kernel and tangent_kernel; slab = 132
+#   slabs    n = 66 003: slabs 971 .. 1023 are empty in the column-split wgrad_kernel<1> (the head on K = 128) and in
+#            ppo_loss_kernel / trpo_metric_kernel; two 64-output slices
+EDGES = {'min4': ((4,), 'tanh', (1, 1, 333)), 'steps': ((20, 36, 48, 68), 'relu', (65, 5, 333)),
+         'k116': ((116, 112), 'tanh', (17, 4, 333)), 'wide256': ((256, 256), 'tanh', (17, 6, 333)),
+         'wide384': ((384, 260), 'relu', (4, 32, 333)), 'stride': ((68, 4), 'tanh', (5, 2, 2048 * 64 + 17)),
+         'slabs': ((128,), 'relu', (17, 6, 66003))}
+TORSOS.update({name: edge[:2] for name, edge in EDGES.items()})
+EDGE_CASES = [(*edge[2], name) for name, edge in EDGES.items()]
 
 
 @pytest.fixture(scope='module')
@@ -38,7 +59,7 @@ def dev(x):
     return torch.as_tensor(np.ascontiguousarray(x), dtype=torch.float32).cuda().contiguous()
 
 
-@functools.lru_cache(maxsize=4)
+@functools.lru_cache(maxsize=32)      # every case of this module and of test_gpu_layerwise_edges.py, once
 def problem(O, A, n, torso):
     """Float32 parameters and batch, and the float64 values every test of the shape shares (read-only)."""
     sizes, activation = TORSOS[torso]
@@ -175,7 +196,7 @@ def assert_per_tensor(p, got, want, stock, what):
 
 # ------------------------------------------------------------------------ 1. Fisher-vector product
 
-@pytest.mark.parametrize('O,A,n,torso', CASES)
+@pytest.mark.parametrize('O,A,n,torso', CASES + EDGE_CASES)
 def test_fisher_vector_vs_float64(lib, O, A, n, torso):
     p = problem(O, A, n, torso)
     e = Entries(lib, p).prepare()
@@ -193,7 +214,7 @@ def test_fisher_vector_vs_float64(lib, O, A, n, torso):
 # ------------------------------------------------------------------------ 2. loss gradient, line-search trial
 
 @pytest.mark.parametrize('coeff', [0.0, 0.01])
-@pytest.mark.parametrize('O,A,n,torso', CASES)
+@pytest.mark.parametrize('O,A,n,torso', CASES + EDGE_CASES)
 def test_loss_grad_and_evaluate_vs_float64(lib, O, A, n, torso, coeff):
     p = problem(O, A, n, torso)
     e = Entries(lib, p).prepare()

@@ -189,8 +189,10 @@ def hip_ppo_torso(torso):
     layers of 4 .. 256 units (multiples of 4), Tanh or ReLU, no custom initialiser — None otherwise (and for
     the default torso, which the fused kernels serve).  Every other torso runs the same arithmetic as stock
     PyTorch-ROCm operators on the HBM-resident data (see `_StockTorch`).  The entries themselves take layers
-    up to 384 units (tested), but beyond 256 a layer is several 64-output slices each re-reading its input
-    rows and rocBLAS wins — (384, 300) ReLU at N = 1 M: 41.4 ms vs 32.3 ms per learner iteration,
+    up to 384 units (tested per parameter tensor against float64 on (384, 260) ReLU and (256, 256) Tanh — the
+    PPO / A2C entries in tests/test_gpu_layerwise_edges.py, the TRPO entries in tests/test_gpu_trpo_hip.py — and
+    on the whole gradient vector on (384, 300) ReLU and (384, 8) Tanh for PPO / A2C, test_gpu_parity.py), but
+    beyond 256 a layer is several 64-output slices each re-reading its input rows and rocBLAS wins — (384, 300) ReLU at N = 1 M: 41.4 ms vs 32.3 ms per learner iteration,
     profiles/r05_torso_timing.txt — so the agents hand such torsos to the stock operators
     (TONIC_AMD_TORSO_WIDE_HIP=1 keeps them on the HIP entries)."""
     import ctypes
