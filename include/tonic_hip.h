@@ -64,10 +64,11 @@ const char* tonic_last_error(void);
  * tonic_actor_q_grad_ranged (the Return normaliser's value head on the off-policy split entries), 19 =
  * tonic_mlp_torso_head: `H` codes that carry the bounds of a Gaussian policy head's scale (additive: every
  * earlier entry keeps its signature), 20 = tonic_twin_distributional_q_grad / _workspace_bytes (TD4; additive),
- * 21 = tonic_q_regression_grad / tonic_q_regression_workspace_bytes (QRegression; additive)
+ * 21 = tonic_q_regression_grad / tonic_q_regression_workspace_bytes (QRegression; additive),
+ * 22 = tonic_tempered_twin_q_grad / tonic_tempered_actor_q_grad (SAC's learned entropy coefficient; additive)
  * and the gfx target the kernels were built for.  TONIC_ABI_VERSION is what a binding was compiled against:
  * tonic_amd/_fastcall (csrc/fastcall.c) and tonic_amd/_lib.py compare it with the loaded library's answer. */
-#define TONIC_ABI_VERSION 21
+#define TONIC_ABI_VERSION 22
 int32_t tonic_abi_version(void);
 const char* tonic_target_arch(void);
 
@@ -900,6 +901,43 @@ int tonic_q_regression_grad(const float* d_critic, const float* d_norm_mean, con
                             int32_t A, const tonic_critic_loss_t* loss, const float* d_value_low,
                             const float* d_value_high, void* d_workspace, int64_t workspace_bytes,
                             void* stream);
+
+/* ---- SAC with a learned entropy coefficient (ABI 22) ----------------------------------------
+ * tonic_twin_q_grad_ranged / tonic_actor_q_grad_ranged (kind 1) whose entropy coefficient is not the `entropy_coeff`
+ *   argument but alpha = expf(*d_log_entropy_coeff), ONE float32 on the device that the kernels read: the TD target
+ *   y = r + disc (min q' - alpha logp') of critics.py:202-235, the objective alpha logp - min q of actors.py:238-267,
+ *   its logged sum and the head backward.  The host never reads the value, so a captured graph follows the
+ *   coefficient as an optimizer step moves it.  (The reference keeps 0.2; the coefficient's own loss below is SAC's
+ *   automatic temperature adjustment and has no line there.)  Each kernel fetches the scalar once, at entry,
+ *   wave-uniform, and takes expf once.  Served on every route of the *_ranged entries — fp16x2 weight images, the
+ *   float32 one-launch passes, layer-by-layer torsos — with the launches of those entries: none more.
+ * d_entropy_coeff_sums (actor entry) [1 + 8], laid out like every gradient-sum block: the gradient SUM with respect
+ *   to log alpha of J = -mean(log_alpha (logp_m + target_entropy)) over this call's rows,
+ *   -sum_m (logp_m + target_entropy), unscaled; then the statistics {-log_alpha sum_m (logp_m + target_entropy),
+ *   sum_m logp_m, alpha B, 0, 0, B, 0, 0}.  logp_m is the log-probability of the actor step's own sample (d_eps): no
+ *   policy pass and no draw more.  tonic_optimizer_step on a block of one with stats_kind 3 and grad_scale =
+ *   1 / n_global steps log alpha by any rule of the family and logs {loss, mean logp, alpha before the step}.
+ * d_log_entropy_coeff NULL: the launches and bits of the *_ranged entry with the same arguments (`entropy_coeff`
+ *   is used; d_entropy_coeff_sums must be NULL too).  Given with kind != 1, or — on the actor entry — exactly one of
+ *   d_log_entropy_coeff / d_entropy_coeff_sums given, or a target_entropy that is not finite:
+ *   TONIC_ERR_INVALID_ARGUMENT, checked before anything touches the device.  There is no chained form and
+ *   tonic_q_iteration has none: an agent with a learned coefficient takes these entries. */
+int tonic_tempered_twin_q_grad(int32_t kind, const float* d_policy_params, const float* d_target_critics,
+                               const float* d_critics, const float* d_norm_mean, const float* d_norm_std,
+                               double norm_clip, const float* d_observations, const float* d_actions,
+                               const float* d_next_observations, const float* d_rewards,
+                               const float* d_discounts, const float* d_eps, float* d_grad_sums, int32_t B,
+                               int32_t O, int32_t H, int32_t A, double entropy_coeff, double noise_scale,
+                               double noise_clip, const tonic_critic_loss_t* loss, const float* d_value_low,
+                               const float* d_value_high, const float* d_log_entropy_coeff, void* d_workspace,
+                               int64_t workspace_bytes, void* stream);
+int tonic_tempered_actor_q_grad(int32_t kind, const float* d_actor_params, const float* d_critics,
+                                const float* d_norm_mean, const float* d_norm_std, double norm_clip,
+                                const float* d_observations, const float* d_eps, float* d_grad_sums,
+                                int32_t B, int32_t O, int32_t H, int32_t A, double entropy_coeff,
+                                const float* d_value_low, const float* d_value_high,
+                                const float* d_log_entropy_coeff, float* d_entropy_coeff_sums,
+                                double target_entropy, void* d_workspace, int64_t workspace_bytes, void* stream);
 
 /* ---- one whole learner iteration of DDPG / TD3 / SAC in 8 launches (4 when the actor is not due).
  * replaces: the body of DDPG._update's loop (tonic/torch/agents/ddpg.py:95-112; td3.py:38-55 with

@@ -183,6 +183,12 @@ SIGNATURES = {
                                  [c_f64] * 3 + [c_vp] * 3 + [c_vp, c_i64, c_vp]),
     'tonic_actor_q_grad_ranged': (ctypes.c_int, [c_i32] + [c_vp] * 4 + [c_f64] + [c_vp] * 3 + [c_i32] * 4 +
                                   [c_f64] + [c_vp] * 2 + [c_vp, c_i64, c_vp]),
+    # ... SAC with the entropy coefficient read from the device: `d_log_entropy_coeff` [+ the coefficient's own sums
+    # and `target_entropy`] behind the range (ABI 22)
+    'tonic_tempered_twin_q_grad': (ctypes.c_int, [c_i32] + [c_vp] * 5 + [c_f64] + [c_vp] * 7 + [c_i32] * 4 +
+                                   [c_f64] * 3 + [c_vp] * 3 + [c_vp] + [c_vp, c_i64, c_vp]),
+    'tonic_tempered_actor_q_grad': (ctypes.c_int, [c_i32] + [c_vp] * 4 + [c_f64] + [c_vp] * 3 + [c_i32] * 4 +
+                                    [c_f64] + [c_vp] * 2 + [c_vp, c_vp, c_f64] + [c_vp, c_i64, c_vp]),
     # QRegression: one critic on given returns (ABI 21)
     'tonic_q_regression_workspace_bytes': (c_i64, [c_i32] * 4),
     'tonic_q_regression_grad': (ctypes.c_int, [c_vp] * 3 + [c_f64] + [c_vp] * 4 + [c_i32] * 4 + [c_vp] * 3 +
@@ -256,7 +262,7 @@ SIGNATURES = {
 }
 
 
-ABI_VERSION = 21      # include/tonic_hip.h: tonic_abi_version()
+ABI_VERSION = 22      # include/tonic_hip.h: tonic_abi_version()
 
 
 class TonicHipError(RuntimeError):

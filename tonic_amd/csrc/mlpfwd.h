@@ -372,6 +372,33 @@ __device__ __forceinline__ void block_sum3(double& a, double& b, double& c) {
   }
 }
 
+// ---- SAC's learned entropy coefficient (the tonic_tempered_* entries, include/tonic_hip.h): log_alpha is one float32 on
+// the device, the kernels of a step use alpha = expf(*log_alpha) where the others use their entropy_coeff argument
+// (read once per kernel, wave-uniform; kernels of their own).  sums != null (the actor step): the coefficient's own
+// block [1 parameter | 8 statistics] of J = -mean(log_alpha (logp + target_entropy)) on the step's fresh sample.
+struct TemperArg {
+  const float* log_alpha; float* sums; float target_entropy;
+};
+// One workgroup of whole waves; result by thread 0:
+//   sums[0] = -sum_m (logp_m + target)        dJ / d log_alpha, unscaled (the optimizer step applies 1 / n_global)
+//   sums[1 ..] = {-log_alpha sum_m (logp_m + target), sum_m logp_m, alpha B, 0, 0, B, 0, 0}
+// (stats_row_twin_q turns the first three into {loss, mean logp, alpha}; a rank's alpha B adds up to alpha n_global)
+__device__ __forceinline__ void entropy_coeff_sums(const float* logp, int B, float log_alpha, float alpha,
+                                                   float target, float* sums) {
+  double excess = 0, total = 0, unused = 0;
+  for (int r = threadIdx.x; r < B; r += blockDim.x) {
+    const float lp = logp[r];
+    excess += (double)lp + (double)target;
+    total += lp;
+  }
+  block_sum3(excess, total, unused);
+  if (threadIdx.x == 0) {
+    sums[0] = (float)-excess;
+    sums[1] = (float)(-(double)log_alpha * excess); sums[2] = (float)total; sums[3] = alpha * (float)B;
+    sums[4] = 0.f; sums[5] = 0.f; sums[6] = (float)B; sums[7] = 0.f; sums[8] = 0.f;
+  }
+}
+
 // ---- several dependent passes over the same 16-row tiles as ONE launch (q_chain kernels, mlpfwd.hip)
 // The workgroups of a launch are numbered tile-major — the `roles` workgroups of a tile are
 // neighbours in dispatch order and a role only ever waits for values of roles of the same tile (a
@@ -427,5 +454,9 @@ int launch_mlp_backward(const MlpBwdArgs& a, int nets, hipStream_t stream,
                         ValueRangeArg value = ValueRangeArg{nullptr, nullptr}, const float* returns = nullptr);
 int launch_mlp_forward(const MlpFwdArgs& a, int nets, hipStream_t stream,
                        ValueRangeArg value = ValueRangeArg{nullptr, nullptr});
+// The twin critics' chain with LOSS_TD / LOSS_ACTOR of SAC whose coefficient is read from the device (TemperArg):
+// launch_mlp_backward's grid and bodies in kernels of their own; a.l_alpha is not read.
+int launch_mlp_backward_tempered(const MlpBwdArgs& a, int nets, hipStream_t stream, ValueRangeArg value,
+                                 TemperArg temper);
 
 }  // namespace tonic

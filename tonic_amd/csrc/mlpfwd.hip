@@ -559,8 +559,11 @@ __device__ __forceinline__ float load_shared(const float* p, unsigned* exchange_
 
 // The logged sums of the step's loss over the whole batch (one workgroup; result -> l_stats)
 // REGRESS (the regression kernels only): LOSS_REGRESSION, the target of row r is returns[r]
-template <bool REGRESS = false>
-__device__ __forceinline__ void mlp_loss_stats(const MlpBwdArgs& a, const float* returns = nullptr) {
+// TEMPERED (the tempered kernels only): `alpha` = exp(log_entropy_coeff), read from the device, stands for a.l_alpha
+template <bool REGRESS = false, bool TEMPERED = false>
+__device__ __forceinline__ void mlp_loss_stats(const MlpBwdArgs& a, const float* returns = nullptr,
+                                               const float alpha = 0.f) {
+  const float l_alpha = TEMPERED ? alpha : a.l_alpha;
   const int tid = threadIdx.x;
   unsigned* co = a.exchange_failed;                   // null: plain loads
   double s0 = 0, s1 = 0, s2 = 0;
@@ -571,7 +574,7 @@ __device__ __forceinline__ void mlp_loss_stats(const MlpBwdArgs& a, const float*
       s1 += q1;
       s0 += sq;
     } else if (a.loss == LOSS_TD) {
-      const float y = td_target(a.l_rewards, a.l_discounts, a.l_tq, a.l_logp, a.l_alpha, r, a.l_tq_at,
+      const float y = td_target(a.l_rewards, a.l_discounts, a.l_tq, a.l_logp, l_alpha, r, a.l_tq_at,
                                 a.l_nets, co);
       const float q1 = load_shared(a.l_q + a.l_q_at.index(0, r), co);
       const float e1 = q1 - y;
@@ -585,7 +588,7 @@ __device__ __forceinline__ void mlp_loss_stats(const MlpBwdArgs& a, const float*
       }
       s0 += sq;
     } else if (a.l_nets == 2) {
-      s0 += a.l_alpha * a.l_logp[r] -
+      s0 += l_alpha * a.l_logp[r] -
             fminf(load_shared(a.l_q + a.l_q_at.index(0, r), co),
                   load_shared(a.l_q + a.l_q_at.index(1, r), co));
     } else {
@@ -605,10 +608,11 @@ __device__ __forceinline__ void mlp_loss_stats(const MlpBwdArgs& a, const float*
 // everything that does not depend on them (ReLU masks, the first weight operands, the head
 // backward's own operands) has been requested: the hand-over's latency runs under those loads.
 // REGRESS (mlp_backward_regression_kernel only): the critic's dq is formed from `returns` (LOSS_REGRESSION).
-template <bool RANGED = false, bool REGRESS = false>      // (RANGED, value: see mlp_forward_body; the gradient that enters the head)
+// TEMPERED (mlp_backward_tempered_kernel only): `alpha` stands for a.l_alpha (see mlp_loss_stats).
+template <bool RANGED = false, bool REGRESS = false, bool TEMPERED = false>      // (RANGED, value: see mlp_forward_body; the gradient that enters the head)
 __device__ __forceinline__ void mlp_backward_body(const MlpBwdArgs& a, const int net, const int bx,
                                                   float* lds, ValueRangeArg value = ValueRangeArg{nullptr, nullptr},
-                                                  const float* returns = nullptr) {
+                                                  const float* returns = nullptr, const float alpha = 0.f) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int m = lane & 15, kg = lane >> 4;
@@ -746,7 +750,7 @@ __device__ __forceinline__ void mlp_backward_body(const MlpBwdArgs& a, const int
       dq = a.dq[net * a.stride_dq + row];
     } else {                                          // the step's loss, folded into this launch
       if (a.loss == LOSS_TD) {
-        const float y = td_target(a.l_rewards, a.l_discounts, a.l_tq, a.l_logp, a.l_alpha, row,
+        const float y = td_target(a.l_rewards, a.l_discounts, a.l_tq, a.l_logp, TEMPERED ? alpha : a.l_alpha, row,
                                   a.l_tq_at, a.l_nets, co);
         const float q = load_shared(a.l_q + a.l_q_at.index(net, row), co);
         dq = value_squash_dz(critic_loss_dq(q - y, a.l_kind, a.l_param), q, vrange);
@@ -888,7 +892,7 @@ __device__ __forceinline__ void mlp_backward_body(const MlpBwdArgs& a, const int
     }
   }
   // the logged sums (uniform); a chain launch leaves them to its last workgroup
-  if (a.loss != LOSS_GIVEN && co == nullptr && bx == 0 && net == 0) mlp_loss_stats<REGRESS>(a, returns);
+  if (a.loss != LOSS_GIVEN && co == nullptr && bx == 0 && net == 0) mlp_loss_stats<REGRESS, TEMPERED>(a, returns, alpha);
 }
 
 
@@ -960,6 +964,26 @@ __global__ __launch_bounds__(256) void mlp_backward_regression_kernel(MlpBwdArgs
   kernarg_prefetch<sizeof(MlpBwdArgs)>();
   if constexpr (IMG) mlp_backward_body_img<RANGED, true>(a, blockIdx.y, blockIdx.x, lds, 0, value, returns);
   else mlp_backward_body<RANGED, true>(a, blockIdx.y, blockIdx.x, lds, value, returns);
+}
+
+// A critic's chain whose step loss reads SAC's entropy coefficient from the device (launch_mlp_backward with a
+// TemperArg, LOSS_TD / LOSS_ACTOR of twin critics): kernels of their own a fourth time, the pointer beside the
+// argument struct.  The coefficient is fetched at entry with the argument lines (wave-uniform) and exp() is taken
+// once; the bodies then read `alpha` where they read a.l_alpha.  temper.sums != null (the actor step): workgroup
+// (0, 0) also writes the coefficient's own block behind the step's logged sums (entropy_coeff_sums, mlpfwd.h).
+template <bool IMG, bool RANGED>
+__global__ __launch_bounds__(256) void mlp_backward_tempered_kernel(MlpBwdArgs a, ValueRangeArg value,
+                                                                    TemperArg temper) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  kernarg_prefetch<sizeof(MlpBwdArgs)>();
+  const float log_alpha = *temper.log_alpha;
+  const float alpha = expf(log_alpha);
+  if constexpr (IMG) mlp_backward_body_img<RANGED, false, true>(a, blockIdx.y, blockIdx.x, lds, 0, value, nullptr, alpha);
+  else mlp_backward_body<RANGED, false, true>(a, blockIdx.y, blockIdx.x, lds, value, nullptr, alpha);
+  if (temper.sums != nullptr && blockIdx.x == 0 && blockIdx.y == 0) {      // scalar: the workgroup of the logged sums
+    __syncthreads();                                  // (block_sum3's wave partials are free again)
+    entropy_coeff_sums(a.l_logp, a.B, log_alpha, alpha, temper.target_entropy, temper.sums);
+  }
 }
 
 // ------------------------------------------------------------------ chained passes (mlpfwd.h)
@@ -1170,6 +1194,46 @@ static int launch_backward_regression(const MlpBwdArgs& a, size_t lds, hipStream
                      stream, a, value, returns);
   TONIC_CHECK_LAUNCH("mlp_backward_regression_kernel");
   return TONIC_OK;
+}
+
+template <bool IMG, bool RANGED>
+static int launch_backward_tempered(const MlpBwdArgs& a, int nets, size_t lds, hipStream_t stream, ValueRangeArg value,
+                                    TemperArg temper) {
+  if constexpr (IMG) {
+    const int status = allow_image_lds(mlp_backward_tempered_kernel<IMG, RANGED>, "mlp_backward_tempered_kernel");
+    if (status != TONIC_OK) return status;
+  }
+  hipLaunchKernelGGL((mlp_backward_tempered_kernel<IMG, RANGED>), dim3((a.B + kRows - 1) / kRows, nets), dim3(256), lds,
+                     stream, a, value, temper);
+  TONIC_CHECK_LAUNCH("mlp_backward_tempered_kernel");
+  return TONIC_OK;
+}
+
+// launch_mlp_backward for the twin critics' chain of a SAC step whose coefficient lives on the device: the same
+// grid, LDS and bodies as the plain / ranged launch.
+int launch_mlp_backward_tempered(const MlpBwdArgs& a, int nets, hipStream_t stream, ValueRangeArg value,
+                                 TemperArg temper) {
+  TONIC_REQUIRE(mlp_backward_supported(a.H, a.NH, a.heads, a.xa_count) && a.B > 0 && nets == 2 && a.l_nets == 2,
+                TONIC_ERR_INVALID_ARGUMENT, "mlp_backward: H=%d NH=%d heads=%d B=%d nets=%d", a.H, a.NH, a.heads, a.B,
+                nets);
+  TONIC_REQUIRE(a.ldw2 >= a.H && (a.xa_count == 0 || a.ldw1 >= a.K1) && a.ldhid >= a.H && a.ldhid % 4 == 0,
+                TONIC_ERR_INVALID_ARGUMENT, "mlp_backward: strides %d / %d / %d", a.ldw1, a.ldw2, a.ldhid);
+  TONIC_REQUIRE(temper.log_alpha != nullptr && a.heads == 0 && (a.loss == LOSS_TD || a.loss == LOSS_ACTOR) &&
+                    a.l_logp != nullptr && a.l_q != nullptr && a.l_stats != nullptr && a.exchange_failed == nullptr &&
+                    (temper.sums == nullptr || a.loss == LOSS_ACTOR),
+                TONIC_ERR_INVALID_ARGUMENT, "mlp_backward: a device coefficient needs the twin critics' chain of a SAC step");
+  const bool ranged = value.low != nullptr;
+  TONIC_REQUIRE(!ranged || value.high != nullptr, TONIC_ERR_INVALID_ARGUMENT, "mlp_backward: half a value range");
+  if (a.img.block != nullptr) {
+    TONIC_REQUIRE(image_pass_supported(0, a.H), TONIC_ERR_INVALID_ARGUMENT,
+                  "mlp_backward: H=%d outside the image pass", a.H);
+    const size_t img_bytes = img_lds(0, a.H).total;
+    return ranged ? launch_backward_tempered<true, true>(a, nets, img_bytes, stream, value, temper)
+                  : launch_backward_tempered<true, false>(a, nets, img_bytes, stream, value, temper);
+  }
+  const size_t lds = 2 * (size_t)kRows * (a.H + 4) * sizeof(float);
+  return ranged ? launch_backward_tempered<false, true>(a, nets, lds, stream, value, temper)
+                : launch_backward_tempered<false, false>(a, nets, lds, stream, value, temper);
 }
 
 int launch_mlp_backward(const MlpBwdArgs& a, int nets, hipStream_t stream, ValueRangeArg value, const float* returns) {

@@ -446,11 +446,11 @@ __device__ __forceinline__ void mlp_forward_body_img(const MlpFwdArgs& a, const 
 }
 
 // ------------------------------------------------------------------------------------------ backward
-template <bool RANGED = false, bool REGRESS = false>      // (REGRESS, returns: see mlp_backward_body)
+template <bool RANGED = false, bool REGRESS = false, bool TEMPERED = false>      // (REGRESS, returns, TEMPERED, alpha: see mlp_backward_body)
 __device__ __forceinline__ void mlp_backward_body_img(const MlpBwdArgs& a, const int net, const int bx,
                                                       float* lds_f, const int K1_lds,
                                                       ValueRangeArg value = ValueRangeArg{nullptr, nullptr},
-                                                      const float* returns = nullptr) {
+                                                      const float* returns = nullptr, const float alpha = 0.f) {
   char* lds = reinterpret_cast<char*>(lds_f);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -568,8 +568,8 @@ __device__ __forceinline__ void mlp_backward_body_img(const MlpBwdArgs& a, const
       dq = a.dq[net * a.stride_dq + row];
     } else {                                          // the step's loss, folded into this launch
       if (a.loss == LOSS_TD) {
-        const float y = td_target(a.l_rewards, a.l_discounts, a.l_tq, a.l_logp, a.l_alpha, row, a.l_tq_at,
-                                  a.l_nets, co);
+        const float y = td_target(a.l_rewards, a.l_discounts, a.l_tq, a.l_logp, TEMPERED ? alpha : a.l_alpha, row,
+                                  a.l_tq_at, a.l_nets, co);
         const float q = load_shared(a.l_q + a.l_q_at.index(net, row), co);
         dq = value_squash_dz(critic_loss_dq(q - y, a.l_kind, a.l_param), q, vrange);
       } else {
@@ -735,5 +735,5 @@ __device__ __forceinline__ void mlp_backward_body_img(const MlpBwdArgs& a, const
     }
   }
   // the logged sums (uniform); a chain launch leaves them to its last workgroup
-  if (a.loss != LOSS_GIVEN && co == nullptr && bx == 0 && net == 0) mlp_loss_stats<REGRESS>(a, returns);
+  if (a.loss != LOSS_GIVEN && co == nullptr && bx == 0 && net == 0) mlp_loss_stats<REGRESS, TEMPERED>(a, returns, alpha);
 }

@@ -223,10 +223,11 @@ __global__ void copy_actions_kernel(const float* loc, int ld, float* act, int B,
 // y = r + disc * (min(q1', q2') - alpha * logp')  (critics.py:219-221; alpha = 0 and logp = null
 // give TD3's critics.py:166-167), then dq_z = loss'(q_z - y) (critic_loss_dq, mlpfwd.h; MSE: 2 (q_z - y)) and the
 // statistics.  nets == 1 (DDPG, critics.py:72-79): y = r + disc * q', one critic, statistics {loss_terms, q, 0}.
-__global__ void critic_loss_kernel(const float* rewards, const float* discounts,
-                                   const float* tq, const float* logp_next, float alpha,
-                                   const float* q, float* dq, float* stats, int B, int Bp,
-                                   int nets, CriticLoss loss, const float* v_low, const float* v_high) {
+// (critic_loss_rows: the kernel's whole body, shared with the form that reads alpha from the device)
+__device__ __forceinline__ void critic_loss_rows(const float* rewards, const float* discounts,
+                                                 const float* tq, const float* logp_next, float alpha,
+                                                 const float* q, float* dq, float* stats, int B, int Bp,
+                                                 int nets, CriticLoss loss, const float* v_low, const float* v_high) {
   const ValueRange vrange = value_range(v_low, v_high);     // the Return normaliser's head: q / tq are squashed values
   float s_loss = 0.f, s_q1 = 0.f, s_q2 = 0.f;
   for (int m = threadIdx.x; m < B; m += blockDim.x) {
@@ -252,6 +253,20 @@ __global__ void critic_loss_kernel(const float* rewards, const float* discounts,
     stats[4] = 0.f; stats[5] = (float)B; stats[6] = 0.f; stats[7] = 0.f;
   }
 }
+__global__ void critic_loss_kernel(const float* rewards, const float* discounts,
+                                   const float* tq, const float* logp_next, float alpha,
+                                   const float* q, float* dq, float* stats, int B, int Bp,
+                                   int nets, CriticLoss loss, const float* v_low, const float* v_high) {
+  critic_loss_rows(rewards, discounts, tq, logp_next, alpha, q, dq, stats, B, Bp, nets, loss, v_low, v_high);
+}
+// ... with SAC's coefficient read from the device (TemperArg, mlpfwd.h): alpha = expf(*log_alpha), once
+__global__ void critic_loss_tempered_kernel(const float* rewards, const float* discounts,
+                                            const float* tq, const float* logp_next, const float* log_alpha,
+                                            const float* q, float* dq, float* stats, int B, int Bp,
+                                            int nets, CriticLoss loss, const float* v_low, const float* v_high) {
+  const float alpha = expf(*log_alpha);
+  critic_loss_rows(rewards, discounts, tq, logp_next, alpha, q, dq, stats, B, Bp, nets, loss, v_low, v_high);
+}
 
 // QRegression (critics.py:31-53): y = returns[m] as given, one critic — dq = loss'(q - y) at the head's
 // pre-activation and the statistics row critic_loss_kernel writes for one critic (LOSS_REGRESSION, mlpfwd.h).
@@ -276,9 +291,9 @@ __global__ void regression_loss_kernel(const float* returns, const float* q, flo
 // Actor objective: SAC  loss = mean(alpha * logp - min(q1, q2))  (actors.py:254-257)
 //                  TD3  loss = -mean(q1)                          (actors.py:177-179)
 // d loss / d q_z (unscaled by 1/B): -1 on the smaller critic, -1/2 each on ties.
-__global__ void actor_loss_kernel(const float* q, const float* logp, float alpha, int twin,
-                                  float* dq, float* stats, int B, int Bp, const float* v_low,
-                                  const float* v_high) {
+__device__ __forceinline__ void actor_loss_rows(const float* q, const float* logp, float alpha, int twin,
+                                                float* dq, float* stats, int B, int Bp, const float* v_low,
+                                                const float* v_high) {
   const ValueRange vrange = value_range(v_low, v_high);     // the Return normaliser's head: q holds squashed values
   float s = 0.f;
   for (int m = threadIdx.x; m < B; m += blockDim.x) {
@@ -296,6 +311,24 @@ __global__ void actor_loss_kernel(const float* q, const float* logp, float alpha
   if (threadIdx.x == 0) {
     stats[0] = (float)a;
     for (int i = 1; i < 8; ++i) stats[i] = i == 5 ? (float)B : 0.f;
+  }
+}
+__global__ void actor_loss_kernel(const float* q, const float* logp, float alpha, int twin,
+                                  float* dq, float* stats, int B, int Bp, const float* v_low,
+                                  const float* v_high) {
+  actor_loss_rows(q, logp, alpha, twin, dq, stats, B, Bp, v_low, v_high);
+}
+// ... with SAC's coefficient read from the device, and the coefficient's own block (entropy_coeff_sums) formed from
+// the same logp by the same workgroup: no launch more
+__global__ void actor_loss_tempered_kernel(const float* q, const float* logp, TemperArg temper, int twin,
+                                           float* dq, float* stats, int B, int Bp, const float* v_low,
+                                           const float* v_high) {
+  const float log_alpha = *temper.log_alpha;
+  const float alpha = expf(log_alpha);
+  actor_loss_rows(q, logp, alpha, twin, dq, stats, B, Bp, v_low, v_high);
+  if (temper.sums != nullptr) {
+    __syncthreads();                                  // (block_sum3's wave partials are free again)
+    entropy_coeff_sums(logp, B, log_alpha, alpha, temper.target_entropy, temper.sums);
   }
 }
 
@@ -712,12 +745,12 @@ __global__ void mpo_dual_kernel(const float* part, const float* klm, const float
 //   d loss/d loc = d loss/d u ;  d loss/d sigma = d loss/d u * eps - alpha / sigma
 //   d sigma/d spre = sigmoid(spre) inside the clamp, else 0.
 // TD3: a = tanh(z):  d loss/d z = da (1 - a^2).
-__global__ void actor_head_backward_kernel(const float* dxa0, const float* dxa1, int ldxa,
-                                           const float* act,
-                                           const float* eps, const float* sigma,
-                                           const float* spre, int ld, float alpha, int sac,
-                                           float* dloc, float* dspre, int B, int A, float scale_lo,
-                                           float scale_hi) {
+__device__ __forceinline__ void actor_head_backward_element(const float* dxa0, const float* dxa1, int ldxa,
+                                                            const float* act,
+                                                            const float* eps, const float* sigma,
+                                                            const float* spre, int ld, float alpha, int sac,
+                                                            float* dloc, float* dspre, int B, int A, float scale_lo,
+                                                            float scale_hi) {
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= B * A) return;
   const int m = idx / A, a = idx - m * A;
@@ -738,6 +771,26 @@ __global__ void actor_head_backward_kernel(const float* dxa0, const float* dxa1,
   const bool inside = raw >= scale_lo && raw <= scale_hi;
   dloc[(int64_t)m * ld + a] = du;
   dspre[(int64_t)m * ld + a] = inside ? dsigma / (1.f + expf(-pre)) : 0.f;
+}
+__global__ void actor_head_backward_kernel(const float* dxa0, const float* dxa1, int ldxa,
+                                           const float* act,
+                                           const float* eps, const float* sigma,
+                                           const float* spre, int ld, float alpha, int sac,
+                                           float* dloc, float* dspre, int B, int A, float scale_lo,
+                                           float scale_hi) {
+  actor_head_backward_element(dxa0, dxa1, ldxa, act, eps, sigma, spre, ld, alpha, sac, dloc, dspre, B, A, scale_lo,
+                              scale_hi);
+}
+// ... the squashed Gaussian head with SAC's coefficient read from the device (TemperArg, mlpfwd.h)
+__global__ void actor_head_backward_tempered_kernel(const float* dxa0, const float* dxa1, int ldxa,
+                                                    const float* act,
+                                                    const float* eps, const float* sigma,
+                                                    const float* spre, int ld, const float* log_alpha,
+                                                    float* dloc, float* dspre, int B, int A, float scale_lo,
+                                                    float scale_hi) {
+  const float alpha = expf(*log_alpha);
+  actor_head_backward_element(dxa0, dxa1, ldxa, act, eps, sigma, spre, ld, alpha, 1, dloc, dspre, B, A, scale_lo,
+                              scale_hi);
 }
 
 // Buffer.get gather (buffers.py:84-91): one wave per sampled transition.
@@ -1125,6 +1178,7 @@ struct StepLoss {
   CriticLoss rule;                            // LOSS_TD, LOSS_REGRESSION: tonic_critic_loss_t (all-zero: MSE)
   const float* v_low; const float* v_high;    // the Return normaliser's head (q / tq are squashed values); null: plain
   const float* returns;                       // LOSS_REGRESSION: the targets [B] (one critic; all it reads beside q)
+  TemperArg temper;                           // log_alpha != null (SAC, twin critics): exp(*log_alpha) stands for alpha
 };
 
 // The one-launch chain's arguments (mlp_backward_supported(H, 1, 0, dxa ? A : 0)).
@@ -1199,6 +1253,13 @@ int critics_backward(const float* params, CriticShape s, int nets, const float* 
     if (loss->kind == LOSS_REGRESSION) {
       hipLaunchKernelGGL(regression_loss_kernel, dim3(1), dim3(1024), 0, st, loss->returns, loss->q, dq, loss->stats,
                          B, loss->rule, loss->v_low, loss->v_high);
+    } else if (loss->temper.log_alpha != nullptr && loss->kind == LOSS_TD) {
+      hipLaunchKernelGGL(critic_loss_tempered_kernel, dim3(1), dim3(1024), 0, st, loss->rewards,
+                         loss->discounts, loss->tq, loss->logp, loss->temper.log_alpha, loss->q, dq,
+                         loss->stats, B, Bp, nets, loss->rule, loss->v_low, loss->v_high);
+    } else if (loss->temper.log_alpha != nullptr) {
+      hipLaunchKernelGGL(actor_loss_tempered_kernel, dim3(1), dim3(1024), 0, st, loss->q, loss->logp,
+                         loss->temper, nets == 2 ? 1 : 0, dq, loss->stats, B, Bp, loss->v_low, loss->v_high);
     } else if (loss->kind == LOSS_TD) {
       hipLaunchKernelGGL(critic_loss_kernel, dim3(1), dim3(1024), 0, st, loss->rewards,
                          loss->discounts, loss->tq, loss->logp, loss->alpha, loss->q, dq,
@@ -1216,7 +1277,9 @@ int critics_backward(const float* params, CriticShape s, int nets, const float* 
   if (one_launch) {                                               // ... in ONE launch
     MlpBwdArgs b = critics_chain_args(params, s, nets, B, Bp, h1, h2, dq, dh2, dh1, dxa, loss, img);
     b.skip_dz = grads == nullptr ? 1 : 0;          // (a frozen critic's chain: only its action columns are read)
-    TRY(launch_mlp_backward(b, nets, st, loss ? ValueRangeArg{loss->v_low, loss->v_high} : ValueRangeArg{nullptr, nullptr},
+    if (loss && loss->temper.log_alpha != nullptr)
+      TRY(launch_mlp_backward_tempered(b, nets, st, ValueRangeArg{loss->v_low, loss->v_high}, loss->temper));
+    else TRY(launch_mlp_backward(b, nets, st, loss ? ValueRangeArg{loss->v_low, loss->v_high} : ValueRangeArg{nullptr, nullptr},
                             loss ? loss->returns : nullptr));
   } else {
     // dz_top = (dq w3) * act'(h_top)   (two layers: dz2, with h2)
@@ -1593,10 +1656,14 @@ int twin_q_grad(int32_t kind, const float* d_policy_params, const float* d_targe
                 const float* d_discounts, const float* d_eps, float* d_grad_sums, int32_t B, int32_t O, int32_t H,
                 int32_t A, double entropy_coeff, double noise_scale, double noise_clip,
                 const tonic_critic_loss_t* loss, const float* d_value_low, const float* d_value_high,
-                void* d_workspace, int64_t workspace_bytes, void* stream) {
+                void* d_workspace, int64_t workspace_bytes, void* stream,
+                const float* d_log_entropy_coeff = nullptr) {
   TONIC_REQUIRE((d_value_low == nullptr) == (d_value_high == nullptr), TONIC_ERR_INVALID_ARGUMENT,
                 "tonic_twin_q_grad_ranged: %s is NULL and the other bound is not (both or neither)",
                 d_value_low == nullptr ? "d_value_low" : "d_value_high");
+  TONIC_REQUIRE(d_log_entropy_coeff == nullptr || kind == 1, TONIC_ERR_INVALID_ARGUMENT,
+                "tonic_tempered_twin_q_grad: kind %d has no entropy term (d_log_entropy_coeff goes with kind 1, SAC)",
+                kind);
   TRY(tonic_critic_loss_check(loss));
   TONIC_REQUIRE(d_policy_params && d_target_critics && d_critics && d_norm_mean && d_norm_std && d_observations &&
                     d_actions && d_next_observations && d_rewards && d_discounts && (d_eps || kind == 2) &&
@@ -1645,7 +1712,7 @@ int twin_q_grad(int32_t kind, const float* d_policy_params, const float* d_targe
                       d_critics, w.X2, im.on ? &im.target_critics : nullptr, d_value_low, d_value_high));
   const StepLoss td{LOSS_TD, d_rewards, d_discounts, tq, kind == 1 ? w.logp : (const float*)nullptr,
                     (float)entropy_coeff, q, d_grad_sums + nets * Pc, critic_loss_rule(loss),
-                    d_value_low, d_value_high};
+                    d_value_low, d_value_high, nullptr, TemperArg{d_log_entropy_coeff, nullptr, 0.f}};
   TRY(critics_backward(d_critics, cs, nets, w.X2, ldx, B, Bp, c_h1, c_h2, w.dq, w.dh2, w.dh1, d_grad_sums,
                        nullptr, st, &td, nullptr, im.on ? &im.critics : nullptr));
   TONIC_CHECK_LAUNCH("tonic_twin_q_grad");
@@ -1693,6 +1760,23 @@ extern "C" int tonic_twin_q_grad_ranged(
                      d_observations, d_actions, d_next_observations, d_rewards, d_discounts, d_eps, d_grad_sums, B, O,
                      H, A, entropy_coeff, noise_scale, noise_clip, loss, d_value_low, d_value_high, d_workspace,
                      workspace_bytes, stream);
+}
+
+// ... SAC (kind 1) with a LEARNED entropy coefficient: d_log_entropy_coeff is one float32 on the device and the TD
+// target's alpha is expf(*d_log_entropy_coeff), read by the kernels — the host never sees it, so a captured graph
+// follows the coefficient as it moves.  NULL: tonic_twin_q_grad_ranged with `entropy_coeff`, launches and bits.
+extern "C" int tonic_tempered_twin_q_grad(
+    int32_t kind, const float* d_policy_params, const float* d_target_critics, const float* d_critics,
+    const float* d_norm_mean, const float* d_norm_std, double norm_clip, const float* d_observations,
+    const float* d_actions, const float* d_next_observations, const float* d_rewards, const float* d_discounts,
+    const float* d_eps, float* d_grad_sums, int32_t B, int32_t O, int32_t H, int32_t A, double entropy_coeff,
+    double noise_scale, double noise_clip, const tonic_critic_loss_t* loss, const float* d_value_low,
+    const float* d_value_high, const float* d_log_entropy_coeff, void* d_workspace, int64_t workspace_bytes,
+    void* stream) {
+  return twin_q_grad(kind, d_policy_params, d_target_critics, d_critics, d_norm_mean, d_norm_std, norm_clip,
+                     d_observations, d_actions, d_next_observations, d_rewards, d_discounts, d_eps, d_grad_sums, B, O,
+                     H, A, entropy_coeff, noise_scale, noise_clip, loss, d_value_low, d_value_high, d_workspace,
+                     workspace_bytes, stream, d_log_entropy_coeff);
 }
 
 // QRegression.__call__ (tonic/torch/updaters/critics.py:31-53): values = critic(s, a), loss(values, returns) on
@@ -1861,10 +1945,18 @@ int actor_q_grad(int32_t kind, const float* d_actor_params, const float* d_criti
                  const float* d_norm_std, double norm_clip, const float* d_observations, const float* d_eps,
                  float* d_grad_sums, int32_t B, int32_t O, int32_t H, int32_t A, double entropy_coeff,
                  const float* d_value_low, const float* d_value_high, void* d_workspace, int64_t workspace_bytes,
-                 void* stream) {
+                 void* stream, TemperArg temper = TemperArg{nullptr, nullptr, 0.f}) {
   TONIC_REQUIRE((d_value_low == nullptr) == (d_value_high == nullptr), TONIC_ERR_INVALID_ARGUMENT,
                 "tonic_actor_q_grad_ranged: %s is NULL and the other bound is not (both or neither)",
                 d_value_low == nullptr ? "d_value_low" : "d_value_high");
+  TONIC_REQUIRE((temper.log_alpha == nullptr) == (temper.sums == nullptr), TONIC_ERR_INVALID_ARGUMENT,
+                "tonic_tempered_actor_q_grad: %s is NULL and the other is not (both or neither)",
+                temper.log_alpha == nullptr ? "d_log_entropy_coeff" : "d_entropy_coeff_sums");
+  TONIC_REQUIRE(temper.log_alpha == nullptr || kind == 1, TONIC_ERR_INVALID_ARGUMENT,
+                "tonic_tempered_actor_q_grad: kind %d has no entropy term (d_log_entropy_coeff goes with kind 1, SAC)",
+                kind);
+  TONIC_REQUIRE(temper.log_alpha == nullptr || temper.target_entropy - temper.target_entropy == 0.f,
+                TONIC_ERR_INVALID_ARGUMENT, "tonic_tempered_actor_q_grad: target_entropy is not finite");
   TONIC_REQUIRE(d_actor_params && d_critics && d_norm_mean && d_norm_std && d_observations &&
                     d_grad_sums && d_workspace && B > 0 && (kind == 0 || d_eps) && hidden_known(H),
                 TONIC_ERR_INVALID_ARGUMENT, "tonic_actor_q_grad: bad argument");
@@ -1900,10 +1992,14 @@ int actor_q_grad(int32_t kind, const float* d_actor_params, const float* d_criti
   TRY(critics_forward(d_critics, cs, nets, w.X, ldx, B, Bp, w.c_h1, w.c_h2, w.q, st, nullptr, nullptr,
                       im.on ? &im.critics : nullptr, d_value_low, d_value_high));
   const StepLoss objective{LOSS_ACTOR, nullptr, nullptr, nullptr, w.logp, (float)entropy_coeff, w.q,
-                           d_grad_sums + Pa, CriticLoss{TONIC_LOSS_MSE, 0.f}, d_value_low, d_value_high};
+                           d_grad_sums + Pa, CriticLoss{TONIC_LOSS_MSE, 0.f}, d_value_low, d_value_high, nullptr, temper};
   TRY(critics_backward(d_critics, cs, nets, w.X, ldx, B, Bp, w.c_h1, w.c_h2, w.dq, w.dh2, w.dh1, nullptr, w.dxa,
                        st, &objective, nullptr, im.on ? &im.critics : nullptr));
-  hipLaunchKernelGGL(actor_head_backward_kernel, dim3((B * A + threads - 1) / threads), dim3(threads), 0, st, w.dxa,
+  if (temper.log_alpha != nullptr)
+    hipLaunchKernelGGL(actor_head_backward_tempered_kernel, dim3((B * A + threads - 1) / threads), dim3(threads), 0, st,
+                       w.dxa, w.dxa + (int64_t)Bp * ldh, ldh, w.act, d_eps, w.sigma, w.head1, ldh, temper.log_alpha,
+                       w.dloc, w.dspre, B, A, as.scale_lo, as.scale_hi);
+  else hipLaunchKernelGGL(actor_head_backward_kernel, dim3((B * A + threads - 1) / threads), dim3(threads), 0, st, w.dxa,
                      nets == 2 ? w.dxa + (int64_t)Bp * ldh : (float*)nullptr, ldh, w.act, d_eps, w.sigma, w.head1, ldh,
                      (float)entropy_coeff, kind == 1 ? 1 : 0, w.dloc, w.dspre, B, A, as.scale_lo, as.scale_hi);
   TRY(actor_shaped_backward(d_actor_params, as, d_observations, O, B, w.a_h1, w.a_h2, w.dloc,
@@ -1934,6 +2030,24 @@ extern "C" int tonic_actor_q_grad_ranged(
   return actor_q_grad(kind, d_actor_params, d_critics, d_norm_mean, d_norm_std, norm_clip, d_observations, d_eps,
                       d_grad_sums, B, O, H, A, entropy_coeff, d_value_low, d_value_high, d_workspace, workspace_bytes,
                       stream);
+}
+
+// ... SAC (kind 1) with a LEARNED entropy coefficient (tonic_tempered_twin_q_grad): alpha = expf(*d_log_entropy_coeff)
+// in the objective, its logged sum and the head backward, and the coefficient's own block
+// d_entropy_coeff_sums [1 + 8] = {-sum(logp + target_entropy) | -log_alpha sum(logp + target_entropy), sum logp,
+// alpha B, 0, 0, B, 0, 0} from the log-probabilities of THIS step's sample (formed by the workgroup that forms the
+// objective's logged sum: no launch more) — the gradient SUM of J = -mean(log_alpha (logp + target_entropy)) and its
+// statistics, stepped by tonic_optimizer_step on a block of one.  Both pointers or neither; NULL / NULL:
+// tonic_actor_q_grad_ranged with `entropy_coeff`, launches and bits.
+extern "C" int tonic_tempered_actor_q_grad(
+    int32_t kind, const float* d_actor_params, const float* d_critics, const float* d_norm_mean,
+    const float* d_norm_std, double norm_clip, const float* d_observations, const float* d_eps, float* d_grad_sums,
+    int32_t B, int32_t O, int32_t H, int32_t A, double entropy_coeff, const float* d_value_low,
+    const float* d_value_high, const float* d_log_entropy_coeff, float* d_entropy_coeff_sums, double target_entropy,
+    void* d_workspace, int64_t workspace_bytes, void* stream) {
+  return actor_q_grad(kind, d_actor_params, d_critics, d_norm_mean, d_norm_std, norm_clip, d_observations, d_eps,
+                      d_grad_sums, B, O, H, A, entropy_coeff, d_value_low, d_value_high, d_workspace, workspace_bytes,
+                      stream, TemperArg{d_log_entropy_coeff, d_entropy_coeff_sums, (float)target_entropy});
 }
 
 // ------------------------------------------------------------------ one whole learner iteration

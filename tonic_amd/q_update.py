@@ -117,7 +117,8 @@ class Slot:
     eps      float32 [iterations, draws, S * B, A]: the standard-normal draws
     adam     float32 [iterations, 2, 2] (`adam_table`) or None: only the whole fused iteration reads it
     infos    float32 [2, iterations, INFO_WIDTH]: the critic's and the actor's statistics rows
-    stats    float32 [iterations, width] or None: the agent's `_stats_width()` more per iteration (MPO)
+    stats    float32 [iterations, width] or None: the agent's `_stats_width()` more per iteration (MPO; SAC with
+             a learned entropy coefficient: the coefficient's statistics rows)
     graph    the captured hipGraph; None: the next call through a graph captures"""
 
     __slots__ = ('key', 'indices', 'eps', 'adam', 'infos', 'stats', 'graph')
@@ -147,7 +148,7 @@ class QUpdate:
 
     def route(self):
         """tonic_q_iteration serves the plain DDPG / TD3 / SAC updaters (`agent._FUSED`) with plain Adam, no
-        Return normaliser (no squashed value head there) and shapes inside the fused kernels; what needs the
+        Return normaliser (no squashed value head there), no learned entropy coefficient (no tempered form) and shapes inside the fused kernels; what needs the
         complete sums gets it in phases, or the split entry points with TONIC_AMD_FUSED_PHASES=0.
         TONIC_AMD_FUSED_ITERATION=0 keeps the split entry points (the tests compare the two)."""
         agent, critic, actor = self.agent, self.agent.critic_updater, self.agent.actor_updater
@@ -157,6 +158,7 @@ class QUpdate:
         kind, actor_class = agent._FUSED.get(type(critic), (None, None))
         if kind is None or type(actor) is not actor_class or critic.stock or actor.stock \
                 or agent.model.return_normalizer or not (critic.plain and actor.plain) \
+                or getattr(agent, 'entropy_coeff_updater', None) is not None \
                 or os.environ.get('TONIC_AMD_FUSED_ITERATION', '1') == '0' \
                 or not agent.lib.tonic_q_iteration_supported(agent.observation_size, agent.hidden, agent.action_size,
                                                              2 if kind == 1 else 1) \
@@ -299,11 +301,17 @@ class QUpdate:
     def _actor_step(self, observations, eps, it, n_global):
         """The actor updater's own entry (observations None: this rank drew none of the global batch)."""
         actor, slot = self.agent.actor_updater, self.slot
-        more = {} if slot.stats is None else {'stats_row': slot.stats[it]}
+        tuner = getattr(self.agent, 'entropy_coeff_updater', None)     # (SAC: slot.stats rows are the coefficient's)
+        more = {} if slot.stats is None or tuner is not None else {'stats_row': slot.stats[it]}
         if observations is None:
             actor.enqueue_empty(slot.infos[1, it], n_global, self._targets(), **more)
         else:
             actor.enqueue(observations, eps, slot.infos[1, it], n_global, self._targets(), **more)
+        if tuner is not None:       # alpha_t -> alpha_{t+1} from this actor step's sums, ahead of the next critic step
+            if observations is None:
+                tuner.enqueue_empty(slot.stats[it], n_global)
+            else:
+                tuner.enqueue_step(slot.stats[it], n_global or observations.shape[0] * tuner.world_size)
 
     def _issue_split(self, batches, due, counts, global_batch):
         critic, slot = self.agent.critic_updater, self.slot

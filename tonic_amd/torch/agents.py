@@ -1646,12 +1646,17 @@ class TD4(TD3):
 
 
 class SAC(DDPG):
-    """tonic/torch/agents/sac.py:22-51."""
+    """tonic/torch/agents/sac.py:22-51.  `entropy_coeff_updater=updaters.EntropyCoeffTuning()` (None, the default:
+    the reference's fixed coefficients, nothing changes) learns the entropy coefficient: per iteration the critic
+    step and the actor step with alpha_t, then the coefficient's own step to alpha_{t+1} from the actor step's
+    log-probabilities — on the updaters' split entries (tonic_tempered_*_q_grad), the updaters' own `entropy_coeff`
+    floats unused."""
 
     policy_kind = 1
 
     def __init__(self, model=None, replay=None, exploration=None, actor_updater=None,
-                 critic_updater=None):
+                 critic_updater=None, entropy_coeff_updater=None):
+        self.entropy_coeff_updater = entropy_coeff_updater
         head = models.GaussianPolicyHead(loc_activation=torch.nn.Identity,
                                          distribution=models.SquashedMultivariateNormalDiag)
         super().__init__(
@@ -1668,3 +1673,51 @@ class SAC(DDPG):
         B, A = self.replay.batch_size, self.action_size
         return np.stack([np.stack([torch.randn(B, A).numpy(), torch.randn(B, A).numpy()])
                          for _ in range(iterations)])
+
+    def initialize(self, observation_space, action_space, seed=None):
+        tuner = self.entropy_coeff_updater
+        if tuner is not None:       # (before anything is built: the tempered entries are these two updaters')
+            for role, updater, served in (('critic_updater', self.critic_updater, updaters.TwinCriticSoftQLearning),
+                                          ('actor_updater', self.actor_updater,
+                                           updaters.TwinCriticSoftDeterministicPolicyGradient)):
+                if type(updater) is not served:
+                    raise NotImplementedError(
+                        f'SAC(entropy_coeff_updater=...) with {role}={type(updater).__name__}: a learned entropy '
+                        f'coefficient is read on the device by {served.__name__} only')
+        super().initialize(observation_space, action_space, seed=seed)
+        if tuner is not None:
+            tuner.initialize(self.model, self.action_size)
+            self.critic_updater.entropy_coeff_updater = tuner
+            self.actor_updater.entropy_coeff_updater = tuner
+
+    def _stats_width(self):
+        # the coefficient's statistics row {loss, mean log-prob, alpha before the step, ...} per iteration
+        return updaters.INFO_WIDTH if self.entropy_coeff_updater is not None else 0
+
+    def _graph_signature(self):
+        signature, tuner = super()._graph_signature(), self.entropy_coeff_updater
+        if tuner is None:
+            return signature
+        # (the coefficient itself is read through its pointer by the captured launches)
+        return signature + ((tuple(sorted(tuner.hyper.items())), float(tuner.target_entropy),
+                             tuner.log_entropy_coeff.data_ptr()),)
+
+    def _log_update(self, infos, stats):
+        super()._log_update(infos, stats)
+        if self.entropy_coeff_updater is not None and stats is not None:
+            for row in stats:
+                logger.store('entropy_coeff/loss', row[0])
+                logger.store('entropy_coeff/value', row[2])          # alpha the iteration's two steps used
+                logger.store('entropy_coeff/entropy', -row[1])       # mean -log pi of the actor step's sample
+            self.last_entropy_coeff_infos = stats
+
+    def save(self, path):
+        super().save(path)          # the .pt of the reference, as ever
+        if self.entropy_coeff_updater is not None:
+            torch.save(self.entropy_coeff_updater.state_dict(), path + '.entropy_coeff.pt')
+
+    def load(self, path):
+        super().load(path)
+        sibling = path + '.entropy_coeff.pt'
+        if self.entropy_coeff_updater is not None and os.path.exists(sibling):   # (absent: the initial value stays)
+            self.entropy_coeff_updater.load_state_dict(torch.load(sibling, map_location='cpu'))

@@ -13,7 +13,9 @@ The PPO agent drives them through ``enqueue`` for all 80 iterations and reads th
 statistics back once; ``__call__`` (enqueue + read back) exists for drop-in compatibility.
 """
 import ctypes
+import math
 import os
+import types
 
 import numpy as np
 import torch
@@ -1104,6 +1106,16 @@ class _QUpdater(_FlatUpdater):
     def norm_clip(self):
         return float(getattr(self.normalizer, 'clip', None) or 0.0)
 
+    # agents.SAC(entropy_coeff_updater=EntropyCoeffTuning()): the SAC updaters read alpha = exp(log_entropy_coeff)
+    # from the tuner's device tensor (the tonic_tempered_* entries) and their own `entropy_coeff` floats are unused
+    entropy_coeff_updater = None
+
+    def _entropy_coeff(self):
+        """The stock-torch forms' alpha: the float, or — with a tuner — exp(log_entropy_coeff), kept a tensor."""
+        if self.entropy_coeff_updater is None:
+            return self.entropy_coeff
+        return self.entropy_coeff_updater.log_entropy_coeff.detach().exp()
+
     def range_pointers(self):
         """Device pointers of the Return normaliser's (_low, _high); (None, None) without one: the plain heads."""
         if self.return_normalizer is None:
@@ -1201,7 +1213,7 @@ class _TwinCriticQLearning(_QUpdater):
             else:
                 next_values = model.target_critic(batch['next_observations'], actions)
             if self.kind == 1:
-                next_values = next_values - self.entropy_coeff * log_probs
+                next_values = next_values - self._entropy_coeff() * log_probs
             returns = batch['rewards'] + batch['discounts'] * next_values
         critics = (model.critic_1, model.critic_2) if twin else (model.critic,)
         self._stock_regress(critics, batch, returns, n, info_row)
@@ -1239,6 +1251,9 @@ class _TwinCriticQLearning(_QUpdater):
         entry, value_range = 'tonic_twin_q_grad_loss', ()
         if self.return_normalizer is not None:
             entry, value_range = 'tonic_twin_q_grad_ranged', self.range_pointers()
+        if self.entropy_coeff_updater is not None:       # (SAC: the coefficient is read on the device)
+            entry = 'tonic_tempered_twin_q_grad'
+            value_range = self.range_pointers() + (p(self.entropy_coeff_updater.log_entropy_coeff),)
         _lib.check(getattr(self.lib, entry)(
             self.kind, p(self._policy_params()), p(self.model.flat_target_critics.flat),
             p(self.flat.flat), p(mean), p(std), self.norm_clip(), p(batch['observations']),
@@ -1564,7 +1579,9 @@ class _ActorQGradient(_QUpdater):
             actions, log_probs = squashed_sample(model.actor(observations), eps)
             values = torch.min(model.critic_1(observations, actions),
                                model.critic_2(observations, actions))
-            loss = (self.entropy_coeff * log_probs - values).sum() / n
+            loss = (self._entropy_coeff() * log_probs - values).sum() / n
+            if self.entropy_coeff_updater is not None:      # the coefficient's sums from the same log-probabilities
+                self.entropy_coeff_updater.stock_sums(log_probs.detach())
         else:
             critic = model.critic if hasattr(model, 'critic') else model.critic_1
             loss = -critic(observations, model.actor(observations)).sum() / n
@@ -1596,6 +1613,11 @@ class _ActorQGradient(_QUpdater):
         entry, value_range = 'tonic_actor_q_grad', ()
         if self.return_normalizer is not None:
             entry, value_range = 'tonic_actor_q_grad_ranged', self.range_pointers()
+        tuner = self.entropy_coeff_updater
+        if tuner is not None:                            # (SAC: the coefficient is read, its sums written, on the device)
+            entry = 'tonic_tempered_actor_q_grad'
+            value_range = self.range_pointers() + (p(tuner.log_entropy_coeff), p(tuner.grad_sums),
+                                                   float(tuner.target_entropy))
         _lib.check(getattr(self.lib, entry)(
             self.kind, p(self.flat.flat), p(self.model.flat_critics.flat), p(mean), p(std),
             self.norm_clip(), p(observations), p(eps), p(self.grad_sums), B, self.observation_size, self.hidden,
@@ -1800,3 +1822,80 @@ class TwinCriticSoftDeterministicPolicyGradient(_ActorQGradient):
         self.optimizer = optimizer
         self.gradient_clip = gradient_clip
         self.entropy_coeff = entropy_coeff
+
+
+class EntropyCoeffTuning(_FlatUpdater):
+    """SAC's automatic temperature adjustment (Haarnoja et al. 2018b, section 5; the reference keeps its 0.2): the
+    entropy coefficient alpha = exp(log_entropy_coeff) descends J = -mean(log_entropy_coeff * (log_probs +
+    target_entropy)) on the log-probabilities of the actor step's own sample.  `log_entropy_coeff` is ONE float32 on
+    the device; the SAC updaters' tonic_tempered_* entries read it there and tonic_tempered_actor_q_grad writes the
+    gradient sum and the statistics into `grad_sums` [1 + 8], which steps through tonic_optimizer_step like every
+    other block (any rule of `optimizer_hyperparameters`, the ranks' exchange included).  The host never reads the
+    coefficient during training: a captured update graph follows it.
+
+    target_entropy          None: -action_size, resolved at `initialize`
+    initial_entropy_coeff   alpha before the first step (> 0, finite)
+    optimizer               reference style, ``lambda params: torch.optim.X(params, ...)``; default Adam(lr=3e-4)"""
+
+    stats_kind = 3          # {loss, mean log-prob, alpha before the step}
+    default_lr = 3e-4
+    INFO = ('loss', 'log_prob', 'value')
+
+    def __init__(self, target_entropy=None, initial_entropy_coeff=1.0, optimizer=None):
+        initial = float(initial_entropy_coeff)
+        if not (math.isfinite(initial) and initial > 0):
+            raise ValueError(f'initial_entropy_coeff={initial_entropy_coeff!r}: the coefficient is exp(log_entropy_coeff), '
+                             'a finite number above 0')
+        if target_entropy is not None and not math.isfinite(float(target_entropy)):
+            raise ValueError(f'target_entropy={target_entropy!r} is not finite')
+        self.target_entropy = None if target_entropy is None else float(target_entropy)
+        self.initial_entropy_coeff = initial
+        self.optimizer = optimizer
+        self.hyper = optimizer_hyperparameters(optimizer, self.default_lr)      # (the refusals, by name, right here)
+        self.log_entropy_coeff = None
+
+    def initialize(self, model, action_size=None):
+        if action_size is None:
+            action_size = model.actor.head.loc_layer[0].out_features
+        if self.target_entropy is None:
+            self.target_entropy = -float(action_size)
+        device = model.flat_online.device
+        self.log_entropy_coeff = torch.full((1,), math.log(self.initial_entropy_coeff), dtype=torch.float32,
+                                            device=device)
+        self._setup(types.SimpleNamespace(flat=self.log_entropy_coeff, count=1),
+                    optimizer_hyperparameters(self.optimizer, self.default_lr))
+        self.variables = [self.log_entropy_coeff]
+
+    @property
+    def entropy_coeff(self):
+        """alpha as a Python float (one read-back: for logs and tests, never on the update path)."""
+        return float(self.log_entropy_coeff.exp())
+
+    def stock_sums(self, log_probs):
+        """`grad_sums` as tonic_tempered_actor_q_grad writes it, from stock torch operators (the stock-torch actor
+        step: the same layout, so the step and the ranks' exchange are the same)."""
+        log_alpha = self.log_entropy_coeff.detach()[0]
+        excess = (log_probs.double() + self.target_entropy).sum()
+        rows = float(log_probs.shape[0])
+        self.grad_sums.zero_()
+        self.grad_sums[0] = -excess
+        self.grad_sums[1] = -log_alpha.double() * excess
+        self.grad_sums[2] = log_probs.double().sum()
+        self.grad_sums[3] = log_alpha.exp() * rows
+        self.grad_sums[6] = rows
+
+    def enqueue_step(self, info_row, n_global):
+        """log_alpha_t -> log_alpha_{t+1} from the sums of this iteration's actor step; info_row {loss, mean log-prob,
+        alpha_t, ...}."""
+        self._step(n_global, info_row)
+
+    def enqueue_empty(self, info_row, n_global):
+        """This rank drew none of the global batch: zero sums, the same step."""
+        self.grad_sums.zero_()
+        self._step(n_global, info_row)
+
+    def state_dict(self):
+        return {'log_entropy_coeff': self.log_entropy_coeff.detach().cpu().clone()}
+
+    def load_state_dict(self, state):
+        self.log_entropy_coeff.copy_(state['log_entropy_coeff'].to(self.log_entropy_coeff.device).reshape(1))
