@@ -235,26 +235,45 @@ extern "C" int tonic_collector_synthetic_step(void* block, const float* next_obs
                 "tonic_collector_synthetic_step: bad argument");
   char* base = static_cast<char*>(block);
   const size_t bytes = (size_t)h->W * h->O * sizeof(float);
-  memcpy(base + h->offset[TONIC_COLLECTOR_NEXT_OBSERVATIONS], next_observations, bytes);
   // A push collector's kernel reads the observation rows from its window: when this call issues the command
   // they go THERE first, the command follows, and the block's own copy (what the trainer is handed) is made
   // while the GPU is already at work.
   char* window = ring && __atomic_load_n(&h->armed, __ATOMIC_RELAXED) != 0 ? push_window_of(h) : nullptr;
-  if (window == nullptr) memcpy(base + h->offset[TONIC_COLLECTOR_OBSERVATIONS], next_observations, bytes);
   const float* a = actions != nullptr ? actions
                                       : reinterpret_cast<const float*>(base + h->offset[TONIC_COLLECTOR_ACTIONS]);
   float* rewards = reinterpret_cast<float*>(base + h->offset[TONIC_COLLECTOR_REWARDS]);
   const int A = h->A;
-  for (int64_t w = 0; w < h->W; ++w) {
-    float sum = 0.f;
-    for (int k = 0; k < A; ++k) sum += a[w * A + k] * a[w * A + k];
-    rewards[w] = -sum;
+  auto reward = [&](int64_t first, int64_t last) {
+    for (int64_t w = first; w < last; ++w) {
+      float sum = 0.f;
+      for (int k = 0; k < A; ++k) sum += a[w * A + k] * a[w * A + k];
+      rewards[w] = -sum;
+    }
+  };
+  char* next = base + h->offset[TONIC_COLLECTOR_NEXT_OBSERVATIONS];
+  const char* rows = reinterpret_cast<const char*>(next_observations);
+  if (window != nullptr) {
+    // Everything the kernel reads for this command, in chunks of 16 workers (one actor tile's rows: 64 * O
+    // bytes, whole lines of the window): a chunk's rows leave for the window first, and its rewards and its
+    // NEXT_OBSERVATIONS rows — ordinary cached work — are done while the write-combining buffers drain,
+    // instead of one field after the other with the drain at the end.
+    char* pushed = window + h->offset[TONIC_COLLECTOR_OBSERVATIONS];
+    const int64_t row_bytes = (int64_t)h->O * sizeof(float);
+    for (int64_t w = 0; w < h->W; w += 16) {
+      const int64_t last = w + 16 < h->W ? w + 16 : h->W;
+      memcpy(pushed + w * row_bytes, rows + w * row_bytes, (size_t)((last - w) * row_bytes));
+      reward(w, last);
+      memcpy(next + w * row_bytes, rows + w * row_bytes, (size_t)((last - w) * row_bytes));
+    }
+  } else {
+    memcpy(next, rows, bytes);
+    memcpy(base + h->offset[TONIC_COLLECTOR_OBSERVATIONS], rows, bytes);
+    reward(0, h->W);
   }
   // ring: the caller knows that the flags in the block are final too (nobody resets at this
   // step) -> the record is complete, the agent's armed command goes out from here
-  if (window != nullptr) memcpy(window + h->offset[TONIC_COLLECTOR_OBSERVATIONS], next_observations, bytes);
   if (ring) ring_armed(h, window != nullptr);
-  if (window != nullptr) memcpy(base + h->offset[TONIC_COLLECTOR_OBSERVATIONS], next_observations, bytes);
+  if (window != nullptr) memcpy(base + h->offset[TONIC_COLLECTOR_OBSERVATIONS], rows, bytes);
   return TONIC_OK;
 }
 
@@ -988,6 +1007,12 @@ extern "C" int tonic_collector_wait_actions(tonic_collector_t* c, double timeout
         return TONIC_ERR_TIMEOUT;
       }
     }
+  }
+  if (c->transport >= 2) {
+    // The actions came over PCIe: every line of them is a miss for whoever reads them first.  Asked for here,
+    // they travel while the interpreter returns to the caller and enters the environment.
+    const char* actions = reinterpret_cast<const char*>(c->host) + c->host->offset[TONIC_COLLECTOR_ACTIONS];
+    for (int64_t at = 0; at < c->W * c->A * 4; at += 64) _mm_prefetch(actions + at, _MM_HINT_T0);
   }
   c->waiting = false;
   c->q_words = 0;

@@ -122,8 +122,13 @@ class SyntheticBatch:
             next_observations = self._observe()
             np.copyto(block.next_observations, next_observations)
             np.copyto(block.observations, next_observations)
-            np.einsum('ij,ij->i', actions, actions, out=block.rewards, casting='same_kind')
-            np.negative(block.rewards, out=block.rewards)
+            # the reward of the host call above, bit for bit: float32 products added left to right (einsum
+            # sums in another order: the last bit of a reward then depended on which path a step took)
+            actions, rewards = np.asarray(actions), block.rewards
+            np.multiply(actions[:, 0], actions[:, 0], out=rewards, casting='same_kind')
+            for k in range(1, actions.shape[1]):
+                np.add(rewards, actions[:, k] * actions[:, k], out=rewards, casting='same_kind')
+            np.negative(rewards, out=rewards)
         if quiet:
             self._quiet += 1
             if self._flags_set:
