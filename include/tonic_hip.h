@@ -66,6 +66,7 @@ const char* tonic_last_error(void);
  * earlier entry keeps its signature), 20 = tonic_twin_distributional_q_grad / _workspace_bytes (TD4; additive),
  * 21 = tonic_q_regression_grad / tonic_q_regression_workspace_bytes (QRegression; additive),
  * 22 = tonic_tempered_twin_q_grad / tonic_tempered_actor_q_grad (SAC's learned entropy coefficient; additive)
+ * (still 22, purely additive: the tonic_priority_* entries and the tonic_weighted_* distributional critic steps — prioritized replay)
  * and the gfx target the kernels were built for.  TONIC_ABI_VERSION is what a binding was compiled against:
  * tonic_amd/_fastcall (csrc/fastcall.c) and tonic_amd/_lib.py compare it with the loaded library's answer. */
 #define TONIC_ABI_VERSION 22
@@ -1125,6 +1126,67 @@ int tonic_twin_distributional_q_grad(const float* d_target_actor, const float* d
                                      float* d_grad_sums, int32_t B, int32_t O, int32_t H, int32_t A,
                                      int32_t NA, double noise_scale, double noise_clip, void* d_workspace,
                                      int64_t workspace_bytes, void* stream);
+
+/* ---- prioritized replay (D4PG, TD4; added under ABI 22) --------------------------------------
+ *   The weighted critic steps: the entries of the same name without `weighted_` plus
+ *     d_weights        float32 [B] or NULL: a row's dlogits are scaled by w_m ahead of the backward pass, and the
+ *                      first statistic is sum_m w_m loss_m (TD4's q1 / q2 sums stay unweighted)
+ *     d_sample_losses  float32 [B] or NULL: receives the UNWEIGHTED row loss as the statistics sum it — loss_m for
+ *                      D4PG, loss_1 + loss_2 for TD4
+ *   Either may be NULL on its own; both NULL: the launches and the bits of the unweighted entry, which
+ *   runs the same body.  Status codes as there. */
+int tonic_weighted_distributional_q_grad(const float* d_target_actor, const float* d_target_critic,
+                                         const float* d_critic, const float* d_norm_mean,
+                                         const float* d_norm_std, double norm_clip,
+                                         const float* d_observations, const float* d_actions,
+                                         const float* d_next_observations, const float* d_rewards,
+                                         const float* d_discounts, const float* d_values, float* d_grad_sums,
+                                         int32_t B, int32_t O, int32_t H, int32_t A, int32_t NA,
+                                         const float* d_weights, float* d_sample_losses, void* d_workspace,
+                                         int64_t workspace_bytes, void* stream);
+int tonic_weighted_twin_distributional_q_grad(const float* d_target_actor, const float* d_target_critics,
+                                              const float* d_critics, const float* d_norm_mean,
+                                              const float* d_norm_std, double norm_clip,
+                                              const float* d_observations, const float* d_actions,
+                                              const float* d_next_observations, const float* d_rewards,
+                                              const float* d_discounts, const float* d_eps, const float* d_values,
+                                              float* d_grad_sums, int32_t B, int32_t O, int32_t H, int32_t A,
+                                              int32_t NA, double noise_scale, double noise_clip,
+                                              const float* d_weights, float* d_sample_losses, void* d_workspace,
+                                              int64_t workspace_bytes, void* stream);
+
+/*   The priority tree: one device block per replay of `capacity` transitions (csrc/priority.hip) —
+ *     [0, 64)       float32 max_leaf, the priority of a freshly stored transition; 1 after the init
+ *     level 0       float32 [pad64(capacity)], the leaves: (loss + epsilon)^alpha per flat transition index
+ *                   row * W + col, 0 for a slot never stored
+ *     level l >= 1  float64 [pad64(n_l)], n_l = ceil(n_{l-1} / 64): every node the sum of its 64 children in
+ *                   ASCENDING order, recomputed from them after a change (never adjusted by a difference: no drift,
+ *                   no atomics, the same inputs give the same bits)
+ *   The levels stop at the first one with <= 64 nodes; the total is the ascending sum of that level.  10^6
+ *   transitions: 4 MB of leaves, 128 KB of sums.  Every entry checks its arguments before anything touches the
+ *   device: -1 a NULL pointer, a block that is not 16-byte aligned, a capacity outside 1 .. 2^40, B <= 0, leaves outside the capacity, a negative or
+ *   non-finite alpha / beta / epsilon; -4 a block below the size query's answer.
+ *
+ *   The size query needs no GPU (0: a capacity outside 1 .. 2^40).  The init leaves every leaf and sum 0 and
+ *   max_leaf 1.  The store sets the leaves [first, first + count) to max_leaf (a freshly stored time row:
+ *   first = row * W, count = W) and recomputes their ancestors.
+ *   The sample: d_uniforms float64 [B] in [0, 1), drawn by the host; one wave per draw descends from the top level
+ *   with t = u * total: at each node the smallest child whose inclusive prefix sum exceeds t (strictly), t less
+ *   that child's exclusive prefix; where rounding leaves no such child, the last child with a non-zero value.  A
+ *   zero leaf is never returned (a tree without any priority answers index 0).  d_indices int64 [B];
+ *   d_weights float32 [B] or NULL: w_i = (min_j leaf_j / leaf_i)^beta, the minimum over the batch — the importance
+ *   weight (N P_i)^-beta over the batch's largest, in which N and the total cancel (one more launch).
+ *   The update: leaf[idx_m] = (loss_m + epsilon)^alpha, the HIGHEST batch position winning an index that occurs
+ *   more than once (an index outside the capacity is skipped), max_leaf = max(max_leaf, the leaves written), the
+ *   ancestors recomputed level by level by one workgroup: B <= 1024. */
+int64_t tonic_priority_tree_bytes(int64_t capacity);
+int tonic_priority_tree_init(void* d_tree, int64_t tree_bytes, int64_t capacity, void* stream);
+int tonic_priority_store(void* d_tree, int64_t tree_bytes, int64_t capacity, int64_t first, int64_t count,
+                         void* stream);
+int tonic_priority_sample(const void* d_tree, int64_t tree_bytes, int64_t capacity, const double* d_uniforms,
+                          int64_t* d_indices, float* d_weights, int32_t B, double beta, void* stream);
+int tonic_priority_update(void* d_tree, int64_t tree_bytes, int64_t capacity, const int64_t* d_indices,
+                          const float* d_sample_losses, int32_t B, double alpha, double epsilon, void* stream);
 
 /* ---- MPO (tonic/torch/agents/mpo.py): Gaussian policy head with a tanh loc and
  *   sigma = clamp(softplus(.), 1e-4, 1) (models/actors.py:69-98, two heads), ONE critic with

@@ -201,6 +201,16 @@ SIGNATURES = {
     'tonic_twin_distributional_workspace_bytes': (c_i64, [c_i32] * 5),
     'tonic_twin_distributional_q_grad': (ctypes.c_int, [c_vp] * 5 + [c_f64] + [c_vp] * 8 + [c_i32] * 5 +
                                          [c_f64] * 2 + [c_vp, c_i64, c_vp]),
+    # prioritized replay (D4PG, TD4; additive under ABI 22): `d_weights`, `d_sample_losses` ahead of the workspace
+    'tonic_weighted_distributional_q_grad': (ctypes.c_int, [c_vp] * 5 + [c_f64] + [c_vp] * 7 + [c_i32] * 5 +
+                                             [c_vp] * 2 + [c_vp, c_i64, c_vp]),
+    'tonic_weighted_twin_distributional_q_grad': (ctypes.c_int, [c_vp] * 5 + [c_f64] + [c_vp] * 8 + [c_i32] * 5 +
+                                                  [c_f64] * 2 + [c_vp] * 2 + [c_vp, c_i64, c_vp]),
+    'tonic_priority_tree_bytes': (c_i64, [c_i64]),
+    'tonic_priority_tree_init': (ctypes.c_int, [c_vp, c_i64, c_i64, c_vp]),
+    'tonic_priority_store': (ctypes.c_int, [c_vp, c_i64, c_i64, c_i64, c_i64, c_vp]),
+    'tonic_priority_sample': (ctypes.c_int, [c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_i32, c_f64, c_vp]),
+    'tonic_priority_update': (ctypes.c_int, [c_vp, c_i64, c_i64, c_vp, c_vp, c_i32, c_f64, c_f64, c_vp]),
     'tonic_mpo_workspace_bytes': (c_i64, [c_i32] * 5),
     'tonic_expected_sarsa_grad': (ctypes.c_int, [c_vp] * 5 + [c_f64] + [c_vp] * 7 + [c_i32] * 5 +
                                   [c_vp, c_i64, c_vp]),

@@ -353,9 +353,12 @@ __device__ __forceinline__ float wave_softmax(float logit, bool live, float* log
 //   critic's distribution (critics.py:32-46, restated with the same float32 expressions) ;
 //   loss = -sum_i targets_i log_softmax(logits)_i ; d loss / d logits_i = softmax_i sum_k targets_k - targets_i
 // (gradient of the SUM over the batch; the optimizer step divides by B).  loss_m: per-sample losses.
+// Prioritized replay: `weights` [B] scales a row's dlogits and its loss_m by w_m (the statistics then sum
+// w_m loss_m), `sample_losses` [B] receives the unweighted loss; each may be null, both null: the bits as before.
 __global__ __launch_bounds__(256) void distributional_critic_loss_kernel(
     const float* target_logits, const float* logits, int ld, const float* rewards,
-    const float* discounts, const float* values, int NA, float* dlogits, float* loss_m, int B) {
+    const float* discounts, const float* values, int NA, float* dlogits, float* loss_m, int B,
+    const float* weights, float* sample_losses) {
   const int lane = threadIdx.x & 63;
   const int m = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (m >= B) return;
@@ -380,8 +383,13 @@ __global__ __launch_bounds__(256) void distributional_critic_loss_kernel(
   const float p = wave_softmax(logit, live, &log_norm);
   const float total = wave_sum(target);
   const float loss = -wave_sum(live ? target * (logit - log_norm) : 0.f);
-  if (lane < ld) dlogits[(int64_t)m * ld + lane] = live ? p * total - target : 0.f;
-  if (lane == 0) loss_m[m] = loss;
+  float grad = live ? p * total - target : 0.f;
+  if (weights != nullptr) grad *= weights[m];
+  if (lane < ld) dlogits[(int64_t)m * ld + lane] = grad;
+  if (lane == 0) {
+    loss_m[m] = weights != nullptr ? weights[m] * loss : loss;
+    if (sample_losses != nullptr) sample_losses[m] = loss;
+  }
 }
 
 // TD4 (the library's TwinCriticDistributionalDeterministicQLearning): two target critics and two online critics over
@@ -391,10 +399,12 @@ __global__ __launch_bounds__(256) void distributional_critic_loss_kernel(
 // the selected p_next.  Each online critic takes the cross-entropy against the same target:
 //   d loss_k / d logits_k,i = softmax_k,i sum(T) - T_i ;  sample_m [3][Bp] = {loss_1 + loss_2, q1, q2} per sample,
 // q_k = sum_i softmax(logits_k)_i z_i the ONLINE critics' means (the logged critic/q1, critic/q2).
+// Prioritized replay: `weights` / `sample_losses` as in the kernel above — both dlogits and sample_m's first entry
+// take w_m, q1 / q2 do not; sample_losses receives loss_1 + loss_2.
 __global__ __launch_bounds__(256) void twin_distributional_critic_loss_kernel(
     const float* target_logits_1, const float* target_logits_2, const float* logits_1, const float* logits_2, int ld,
     const float* rewards, const float* discounts, const float* values, int NA, float* dlogits_1, float* dlogits_2,
-    float* sample_m, int B, int Bp) {
+    float* sample_m, int B, int Bp, const float* weights, float* sample_losses) {
   const int lane = threadIdx.x & 63;
   const int m = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (m >= B) return;
@@ -424,11 +434,17 @@ __global__ __launch_bounds__(256) void twin_distributional_critic_loss_kernel(
   const float loss_1 = -wave_sum(live ? target * (logit_1 - log_norm_1) : 0.f);
   const float loss_2 = -wave_sum(live ? target * (logit_2 - log_norm_2) : 0.f);
   const float q1 = wave_sum(live ? q1p * z : 0.f), q2 = wave_sum(live ? q2p * z : 0.f);
+  float grad_1 = live ? q1p * total - target : 0.f, grad_2 = live ? q2p * total - target : 0.f;
+  if (weights != nullptr) { grad_1 *= weights[m]; grad_2 *= weights[m]; }
   if (lane < ld) {
-    dlogits_1[(int64_t)m * ld + lane] = live ? q1p * total - target : 0.f;
-    dlogits_2[(int64_t)m * ld + lane] = live ? q2p * total - target : 0.f;
+    dlogits_1[(int64_t)m * ld + lane] = grad_1;
+    dlogits_2[(int64_t)m * ld + lane] = grad_2;
   }
-  if (lane == 0) { sample_m[m] = loss_1 + loss_2; sample_m[Bp + m] = q1; sample_m[2 * Bp + m] = q2; }
+  if (lane == 0) {
+    const float loss = loss_1 + loss_2;
+    sample_m[m] = weights != nullptr ? weights[m] * loss : loss; sample_m[Bp + m] = q1; sample_m[2 * Bp + m] = q2;
+    if (sample_losses != nullptr) sample_losses[m] = loss;
+  }
 }
 
 // the 8 statistics {sum loss_1 + loss_2, sum q1, sum q2, 0, 0, B, 0, 0} (the stats_kind 3 row) from the per-sample
@@ -2373,20 +2389,23 @@ extern "C" int64_t tonic_distributional_workspace_bytes(int32_t B, int32_t O, in
   return measure<DistributionalBuffers>(B, O, A, H, NA);
 }
 
-extern "C" int tonic_distributional_q_grad(
-    const float* d_target_actor, const float* d_target_critic, const float* d_critic,
+namespace {
+
+// tonic_distributional_q_grad and its weighted form (`what`: the entry's name in the messages): one body
+int distributional_q_grad(
+    const char* what, const float* d_target_actor, const float* d_target_critic, const float* d_critic,
     const float* d_norm_mean, const float* d_norm_std, double norm_clip,
     const float* d_observations, const float* d_actions, const float* d_next_observations,
     const float* d_rewards, const float* d_discounts, const float* d_values, float* d_grad_sums,
-    int32_t B, int32_t O, int32_t H, int32_t A, int32_t NA, void* d_workspace,
-    int64_t workspace_bytes, void* stream) {
+    int32_t B, int32_t O, int32_t H, int32_t A, int32_t NA, const float* d_weights, float* d_sample_losses,
+    void* d_workspace, int64_t workspace_bytes, void* stream) {
   TONIC_REQUIRE(d_target_actor && d_target_critic && d_critic && d_norm_mean && d_norm_std &&
                     d_observations && d_actions && d_next_observations && d_rewards &&
                     d_discounts && d_values && d_grad_sums && d_workspace && B > 0 && NA >= 2 &&
                     NA <= 64 && hidden_known(H),
-                TONIC_ERR_INVALID_ARGUMENT, "tonic_distributional_q_grad: bad argument (2 <= atoms <= 64)");
+                TONIC_ERR_INVALID_ARGUMENT, "%s: bad argument (2 <= atoms <= 64)", what);
   TONIC_REQUIRE(workspace_bytes >= tonic_distributional_workspace_bytes(B, O, A, H, NA),
-                TONIC_ERR_WORKSPACE, "tonic_distributional_q_grad: workspace too small");
+                TONIC_ERR_WORKSPACE, "%s: workspace too small", what);
   hipStream_t st = as_stream(stream);
   const int ldx = pitch16(O + A), ldh = pad16(A), ldl = pad16(NA);
   Workspace ws{static_cast<char*>(d_workspace), 0};
@@ -2405,13 +2424,42 @@ extern "C" int tonic_distributional_q_grad(
                     nullptr, nullptr, ldx));
   hipLaunchKernelGGL(distributional_critic_loss_kernel, dim3((B + 3) / 4), dim3(256), 0, st,
                      w.t_logits, w.logits, ldl, d_rewards, d_discounts, d_values, NA, w.dlogits,
-                     w.loss_m, B);
+                     w.loss_m, B, d_weights, d_sample_losses);
   hipLaunchKernelGGL(loss_stats_kernel, dim3(1), dim3(1024), 0, st, w.loss_m,
                      d_grad_sums + actor_count(cs), B);
   TRY(actor_shaped_backward(d_critic, cs, w.X2, ldx, B, w.c_h1, w.c_h2, w.dlogits, nullptr, ldl,
                             w.dz2, w.dz1, d_grad_sums, nullptr, 0, 0, st));
-  TONIC_CHECK_LAUNCH("tonic_distributional_q_grad");
+  TONIC_CHECK_LAUNCH(what);
   return TONIC_OK;
+}
+
+}  // namespace
+
+extern "C" int tonic_distributional_q_grad(
+    const float* d_target_actor, const float* d_target_critic, const float* d_critic,
+    const float* d_norm_mean, const float* d_norm_std, double norm_clip,
+    const float* d_observations, const float* d_actions, const float* d_next_observations,
+    const float* d_rewards, const float* d_discounts, const float* d_values, float* d_grad_sums,
+    int32_t B, int32_t O, int32_t H, int32_t A, int32_t NA, void* d_workspace,
+    int64_t workspace_bytes, void* stream) {
+  return distributional_q_grad("tonic_distributional_q_grad", d_target_actor, d_target_critic, d_critic, d_norm_mean,
+                               d_norm_std, norm_clip, d_observations, d_actions, d_next_observations, d_rewards,
+                               d_discounts, d_values, d_grad_sums, B, O, H, A, NA, nullptr, nullptr, d_workspace,
+                               workspace_bytes, stream);
+}
+
+// ... on a prioritized batch: the rows' importance weights in, the unweighted row losses out (each may be NULL)
+extern "C" int tonic_weighted_distributional_q_grad(
+    const float* d_target_actor, const float* d_target_critic, const float* d_critic,
+    const float* d_norm_mean, const float* d_norm_std, double norm_clip,
+    const float* d_observations, const float* d_actions, const float* d_next_observations,
+    const float* d_rewards, const float* d_discounts, const float* d_values, float* d_grad_sums,
+    int32_t B, int32_t O, int32_t H, int32_t A, int32_t NA, const float* d_weights, float* d_sample_losses,
+    void* d_workspace, int64_t workspace_bytes, void* stream) {
+  return distributional_q_grad("tonic_weighted_distributional_q_grad", d_target_actor, d_target_critic, d_critic,
+                               d_norm_mean, d_norm_std, norm_clip, d_observations, d_actions, d_next_observations,
+                               d_rewards, d_discounts, d_values, d_grad_sums, B, O, H, A, NA, d_weights,
+                               d_sample_losses, d_workspace, workspace_bytes, stream);
 }
 
 extern "C" int tonic_distributional_actor_grad(
@@ -2482,23 +2530,27 @@ extern "C" int64_t tonic_twin_distributional_workspace_bytes(int32_t B, int32_t 
   return measure<TwinDistributionalBuffers>(B, O, A, H, NA);
 }
 
-extern "C" int tonic_twin_distributional_q_grad(
-    const float* d_target_actor, const float* d_target_critics, const float* d_critics,
+namespace {
+
+// tonic_twin_distributional_q_grad and its weighted form (`what`: the entry's name in the messages): one body
+int twin_distributional_q_grad(
+    const char* what, const float* d_target_actor, const float* d_target_critics, const float* d_critics,
     const float* d_norm_mean, const float* d_norm_std, double norm_clip,
     const float* d_observations, const float* d_actions, const float* d_next_observations,
     const float* d_rewards, const float* d_discounts, const float* d_eps, const float* d_values,
     float* d_grad_sums, int32_t B, int32_t O, int32_t H, int32_t A, int32_t NA, double noise_scale,
-    double noise_clip, void* d_workspace, int64_t workspace_bytes, void* stream) {
+    double noise_clip, const float* d_weights, float* d_sample_losses, void* d_workspace, int64_t workspace_bytes,
+    void* stream) {
   TONIC_REQUIRE(d_target_actor && d_target_critics && d_critics && d_norm_mean && d_norm_std &&
                     d_observations && d_actions && d_next_observations && d_rewards &&
                     d_discounts && d_eps && d_values && d_grad_sums && d_workspace && B > 0 && NA >= 2 &&
                     NA <= 64 && hidden_known(H),
-                TONIC_ERR_INVALID_ARGUMENT, "tonic_twin_distributional_q_grad: bad argument (2 <= atoms <= 64)");
+                TONIC_ERR_INVALID_ARGUMENT, "%s: bad argument (2 <= atoms <= 64)", what);
   TONIC_REQUIRE(std::isfinite(noise_scale) && std::isfinite(noise_clip) && noise_scale >= 0 && noise_clip >= 0,
                 TONIC_ERR_INVALID_ARGUMENT,
-                "tonic_twin_distributional_q_grad: noise scale %g, clip %g (finite and >= 0)", noise_scale, noise_clip);
+                "%s: noise scale %g, clip %g (finite and >= 0)", what, noise_scale, noise_clip);
   TONIC_REQUIRE(workspace_bytes >= tonic_twin_distributional_workspace_bytes(B, O, A, H, NA),
-                TONIC_ERR_WORKSPACE, "tonic_twin_distributional_q_grad: workspace too small");
+                TONIC_ERR_WORKSPACE, "%s: workspace too small", what);
   hipStream_t st = as_stream(stream);
   const int Bp = pad16(B), ldx = pitch16(O + A), ldh = pad16(A), ldl = pad16(NA);
   Workspace ws{static_cast<char*>(d_workspace), 0};
@@ -2528,15 +2580,47 @@ extern "C" int tonic_twin_distributional_q_grad(
   // 4 + 5  the loss on the target distribution of the smaller mean, and the statistics behind both gradient blocks
   hipLaunchKernelGGL(twin_distributional_critic_loss_kernel, dim3((B + 3) / 4), dim3(256), 0, st, w1.t_logits,
                      w.t_logits, w1.logits, w.logits, ldl, d_rewards, d_discounts, d_values, NA, w1.dlogits, w.dlogits,
-                     w.sample_m, B, Bp);
+                     w.sample_m, B, Bp, d_weights, d_sample_losses);
   hipLaunchKernelGGL(twin_loss_stats_kernel, dim3(1), dim3(1024), 0, st, w.sample_m, d_grad_sums + 2 * Pc, B, Bp);
   // 6  each online critic's backward into its own block of the sums
   TRY(actor_shaped_backward(d_critics, cs, w1.X2, ldx, B, w1.c_h1, w1.c_h2, w1.dlogits, nullptr, ldl, w1.dz2, w1.dz1,
                             d_grad_sums, nullptr, 0, 0, st));
   TRY(actor_shaped_backward(d_critics + Pc, cs, w1.X2, ldx, B, w.c_h1, w.c_h2, w.dlogits, nullptr, ldl, w1.dz2,
                             w1.dz1, d_grad_sums + Pc, nullptr, 0, 0, st));
-  TONIC_CHECK_LAUNCH("tonic_twin_distributional_q_grad");
+  TONIC_CHECK_LAUNCH(what);
   return TONIC_OK;
+}
+
+}  // namespace
+
+extern "C" int tonic_twin_distributional_q_grad(
+    const float* d_target_actor, const float* d_target_critics, const float* d_critics,
+    const float* d_norm_mean, const float* d_norm_std, double norm_clip,
+    const float* d_observations, const float* d_actions, const float* d_next_observations,
+    const float* d_rewards, const float* d_discounts, const float* d_eps, const float* d_values,
+    float* d_grad_sums, int32_t B, int32_t O, int32_t H, int32_t A, int32_t NA, double noise_scale,
+    double noise_clip, void* d_workspace, int64_t workspace_bytes, void* stream) {
+  return twin_distributional_q_grad("tonic_twin_distributional_q_grad", d_target_actor, d_target_critics, d_critics,
+                                    d_norm_mean, d_norm_std, norm_clip, d_observations, d_actions,
+                                    d_next_observations, d_rewards, d_discounts, d_eps, d_values, d_grad_sums, B, O, H,
+                                    A, NA, noise_scale, noise_clip, nullptr, nullptr, d_workspace, workspace_bytes,
+                                    stream);
+}
+
+// ... on a prioritized batch: the rows' importance weights in, the unweighted loss_1 + loss_2 out (each may be NULL)
+extern "C" int tonic_weighted_twin_distributional_q_grad(
+    const float* d_target_actor, const float* d_target_critics, const float* d_critics,
+    const float* d_norm_mean, const float* d_norm_std, double norm_clip,
+    const float* d_observations, const float* d_actions, const float* d_next_observations,
+    const float* d_rewards, const float* d_discounts, const float* d_eps, const float* d_values,
+    float* d_grad_sums, int32_t B, int32_t O, int32_t H, int32_t A, int32_t NA, double noise_scale,
+    double noise_clip, const float* d_weights, float* d_sample_losses, void* d_workspace, int64_t workspace_bytes,
+    void* stream) {
+  return twin_distributional_q_grad("tonic_weighted_twin_distributional_q_grad", d_target_actor, d_target_critics,
+                                    d_critics, d_norm_mean, d_norm_std, norm_clip, d_observations, d_actions,
+                                    d_next_observations, d_rewards, d_discounts, d_eps, d_values, d_grad_sums, B, O, H,
+                                    A, NA, noise_scale, noise_clip, d_weights, d_sample_losses, d_workspace,
+                                    workspace_bytes, stream);
 }
 
 

@@ -119,12 +119,17 @@ class Slot:
     infos    float32 [2, iterations, INFO_WIDTH]: the critic's and the actor's statistics rows
     stats    float32 [iterations, width] or None: the agent's `_stats_width()` more per iteration (MPO; SAC with
              a learned entropy coefficient: the coefficient's statistics rows)
-    graph    the captured hipGraph; None: the next call through a graph captures"""
+    graph    the captured hipGraph; None: the next call through a graph captures
+    With a PrioritizedBuffer `indices` is an OUTPUT of the graph, and there are three more:
+    uniforms       float64 [iterations, B]: the host's draws, uploaded like `indices` otherwise
+    weights        float32 [iterations, B]: the batches' importance weights
+    sample_losses  float32 [iterations, B]: the rows' unweighted critic losses, the next priorities"""
 
-    __slots__ = ('key', 'indices', 'eps', 'adam', 'infos', 'stats', 'graph')
+    __slots__ = ('key', 'indices', 'eps', 'adam', 'infos', 'stats', 'graph', 'uniforms', 'weights', 'sample_losses')
 
     def __init__(self):
         self.key = self.indices = self.eps = self.adam = self.infos = self.stats = self.graph = None
+        self.uniforms = self.weights = self.sample_losses = None
 
 
 class QUpdate:
@@ -145,6 +150,12 @@ class QUpdate:
         self.slots = (Slot(), Slot())
         self.slot = self.slots[0]
         self.workspace, self.phased, self.mirror_valid = None, False, False
+
+    @property
+    def prioritized(self):
+        """The replay draws by priority: the split route in its prioritized form (`_issue_prioritized`)."""
+        from tonic_amd.replays import PrioritizedBuffer
+        return isinstance(self.agent.replay, PrioritizedBuffer)
 
     def route(self):
         """tonic_q_iteration serves the plain DDPG / TD3 / SAC updaters (`agent._FUSED`) with plain Adam, no
@@ -182,7 +193,7 @@ class QUpdate:
             self.slot = self.slots[0]
             infos = torch.cat(parts, dim=1).cpu().numpy()
         else:
-            indices = replay.sample_indices()
+            indices = replay.sample_uniforms() if self.prioritized else replay.sample_indices()
             eps = agent._draw_noise(indices.shape[0])
             infos = agent.enqueue_update(indices, eps).cpu().numpy()
             if self.slot.stats is not None:
@@ -202,8 +213,10 @@ class QUpdate:
         return infos, stats
 
     def enqueue(self, indices, eps, graph=None, route=None):
-        """`agent.enqueue_update`: shard, fill the current slot, issue the iterations or replay their graph."""
+        """`agent.enqueue_update`: shard, fill the current slot, issue the iterations or replay their graph.
+        With a PrioritizedBuffer `indices` are its uniforms (float64 [iterations, B])."""
         agent = self.agent
+        prioritized = self.prioritized
         iterations, global_batch = indices.shape
         agent._q.parameters_changed()
         counts = None
@@ -227,6 +240,8 @@ class QUpdate:
 
         def issue():
             slot.infos.zero_()
+            if prioritized:
+                return self._issue_prioritized(due)
             # the store does not change during an update: the batches of ALL its iterations are
             # gathered by one launch (the rows a rank does not own are padding, never read)
             batches = agent.replay.gather_many(slot.indices)
@@ -241,7 +256,7 @@ class QUpdate:
             issue()
         else:
             if slot.graph is None:
-                self._capture(slot, route, indices.shape[1], issue)
+                self._capture(slot, route, indices.shape[1], issue, gathers_many=not prioritized)
             slot.graph.replay()
         self.mirror_valid = route.fused_kind is not None and not route.phased
         return slot.infos
@@ -250,8 +265,10 @@ class QUpdate:
         agent, slot, iterations = self.agent, self.slot, indices.shape[0]
         # everything a captured graph bakes in: shapes, the replay's storage, the updaters'
         # hyper-parameters and schedules — a change of any of them re-captures
+        prioritized = self.prioritized
         key = (iterations, tuple(eps.shape), agent.replay.buffers['observations'].data_ptr(),
-               agent.replay.max_size, agent._graph_signature())
+               agent.replay.max_size, agent._graph_signature(),
+               agent.replay.graph_signature() if prioritized else None)
         if slot.key != key:
             from tonic_amd.torch.updaters import INFO_WIDTH      # (tonic_amd.torch imports this module)
             slot.key = key
@@ -259,11 +276,16 @@ class QUpdate:
             slot.eps = torch.zeros(eps.shape, dtype=torch.float32, device=agent.device)
             slot.infos = torch.zeros(2, iterations, INFO_WIDTH, device=agent.device)
             slot.graph = None
+            slot.uniforms = slot.weights = slot.sample_losses = None
+            if prioritized:
+                slot.uniforms = torch.zeros(indices.shape, dtype=torch.float64, device=agent.device)
+                slot.weights = torch.zeros(indices.shape, dtype=torch.float32, device=agent.device)
+                slot.sample_losses = torch.zeros(indices.shape, dtype=torch.float32, device=agent.device)
         width = agent._stats_width()
         if width and (slot.stats is None or tuple(slot.stats.shape) != (iterations, width)):
             slot.stats = torch.zeros(iterations, width, device=agent.device)
             slot.graph = None
-        slot.indices.copy_(torch.as_tensor(indices), non_blocking=True)
+        (slot.uniforms if prioritized else slot.indices).copy_(torch.as_tensor(indices), non_blocking=True)
         slot.eps.copy_(torch.as_tensor(eps), non_blocking=True)
         return slot
 
@@ -280,11 +302,12 @@ class QUpdate:
             slot.graph = None
         slot.adam.copy_(torch.as_tensor(table), non_blocking=True)
 
-    def _capture(self, slot, route, batch_size, issue):
+    def _capture(self, slot, route, batch_size, issue, gathers_many=True):
         agent = self.agent
         agent.critic_updater._offpolicy_workspace(batch_size)    # allocate outside the capture
         agent.actor_updater._offpolicy_workspace(batch_size)
-        agent.replay.gather_many(slot.indices)
+        if gathers_many:
+            agent.replay.gather_many(slot.indices)
         if route.fused_kind is not None:
             self._workspace_for(batch_size)
         torch.cuda.synchronize()
@@ -328,6 +351,21 @@ class QUpdate:
             if due[it]:
                 actor_eps = slot.eps[it, 1, :c * samples[1]] if c > 0 and draws > 1 else None
                 self._actor_step(batch['observations'] if c > 0 else None, actor_eps, it, n_global)
+
+    def _issue_prioritized(self, due):
+        """The split route on a PrioritizedBuffer (one rank): the batch of iteration k + 1 depends on the losses of
+        iteration k, so every iteration draws and gathers its own — sample -> single-batch gather -> weighted
+        critic step -> priority update -> actor step when due — all of it inside the captured graph."""
+        critic, slot, replay = self.agent.critic_updater, self.slot, self.agent.replay
+        draws = slot.eps.shape[1]
+        for it in range(len(due)):
+            replay.sample(slot.uniforms[it], slot.indices[it], slot.weights[it])
+            batch = replay.gather(slot.indices[it])
+            critic.enqueue(batch, slot.eps[it, 0], slot.infos[0, it], None, weights=slot.weights[it],
+                           sample_losses=slot.sample_losses[it])
+            replay.update_priorities(slot.indices[it], slot.sample_losses[it])
+            if due[it]:
+                self._actor_step(batch['observations'], slot.eps[it, 1] if draws > 1 else None, it, None)
 
     def _issue_phased(self, kind, batches, due, counts, global_batch):
         """An iteration as [policy passes + critic step + critics' weight gradients] -> exchange / clip + Adam

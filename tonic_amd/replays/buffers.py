@@ -184,3 +184,96 @@ class Buffer:
                 out = self.gather(device_indices, out)
             yield {k: out[k] for k in keys}
         self.last_steps = steps
+
+
+class PrioritizedBuffer(Buffer):
+    """Proportional prioritized replay (Schaul et al. 2016, the third part of D4PG): P_i = p_i / sum_j p_j with
+    p_i = (loss_i + epsilon)^alpha, importance weights w_i = (N P_i)^-beta over the batch's largest.  The
+    priorities live in a sum tree on the device (csrc/priority.hip, include/tonic_hip.h) next to the store: the
+    batch of iteration k + 1 depends on the losses of iteration k, so it is drawn there, between the critic steps,
+    from uniforms the host drew ahead (`sample_uniforms`, the only host stream).  A stored row starts at the
+    largest priority seen so far, a wrapped-around row again.  `alpha`, `beta`, `epsilon` are fixed for the
+    lifetime (a captured update graph bakes them in).  One rank only; the priorities are not checkpointed."""
+
+    def __init__(self, size=int(1e6), return_steps=1, batch_iterations=50, batch_size=100,
+                 discount_factor=0.99, steps_before_batches=int(1e4), steps_between_batches=50,
+                 alpha=0.6, beta=0.4, epsilon=1e-6):
+        super().__init__(size, return_steps, batch_iterations, batch_size, discount_factor, steps_before_batches,
+                         steps_between_batches)
+        for name, value in (('alpha', alpha), ('beta', beta), ('epsilon', epsilon)):
+            if not (np.isfinite(value) and value >= 0):
+                raise ValueError(f'PrioritizedBuffer: {name} = {value!r} (finite and >= 0)')
+        if not 0 < batch_size <= 1024:
+            raise ValueError(f'PrioritizedBuffer: batch_size = {batch_size!r} (1 .. 1024: one workgroup recomputes '
+                             'the sums above a batch\'s leaves)')
+        self.alpha, self.beta, self.epsilon = float(alpha), float(beta), float(epsilon)
+
+    def initialize(self, seed=None, device=None):
+        if parallel.world_size() > 1:
+            raise NotImplementedError(
+                f'PrioritizedBuffer on {parallel.world_size()} ranks is not served: the shards of the store would '
+                'need one global priority tree (use Buffer)')
+        super().initialize(seed, device)
+        self.tree = None
+
+    def _allocate(self, num_workers, observation_size, action_size):
+        super()._allocate(num_workers, observation_size, action_size)
+        self.capacity = self.max_size * num_workers
+        self.tree = torch.empty(self.lib.tonic_priority_tree_bytes(self.capacity), dtype=torch.uint8,
+                                device=self.device)
+        _lib.check(self.lib.tonic_priority_tree_init(_lib.ptr(self.tree), self.tree.numel(), self.capacity,
+                                                     _lib.current_stream()), 'tonic_priority_tree_init')
+        self._drawn = (torch.zeros(self.batch_size, dtype=torch.float64, device=self.device),
+                       torch.zeros(self.batch_size, dtype=torch.int64, device=self.device),
+                       torch.zeros(self.batch_size, dtype=torch.float32, device=self.device))
+
+    def _take_row(self, normalizer):
+        """... and the row's leaves set to the largest priority so far (a reserved row, whose data write rides in
+        the acting launch, too: nothing samples before the update that follows both)."""
+        row = super()._take_row(normalizer)
+        _lib.check(self.lib.tonic_priority_store(_lib.ptr(self.tree), self.tree.numel(), self.capacity,
+                                                 row * self.num_workers, self.num_workers, _lib.current_stream()),
+                   'tonic_priority_store')
+        return row
+
+    def graph_signature(self):
+        """What a captured update graph bakes in of this replay."""
+        return (self.alpha, self.beta, self.epsilon, self.tree.data_ptr() if self.tree is not None else 0)
+
+    def sample_uniforms(self, iterations=None):
+        """The uniform stream of `iterations` successive batches, float64 [iterations, B] in [0, 1): drawn where
+        Buffer.sample_indices draws, ahead of the update that turns them into indices on the device."""
+        count = self.batch_iterations if iterations is None else iterations
+        return self.np_random.random_sample((count, self.batch_size))
+
+    def sample(self, uniforms, indices, weights=None):
+        """One batch's draw on the device: float64 uniforms [B] -> int64 `indices` [B] and, when given, float32
+        `weights` [B] (tonic_priority_sample)."""
+        _lib.check(self.lib.tonic_priority_sample(
+            _lib.ptr(self.tree), self.tree.numel(), self.capacity, _lib.ptr(uniforms), _lib.ptr(indices),
+            _lib.ptr(weights), uniforms.shape[0], self.beta, _lib.current_stream()), 'tonic_priority_sample')
+
+    def update_priorities(self, indices, sample_losses):
+        """Closes the loop: the drawn transitions' priorities from their (unweighted) losses, device tensors [B]
+        (tonic_priority_update)."""
+        _lib.check(self.lib.tonic_priority_update(
+            _lib.ptr(self.tree), self.tree.numel(), self.capacity, _lib.ptr(indices), _lib.ptr(sample_losses),
+            indices.shape[0], self.alpha, self.epsilon, _lib.current_stream()), 'tonic_priority_update')
+
+    def sample_indices(self, iterations=None):
+        raise NotImplementedError('PrioritizedBuffer draws its indices on the device from `sample_uniforms` '
+                                  '(`sample`): there is no host index stream')
+
+    def get(self, *keys, steps):
+        """The generator API for custom agents: batches drawn by priority; `keys` may name 'indices' and 'weights'
+        besides the stored fields, and `update_priorities(batch['indices'], losses)` between two batches moves the
+        priorities the next one is drawn from."""
+        uniforms, indices, weights = self._drawn
+        for _ in range(self.batch_iterations):
+            uniforms.copy_(torch.as_tensor(self.sample_uniforms(1)[0]))
+            self.sample(uniforms, indices, weights)
+            out = {k: torch.empty_like(v) for k, v in self.batch.items()}
+            out = self.gather(indices, out)
+            out['indices'], out['weights'] = indices.clone(), weights.clone()
+            yield {k: out[k] for k in keys}
+        self.last_steps = steps

@@ -1252,7 +1252,16 @@ class DDPG(Agent):
         self.actor_updater = actor_updater or updaters.DeterministicPolicyGradient()
         self.critic_updater = critic_updater or updaters.DeterministicQLearning()
 
+    # the critic updaters whose steps take a prioritized batch's weights and return its rows' losses
+    _PRIORITIZED = (updaters.DistributionalDeterministicQLearning,
+                    updaters.TwinCriticDistributionalDeterministicQLearning)
+
     def initialize(self, observation_space, action_space, seed=None):
+        if isinstance(self.replay, replays.PrioritizedBuffer) and type(self.critic_updater) not in self._PRIORITIZED:
+            raise NotImplementedError(
+                f'PrioritizedBuffer with the critic updater {type(self.critic_updater).__name__} is not served: the '
+                f'weighted critic steps are those of {" and ".join(c.__name__ for c in self._PRIORITIZED)} '
+                '(D4PG, TD4)')
         super().initialize(seed=seed)
         self.device = _device()
         if not getattr(self, '_holds_affinity', False):
@@ -1402,7 +1411,8 @@ class DDPG(Agent):
 
     def enqueue_update(self, indices, eps, graph=None):
         """Enqueues `indices.shape[0]` learner iterations (no host sync).  indices: int64
-        [iterations, B] host array; eps: float32 [iterations, draws, B, A] host array with the
+        [iterations, B] host array (with a PrioritizedBuffer: its `sample_uniforms`, float64 [iterations, B] — the
+        indices are drawn on the device between the critic steps); eps: float32 [iterations, draws, B, A] host array with the
         standard-normal draws in the order the reference consumes them.  With `graph` (default:
         on unless TONIC_AMD_NO_GRAPH=1) the launch sequence — gather, the fused forward / backward /
         grouped weight-gradient launches, Adam + polyak: 13 per SAC iteration — is captured once into a hipGraph

@@ -1436,18 +1436,22 @@ class DistributionalDeterministicQLearning(_TwinCriticQLearning):
             raise NotImplementedError('DistributionalDeterministicQLearning needs a critic with a '
                                       'DistributionalValueHead')
 
-    def enqueue(self, batch, eps, info_row, n_global=None):
+    def enqueue(self, batch, eps, info_row, n_global=None, weights=None, sample_losses=None):
+        """weights / sample_losses: float32 [B] device tensors of a prioritized batch — the rows' importance weights
+        in, their unweighted losses out (tonic_weighted_distributional_q_grad); without them the plain entry."""
         B = batch['observations'].shape[0]
         ws = self._offpolicy_workspace(B)
         mean, std = self.norm_tensors()
         p = _lib.ptr
-        _lib.check(self.lib.tonic_distributional_q_grad(
+        weighted = weights is not None or sample_losses is not None
+        entry = 'tonic_weighted_distributional_q_grad' if weighted else 'tonic_distributional_q_grad'
+        _lib.check(getattr(self.lib, entry)(
             p(self.model.flat_target_actor.flat), p(self.model.flat_target_critics.flat),
             p(self.flat.flat), p(mean), p(std), self.norm_clip(), p(batch['observations']),
             p(batch['actions']), p(batch['next_observations']), p(batch['rewards']),
             p(batch['discounts']), p(self.target_values), p(self.grad_sums), B, self.observation_size,
-            self.hidden, self.action_size, self.atoms, p(ws), ws.numel(), _lib.current_stream()),
-            'tonic_distributional_q_grad')
+            self.hidden, self.action_size, self.atoms, *((p(weights), p(sample_losses)) if weighted else ()),
+            p(ws), ws.numel(), _lib.current_stream()), entry)
         self._step(n_global or B * self.world_size, info_row)
 
     def __call__(self, observations, actions, next_observations, rewards, discounts):
@@ -1495,19 +1499,24 @@ class TwinCriticDistributionalDeterministicQLearning(_TwinCriticQLearning):
             self.workspace = torch.empty(need, dtype=torch.uint8, device=self.grad_sums.device)
         return self.workspace
 
-    def enqueue(self, batch, eps, info_row, n_global=None):
-        """eps: the [B, A] standard-normal draw of the target-action noise."""
+    def enqueue(self, batch, eps, info_row, n_global=None, weights=None, sample_losses=None):
+        """eps: the [B, A] standard-normal draw of the target-action noise.  weights / sample_losses: float32 [B]
+        device tensors of a prioritized batch — the rows' importance weights in, their unweighted loss_1 + loss_2
+        out (tonic_weighted_twin_distributional_q_grad); without them the plain entry."""
         B = batch['observations'].shape[0]
         ws = self._offpolicy_workspace(B)
         mean, std = self.norm_tensors()
         noise = self.target_action_noise
         p = _lib.ptr
-        _lib.check(self.lib.tonic_twin_distributional_q_grad(
+        weighted = weights is not None or sample_losses is not None
+        entry = 'tonic_weighted_twin_distributional_q_grad' if weighted else 'tonic_twin_distributional_q_grad'
+        _lib.check(getattr(self.lib, entry)(
             p(self._policy_params()), p(self.model.flat_target_critics.flat), p(self.flat.flat), p(mean), p(std),
             self.norm_clip(), p(batch['observations']), p(batch['actions']), p(batch['next_observations']),
             p(batch['rewards']), p(batch['discounts']), p(eps), p(self.values), p(self.grad_sums), B,
             self.observation_size, self.hidden, self.action_size, self.atoms, float(noise.scale), float(noise.clip),
-            p(ws), ws.numel(), _lib.current_stream()), 'tonic_twin_distributional_q_grad')
+            *((p(weights), p(sample_losses)) if weighted else ()),
+            p(ws), ws.numel(), _lib.current_stream()), entry)
         self._step(n_global or B * self.world_size, info_row)
 
 
