@@ -2,6 +2,8 @@
 
     python scripts/td4_timing.py [--out profiles/td4_timing.json] [--repeats 7]
 
+(PROBE_LIBRARY=<a libtonic_hip.so>: that build of the library, as in scripts/offpolicy_entry_bits.py.)
+
 B = 256, O = 17, A = 6, the agents' default (256, 256) ReLU torsos, 51 atoms, 50 iterations per update call, a full
 HBM Buffer of synthetic transitions (as scripts/offpolicy_torso_rate.py fills it).
 
@@ -25,6 +27,10 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from tonic_amd import _lib   # noqa: E402
+
+if os.environ.get('PROBE_LIBRARY'):            # a variant build of the library (developer)
+    _lib.LIBRARY_PATH = os.environ['PROBE_LIBRARY']
 
 O, A, B, ITERATIONS, ROWS, CALLS, ENTRY_CALLS = 17, 6, 256, 50, 100000, 4, 200
 

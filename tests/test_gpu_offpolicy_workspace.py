@@ -73,6 +73,11 @@ class Data:
         self.mean, self.std = rand(O) * 0.1, 1.0 + rand(O).abs() * 0.1
         self.low, self.high = torch.tensor([-3.0]).cuda(), torch.tensor([4.0]).cuda()
         self.values = torch.linspace(-10.0, 10.0, max(atoms, 2)).cuda()
+        # importance weights > 0 and SAC's log entropy coefficient, from a generator of their own: `gen` goes on to draw
+        # the networks, which keep their values
+        more = torch.Generator().manual_seed(B * 1000 + O * 100 + A + 7)
+        self.weights = (torch.rand(B, generator=more) + 0.1).cuda()
+        self.log_coeff = (torch.randn(1, generator=more) * 0.5 - 1.0).cuda()
 
 
 def guarded(need):
@@ -122,15 +127,67 @@ def actor_q(lib, p, kind, torso, B, O, A, ranged):
     return status, {'grad_sums': out}, ws, need
 
 
-def distributional_q(lib, p, torso, B, O, A, NA):
+def tempered_twin_q(lib, p, torso, B, O, A, ranged):
+    d = Data(lib, torso, B, O, A)
+    policy, targets, critics = d.actor(2), d.critics(2), d.critics(2)
+    need = lib.tonic_offpolicy_workspace_bytes(B, O, A, d.H)
+    ws, out = guarded(need), zeros(critics.numel() + 8)
+    status = lib.tonic_tempered_twin_q_grad(
+        1, p(policy), p(targets), p(critics), p(d.mean), p(d.std), 5.0, p(d.obs), p(d.actions), p(d.next_obs),
+        p(d.rewards), p(d.discounts), p(d.eps), p(out), B, O, d.H, A, 0.2, 0.2, 0.5, None,
+        p(d.low) if ranged else None, p(d.high) if ranged else None, p(d.log_coeff), p(ws), need, None)
+    return status, {'grad_sums': out}, ws, need
+
+
+def tempered_actor_q(lib, p, torso, B, O, A, ranged):
+    d = Data(lib, torso, B, O, A)
+    actor, critics = d.actor(2), d.critics(2)
+    need = lib.tonic_offpolicy_workspace_bytes(B, O, A, d.H)
+    ws, out, coeff_sums = guarded(need), zeros(actor.numel() + 8), zeros(1 + 8)
+    status = lib.tonic_tempered_actor_q_grad(
+        1, p(actor), p(critics), p(d.mean), p(d.std), 5.0, p(d.obs), p(d.eps), p(out), B, O, d.H, A, 0.2,
+        p(d.low) if ranged else None, p(d.high) if ranged else None, p(d.log_coeff), p(coeff_sums), -float(A), p(ws),
+        need, None)
+    return status, {'grad_sums': out, 'entropy_coeff_sums': coeff_sums}, ws, need
+
+
+def q_regression(lib, p, torso, B, O, A, ranged):
+    d = Data(lib, torso, B, O, A)
+    critic = d.critics(1)
+    need = lib.tonic_q_regression_workspace_bytes(B, O, A, d.H)
+    ws, out = guarded(need), zeros(critic.numel() + 8)
+    status = lib.tonic_q_regression_grad(
+        p(critic), p(d.mean), p(d.std), 5.0, p(d.obs), p(d.actions), p(d.rewards), p(out), B, O, d.H, A, None,
+        p(d.low) if ranged else None, p(d.high) if ranged else None, p(ws), need, None)
+    return status, {'grad_sums': out}, ws, need
+
+
+def distributional_q(lib, p, torso, B, O, A, NA, weighted=False):
     d = Data(lib, torso, B, O, A, atoms=NA)
     target_actor, target_critic, critic = d.actor(1), d.critics(1, NA), d.critics(1, NA)
     need = lib.tonic_distributional_workspace_bytes(B, O, A, d.H, NA)
     ws, out = guarded(need), zeros(critic.numel() + 8)
-    status = lib.tonic_distributional_q_grad(
-        p(target_actor), p(target_critic), p(critic), p(d.mean), p(d.std), 5.0, p(d.obs), p(d.actions), p(d.next_obs),
-        p(d.rewards), p(d.discounts), p(d.values), p(out), B, O, d.H, A, NA, p(ws), need, None)
-    return status, {'grad_sums': out}, ws, need
+    head = [p(target_actor), p(target_critic), p(critic), p(d.mean), p(d.std), 5.0, p(d.obs), p(d.actions),
+            p(d.next_obs), p(d.rewards), p(d.discounts), p(d.values), p(out), B, O, d.H, A, NA]
+    if not weighted:
+        return lib.tonic_distributional_q_grad(*head, p(ws), need, None), {'grad_sums': out}, ws, need
+    losses = zeros(B)
+    status = lib.tonic_weighted_distributional_q_grad(*head, p(d.weights), p(losses), p(ws), need, None)
+    return status, {'grad_sums': out, 'sample_losses': losses}, ws, need
+
+
+def twin_distributional_q(lib, p, torso, B, O, A, NA, weighted=False):
+    d = Data(lib, torso, B, O, A, atoms=NA)
+    target_actor, target_critics, critics = d.actor(1), d.critics(2, NA), d.critics(2, NA)
+    need = lib.tonic_twin_distributional_workspace_bytes(B, O, A, d.H, NA)
+    ws, out = guarded(need), zeros(critics.numel() + 8)
+    head = [p(target_actor), p(target_critics), p(critics), p(d.mean), p(d.std), 5.0, p(d.obs), p(d.actions),
+            p(d.next_obs), p(d.rewards), p(d.discounts), p(d.eps), p(d.values), p(out), B, O, d.H, A, NA, 0.2, 0.5]
+    if not weighted:
+        return lib.tonic_twin_distributional_q_grad(*head, p(ws), need, None), {'grad_sums': out}, ws, need
+    losses = zeros(B)
+    status = lib.tonic_weighted_twin_distributional_q_grad(*head, p(d.weights), p(losses), p(ws), need, None)
+    return status, {'grad_sums': out, 'sample_losses': losses}, ws, need
 
 
 def distributional_actor(lib, p, torso, B, O, A, NA):
@@ -218,15 +275,26 @@ def _cases():
                 add(twin_q, kind=kind, ranged=ranged, **shape)
                 if kind < 2:
                     add(actor_q, kind=kind, ranged=ranged, **shape)
+        for ranged in (False, True):
+            add(q_regression, ranged=ranged, **shape)
+            add(tempered_twin_q, ranged=ranged, **shape)
+            add(tempered_actor_q, ranged=ranged, **shape)
     for torso in TORSOS:
         shape = dict(torso=torso, B=17, O=3, A=17)
-        for NA in (2, 51):
+        for NA in (2, 51, 64):                  # 2: a row of 2 in a pitch of 16; 64: lane 63 is the last atom
             add(distributional_q, NA=NA, **shape)
+            add(distributional_q, NA=NA, weighted=True, **shape)
+            add(twin_distributional_q, NA=NA, **shape)
+            add(twin_distributional_q, NA=NA, weighted=True, **shape)
             add(distributional_actor, NA=NA, **shape)
         for S in (1, 65):                       # 65: two register slots in the state kernel
             add(expected_sarsa, S=S, **shape)
             for joint_kl, shard in itertools.product((0, 1), (False, True)):
                 add(mpo_actor, S=S, joint_kl=joint_kl, shard=shard, **shape)
+    for B in (1, 5):                            # the loss kernels place 4 samples per block: a lone wave, a ragged block
+        shape = dict(torso='plain64', B=B, O=3, A=17, NA=51)
+        for function, weighted in itertools.product((distributional_q, twin_distributional_q), (False, True)):
+            add(function, weighted=weighted, **shape)
     for kind, due, slot in itertools.product((0, 1, 2), (0, 1), (0, 1)):
         add(q_iteration, kind=kind, due=due, slot=slot)
     return cases

@@ -221,8 +221,9 @@ def test_projection_edges_vs_float64(lib):
 
 def test_identical_twins_without_noise_are_two_d4pg_steps(lib):
     """critic_2 := critic_1, target_critic_2 := target_critic_1 and noise scale 0: each critic block of the sums
-    equals tonic_distributional_q_grad's sums for that critic to 1e-5 of the largest element, the loss sum is twice
-    D4PG's (the equal means select critic 1: no precondition is needed, both choices are the same numbers)."""
+    equals tonic_distributional_q_grad's sums for that critic bit for bit (one statement of the arithmetic serves
+    both entries; a + clamp(0 * eps) is a), the loss sum is twice D4PG's (the equal means select critic 1: no
+    precondition is needed, both choices are the same numbers)."""
     O, A, B, NA, sizes = 17, 6, 37, 51, (32, 32)
     twin = _agent(O, A, sizes, 'ReLU', B, NA, noise=(0.0, 0.5))
     single = _agent(O, A, sizes, 'ReLU', B, NA, twin=False)
@@ -244,10 +245,9 @@ def test_identical_twins_without_noise_are_two_d4pg_steps(lib):
     want = single.critic_updater.grad_sums
     count = single.critic_updater.count
     assert twin.critic_updater.count == 2 * count
-    scale = float(want[:count].abs().max())
     for block in (0, 1):
-        diff = float((got[block * count:(block + 1) * count] - want[:count]).abs().max())
-        assert diff <= 1e-5 * scale, (block, diff, scale)
+        mine = got[block * count:(block + 1) * count]
+        assert torch.equal(mine, want[:count]), (block, float((mine - want[:count]).abs().max()))
     stats, d4pg = got[2 * count:].cpu().numpy(), want[count:].cpu().numpy()
     assert stats[5] == d4pg[5] == B
     np.testing.assert_allclose(stats[0], 2 * d4pg[0], rtol=1e-5)

@@ -348,28 +348,28 @@ __device__ __forceinline__ float wave_softmax(float logit, bool live, float* log
   return e / sum;
 }
 
-// DistributionalDeterministicQLearning (critics.py:100-122):
-//   returns_j = r + disc * z_j ; targets = CategoricalWithSupport.project(returns) of the TARGET
-//   critic's distribution (critics.py:32-46, restated with the same float32 expressions) ;
-//   loss = -sum_i targets_i log_softmax(logits)_i ; d loss / d logits_i = softmax_i sum_k targets_k - targets_i
-// (gradient of the SUM over the batch; the optimizer step divides by B).  loss_m: per-sample losses.
-// Prioritized replay: `weights` [B] scales a row's dlogits and its loss_m by w_m (the statistics then sum
-// w_m loss_m), `sample_losses` [B] receives the unweighted loss; each may be null, both null: the bits as before.
-__global__ __launch_bounds__(256) void distributional_critic_loss_kernel(
-    const float* target_logits, const float* logits, int ld, const float* rewards,
-    const float* discounts, const float* values, int NA, float* dlogits, float* loss_m, int B,
-    const float* weights, float* sample_losses) {
-  const int lane = threadIdx.x & 63;
-  const int m = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  if (m >= B) return;
-  const bool live = lane < NA;
-  const int i = live ? lane : NA - 1;
-  const float z = values[i], vmin = values[0], vmax = values[NA - 1];
-  const float p_next = wave_softmax(target_logits[(int64_t)m * ld + i], live, nullptr);
-  const float ret = rewards[m] + discounts[m] * z;
+// The wave's row of a [B, ld] logits array: sample m, lane = atom; a lane past the support reads atom NA - 1 and is
+// not `live`.  False: no row for this wave (the ragged last workgroup).
+struct AtomRow { int lane, m, i; bool live; float z; };
+__device__ __forceinline__ bool atom_row(const float* values, int NA, int B, AtomRow& r) {
+  r.lane = threadIdx.x & 63;
+  r.m = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (r.m >= B) return false;
+  r.live = r.lane < NA;
+  r.i = r.live ? r.lane : NA - 1;
+  r.z = values[r.i];
+  return true;
+}
+
+// CategoricalWithSupport.project (critics.py:32-46, restated with the same float32 expressions): atom i's share of
+// the distribution p_next (lane = atom) moved to the returns r + disc * z_j; 0 on a lane that is not live.
+__device__ __forceinline__ float projected_target(const AtomRow& r, const float* values, int NA, float reward,
+                                                  float discount, float p_next) {
+  const float z = r.z, vmin = values[0], vmax = values[NA - 1];
+  const float ret = reward + discount * z;
   const float clipped = fminf(fmaxf(ret, vmin), vmax);
-  const float d_pos = (i + 1 < NA ? values[i + 1] : vmin) - z;      // critics.py:34-35
-  const float d_neg = z - (i > 0 ? values[i - 1] : vmax);           // critics.py:36-37
+  const float d_pos = (r.i + 1 < NA ? values[r.i + 1] : vmin) - z;  // critics.py:34-35
+  const float d_neg = z - (r.i > 0 ? values[r.i - 1] : vmax);       // critics.py:36-37
   float target = 0.f;
   for (int j = 0; j < NA; ++j) {
     const float delta = __shfl(clipped, j, 64) - z;                 // critics.py:40
@@ -377,73 +377,81 @@ __global__ __launch_bounds__(256) void distributional_critic_loss_kernel(
     const float hat = (sign * delta / d_pos) - ((1.f - sign) * delta / d_neg);
     target += fminf(fmaxf(1.f - hat, 0.f), 1.f) * __shfl(p_next, j, 64);
   }
-  if (!live) target = 0.f;
+  return r.live ? target : 0.f;
+}
+
+// One online critic (its logit on this lane) against the row's target T (total = sum_i T_i): the softmax,
+// loss = -sum_i T_i log_softmax(logits)_i and grad = d loss / d logits_i = softmax_i total - T_i (0 on a padded lane).
+// No memory access: the kernels load before and store after, so that no store stands between two critics' loads.
+struct CriticRow { float p, loss, grad; };
+__device__ __forceinline__ CriticRow critic_row(const AtomRow& r, float logit, float target, float total) {
   float log_norm;
-  const float logit = logits[(int64_t)m * ld + i];
-  const float p = wave_softmax(logit, live, &log_norm);
-  const float total = wave_sum(target);
-  const float loss = -wave_sum(live ? target * (logit - log_norm) : 0.f);
-  float grad = live ? p * total - target : 0.f;
-  if (weights != nullptr) grad *= weights[m];
-  if (lane < ld) dlogits[(int64_t)m * ld + lane] = grad;
-  if (lane == 0) {
-    loss_m[m] = weights != nullptr ? weights[m] * loss : loss;
-    if (sample_losses != nullptr) sample_losses[m] = loss;
-  }
+  const float p = wave_softmax(logit, r.live, &log_norm);
+  const float loss = -wave_sum(r.live ? target * (logit - log_norm) : 0.f);
+  return CriticRow{p, loss, r.live ? p * total - target : 0.f};
+}
+
+// Prioritized replay: `weights` [B] scales a row's dlogits (in the kernels) and, here on lane 0, its loss_m — the
+// statistics then sum w_m loss_m — and `sample_losses` [B] receives the unweighted loss; each may be null, both null:
+// the bits as before.
+__device__ __forceinline__ void store_row_loss(int m, float loss, const float* weights, float* loss_m,
+                                               float* sample_losses) {
+  loss_m[m] = weights != nullptr ? weights[m] * loss : loss;
+  if (sample_losses != nullptr) sample_losses[m] = loss;
+}
+
+// DistributionalDeterministicQLearning (critics.py:100-122):
+//   returns_j = r + disc * z_j ; targets = CategoricalWithSupport.project(returns) of the TARGET
+//   critic's distribution ;
+//   loss = -sum_i targets_i log_softmax(logits)_i ; d loss / d logits_i = softmax_i sum_k targets_k - targets_i
+// (gradient of the SUM over the batch; the optimizer step divides by B).  loss_m: per-sample losses.
+__global__ __launch_bounds__(256) void distributional_critic_loss_kernel(
+    const float* target_logits, const float* logits, int ld, const float* rewards,
+    const float* discounts, const float* values, int NA, float* dlogits, float* loss_m, int B,
+    const float* weights, float* sample_losses) {
+  AtomRow r;
+  if (!atom_row(values, NA, B, r)) return;
+  const float p_next = wave_softmax(target_logits[(int64_t)r.m * ld + r.i], r.live, nullptr);
+  const float target = projected_target(r, values, NA, rewards[r.m], discounts[r.m], p_next);
+  const CriticRow c = critic_row(r, logits[(int64_t)r.m * ld + r.i], target, wave_sum(target));
+  float grad = c.grad;
+  if (weights != nullptr) grad *= weights[r.m];
+  if (r.lane < ld) dlogits[(int64_t)r.m * ld + r.lane] = grad;
+  if (r.lane == 0) store_row_loss(r.m, c.loss, weights, loss_m, sample_losses);
 }
 
 // TD4 (the library's TwinCriticDistributionalDeterministicQLearning): two target critics and two online critics over
 // ONE support.  p_k = softmax(target_logits_k), mu_k = sum_i p_k,i z_i; the row's target distribution is that of the
 // target critic with the smaller mean — critic 2 only when mu_2 < mu_1, so a tie and a NaN mean select critic 1 —
 // projected as above.  The triangular weights depend on the returns and the support alone, so the loop runs once, on
-// the selected p_next.  Each online critic takes the cross-entropy against the same target:
-//   d loss_k / d logits_k,i = softmax_k,i sum(T) - T_i ;  sample_m [3][Bp] = {loss_1 + loss_2, q1, q2} per sample,
-// q_k = sum_i softmax(logits_k)_i z_i the ONLINE critics' means (the logged critic/q1, critic/q2).
-// Prioritized replay: `weights` / `sample_losses` as in the kernel above — both dlogits and sample_m's first entry
-// take w_m, q1 / q2 do not; sample_losses receives loss_1 + loss_2.
+// the selected p_next.  Each online critic takes the cross-entropy against the same target;
+// sample_m [3][Bp] = {loss_1 + loss_2, q1, q2} per sample, q_k = sum_i softmax(logits_k)_i z_i the ONLINE critics'
+// means (the logged critic/q1, critic/q2).  Prioritized replay: both dlogits and sample_m's first entry take w_m,
+// q1 / q2 do not; sample_losses receives loss_1 + loss_2.
 __global__ __launch_bounds__(256) void twin_distributional_critic_loss_kernel(
     const float* target_logits_1, const float* target_logits_2, const float* logits_1, const float* logits_2, int ld,
     const float* rewards, const float* discounts, const float* values, int NA, float* dlogits_1, float* dlogits_2,
     float* sample_m, int B, int Bp, const float* weights, float* sample_losses) {
-  const int lane = threadIdx.x & 63;
-  const int m = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  if (m >= B) return;
-  const bool live = lane < NA;
-  const int i = live ? lane : NA - 1;
-  const float z = values[i], vmin = values[0], vmax = values[NA - 1];
-  const float p1 = wave_softmax(target_logits_1[(int64_t)m * ld + i], live, nullptr);
-  const float p2 = wave_softmax(target_logits_2[(int64_t)m * ld + i], live, nullptr);
-  const float mu1 = wave_sum(live ? p1 * z : 0.f), mu2 = wave_sum(live ? p2 * z : 0.f);
+  AtomRow r;
+  if (!atom_row(values, NA, B, r)) return;
+  const float p1 = wave_softmax(target_logits_1[(int64_t)r.m * ld + r.i], r.live, nullptr);
+  const float p2 = wave_softmax(target_logits_2[(int64_t)r.m * ld + r.i], r.live, nullptr);
+  const float mu1 = wave_sum(r.live ? p1 * r.z : 0.f), mu2 = wave_sum(r.live ? p2 * r.z : 0.f);
   const float p_next = mu2 < mu1 ? p2 : p1;                          // (wave-uniform: every lane holds both sums)
-  const float ret = rewards[m] + discounts[m] * z;
-  const float clipped = fminf(fmaxf(ret, vmin), vmax);
-  const float d_pos = (i + 1 < NA ? values[i + 1] : vmin) - z;
-  const float d_neg = z - (i > 0 ? values[i - 1] : vmax);
-  float target = 0.f;
-  for (int j = 0; j < NA; ++j) {
-    const float delta = __shfl(clipped, j, 64) - z;
-    const float sign = delta >= 0.f ? 1.f : 0.f;
-    const float hat = (sign * delta / d_pos) - ((1.f - sign) * delta / d_neg);
-    target += fminf(fmaxf(1.f - hat, 0.f), 1.f) * __shfl(p_next, j, 64);
-  }
-  if (!live) target = 0.f;
+  const float target = projected_target(r, values, NA, rewards[r.m], discounts[r.m], p_next);
   const float total = wave_sum(target);
-  float log_norm_1, log_norm_2;
-  const float logit_1 = logits_1[(int64_t)m * ld + i], logit_2 = logits_2[(int64_t)m * ld + i];
-  const float q1p = wave_softmax(logit_1, live, &log_norm_1), q2p = wave_softmax(logit_2, live, &log_norm_2);
-  const float loss_1 = -wave_sum(live ? target * (logit_1 - log_norm_1) : 0.f);
-  const float loss_2 = -wave_sum(live ? target * (logit_2 - log_norm_2) : 0.f);
-  const float q1 = wave_sum(live ? q1p * z : 0.f), q2 = wave_sum(live ? q2p * z : 0.f);
-  float grad_1 = live ? q1p * total - target : 0.f, grad_2 = live ? q2p * total - target : 0.f;
-  if (weights != nullptr) { grad_1 *= weights[m]; grad_2 *= weights[m]; }
-  if (lane < ld) {
-    dlogits_1[(int64_t)m * ld + lane] = grad_1;
-    dlogits_2[(int64_t)m * ld + lane] = grad_2;
+  const CriticRow c1 = critic_row(r, logits_1[(int64_t)r.m * ld + r.i], target, total);
+  const CriticRow c2 = critic_row(r, logits_2[(int64_t)r.m * ld + r.i], target, total);
+  const float q1 = wave_sum(r.live ? c1.p * r.z : 0.f), q2 = wave_sum(r.live ? c2.p * r.z : 0.f);
+  float grad_1 = c1.grad, grad_2 = c2.grad;
+  if (weights != nullptr) { grad_1 *= weights[r.m]; grad_2 *= weights[r.m]; }
+  if (r.lane < ld) {
+    dlogits_1[(int64_t)r.m * ld + r.lane] = grad_1;
+    dlogits_2[(int64_t)r.m * ld + r.lane] = grad_2;
   }
-  if (lane == 0) {
-    const float loss = loss_1 + loss_2;
-    sample_m[m] = weights != nullptr ? weights[m] * loss : loss; sample_m[Bp + m] = q1; sample_m[2 * Bp + m] = q2;
-    if (sample_losses != nullptr) sample_losses[m] = loss;
+  if (r.lane == 0) {
+    store_row_loss(r.m, c1.loss + c2.loss, weights, sample_m, sample_losses);
+    sample_m[Bp + r.m] = q1; sample_m[2 * Bp + r.m] = q2;
   }
 }
 
@@ -464,16 +472,12 @@ __global__ void twin_loss_stats_kernel(const float* sample_m, float* stats, int 
 __global__ __launch_bounds__(256) void distributional_actor_loss_kernel(
     const float* logits, int ld, const float* values, int NA, float* dlogits, float* loss_m,
     int B) {
-  const int lane = threadIdx.x & 63;
-  const int m = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  if (m >= B) return;
-  const bool live = lane < NA;
-  const int i = live ? lane : NA - 1;
-  const float z = values[i];
-  const float p = wave_softmax(logits[(int64_t)m * ld + i], live, nullptr);
-  const float value = wave_sum(live ? p * z : 0.f);
-  if (lane < ld) dlogits[(int64_t)m * ld + lane] = live ? -(p * (z - value)) : 0.f;
-  if (lane == 0) loss_m[m] = -value;
+  AtomRow r;
+  if (!atom_row(values, NA, B, r)) return;
+  const float p = wave_softmax(logits[(int64_t)r.m * ld + r.i], r.live, nullptr);
+  const float value = wave_sum(r.live ? p * r.z : 0.f);
+  if (r.lane < ld) dlogits[(int64_t)r.m * ld + r.lane] = r.live ? -(p * (r.z - value)) : 0.f;
+  if (r.lane == 0) loss_m[r.m] = -value;
 }
 
 // the 8 statistics {loss_sum, 0, 0, 0, 0, B, 0, 0} from per-sample losses (fixed order, float64)
@@ -2364,21 +2368,31 @@ extern "C" int tonic_q_iteration(const tonic_q_iteration_t* it, void* stream) {
 namespace {
 
 // Every (h1, h2) / (dz2, dz1) pair is the first two layers of a region of hidden_layers(H) layers (see layer_at).
+// One critic's arrays, target (t_) and online (c_): the hidden regions, the logits and the online logits' gradient.
+struct DistributionalCritic {
+  float *t_h1, *t_h2, *c_h1, *c_h2, *t_logits, *logits, *dlogits;
+  void take(Workspace& ws, int64_t hid, int64_t region, int64_t rows) {
+    t_h1 = ws.take(region); t_h2 = behind(t_h1, hid); c_h1 = ws.take(region); c_h2 = behind(c_h1, hid);
+    t_logits = ws.take(rows); logits = ws.take(rows); dlogits = ws.take(rows);
+  }
+};
+// nets == 1: D4PG's arrays.  nets == 2 (TD4): the same — a workspace of that size serves
+// tonic_distributional_actor_grad as well — and behind them the second critic's and sample_m; the policy pass, X / X2
+// and the chain's (dz2, dz1), which the two backward passes use one after the other, exist once.
 struct DistributionalBuffers {
-  float *a_h1, *a_h2, *head, *act, *X, *X2, *t_h1, *t_h2, *t_logits, *c_h1, *c_h2, *logits,
-      *dlogits, *loss_m, *dz2, *dz1, *dxa, *dloc, *da_h2, *da_h1;
-  DistributionalBuffers(Workspace& ws, int B, int O, int A, int32_t H, int NA) {
+  float *a_h1, *a_h2, *head, *act, *X, *X2, *loss_m, *dz2, *dz1, *dxa, *dloc, *da_h2, *da_h1, *sample_m;
+  DistributionalCritic k[2];
+  DistributionalBuffers(Workspace& ws, int B, int O, int A, int32_t H, int NA, int nets = 1) : sample_m(nullptr), k{} {
     const int64_t Bp = pad16(B), ldx = pitch16(O + A), ldh = pad16(A), ldl = pad16(NA);
     const int64_t hid = Bp * hidden_pitch(H), region = hid * hidden_layers(H);
     a_h1 = ws.take(region); a_h2 = behind(a_h1, hid);
     head = ws.take(Bp * ldh); act = ws.take(Bp * A);
     X = ws.take(Bp * ldx); X2 = ws.take(Bp * ldx);
-    t_h1 = ws.take(region); t_h2 = behind(t_h1, hid); c_h1 = ws.take(region); c_h2 = behind(c_h1, hid);
-    t_logits = ws.take(Bp * ldl); logits = ws.take(Bp * ldl);
-    dlogits = ws.take(Bp * ldl); loss_m = ws.take(Bp);
+    k[0].take(ws, hid, region, Bp * ldl); loss_m = ws.take(Bp);
     dz2 = ws.take(region); dz1 = behind(dz2, hid);
     dxa = ws.take(Bp * ldh); dloc = ws.take(Bp * ldh);
     da_h2 = ws.take(region); da_h1 = behind(da_h2, hid);
+    if (nets == 2) { k[1].take(ws, hid, region, Bp * ldl); sample_m = ws.take(3 * Bp); }
   }
 };
 
@@ -2389,46 +2403,78 @@ extern "C" int64_t tonic_distributional_workspace_bytes(int32_t B, int32_t O, in
   return measure<DistributionalBuffers>(B, O, A, H, NA);
 }
 
+// TD4: TD3's twin critics, clipped target-action noise and delayed actor steps on D4PG's categorical critic.  The
+// flat blocks are [critic_1 | critic_2]; the actor step is tonic_distributional_actor_grad on the first, critic_1.
+extern "C" int64_t tonic_twin_distributional_workspace_bytes(int32_t B, int32_t O, int32_t A, int32_t H,
+                                                             int32_t NA) {
+  return measure<DistributionalBuffers>(B, O, A, H, NA, 2);
+}
+
 namespace {
 
-// tonic_distributional_q_grad and its weighted form (`what`: the entry's name in the messages): one body
+// The critic step of D4PG (nets == 1) and TD4 (nets == 2: the flat blocks [critic_1 | critic_2]) and their weighted
+// forms, one body (`what`: the entry's name in the messages).  d_eps == null: the target actor's action as it is;
+// else TD3's clipped target-action noise on it.
 int distributional_q_grad(
-    const char* what, const float* d_target_actor, const float* d_target_critic, const float* d_critic,
+    const char* what, int nets, const float* d_target_actor, const float* d_target_critics, const float* d_critics,
     const float* d_norm_mean, const float* d_norm_std, double norm_clip,
     const float* d_observations, const float* d_actions, const float* d_next_observations,
-    const float* d_rewards, const float* d_discounts, const float* d_values, float* d_grad_sums,
-    int32_t B, int32_t O, int32_t H, int32_t A, int32_t NA, const float* d_weights, float* d_sample_losses,
-    void* d_workspace, int64_t workspace_bytes, void* stream) {
-  TONIC_REQUIRE(d_target_actor && d_target_critic && d_critic && d_norm_mean && d_norm_std &&
+    const float* d_rewards, const float* d_discounts, const float* d_eps, const float* d_values,
+    float* d_grad_sums, int32_t B, int32_t O, int32_t H, int32_t A, int32_t NA, double noise_scale,
+    double noise_clip, const float* d_weights, float* d_sample_losses, void* d_workspace, int64_t workspace_bytes,
+    void* stream) {
+  TONIC_REQUIRE(d_target_actor && d_target_critics && d_critics && d_norm_mean && d_norm_std &&
                     d_observations && d_actions && d_next_observations && d_rewards &&
-                    d_discounts && d_values && d_grad_sums && d_workspace && B > 0 && NA >= 2 &&
-                    NA <= 64 && hidden_known(H),
+                    d_discounts && (d_eps || nets == 1) && d_values && d_grad_sums && d_workspace && B > 0 &&
+                    NA >= 2 && NA <= 64 && hidden_known(H),
                 TONIC_ERR_INVALID_ARGUMENT, "%s: bad argument (2 <= atoms <= 64)", what);
-  TONIC_REQUIRE(workspace_bytes >= tonic_distributional_workspace_bytes(B, O, A, H, NA),
+  TONIC_REQUIRE(d_eps == nullptr ||
+                    (std::isfinite(noise_scale) && std::isfinite(noise_clip) && noise_scale >= 0 && noise_clip >= 0),
+                TONIC_ERR_INVALID_ARGUMENT,
+                "%s: noise scale %g, clip %g (finite and >= 0)", what, noise_scale, noise_clip);
+  TONIC_REQUIRE(workspace_bytes >= measure<DistributionalBuffers>(B, O, A, H, NA, nets),
                 TONIC_ERR_WORKSPACE, "%s: workspace too small", what);
   hipStream_t st = as_stream(stream);
-  const int ldx = pitch16(O + A), ldh = pad16(A), ldl = pad16(NA);
+  const int Bp = pad16(B), ldx = pitch16(O + A), ldh = pad16(A), ldl = pad16(NA);
   Workspace ws{static_cast<char*>(d_workspace), 0};
-  const DistributionalBuffers w(ws, B, O, A, H, NA);
+  const DistributionalBuffers w(ws, B, O, A, H, NA, nets);
   const ActorShape as = actor_shape(O, H, A, 1), cs = actor_shape(O + A, H, NA, 1);
-  // a' = target_actor(s') (critics.py:104); its tail encodes (s', a') -> X and the stored (s, a) -> X2
+  const int64_t Pc = actor_count(cs);
+  // 1  a' = target_actor(s') (critics.py:104) [TD4: clamp(a' + clamp(scale eps, -clip, clip), -1, 1)]; the tail
+  //    encodes (s', a') -> X and the stored (s, a) -> X2
   PolicyTail tail{};
   tail.post = POST_COPY; tail.actions = w.act;
+  if (d_eps != nullptr) {
+    tail.post = POST_TARGET_NOISE; tail.eps = d_eps;
+    tail.noise_scale = (float)noise_scale; tail.noise_clip = (float)noise_clip;
+  }
   tail.enc_obs = d_next_observations; tail.enc_obs2 = d_observations; tail.enc_act2 = d_actions;
   tail.enc_mean = d_norm_mean; tail.enc_std = d_norm_std; tail.enc_clip = clip_bound(norm_clip);
   tail.enc_out = w.X; tail.enc_out2 = w.X2; tail.enc_ld = ldx;
   TRY(policy_pass(d_target_actor, as, d_next_observations, B, w.a_h1, w.a_h2, w.head, w.head, ldh, true, st, tail));
-  TRY(actor_forward(d_target_critic, cs, w.X, B, w.t_h1, w.t_h2, w.t_logits, w.t_logits, ldl, false,
-                    st, nullptr, nullptr, ldx));
-  TRY(actor_forward(d_critic, cs, w.X2, B, w.c_h1, w.c_h2, w.logits, w.logits, ldl, false, st,
-                    nullptr, nullptr, ldx));
-  hipLaunchKernelGGL(distributional_critic_loss_kernel, dim3((B + 3) / 4), dim3(256), 0, st,
-                     w.t_logits, w.logits, ldl, d_rewards, d_discounts, d_values, NA, w.dlogits,
-                     w.loss_m, B, d_weights, d_sample_losses);
-  hipLaunchKernelGGL(loss_stats_kernel, dim3(1), dim3(1024), 0, st, w.loss_m,
-                     d_grad_sums + actor_count(cs), B);
-  TRY(actor_shaped_backward(d_critic, cs, w.X2, ldx, B, w.c_h1, w.c_h2, w.dlogits, nullptr, ldl,
-                            w.dz2, w.dz1, d_grad_sums, nullptr, 0, 0, st));
+  // 2  the target critics on (s', a'), then  3  the online critics on (s, a)
+  for (int k = 0; k < nets; ++k)
+    TRY(actor_forward(d_target_critics + k * Pc, cs, w.X, B, w.k[k].t_h1, w.k[k].t_h2, w.k[k].t_logits,
+                      w.k[k].t_logits, ldl, false, st, nullptr, nullptr, ldx));
+  for (int k = 0; k < nets; ++k)
+    TRY(actor_forward(d_critics + k * Pc, cs, w.X2, B, w.k[k].c_h1, w.k[k].c_h2, w.k[k].logits, w.k[k].logits, ldl,
+                      false, st, nullptr, nullptr, ldx));
+  // 4 + 5  the loss [TD4: on the target distribution of the smaller mean] and the statistics behind the gradient blocks
+  if (nets == 1) {
+    hipLaunchKernelGGL(distributional_critic_loss_kernel, dim3((B + 3) / 4), dim3(256), 0, st, w.k[0].t_logits,
+                       w.k[0].logits, ldl, d_rewards, d_discounts, d_values, NA, w.k[0].dlogits, w.loss_m, B,
+                       d_weights, d_sample_losses);
+    hipLaunchKernelGGL(loss_stats_kernel, dim3(1), dim3(1024), 0, st, w.loss_m, d_grad_sums + Pc, B);
+  } else {
+    hipLaunchKernelGGL(twin_distributional_critic_loss_kernel, dim3((B + 3) / 4), dim3(256), 0, st, w.k[0].t_logits,
+                       w.k[1].t_logits, w.k[0].logits, w.k[1].logits, ldl, d_rewards, d_discounts, d_values, NA,
+                       w.k[0].dlogits, w.k[1].dlogits, w.sample_m, B, Bp, d_weights, d_sample_losses);
+    hipLaunchKernelGGL(twin_loss_stats_kernel, dim3(1), dim3(1024), 0, st, w.sample_m, d_grad_sums + 2 * Pc, B, Bp);
+  }
+  // 6  each online critic's backward into its own block of the sums
+  for (int k = 0; k < nets; ++k)
+    TRY(actor_shaped_backward(d_critics + k * Pc, cs, w.X2, ldx, B, w.k[k].c_h1, w.k[k].c_h2, w.k[k].dlogits, nullptr,
+                              ldl, w.dz2, w.dz1, d_grad_sums + k * Pc, nullptr, 0, 0, st));
   TONIC_CHECK_LAUNCH(what);
   return TONIC_OK;
 }
@@ -2442,10 +2488,10 @@ extern "C" int tonic_distributional_q_grad(
     const float* d_rewards, const float* d_discounts, const float* d_values, float* d_grad_sums,
     int32_t B, int32_t O, int32_t H, int32_t A, int32_t NA, void* d_workspace,
     int64_t workspace_bytes, void* stream) {
-  return distributional_q_grad("tonic_distributional_q_grad", d_target_actor, d_target_critic, d_critic, d_norm_mean,
-                               d_norm_std, norm_clip, d_observations, d_actions, d_next_observations, d_rewards,
-                               d_discounts, d_values, d_grad_sums, B, O, H, A, NA, nullptr, nullptr, d_workspace,
-                               workspace_bytes, stream);
+  return distributional_q_grad("tonic_distributional_q_grad", 1, d_target_actor, d_target_critic, d_critic,
+                               d_norm_mean, d_norm_std, norm_clip, d_observations, d_actions, d_next_observations,
+                               d_rewards, d_discounts, nullptr, d_values, d_grad_sums, B, O, H, A, NA, 0.0, 0.0, nullptr,
+                               nullptr, d_workspace, workspace_bytes, stream);
 }
 
 // ... on a prioritized batch: the rows' importance weights in, the unweighted row losses out (each may be NULL)
@@ -2456,10 +2502,10 @@ extern "C" int tonic_weighted_distributional_q_grad(
     const float* d_rewards, const float* d_discounts, const float* d_values, float* d_grad_sums,
     int32_t B, int32_t O, int32_t H, int32_t A, int32_t NA, const float* d_weights, float* d_sample_losses,
     void* d_workspace, int64_t workspace_bytes, void* stream) {
-  return distributional_q_grad("tonic_weighted_distributional_q_grad", d_target_actor, d_target_critic, d_critic,
+  return distributional_q_grad("tonic_weighted_distributional_q_grad", 1, d_target_actor, d_target_critic, d_critic,
                                d_norm_mean, d_norm_std, norm_clip, d_observations, d_actions, d_next_observations,
-                               d_rewards, d_discounts, d_values, d_grad_sums, B, O, H, A, NA, d_weights,
-                               d_sample_losses, d_workspace, workspace_bytes, stream);
+                               d_rewards, d_discounts, nullptr, d_values, d_grad_sums, B, O, H, A, NA, 0.0, 0.0,
+                               d_weights, d_sample_losses, d_workspace, workspace_bytes, stream);
 }
 
 extern "C" int tonic_distributional_actor_grad(
@@ -2482,14 +2528,15 @@ extern "C" int tonic_distributional_actor_grad(
   tail.enc_obs = d_observations; tail.enc_mean = d_norm_mean; tail.enc_std = d_norm_std;
   tail.enc_clip = clip_bound(norm_clip); tail.enc_out = w.X; tail.enc_ld = ldx;
   TRY(policy_pass(d_actor_params, as, d_observations, B, w.a_h1, w.a_h2, w.head, w.head, ldh, true, st, tail));
-  TRY(actor_forward(d_critic, cs, w.X, B, w.c_h1, w.c_h2, w.logits, w.logits, ldl, false, st,
+  const DistributionalCritic& c = w.k[0];
+  TRY(actor_forward(d_critic, cs, w.X, B, c.c_h1, c.c_h2, c.logits, c.logits, ldl, false, st,
                     nullptr, nullptr, ldx));
   hipLaunchKernelGGL(distributional_actor_loss_kernel, dim3((B + 3) / 4), dim3(256), 0, st,
-                     w.logits, ldl, d_values, NA, w.dlogits, w.loss_m, B);
+                     c.logits, ldl, d_values, NA, c.dlogits, w.loss_m, B);
   hipLaunchKernelGGL(loss_stats_kernel, dim3(1), dim3(1024), 0, st, w.loss_m,
                      d_grad_sums + actor_count(as), B);
   // through the frozen critic to the action columns of its input, then the tanh head and the actor
-  TRY(actor_shaped_backward(d_critic, cs, w.X, ldx, B, w.c_h1, w.c_h2, w.dlogits, nullptr, ldl,
+  TRY(actor_shaped_backward(d_critic, cs, w.X, ldx, B, c.c_h1, c.c_h2, c.dlogits, nullptr, ldl,
                             w.dz2, w.dz1, nullptr, w.dxa, O, A, st));
   hipLaunchKernelGGL(actor_head_backward_kernel, dim3((B * A + threads - 1) / threads),
                      dim3(threads), 0, st, w.dxa, (const float*)nullptr, ldh, w.act,
@@ -2502,96 +2549,7 @@ extern "C" int tonic_distributional_actor_grad(
 }
 
 // ------------------------------------------------------------------ TD4 (twin distributional critics)
-// TD3's twin critics, clipped target-action noise and delayed actor steps on D4PG's categorical critic: the critic
-// step of both online critics in one entry.  The actor step is tonic_distributional_actor_grad on the first block of
-// the flat critics, critic_1.
-
-namespace {
-
-// D4PG's arrays — a workspace of this size serves tonic_distributional_actor_grad as well — and the second critic's:
-// `one` holds the policy pass, X / X2, critic 1 (target and online) and the chain's (dz2, dz1), which the two
-// backward passes use one after the other.
-struct TwinDistributionalBuffers {
-  DistributionalBuffers one;
-  float *t_h1, *t_h2, *t_logits, *c_h1, *c_h2, *logits, *dlogits, *sample_m;
-  TwinDistributionalBuffers(Workspace& ws, int B, int O, int A, int32_t H, int NA) : one(ws, B, O, A, H, NA) {
-    const int64_t Bp = pad16(B), ldl = pad16(NA);
-    const int64_t hid = Bp * hidden_pitch(H), region = hid * hidden_layers(H);
-    t_h1 = ws.take(region); t_h2 = behind(t_h1, hid); c_h1 = ws.take(region); c_h2 = behind(c_h1, hid);
-    t_logits = ws.take(Bp * ldl); logits = ws.take(Bp * ldl); dlogits = ws.take(Bp * ldl);
-    sample_m = ws.take(3 * Bp);
-  }
-};
-
-}  // namespace
-
-extern "C" int64_t tonic_twin_distributional_workspace_bytes(int32_t B, int32_t O, int32_t A, int32_t H,
-                                                             int32_t NA) {
-  return measure<TwinDistributionalBuffers>(B, O, A, H, NA);
-}
-
-namespace {
-
-// tonic_twin_distributional_q_grad and its weighted form (`what`: the entry's name in the messages): one body
-int twin_distributional_q_grad(
-    const char* what, const float* d_target_actor, const float* d_target_critics, const float* d_critics,
-    const float* d_norm_mean, const float* d_norm_std, double norm_clip,
-    const float* d_observations, const float* d_actions, const float* d_next_observations,
-    const float* d_rewards, const float* d_discounts, const float* d_eps, const float* d_values,
-    float* d_grad_sums, int32_t B, int32_t O, int32_t H, int32_t A, int32_t NA, double noise_scale,
-    double noise_clip, const float* d_weights, float* d_sample_losses, void* d_workspace, int64_t workspace_bytes,
-    void* stream) {
-  TONIC_REQUIRE(d_target_actor && d_target_critics && d_critics && d_norm_mean && d_norm_std &&
-                    d_observations && d_actions && d_next_observations && d_rewards &&
-                    d_discounts && d_eps && d_values && d_grad_sums && d_workspace && B > 0 && NA >= 2 &&
-                    NA <= 64 && hidden_known(H),
-                TONIC_ERR_INVALID_ARGUMENT, "%s: bad argument (2 <= atoms <= 64)", what);
-  TONIC_REQUIRE(std::isfinite(noise_scale) && std::isfinite(noise_clip) && noise_scale >= 0 && noise_clip >= 0,
-                TONIC_ERR_INVALID_ARGUMENT,
-                "%s: noise scale %g, clip %g (finite and >= 0)", what, noise_scale, noise_clip);
-  TONIC_REQUIRE(workspace_bytes >= tonic_twin_distributional_workspace_bytes(B, O, A, H, NA),
-                TONIC_ERR_WORKSPACE, "%s: workspace too small", what);
-  hipStream_t st = as_stream(stream);
-  const int Bp = pad16(B), ldx = pitch16(O + A), ldh = pad16(A), ldl = pad16(NA);
-  Workspace ws{static_cast<char*>(d_workspace), 0};
-  const TwinDistributionalBuffers w(ws, B, O, A, H, NA);
-  const DistributionalBuffers& w1 = w.one;
-  const ActorShape as = actor_shape(O, H, A, 1), cs = actor_shape(O + A, H, NA, 1);
-  const int64_t Pc = actor_count(cs);               // the flat blocks: [critic_1 | critic_2]
-  // 1  a' = clamp(target_actor(s') + clamp(scale eps, -clip, clip), -1, 1); the tail encodes (s', a') -> X and the
-  //    stored (s, a) -> X2
-  PolicyTail tail{};
-  tail.post = POST_TARGET_NOISE; tail.eps = d_eps; tail.actions = w1.act;
-  tail.noise_scale = (float)noise_scale; tail.noise_clip = (float)noise_clip;
-  tail.enc_obs = d_next_observations; tail.enc_obs2 = d_observations; tail.enc_act2 = d_actions;
-  tail.enc_mean = d_norm_mean; tail.enc_std = d_norm_std; tail.enc_clip = clip_bound(norm_clip);
-  tail.enc_out = w1.X; tail.enc_out2 = w1.X2; tail.enc_ld = ldx;
-  TRY(policy_pass(d_target_actor, as, d_next_observations, B, w1.a_h1, w1.a_h2, w1.head, w1.head, ldh, true, st, tail));
-  // 2  the two target critics on (s', a')
-  TRY(actor_forward(d_target_critics, cs, w1.X, B, w1.t_h1, w1.t_h2, w1.t_logits, w1.t_logits, ldl, false, st,
-                    nullptr, nullptr, ldx));
-  TRY(actor_forward(d_target_critics + Pc, cs, w1.X, B, w.t_h1, w.t_h2, w.t_logits, w.t_logits, ldl, false, st,
-                    nullptr, nullptr, ldx));
-  // 3  the two online critics on (s, a)
-  TRY(actor_forward(d_critics, cs, w1.X2, B, w1.c_h1, w1.c_h2, w1.logits, w1.logits, ldl, false, st, nullptr,
-                    nullptr, ldx));
-  TRY(actor_forward(d_critics + Pc, cs, w1.X2, B, w.c_h1, w.c_h2, w.logits, w.logits, ldl, false, st, nullptr,
-                    nullptr, ldx));
-  // 4 + 5  the loss on the target distribution of the smaller mean, and the statistics behind both gradient blocks
-  hipLaunchKernelGGL(twin_distributional_critic_loss_kernel, dim3((B + 3) / 4), dim3(256), 0, st, w1.t_logits,
-                     w.t_logits, w1.logits, w.logits, ldl, d_rewards, d_discounts, d_values, NA, w1.dlogits, w.dlogits,
-                     w.sample_m, B, Bp, d_weights, d_sample_losses);
-  hipLaunchKernelGGL(twin_loss_stats_kernel, dim3(1), dim3(1024), 0, st, w.sample_m, d_grad_sums + 2 * Pc, B, Bp);
-  // 6  each online critic's backward into its own block of the sums
-  TRY(actor_shaped_backward(d_critics, cs, w1.X2, ldx, B, w1.c_h1, w1.c_h2, w1.dlogits, nullptr, ldl, w1.dz2, w1.dz1,
-                            d_grad_sums, nullptr, 0, 0, st));
-  TRY(actor_shaped_backward(d_critics + Pc, cs, w1.X2, ldx, B, w.c_h1, w.c_h2, w.dlogits, nullptr, ldl, w1.dz2,
-                            w1.dz1, d_grad_sums + Pc, nullptr, 0, 0, st));
-  TONIC_CHECK_LAUNCH(what);
-  return TONIC_OK;
-}
-
-}  // namespace
+// The critic step of both online critics in one entry (distributional_q_grad with nets == 2).
 
 extern "C" int tonic_twin_distributional_q_grad(
     const float* d_target_actor, const float* d_target_critics, const float* d_critics,
@@ -2600,11 +2558,10 @@ extern "C" int tonic_twin_distributional_q_grad(
     const float* d_rewards, const float* d_discounts, const float* d_eps, const float* d_values,
     float* d_grad_sums, int32_t B, int32_t O, int32_t H, int32_t A, int32_t NA, double noise_scale,
     double noise_clip, void* d_workspace, int64_t workspace_bytes, void* stream) {
-  return twin_distributional_q_grad("tonic_twin_distributional_q_grad", d_target_actor, d_target_critics, d_critics,
-                                    d_norm_mean, d_norm_std, norm_clip, d_observations, d_actions,
-                                    d_next_observations, d_rewards, d_discounts, d_eps, d_values, d_grad_sums, B, O, H,
-                                    A, NA, noise_scale, noise_clip, nullptr, nullptr, d_workspace, workspace_bytes,
-                                    stream);
+  return distributional_q_grad("tonic_twin_distributional_q_grad", 2, d_target_actor, d_target_critics, d_critics,
+                               d_norm_mean, d_norm_std, norm_clip, d_observations, d_actions, d_next_observations,
+                               d_rewards, d_discounts, d_eps, d_values, d_grad_sums, B, O, H, A, NA, noise_scale,
+                               noise_clip, nullptr, nullptr, d_workspace, workspace_bytes, stream);
 }
 
 // ... on a prioritized batch: the rows' importance weights in, the unweighted loss_1 + loss_2 out (each may be NULL)
@@ -2616,11 +2573,11 @@ extern "C" int tonic_weighted_twin_distributional_q_grad(
     float* d_grad_sums, int32_t B, int32_t O, int32_t H, int32_t A, int32_t NA, double noise_scale,
     double noise_clip, const float* d_weights, float* d_sample_losses, void* d_workspace, int64_t workspace_bytes,
     void* stream) {
-  return twin_distributional_q_grad("tonic_weighted_twin_distributional_q_grad", d_target_actor, d_target_critics,
-                                    d_critics, d_norm_mean, d_norm_std, norm_clip, d_observations, d_actions,
-                                    d_next_observations, d_rewards, d_discounts, d_eps, d_values, d_grad_sums, B, O, H,
-                                    A, NA, noise_scale, noise_clip, d_weights, d_sample_losses, d_workspace,
-                                    workspace_bytes, stream);
+  return distributional_q_grad("tonic_weighted_twin_distributional_q_grad", 2, d_target_actor, d_target_critics,
+                               d_critics, d_norm_mean, d_norm_std, norm_clip, d_observations, d_actions,
+                               d_next_observations, d_rewards, d_discounts, d_eps, d_values, d_grad_sums, B, O, H, A, NA,
+                               noise_scale, noise_clip, d_weights, d_sample_losses, d_workspace, workspace_bytes,
+                               stream);
 }
 
 

@@ -1058,7 +1058,7 @@ class _QUpdater(_FlatUpdater):
         # target critics): the *_ranged entries squash with its _low / _high, read on the device
         self.return_normalizer = getattr(model, 'return_normalizer', None) or None
         device = model.flat_online.device
-        self.atoms = getattr(critic.head, 'num_atoms', 0)
+        self.atoms = getattr(critic.head, 'num_atoms', 0)          # > 0: distributional critic (D4PG)
         if self.normalizer is None:
             self._unit = (torch.zeros(self.observation_size, device=device),
                           torch.ones(self.observation_size, device=device))
@@ -1069,7 +1069,6 @@ class _QUpdater(_FlatUpdater):
         lib = _lib.load()
         want_actor = lib.tonic_mlp_actor_param_count(
             self.observation_size, self.hidden, self.action_size, heads)
-        self.atoms = getattr(critic.head, 'num_atoms', 0)          # > 0: distributional critic (D4PG)
         if self.atoms:
             if not 2 <= self.atoms <= 64:
                 raise NotImplementedError('the distributional kernels serve 2 .. 64 atoms')
@@ -1094,9 +1093,6 @@ class _QUpdater(_FlatUpdater):
                 f'network shapes outside the packed off-policy layout: actor '
                 f'{model.flat_actor.count} vs {want_actor}, critics {model.flat_critics.count} '
                 f'vs {n_critics} x {want_critic}')
-        if self.normalizer is None:
-            self._unit = (torch.zeros(self.observation_size, device=device),
-                          torch.ones(self.observation_size, device=device))
 
     def norm_tensors(self):
         if self.normalizer is None:
@@ -1122,13 +1118,15 @@ class _QUpdater(_FlatUpdater):
             return None, None
         return _lib.ptr(self.return_normalizer._low.data), _lib.ptr(self.return_normalizer._high.data)
 
-    def _offpolicy_workspace(self, batch):
+    def _workspace_bytes(self, batch):
+        """What this updater's entries ask of their workspace at `batch` rows (the hook of `_offpolicy_workspace`)."""
+        shape = (batch, self.observation_size, self.action_size, self.hidden)
         if self.atoms:
-            need = self.lib.tonic_distributional_workspace_bytes(
-                batch, self.observation_size, self.action_size, self.hidden, self.atoms)
-        else:
-            need = self.lib.tonic_offpolicy_workspace_bytes(batch, self.observation_size,
-                                                            self.action_size, self.hidden)
+            return self.lib.tonic_distributional_workspace_bytes(*shape, self.atoms)
+        return self.lib.tonic_offpolicy_workspace_bytes(*shape)
+
+    def _offpolicy_workspace(self, batch):
+        need = self._workspace_bytes(batch)
         if self.workspace is None or self.workspace.numel() < need:
             self.workspace = torch.empty(need, dtype=torch.uint8, device=self.grad_sums.device)
         return self.workspace
@@ -1357,12 +1355,8 @@ class QRegression(_TwinCriticQLearning):
         if self.hidden is None:
             self._stock_setup(self.optimizer, self.default_lr)
 
-    def _offpolicy_workspace(self, batch):
-        need = self.lib.tonic_q_regression_workspace_bytes(batch, self.observation_size, self.action_size,
-                                                           self.hidden)
-        if self.workspace is None or self.workspace.numel() < need:
-            self.workspace = torch.empty(need, dtype=torch.uint8, device=self.grad_sums.device)
-        return self.workspace
+    def _workspace_bytes(self, batch):
+        return self.lib.tonic_q_regression_workspace_bytes(batch, self.observation_size, self.action_size, self.hidden)
 
     def _stock_enqueue(self, batch, info_row, n_global):
         """critics.py:43-53 as stock torch operators; the loss is the SUM over this rank's part of the batch divided
@@ -1420,11 +1414,51 @@ class TwinCriticSoftQLearning(_TwinCriticQLearning):
         return self.model.flat_actor.flat
 
 
-class DistributionalDeterministicQLearning(_TwinCriticQLearning):
+class _DistributionalQLearning(_TwinCriticQLearning):
+    """The categorical critic step of D4PG and TD4: one `enqueue` for tonic_distributional_q_grad, its twin and their
+    weighted forms.  A subclass names its two entries and, for the twin entry, carries a `target_action_noise`."""
+    stock_capable = False
+    entries = None          # (the plain entry, its weighted form)
+
+    def _policy_params(self):
+        return self.model.flat_target_actor.flat
+
+    def _support(self):
+        """The support the target distribution is projected onto."""
+        raise NotImplementedError
+
+    def enqueue(self, batch, eps, info_row, n_global=None, weights=None, sample_losses=None):
+        """eps: the [B, A] standard-normal draw of the target-action noise (the twin entry; D4PG has none).
+        weights / sample_losses: float32 [B] device tensors of a prioritized batch — the rows' importance weights in,
+        their unweighted losses (TD4: loss_1 + loss_2) out, through the weighted entry; without them the plain one."""
+        B = batch['observations'].shape[0]
+        ws = self._offpolicy_workspace(B)
+        mean, std = self.norm_tensors()
+        noise = getattr(self, 'target_action_noise', None)
+        p = _lib.ptr
+        weighted = weights is not None or sample_losses is not None
+        entry = self.entries[weighted]
+        # the arguments every entry takes, in the prototypes' order; the twin entry's eps and noise floats and the
+        # weighted entry's pair go where the prototypes have them
+        networks = (p(self._policy_params()), p(self.model.flat_target_critics.flat), p(self.flat.flat), p(mean),
+                    p(std), self.norm_clip())
+        rows = (p(batch['observations']), p(batch['actions']), p(batch['next_observations']), p(batch['rewards']),
+                p(batch['discounts']))
+        sums = (p(self._support()), p(self.grad_sums), B, self.observation_size, self.hidden, self.action_size,
+                self.atoms)
+        workspace = (p(ws), ws.numel(), _lib.current_stream())
+        draw = (p(eps),) if noise is not None else ()
+        clipping = (float(noise.scale), float(noise.clip)) if noise is not None else ()
+        priorities = (p(weights), p(sample_losses)) if weighted else ()
+        _lib.check(getattr(self.lib, entry)(*networks, *rows, *draw, *sums, *clipping, *priorities, *workspace), entry)
+        self._step(n_global or B * self.world_size, info_row)
+
+
+class DistributionalDeterministicQLearning(_DistributionalQLearning):
     """critics.py:89-122 (D4PG): cross-entropy of the online critic's categorical distribution
     against the projected target distribution (tonic_distributional_q_grad)."""
-    stock_capable = False
     stats_kind = 4          # {loss}
+    entries = ('tonic_distributional_q_grad', 'tonic_weighted_distributional_q_grad')
 
     def __init__(self, optimizer=None, gradient_clip=0):
         self.optimizer = optimizer
@@ -1436,23 +1470,8 @@ class DistributionalDeterministicQLearning(_TwinCriticQLearning):
             raise NotImplementedError('DistributionalDeterministicQLearning needs a critic with a '
                                       'DistributionalValueHead')
 
-    def enqueue(self, batch, eps, info_row, n_global=None, weights=None, sample_losses=None):
-        """weights / sample_losses: float32 [B] device tensors of a prioritized batch — the rows' importance weights
-        in, their unweighted losses out (tonic_weighted_distributional_q_grad); without them the plain entry."""
-        B = batch['observations'].shape[0]
-        ws = self._offpolicy_workspace(B)
-        mean, std = self.norm_tensors()
-        p = _lib.ptr
-        weighted = weights is not None or sample_losses is not None
-        entry = 'tonic_weighted_distributional_q_grad' if weighted else 'tonic_distributional_q_grad'
-        _lib.check(getattr(self.lib, entry)(
-            p(self.model.flat_target_actor.flat), p(self.model.flat_target_critics.flat),
-            p(self.flat.flat), p(mean), p(std), self.norm_clip(), p(batch['observations']),
-            p(batch['actions']), p(batch['next_observations']), p(batch['rewards']),
-            p(batch['discounts']), p(self.target_values), p(self.grad_sums), B, self.observation_size,
-            self.hidden, self.action_size, self.atoms, *((p(weights), p(sample_losses)) if weighted else ()),
-            p(ws), ws.numel(), _lib.current_stream()), entry)
-        self._step(n_global or B * self.world_size, info_row)
+    def _support(self):
+        return self.target_values          # (the TARGET head's: `_shapes`)
 
     def __call__(self, observations, actions, next_observations, rewards, discounts):
         batch = dict(observations=observations, actions=actions,
@@ -1460,14 +1479,14 @@ class DistributionalDeterministicQLearning(_TwinCriticQLearning):
         return self._info(lambda row: self.enqueue(batch, None, row), ('loss',))
 
 
-class TwinCriticDistributionalDeterministicQLearning(_TwinCriticQLearning):
+class TwinCriticDistributionalDeterministicQLearning(_DistributionalQLearning):
     """TD4's critic step (the library's tensorflow/updaters/critics.py:279-336, which has no torch form): TD3's
     clipped target-action noise and twin critics on D4PG's categorical critic.  Per row, the target distribution is
     that of the target critic with the smaller mean (the first on a tie), projected onto the support at
     r + discount * z; both online critics take the cross-entropy against it (tonic_twin_distributional_q_grad).
     Logs the row of TD3 and SAC: loss, and the online critics' mean values q1, q2."""
-    stock_capable = False
     stats_kind = 3          # {loss, q1 mean, q2 mean}
+    entries = ('tonic_twin_distributional_q_grad', 'tonic_weighted_twin_distributional_q_grad')
 
     def __init__(self, optimizer=None, target_action_noise=None, gradient_clip=0):
         self.optimizer = optimizer
@@ -1489,35 +1508,12 @@ class TwinCriticDistributionalDeterministicQLearning(_TwinCriticQLearning):
                 raise NotImplementedError(f'{name} needs the same support in all four critics\' heads')
         super().initialize(model)
 
-    def _policy_params(self):
-        return self.model.flat_target_actor.flat
+    def _support(self):
+        return self.values                 # (the one support `initialize` checked all four heads to share)
 
-    def _offpolicy_workspace(self, batch):
-        need = self.lib.tonic_twin_distributional_workspace_bytes(
+    def _workspace_bytes(self, batch):
+        return self.lib.tonic_twin_distributional_workspace_bytes(
             batch, self.observation_size, self.action_size, self.hidden, self.atoms)
-        if self.workspace is None or self.workspace.numel() < need:
-            self.workspace = torch.empty(need, dtype=torch.uint8, device=self.grad_sums.device)
-        return self.workspace
-
-    def enqueue(self, batch, eps, info_row, n_global=None, weights=None, sample_losses=None):
-        """eps: the [B, A] standard-normal draw of the target-action noise.  weights / sample_losses: float32 [B]
-        device tensors of a prioritized batch — the rows' importance weights in, their unweighted loss_1 + loss_2
-        out (tonic_weighted_twin_distributional_q_grad); without them the plain entry."""
-        B = batch['observations'].shape[0]
-        ws = self._offpolicy_workspace(B)
-        mean, std = self.norm_tensors()
-        noise = self.target_action_noise
-        p = _lib.ptr
-        weighted = weights is not None or sample_losses is not None
-        entry = 'tonic_weighted_twin_distributional_q_grad' if weighted else 'tonic_twin_distributional_q_grad'
-        _lib.check(getattr(self.lib, entry)(
-            p(self._policy_params()), p(self.model.flat_target_critics.flat), p(self.flat.flat), p(mean), p(std),
-            self.norm_clip(), p(batch['observations']), p(batch['actions']), p(batch['next_observations']),
-            p(batch['rewards']), p(batch['discounts']), p(eps), p(self.values), p(self.grad_sums), B,
-            self.observation_size, self.hidden, self.action_size, self.atoms, float(noise.scale), float(noise.clip),
-            *((p(weights), p(sample_losses)) if weighted else ()),
-            p(ws), ws.numel(), _lib.current_stream()), entry)
-        self._step(n_global or B * self.world_size, info_row)
 
 
 class ExpectedSARSA(_TwinCriticQLearning):
@@ -1534,12 +1530,9 @@ class ExpectedSARSA(_TwinCriticQLearning):
         self.optimizer = optimizer
         self.gradient_clip = gradient_clip
 
-    def _offpolicy_workspace(self, batch):
-        need = self.lib.tonic_mpo_workspace_bytes(batch, self.observation_size, self.action_size,
-                                                  self.hidden, self.num_samples)
-        if self.workspace is None or self.workspace.numel() < need:
-            self.workspace = torch.empty(need, dtype=torch.uint8, device=self.grad_sums.device)
-        return self.workspace
+    def _workspace_bytes(self, batch):
+        return self.lib.tonic_mpo_workspace_bytes(batch, self.observation_size, self.action_size, self.hidden,
+                                                  self.num_samples)
 
     def enqueue(self, batch, eps, info_row, n_global=None):
         """eps: the [num_samples * B, A] standard-normal draws of `rsample((num_samples,))`."""
@@ -1738,12 +1731,9 @@ class MaximumAPosterioriPolicyOptimization(_ActorQGradient):
         self.dual_clip_workspace = torch.zeros(
             self.lib.tonic_clip_workspace_bytes(2 * K + 2), dtype=torch.uint8, device=device)
 
-    def _offpolicy_workspace(self, batch):
-        need = self.lib.tonic_mpo_workspace_bytes(batch, self.observation_size, self.action_size,
-                                                  self.hidden, self.num_samples)
-        if self.workspace is None or self.workspace.numel() < need:
-            self.workspace = torch.empty(need, dtype=torch.uint8, device=self.grad_sums.device)
-        return self.workspace
+    def _workspace_bytes(self, batch):
+        return self.lib.tonic_mpo_workspace_bytes(batch, self.observation_size, self.action_size, self.hidden,
+                                                  self.num_samples)
 
     def enqueue(self, observations, eps, info_row, n_global=None, targets=None, stats_row=None):
         from tonic_amd import parallel
