@@ -403,6 +403,69 @@ int tonic_optimizer_step(float* d_params, const float* d_grad_sums, float* d_slo
                          float* d_target, const float* d_online, int64_t total_count, int64_t block_offset,
                          double coeff, void* stream);
 
+/* Learning-rate schedules (additive under ABI 22): the `lr_scheduler=lambda optimizer: torch.optim.lr_scheduler.X(
+ * optimizer, ...)` argument of the updaters.  The rate of a step is formed WHERE the step is taken, in float64, from
+ * the rule's `lr` (the base rate) and t = d_state[0], the number of optimizer steps taken so far (torch's convention
+ * of `scheduler.step()` after each `optimizer.step()`; a skipped launch does not advance it), by torch's
+ * `_get_closed_form_lr`, operation by operation:
+ *   kind          torch class         reads                       lr_t
+ *   CONSTANT      ConstantLR          a = factor, period = total_iters       lr * (a + (t >= period) * (1 - a))
+ *   LINEAR        LinearLR            a = start_factor, b = end_factor,      lr * (a + (b - a) * min(period, t) / period)
+ *                                     period = total_iters
+ *   EXPONENTIAL   ExponentialLR       a = gamma                              lr * a ** t
+ *   STEP          StepLR              a = gamma, period = step_size          lr * a ** (t / period), integer division
+ *   POLYNOMIAL    PolynomialLR        a = power, period = total_iters        lr * (1 - min(period, t) / period) ** a
+ *   COSINE        CosineAnnealingLR   a = eta_min, period = T_max            a + (lr - a) * (1 + cos(pi * t / period)) / 2,
+ *                                                                            periodic beyond T_max like the closed form
+ * What a kind does not read must be zero.  count == 2 is SequentialLR([first, second], milestones=[milestone]): t <
+ * milestone: segment[0] at t; otherwise segment[1] at t - milestone, from the same base rate.  lr_t then stands where
+ * lr stands in the rule, rounded at the same places: Adam / AdamW step_size = F32(lr_t / bias_correction1), AdamW
+ * F32(1 - lr_t * weight_decay), SGD / RMSprop F32(lr_t). */
+enum { TONIC_LR_CONSTANT = 0, TONIC_LR_LINEAR = 1, TONIC_LR_EXPONENTIAL = 2, TONIC_LR_STEP = 3,
+       TONIC_LR_POLYNOMIAL = 4, TONIC_LR_COSINE = 5 };
+typedef struct tonic_lr_segment_t {
+  int32_t kind, reserved;     /* TONIC_LR_CONSTANT .. TONIC_LR_COSINE; 0 */
+  int64_t period;
+  double a, b;
+} tonic_lr_segment_t;
+typedef struct tonic_lr_schedule_t {
+  int32_t count, reserved;    /* 1 | 2 segments; 0 */
+  int64_t milestone;          /* count == 2: >= 1; count == 1: 0 */
+  tonic_lr_segment_t segment[2];
+} tonic_lr_schedule_t;
+/* Host only.  0 for NULL (no schedule) and for a schedule the steps serve; TONIC_ERR_INVALID_ARGUMENT, with
+ * tonic_last_error naming the field, for: count other than 1 / 2, a non-zero reserved word, a milestone < 1 with two
+ * segments or != 0 with one, a non-zero unused segment, an unknown kind, anything not finite, a field the kind does
+ * not read that is not zero, and what torch's constructors or the closed forms reject — CONSTANT: a outside [0, 1],
+ * period < 0; LINEAR: a outside (0, 1], b outside [0, 1], period < 1; EXPONENTIAL: a < 0; STEP: a < 0, period < 1;
+ * POLYNOMIAL: a < 0, period < 1; COSINE: a < 0, period < 1. */
+int tonic_lr_schedule_check(const tonic_lr_schedule_t* schedule);
+/* Host: THE statement — the rate of the step taken after `step` steps from `base_lr` (NULL: base_lr itself; an
+ * invalid schedule or step < 0: NaN, tonic_last_error set). */
+double tonic_lr_schedule_value(const tonic_lr_schedule_t* schedule, double base_lr, int64_t step);
+/* tonic_optimizer_step with the rate of the step read from `schedule` at d_state[0] on the device: graph replays
+ * follow the device counter.  schedule == NULL: tonic_optimizer_step itself, same launch, same bits. */
+int tonic_scheduled_optimizer_step(float* d_params, const float* d_grad_sums, float* d_slots, int32_t* d_state,
+                                   int64_t param_count, double grad_scale, const tonic_optimizer_t* rule,
+                                   int32_t stats_kind, double kl_threshold, double entropy_coeff,
+                                   const float* d_adv_stats, float* d_info_row, const int32_t* d_skip_flag,
+                                   float* d_target, const float* d_online, int64_t total_count,
+                                   int64_t block_offset, double coeff, const tonic_lr_schedule_t* schedule,
+                                   void* stream);
+/* tonic_adam_step_pair with a schedule per network, each on its own step counter (the actor's stops advancing with
+ * the KL stop, the critic's goes on); still ONE launch.  Either may be NULL (that network keeps its lr); both NULL:
+ * tonic_adam_step_pair itself, same launch, same bits. */
+int tonic_scheduled_adam_step_pair(
+    float* d_params_a, const float* d_grad_sums_a, float* d_exp_avg_a, float* d_exp_avg_sq_a,
+    int32_t* d_state_a, int64_t param_count_a, double lr_a, int32_t stats_kind_a,
+    double kl_threshold, double entropy_coeff, const float* d_adv_stats, float* d_info_row_a,
+    const int32_t* d_skip_flag_a,
+    float* d_params_b, const float* d_grad_sums_b, float* d_exp_avg_b, float* d_exp_avg_sq_b,
+    int32_t* d_state_b, int64_t param_count_b, double lr_b, int32_t stats_kind_b,
+    float* d_info_row_b,
+    double grad_scale, double beta1, double beta2, double eps, const tonic_lr_schedule_t* schedule_a,
+    const tonic_lr_schedule_t* schedule_b, void* stream);
+
 /* ---- replay: HBM-resident Segment -----------------------------------------------------------
  * replaces: tonic/replays/segments.py:27-36 (Segment.store, one time row for all W workers)
  *   and tonic/torch/normalizers/mean_stds.py:44-48 (MeanStd.record: sequential float32

@@ -31,6 +31,24 @@ OPTIMIZER_KINDS = {'adam': 0, 'adamw': 1, 'sgd': 2, 'rmsprop': 3}               
 OPTIMIZER_FLAGS = {'amsgrad': 1, 'nesterov': 2, 'centered': 4, 'maximize': 8}     # TONIC_OPT_AMSGRAD ..
 
 
+class LrSegment(ctypes.Structure):
+    """tonic_lr_segment_t of include/tonic_hip.h (field for field)."""
+    _fields_ = [('kind', c_i32), ('reserved', c_i32), ('period', c_i64), ('a', c_f64), ('b', c_f64)]
+
+
+class LrSchedule(ctypes.Structure):
+    """tonic_lr_schedule_t of include/tonic_hip.h (field for field)."""
+    _fields_ = [('count', c_i32), ('reserved', c_i32), ('milestone', c_i64), ('segment', LrSegment * 2)]
+
+    def signature(self):
+        """The schedule as a hashable value: what a captured graph bakes in."""
+        return (self.count, self.milestone) + tuple(
+            (s.kind, s.period, s.a, s.b) for s in self.segment[:self.count])
+
+
+LR_KINDS = {'constant': 0, 'linear': 1, 'exponential': 2, 'step': 3, 'polynomial': 4, 'cosine': 5}   # TONIC_LR_..
+
+
 class CriticLoss(ctypes.Structure):
     """tonic_critic_loss_t of include/tonic_hip.h (field for field); all-zero: MSE."""
     _fields_ = [('kind', c_i32), ('reserved', c_i32), ('param', c_f64)]
@@ -140,6 +158,14 @@ SIGNATURES = {
     'tonic_optimizer_state_slots': (c_i32, [c_vp]),
     'tonic_optimizer_step': (ctypes.c_int, [c_vp] * 4 + [c_i64, c_f64, c_vp, c_i32, c_f64, c_f64] + [c_vp] * 5 +
                              [c_i64, c_i64, c_f64, c_vp]),
+    # learning-rate schedules (additive under ABI 22): the entries above with `schedule[_a, _b]` ahead of the stream
+    'tonic_lr_schedule_check': (ctypes.c_int, [c_vp]),
+    'tonic_lr_schedule_value': (c_f64, [c_vp, c_f64, c_i64]),
+    'tonic_scheduled_optimizer_step': (ctypes.c_int, [c_vp] * 4 + [c_i64, c_f64, c_vp, c_i32, c_f64, c_f64] +
+                                       [c_vp] * 5 + [c_i64, c_i64, c_f64, c_vp, c_vp]),
+    'tonic_scheduled_adam_step_pair': (ctypes.c_int,
+                                       [c_vp] * 5 + [c_i64, c_f64, c_i32, c_f64, c_f64, c_vp, c_vp, c_vp] +
+                                       [c_vp] * 5 + [c_i64, c_f64, c_i32, c_vp] + [c_f64] * 4 + [c_vp] * 3),
     'tonic_segment_store': (ctypes.c_int, [c_vp] * 15 + [c_i64, c_i64, c_i32, c_i32, c_vp]),
     'tonic_meanstd_record': (ctypes.c_int, [c_vp, c_vp, c_i64, c_i32, c_vp]),
     'tonic_segment_gather': (ctypes.c_int, [c_vp] * 11 + [c_i64, c_i64, c_i32, c_i32, c_vp]),

@@ -13,10 +13,13 @@
 // ClippedRatio.__call__ (actors.py:101-112: loss/kl/entropy/clip_fraction/std/stop) and of
 // VRegression.__call__ (critics.py:28).  The optimizer step counter and the PPO early-stop
 // flag live on the device so the 80-iteration loop of ppo.py:33-46 needs no host sync.
+// scheduled_optimizer_kernel is the same step at the rate of a learning-rate schedule (lr_schedule.h), formed from
+// the device's step counter.
 // Bytes of HBM traffic per parameter (p and g read, p written = 12, + 8 per state buffer): Adam / AdamW 28, with
 // amsgrad 36; SGD 12, with momentum 20; RMSprop 20, + 8 centered, + 8 with momentum.
 #include "common.h"
 #include "optim_rule.h"
+#include "lr_schedule.h"
 
 namespace tonic {
 
@@ -203,6 +206,60 @@ __global__ __launch_bounds__(256) void optimizer_kernel(OptimPair pair) {
   last_arrival_finalizes(a, grid);
 }
 
+// The schedule of one network beside its OptimArgs (lr_schedule.h): `active` 0 leaves the network's rate what
+// optim_fill packed; `weight_decay`: AdamW's, in float64 as decay_keep is formed from it.
+struct LrScheduleArg { tonic_lr_schedule_t schedule; double weight_decay; int32_t active, reserved; };
+struct LrSchedulePair { LrScheduleArg net[2]; };
+
+// The same step at the rate of a schedule.  The schedules travel beside the OptimPair, as an argument of kernels of
+// their own (the convention of ValueRangeArg): optimizer_kernel above is not touched — sharing its body through a
+// function changes its instantiations' code — so the walk is stated here a second time, behind a copy of the
+// network's arguments that holds the rate of THIS step: lr_t from the device's own step count in float64, and what
+// optim_fill rounds from lr rounded the same way.  Every workgroup reads state[0] before it arrives
+// (last_arrival_finalizes), so the count is the one the launch began with in all of them.
+template <typename Rule>
+__global__ __launch_bounds__(256) void scheduled_optimizer_kernel(OptimPair pair, LrSchedulePair schedules) {
+  const OptimArgs& packed = blockIdx.y == 0 ? pair.net[0] : pair.net[1];
+  const LrScheduleArg& s = blockIdx.y == 0 ? schedules.net[0] : schedules.net[1];
+  if (packed.polyak_target != nullptr && (int)blockIdx.x >= packed.adam_blocks) {
+    const int64_t first = (int64_t)((int)blockIdx.x - packed.adam_blocks) * blockDim.x + threadIdx.x;
+    const int64_t stride = (int64_t)((int)gridDim.x - packed.adam_blocks) * blockDim.x;
+    for (int64_t i = first; i < packed.polyak_total; i += stride) {
+      if (i >= packed.polyak_offset && i < packed.polyak_offset + packed.n) continue;
+      packed.polyak_target[i] = polyak(packed.polyak_target[i], packed.polyak_online[i], packed.polyak_keep,
+                                       packed.polyak_mix);
+    }
+    return;
+  }
+  if (packed.skip != nullptr && *packed.skip != 0) return;
+  const int64_t grid = packed.polyak_target != nullptr ? packed.adam_blocks : (int64_t)gridDim.x;
+  const bool all_zero = packed.stats_kind == 1 && packed.adv_stats != nullptr && packed.adv_stats[2] != 0.f;
+  if (!all_zero) {
+    OptimArgs a = packed;
+    if (s.active) {
+      const double lr_t = lr_schedule_value(s.schedule, packed.lr_d, (int64_t)packed.state[0]);
+      a.lr_d = lr_t;                                                 // Adam / AdamW: step_size = F32(lr_t / bias1)
+      a.lr = (float)lr_t;                                            // SGD / RMSprop
+      a.decay_keep = (float)(1.0 - lr_t * s.weight_decay);           // AdamW (adam.py:419)
+    }
+    Rule rule;
+    rule.prepare(a);
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += grid * blockDim.x) {
+      const float before = a.params[i];
+      float g = a.grad_sums[i] * a.grad_scale;
+      if (a.maximize) g = -g;
+      if (a.weight_decay != 0.f && !a.decoupled) g = g + a.weight_decay * before;
+      const float p = rule.apply(a, i, before, g);
+      a.params[i] = p;
+      if (a.polyak_target != nullptr) {
+        float* t = a.polyak_target + a.polyak_offset + i;
+        *t = polyak(*t, p, a.polyak_keep, a.polyak_mix);
+      }
+    }
+  }
+  last_arrival_finalizes(packed, grid);
+}
+
 // ---- gradient-norm clipping: torch.nn.utils.clip_grad_norm_ on the flat gradient-sum block ----
 // Norm and factor are formed in float64 and rounded once (torch: float32 throughout): within one
 // float32 ulp of numpy_port.clip_grad_norm_f64, the scaled sums within two (tests/test_gpu_optim.py).
@@ -360,28 +417,77 @@ int optim_fill(OptimArgs& a, unsigned& blocks, const char* what, float* d_params
   return TONIC_OK;
 }
 
+// `schedules` null: the rule's own kernel; otherwise its scheduled instantiation.
 template <typename Rule>
-void launch_as(const OptimPair& pair, dim3 grid, hipStream_t st) {
-  hipLaunchKernelGGL(optimizer_kernel<Rule>, grid, dim3(256), 0, st, pair);
+void launch_as(const OptimPair& pair, const LrSchedulePair* schedules, dim3 grid, hipStream_t st) {
+  if (schedules == nullptr) hipLaunchKernelGGL(optimizer_kernel<Rule>, grid, dim3(256), 0, st, pair);
+  else hipLaunchKernelGGL(scheduled_optimizer_kernel<Rule>, grid, dim3(256), 0, st, pair, *schedules);
 }
 
-int optim_launch(const tonic_optimizer_t& rule, const OptimPair& pair, dim3 grid, void* stream, const char* what) {
+int optim_launch(const tonic_optimizer_t& rule, const OptimPair& pair, dim3 grid, void* stream, const char* what,
+                 const LrSchedulePair* schedules = nullptr) {
   hipStream_t st = as_stream(stream);
   const bool momentum = rule.momentum != 0.0, centered = (rule.flags & TONIC_OPT_CENTERED) != 0;
   if (rule.kind == TONIC_OPT_SGD) {
-    if (momentum) launch_as<SgdRule<true>>(pair, grid, st);
-    else launch_as<SgdRule<false>>(pair, grid, st);
+    if (momentum) launch_as<SgdRule<true>>(pair, schedules, grid, st);
+    else launch_as<SgdRule<false>>(pair, schedules, grid, st);
   } else if (rule.kind == TONIC_OPT_RMSPROP) {
-    if (centered && momentum) launch_as<RmspropRule<true, true>>(pair, grid, st);
-    else if (centered) launch_as<RmspropRule<true, false>>(pair, grid, st);
-    else if (momentum) launch_as<RmspropRule<false, true>>(pair, grid, st);
-    else launch_as<RmspropRule<false, false>>(pair, grid, st);
+    if (centered && momentum) launch_as<RmspropRule<true, true>>(pair, schedules, grid, st);
+    else if (centered) launch_as<RmspropRule<true, false>>(pair, schedules, grid, st);
+    else if (momentum) launch_as<RmspropRule<false, true>>(pair, schedules, grid, st);
+    else launch_as<RmspropRule<false, false>>(pair, schedules, grid, st);
   } else if (rule.flags & TONIC_OPT_AMSGRAD) {
-    launch_as<AdamRule<true>>(pair, grid, st);
+    launch_as<AdamRule<true>>(pair, schedules, grid, st);
   } else {
-    launch_as<AdamRule<false>>(pair, grid, st);
+    launch_as<AdamRule<false>>(pair, schedules, grid, st);
   }
   TONIC_CHECK_LAUNCH(what);
+  return TONIC_OK;
+}
+
+bool finite_in(double v, double low, double high) { return v == v && v >= low && v <= high; }
+
+// What the header says tonic_lr_schedule_check rejects, one segment (`which`: for the messages).
+int lr_segment_check(const tonic_lr_segment_t& s, int which) {
+  TONIC_REQUIRE(s.kind >= TONIC_LR_CONSTANT && s.kind <= TONIC_LR_COSINE, TONIC_ERR_INVALID_ARGUMENT,
+                "tonic_lr_schedule_t: segment[%d].kind %d is not a TONIC_LR_* kind", which, s.kind);
+  TONIC_REQUIRE(s.reserved == 0, TONIC_ERR_INVALID_ARGUMENT, "tonic_lr_schedule_t: segment[%d].reserved %d", which,
+                s.reserved);
+  const double huge = 1.7976931348623157e308;
+  TONIC_REQUIRE(finite_in(s.a, -huge, huge) && finite_in(s.b, -huge, huge), TONIC_ERR_INVALID_ARGUMENT,
+                "tonic_lr_schedule_t: segment[%d] a %g, b %g: not finite", which, s.a, s.b);
+  const bool reads_period = s.kind != TONIC_LR_EXPONENTIAL, reads_b = s.kind == TONIC_LR_LINEAR;
+  TONIC_REQUIRE((reads_period || s.period == 0) && (reads_b || s.b == 0.0), TONIC_ERR_INVALID_ARGUMENT,
+                "tonic_lr_schedule_t: segment[%d] of kind %d: period %lld / b %g is not read and must be zero", which,
+                s.kind, (long long)s.period, s.b);
+  TONIC_REQUIRE(!reads_period || s.period >= (s.kind == TONIC_LR_CONSTANT ? 0 : 1), TONIC_ERR_INVALID_ARGUMENT,
+                "tonic_lr_schedule_t: segment[%d].period %lld (total_iters / step_size / T_max)", which,
+                (long long)s.period);
+  switch (s.kind) {
+    case TONIC_LR_CONSTANT:
+      TONIC_REQUIRE(finite_in(s.a, 0.0, 1.0), TONIC_ERR_INVALID_ARGUMENT,
+                    "tonic_lr_schedule_t: segment[%d].a %g: ConstantLR's factor lies in [0, 1]", which, s.a);
+      break;
+    case TONIC_LR_LINEAR:
+      TONIC_REQUIRE(s.a > 0.0 && s.a <= 1.0 && finite_in(s.b, 0.0, 1.0), TONIC_ERR_INVALID_ARGUMENT,
+                    "tonic_lr_schedule_t: segment[%d] a %g, b %g: LinearLR's start_factor lies in (0, 1], its "
+                    "end_factor in [0, 1]", which, s.a, s.b);
+      break;
+    default:
+      TONIC_REQUIRE(s.a >= 0.0, TONIC_ERR_INVALID_ARGUMENT,
+                    "tonic_lr_schedule_t: segment[%d].a %g (gamma / power / eta_min) is negative", which, s.a);
+  }
+  return TONIC_OK;
+}
+
+// One network's schedule beside its OptimArgs; null: inactive.
+int lr_schedule_fill(LrScheduleArg& s, const tonic_lr_schedule_t* schedule, const tonic_optimizer_t& rule) {
+  s = LrScheduleArg{};
+  if (schedule == nullptr) return TONIC_OK;
+  if (int rc = tonic_lr_schedule_check(schedule)) return rc;
+  s.schedule = *schedule;
+  s.weight_decay = rule.weight_decay;
+  s.active = 1;
   return TONIC_OK;
 }
 
@@ -421,6 +527,95 @@ extern "C" int tonic_optimizer_step(float* d_params, const float* d_grad_sums, f
   return optim_step("tonic_optimizer_step", d_params, d_grad_sums, slot, d_state, param_count, grad_scale, *rule,
                     stats_kind, kl_threshold, entropy_coeff, d_adv_stats, d_info_row, d_skip_flag,
                     PolyakTail{d_target, d_online, total_count, block_offset, coeff}, stream);
+}
+
+extern "C" int tonic_lr_schedule_check(const tonic_lr_schedule_t* s) {
+  if (s == nullptr) return TONIC_OK;
+  TONIC_REQUIRE(s->count == 1 || s->count == 2, TONIC_ERR_INVALID_ARGUMENT,
+                "tonic_lr_schedule_t: count %d (one segment, or two around a milestone)", s->count);
+  TONIC_REQUIRE(s->reserved == 0, TONIC_ERR_INVALID_ARGUMENT, "tonic_lr_schedule_t: reserved %d", s->reserved);
+  TONIC_REQUIRE(s->count == 2 ? s->milestone >= 1 : s->milestone == 0, TONIC_ERR_INVALID_ARGUMENT,
+                "tonic_lr_schedule_t: milestone %lld with %d segment(s)", (long long)s->milestone, s->count);
+  if (int rc = lr_segment_check(s->segment[0], 0)) return rc;
+  if (s->count == 2) return lr_segment_check(s->segment[1], 1);
+  const tonic_lr_segment_t& spare = s->segment[1];
+  TONIC_REQUIRE(spare.kind == 0 && spare.reserved == 0 && spare.period == 0 && spare.a == 0.0 && spare.b == 0.0,
+                TONIC_ERR_INVALID_ARGUMENT, "tonic_lr_schedule_t: segment[1] is not zero with count 1");
+  return TONIC_OK;
+}
+
+extern "C" double tonic_lr_schedule_value(const tonic_lr_schedule_t* schedule, double base_lr, int64_t step) {
+  if (schedule == nullptr) return base_lr;
+  if (tonic_lr_schedule_check(schedule) != TONIC_OK) return (double)NAN;
+  if (step < 0) {
+    set_error("tonic_lr_schedule_value: step %lld", (long long)step);
+    return (double)NAN;
+  }
+  return lr_schedule_value(*schedule, base_lr, step);
+}
+
+extern "C" int tonic_scheduled_optimizer_step(float* d_params, const float* d_grad_sums, float* d_slots,
+                                              int32_t* d_state, int64_t param_count, double grad_scale,
+                                              const tonic_optimizer_t* rule, int32_t stats_kind,
+                                              double kl_threshold, double entropy_coeff, const float* d_adv_stats,
+                                              float* d_info_row, const int32_t* d_skip_flag, float* d_target,
+                                              const float* d_online, int64_t total_count, int64_t block_offset,
+                                              double coeff, const tonic_lr_schedule_t* schedule, void* stream) {
+  if (schedule == nullptr)
+    return tonic_optimizer_step(d_params, d_grad_sums, d_slots, d_state, param_count, grad_scale, rule, stats_kind,
+                                kl_threshold, entropy_coeff, d_adv_stats, d_info_row, d_skip_flag, d_target,
+                                d_online, total_count, block_offset, coeff, stream);
+  const char* what = "tonic_scheduled_optimizer_step";
+  const int slots = tonic_optimizer_state_slots(rule);
+  TONIC_REQUIRE(slots >= 0, TONIC_ERR_INVALID_ARGUMENT, "%s: not a rule of the family (kind %d, flags %d)", what,
+                rule ? rule->kind : -1, rule ? rule->flags : -1);
+  LrSchedulePair schedules{};
+  if (int rc = lr_schedule_fill(schedules.net[0], schedule, *rule)) return rc;
+  float* slot[3] = {nullptr, nullptr, nullptr};
+  for (int k = 0; k < slots && d_slots != nullptr; ++k) slot[k] = d_slots + (int64_t)k * param_count;
+  OptimPair pair{};
+  unsigned blocks = 0;
+  if (int rc = optim_fill(pair.net[0], blocks, what, d_params, d_grad_sums, slot, d_state, param_count, grad_scale,
+                          *rule, stats_kind, kl_threshold, entropy_coeff, d_adv_stats, d_info_row, d_skip_flag,
+                          PolyakTail{d_target, d_online, total_count, block_offset, coeff}))
+    return rc;
+  return optim_launch(*rule, pair, dim3(blocks), stream, what, &schedules);
+}
+
+extern "C" int tonic_scheduled_adam_step_pair(
+    float* d_params_a, const float* d_grad_sums_a, float* d_exp_avg_a, float* d_exp_avg_sq_a,
+    int32_t* d_state_a, int64_t param_count_a, double lr_a, int32_t stats_kind_a,
+    double kl_threshold, double entropy_coeff, const float* d_adv_stats, float* d_info_row_a,
+    const int32_t* d_skip_flag_a,
+    float* d_params_b, const float* d_grad_sums_b, float* d_exp_avg_b, float* d_exp_avg_sq_b,
+    int32_t* d_state_b, int64_t param_count_b, double lr_b, int32_t stats_kind_b,
+    float* d_info_row_b,
+    double grad_scale, double beta1, double beta2, double eps, const tonic_lr_schedule_t* schedule_a,
+    const tonic_lr_schedule_t* schedule_b, void* stream) {
+  if (schedule_a == nullptr && schedule_b == nullptr)
+    return tonic_adam_step_pair(d_params_a, d_grad_sums_a, d_exp_avg_a, d_exp_avg_sq_a, d_state_a, param_count_a,
+                                lr_a, stats_kind_a, kl_threshold, entropy_coeff, d_adv_stats, d_info_row_a,
+                                d_skip_flag_a, d_params_b, d_grad_sums_b, d_exp_avg_b, d_exp_avg_sq_b, d_state_b,
+                                param_count_b, lr_b, stats_kind_b, d_info_row_b, grad_scale, beta1, beta2, eps,
+                                stream);
+  OptimPair pair{};
+  LrSchedulePair schedules{};
+  unsigned blocks_a = 0, blocks_b = 0;
+  float* const slot_a[3] = {d_exp_avg_a, d_exp_avg_sq_a, nullptr};
+  float* const slot_b[3] = {d_exp_avg_b, d_exp_avg_sq_b, nullptr};
+  const tonic_optimizer_t rule_a = plain_adam(lr_a, beta1, beta2, eps), rule_b = plain_adam(lr_b, beta1, beta2, eps);
+  if (int rc = lr_schedule_fill(schedules.net[0], schedule_a, rule_a)) return rc;
+  if (int rc = lr_schedule_fill(schedules.net[1], schedule_b, rule_b)) return rc;
+  if (int rc = optim_fill(pair.net[0], blocks_a, "tonic_scheduled_adam_step_pair (first)", d_params_a,
+                          d_grad_sums_a, slot_a, d_state_a, param_count_a, grad_scale, rule_a, stats_kind_a,
+                          kl_threshold, entropy_coeff, d_adv_stats, d_info_row_a, d_skip_flag_a))
+    return rc;
+  if (int rc = optim_fill(pair.net[1], blocks_b, "tonic_scheduled_adam_step_pair (second)", d_params_b,
+                          d_grad_sums_b, slot_b, d_state_b, param_count_b, grad_scale, rule_b, stats_kind_b, 0.0,
+                          0.0, nullptr, d_info_row_b, nullptr))
+    return rc;
+  return optim_launch(rule_a, pair, dim3(blocks_a > blocks_b ? blocks_a : blocks_b, 2), stream,
+                      "tonic_scheduled_adam_step_pair", &schedules);
 }
 
 extern "C" int tonic_adam_step_pair(

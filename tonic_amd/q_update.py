@@ -62,18 +62,26 @@ def ride_plan(due, ahead_supported):
     return plan
 
 
-def adam_table(iterations, due, critic_hyper, actor_hyper, critic_steps, actor_steps):
+def adam_table(iterations, due, critic_hyper, actor_hyper, critic_steps, actor_steps, schedules=(None, None)):
     """The optimizer steps' float64 constants, formed on the host like the reference's Python floats:
     [iteration, {critic, actor}, {step_size, bias_correction2_sqrt}] as float32 (an actor row that is not due stays
-    zero), and the two step counters behind the last iteration."""
-    from tonic_amd.torch.updaters import adam_step_constants
+    zero), and the two step counters behind the last iteration.  `schedules`: the (critic's, actor's) packed
+    tonic_lr_schedule_t or None — step number `step` (1-based) is taken at the rate of `step - 1` steps taken:
+    step_size = F32(tonic_lr_schedule_value(schedule, lr, step - 1) / bias_correction1)."""
+    from tonic_amd.torch.updaters import adam_step_constants, lr_schedule_value
+
+    def constants(hyper, schedule, step):
+        if schedule is not None:
+            hyper = dict(hyper, lr=lr_schedule_value(schedule, hyper['lr'], step - 1))
+        return adam_step_constants(hyper, step)
+
     table = np.zeros((iterations, 2, 2), np.float32)
     for it in range(iterations):
         critic_steps += 1
-        table[it, 0] = adam_step_constants(critic_hyper, critic_steps)
+        table[it, 0] = constants(critic_hyper, schedules[0], critic_steps)
         if due[it]:
             actor_steps += 1
-            table[it, 1] = adam_step_constants(actor_hyper, actor_steps)
+            table[it, 1] = constants(actor_hyper, schedules[1], actor_steps)
     return table, critic_steps, actor_steps
 
 
@@ -296,7 +304,8 @@ class QUpdate:
             actor.steps_enqueued = int(actor.state[0])
         self.mirror_valid = False            # until this update's launches are out
         table, critic.steps_enqueued, actor.steps_enqueued = adam_table(
-            len(due), due, critic.hyper, actor.hyper, critic.steps_enqueued, actor.steps_enqueued)
+            len(due), due, critic.hyper, actor.hyper, critic.steps_enqueued, actor.steps_enqueued,
+            schedules=(critic.schedule, actor.schedule))
         if slot.adam is None or slot.adam.shape != table.shape:
             slot.adam = torch.zeros(table.shape, device=self.agent.device)
             slot.graph = None

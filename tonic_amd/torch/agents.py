@@ -1009,6 +1009,7 @@ class PPO(A2C):
         self.critic_chain_ms = pending['clock'].elapsed_time(pending['done'])    # (bench.py reports it)
         log_ppo_critic_rows(rows)
         logger.store('critic/iterations', len(rows))
+        log_learning_rate('critic', self.critic_updater, self)
         if getattr(self, '_last_infos', None) is not None:
             self._last_infos[1] = rows
 
@@ -1031,6 +1032,8 @@ class PPO(A2C):
             infos = self.enqueue_update().cpu().numpy()          # the only sync of the update
             parallel.check_one_shot()
             log_ppo_update(infos)
+            log_learning_rate('actor', self.actor_updater, self)
+            log_learning_rate('critic', self.critic_updater, self)
             self.last_infos = infos
             self._record_rewards()
             self._update_normalizers()
@@ -1096,6 +1099,7 @@ class PPO(A2C):
         self.actor_chain_ms = first.elapsed_time(last)   # (bench.py reports it)
         parallel.check_one_shot()
         logger.store('actor/iterations', log_ppo_actor_rows(rows))
+        log_learning_rate('actor', self.actor_updater, self)
         self._last_infos = np.stack([rows, np.zeros_like(rows)])
         if self.model.observation_normalizer and not normaliser_done:
             self.model.observation_normalizer.update()
@@ -1455,7 +1459,11 @@ class DDPG(Agent):
                           float(getattr(updater, 'gradient_clip', 0.0) or 0.0),
                           int(getattr(updater, 'num_samples', 0)),
                           tuple(float(v) for v in getattr(updater, 'scale_bounds', None) or ()),
-                          (noise.scale, noise.clip) if noise is not None else None))
+                          (noise.scale, noise.clip) if noise is not None else None,
+                          # (the packed schedules: replays follow the device's step counters, so a scheduled
+                          #  agent captures once)
+                          updater.schedule_signature(),
+                          dual.signature() if (dual := getattr(updater, 'dual_schedule', None)) is not None else None))
         norm = self.model.observation_normalizer
         # (the Return normaliser's _low / _high are read through their pointers by the captured launches)
         value_range = self.model.return_normalizer or None
@@ -1502,6 +1510,22 @@ class DDPG(Agent):
         for row in infos[1][infos[1][:, 6] > 0]:
             logger.store('actor/loss', row[0])
         self.last_infos = infos
+        log_learning_rate('actor', self.actor_updater, self)
+        log_learning_rate('critic', self.critic_updater, self)
+
+
+def log_learning_rate(name, updater, agent):
+    """With a scheduler on `updater`: one more key per update, `<name>/learning_rate`, the rate of the last step
+    taken — tonic_lr_schedule_value at the device's step count less one, read behind the update's statistics
+    read-back (the stream has drained: four bytes, no wait of its own).  Without a scheduler no key is added.
+    The agent's `last_learning_rates` keeps {name: (rate, steps taken)}."""
+    if getattr(updater, 'schedule', None) is None:
+        return
+    kept = agent.__dict__.setdefault('last_learning_rates', {})
+    taken = int(updater.state[0])
+    rate = updater.learning_rate(max(taken - 1, 0))
+    logger.store(f'{name}/learning_rate', rate)
+    kept[name] = (rate, taken)
 
 
 def record_reward_range(normalizer, rewards):
@@ -1613,6 +1637,8 @@ class MPO(DDPG):
             for key, value in self.actor_updater.infos(actor_row).items():
                 logger.store('actor/' + key, value)
         self.last_infos, self.last_actor_infos = infos, stats
+        log_learning_rate('actor', self.actor_updater, self)
+        log_learning_rate('critic', self.critic_updater, self)
 
 
 class TD3(DDPG):
@@ -1710,7 +1736,7 @@ class SAC(DDPG):
             return signature
         # (the coefficient itself is read through its pointer by the captured launches)
         return signature + ((tuple(sorted(tuner.hyper.items())), float(tuner.target_entropy),
-                             tuner.log_entropy_coeff.data_ptr()),)
+                             tuner.log_entropy_coeff.data_ptr(), tuner.schedule_signature()),)
 
     def _log_update(self, infos, stats):
         super()._log_update(infos, stats)
@@ -1720,6 +1746,8 @@ class SAC(DDPG):
                 logger.store('entropy_coeff/value', row[2])          # alpha the iteration's two steps used
                 logger.store('entropy_coeff/entropy', -row[1])       # mean -log pi of the actor step's sample
             self.last_entropy_coeff_infos = stats
+        if self.entropy_coeff_updater is not None:
+            log_learning_rate('entropy_coeff', self.entropy_coeff_updater, self)
 
     def save(self, path):
         super().save(path)          # the .pt of the reference, as ever

@@ -94,6 +94,81 @@ def optimizer_rule(rule):
                           alpha=rule.get('alpha', 0.0))
 
 
+def _lr_segments():
+    """class -> (kind, what `period`, `a`, `b` of tonic_lr_segment_t read from the scheduler object)."""
+    s = torch.optim.lr_scheduler
+    return {s.ConstantLR: ('constant', 'total_iters', 'factor', None),
+            s.LinearLR: ('linear', 'total_iters', 'start_factor', 'end_factor'),
+            s.ExponentialLR: ('exponential', None, 'gamma', None),
+            s.StepLR: ('step', 'step_size', 'gamma', None),
+            s.PolynomialLR: ('polynomial', 'total_iters', 'power', None),
+            s.CosineAnnealingLR: ('cosine', 'T_max', 'eta_min', None)}
+
+
+_LR_SERVED = 'the schedulers served are torch.optim.lr_scheduler.ConstantLR, LinearLR, ExponentialLR, StepLR, ' \
+             'PolynomialLR, CosineAnnealingLR and a SequentialLR of two of them'
+
+
+def _lr_segment(scheduler):
+    name = f'{type(scheduler).__module__}.{type(scheduler).__qualname__}'
+    entry = _lr_segments().get(type(scheduler))         # (exact classes: a subclass may compute anything)
+    if entry is None:
+        raise NotImplementedError(f'lr_scheduler={name} does not run on the HIP engine: {_LR_SERVED}')
+    kind, period, a, b = entry
+    values = {}
+    for field, key in (('period', period), ('a', a), ('b', b)):
+        value = getattr(scheduler, key) if key else 0
+        if isinstance(value, torch.Tensor) or isinstance(value, bool) or not isinstance(value, (int, float)) or \
+                (field == 'period' and value != int(value)) or not math.isfinite(value):
+            raise NotImplementedError(f'{type(scheduler).__name__}({key}={value!r}) does not run on the HIP engine: '
+                                      f'{"a whole number" if field == "period" else "a finite Python float"} is needed')
+        values[field] = int(value) if field == 'period' else float(value)
+    return _lib.LrSegment(kind=_lib.LR_KINDS[kind], **values)
+
+
+def lr_schedule_rule(factory, optimizer_factory, default_lr):
+    """The schedule behind the reference-style ``lr_scheduler=lambda optimizer: torch.optim.lr_scheduler.X(optimizer,
+    ...)``, probed like `optimizer_hyperparameters` probes the optimizer: the factory is called on the probe
+    optimizer, then the object's class and attributes are read.  -> the tonic_lr_schedule_t of the C ABI (None without
+    a factory).  Exactly ConstantLR, LinearLR, ExponentialLR, StepLR, PolynomialLR, CosineAnnealingLR and a
+    SequentialLR of two of them (the warm-up form) are served: the rate of step t is their closed form at t = the
+    number of optimizer steps taken (include/tonic_hip.h).  Anything else is rejected by name.  Needs no device."""
+    if factory is None:
+        return None
+    parameter = [torch.nn.Parameter(torch.zeros(1))]
+    probe = optimizer_factory(parameter) if optimizer_factory is not None else \
+        torch.optim.Adam(parameter, lr=default_lr)
+    try:
+        scheduler = factory(probe)
+    except (ValueError, TypeError, KeyError, ZeroDivisionError) as error:      # (torch's own constructors' refusals)
+        raise NotImplementedError(f'lr_scheduler: {type(error).__name__}: {error}') from error
+    sequential = torch.optim.lr_scheduler.SequentialLR
+    schedule = _lib.LrSchedule(count=1)
+    if type(scheduler) is sequential:
+        parts, milestones = list(scheduler._schedulers), list(scheduler._milestones)
+        if len(parts) != 2:
+            raise NotImplementedError(f'SequentialLR of {len(parts)} schedulers does not run on the HIP engine: '
+                                      f'{_LR_SERVED}')
+        if any(isinstance(part, sequential) for part in parts):
+            raise NotImplementedError(f'a nested SequentialLR does not run on the HIP engine: {_LR_SERVED}')
+        if isinstance(milestones[0], bool) or not isinstance(milestones[0], int):
+            raise NotImplementedError(f'SequentialLR(milestones={milestones!r}): a whole number of steps is needed')
+        schedule.count, schedule.milestone = 2, milestones[0]
+        schedule.segment[0], schedule.segment[1] = _lr_segment(parts[0]), _lr_segment(parts[1])
+    else:
+        schedule.segment[0] = _lr_segment(scheduler)
+    lib = _lib.load()
+    if lib.tonic_lr_schedule_check(ctypes.byref(schedule)) != 0:
+        raise NotImplementedError(f'lr_scheduler={type(scheduler).__name__}: {lib.tonic_last_error().decode()}')
+    return schedule
+
+
+def lr_schedule_value(schedule, lr, step):
+    """The rate of the step taken after `step` steps from the base rate (tonic_lr_schedule_value: THE statement)."""
+    return _lib.load().tonic_lr_schedule_value(ctypes.byref(schedule) if schedule is not None else None,
+                                               float(lr), int(step))
+
+
 _CRITIC_LOSSES = {torch.nn.MSELoss: ('mse', None), torch.nn.L1Loss: ('l1', None),
                   torch.nn.SmoothL1Loss: ('smooth_l1', 'beta'), torch.nn.HuberLoss: ('huber', 'delta')}
 
@@ -152,8 +227,9 @@ class _OptimizerState:
     arrivals}.  For Adam and AdamW `exp_avg` / `exp_avg_sq` are views of the first two slots (what
     tonic_adam_step_pair and the fused off-policy iteration take); None for SGD and RMSprop."""
 
-    def __init__(self, lib, hyper, count, device):
+    def __init__(self, lib, hyper, count, device, schedule=None):
         self.lib, self.count = lib, count
+        self.schedule = schedule            # the packed tonic_lr_schedule_t of `lr_schedule_rule`, or None
         self.rule, self.slots = optimizer_slots(lib, hyper, count, device)
         self.state = torch.zeros(4, dtype=torch.int32, device=device)
         self.exp_avg = self.exp_avg_sq = None
@@ -170,10 +246,18 @@ class _OptimizerState:
             target, online, offset, coeff = targets
             assert online.data_ptr() + 4 * offset == params.data_ptr()
             polyak = (_lib.ptr(target), _lib.ptr(online), online.numel(), offset, float(coeff))
-        _lib.check(self.lib.tonic_optimizer_step(
+        step, scheduled = self.lib.tonic_optimizer_step, ()
+        if self.schedule is not None:       # the rate of the step is formed on the device, at its own step count
+            step, scheduled = self.lib.tonic_scheduled_optimizer_step, (ctypes.byref(self.schedule),)
+            what = what.replace('tonic_optimizer_step', 'tonic_scheduled_optimizer_step')
+        _lib.check(step(
             _lib.ptr(params), _lib.ptr(grad_sums), _lib.ptr(self.slots), _lib.ptr(self.state), self.count,
             grad_scale, ctypes.byref(self.rule), stats_kind, float(kl_threshold), float(entropy_coeff),
-            _lib.ptr(adv_stats), _lib.ptr(info_row), skip, *polyak, _lib.current_stream()), what)
+            _lib.ptr(adv_stats), _lib.ptr(info_row), skip, *polyak, *scheduled, _lib.current_stream()), what)
+
+    def learning_rate(self, step=None):
+        """The rate of the step taken after `step` steps (None: the device's count, one read-back: the next step's)."""
+        return lr_schedule_value(self.schedule, self.rule.lr, int(self.state[0]) if step is None else step)
 
 
 def fused_ppo_torso(torso):
@@ -229,6 +313,17 @@ class _StockTorch:
             p.requires_grad_(True)
         self.torch_optimizer = (factory(variables) if factory is not None
                                 else torch.optim.Adam(variables, lr=default_lr))
+        # the real torch scheduler on the real optimizer, stepped after each of its steps (`_stock_optimizer_step`)
+        scheduler = getattr(self, 'lr_scheduler', None)
+        self.torch_scheduler = scheduler(self.torch_optimizer) if scheduler is not None else None
+
+    def _stock_optimizer_step(self):
+        """optimizer.step(), scheduler.step(): torch's order, the step counts of the device path."""
+        self.torch_optimizer.step()
+        if self.torch_scheduler is not None:
+            self.torch_scheduler.step()
+        self.steps_enqueued += 1
+        self.state[0] += 1
 
     def _stock_reduce(self):
         """Several ranks (equal shards): the per-rank mean gradients are averaged."""
@@ -245,14 +340,13 @@ class _StockTorch:
         self._stock_reduce()
         if self.gradient_clip > 0:
             torch.nn.utils.clip_grad_norm_(self.variables, self.gradient_clip)
-        self.torch_optimizer.step()
-        self.steps_enqueued += 1
-        self.state[0] += 1
+        self._stock_optimizer_step()
 
 
 class _FlatUpdater(_StockTorch):
     stats_kind = 0
     torso = None            # (layers, sizes, activation): the tonic_*_torso entries serve this network
+    schedule = None         # the packed tonic_lr_schedule_t of `lr_scheduler=` (`_setup`); None: the rate is `lr`
 
     def _setup(self, flat, hyper):
         self.lib = _lib.load()
@@ -262,7 +356,10 @@ class _FlatUpdater(_StockTorch):
         self.count = flat.count
         self.grad_sums = torch.zeros(self.count + INFO_WIDTH, dtype=torch.float32, device=device)
         self.plain = plain_adam(hyper)      # the pair launch and the fused off-policy iteration serve this rule only
-        self.optim = _OptimizerState(self.lib, hyper, self.count, device)
+        # ... scheduled or not: `schedule` is the packed tonic_lr_schedule_t of `lr_scheduler=`, None without one
+        self.schedule = lr_schedule_rule(getattr(self, 'lr_scheduler', None), getattr(self, 'optimizer', None),
+                                         hyper['lr'])
+        self.optim = _OptimizerState(self.lib, hyper, self.count, device, self.schedule)
         self.rule, self.slots, self.state = self.optim.rule, self.optim.slots, self.optim.state
         self.exp_avg, self.exp_avg_sq = self.optim.exp_avg, self.optim.exp_avg_sq
         self.steps_enqueued = 0     # host mirror of state[0] (off-policy: every enqueued step is taken)
@@ -280,6 +377,16 @@ class _FlatUpdater(_StockTorch):
         self.world_size = 1
         if torch.distributed.is_available() and torch.distributed.is_initialized():
             self.world_size = torch.distributed.get_world_size()
+
+    def learning_rate(self, step=None):
+        """The rate the next optimizer step will use (`step`: the rate of the step taken after that many steps)."""
+        if self.stock and step is None:
+            return float(self.torch_optimizer.param_groups[0]['lr'])
+        return self.optim.learning_rate(step)
+
+    def schedule_signature(self):
+        """What a captured graph bakes in of the schedule (None without one)."""
+        return self.schedule.signature() if self.schedule is not None else None
 
     def _workspace_for(self, n):
         """Scratch of the grad kernels: per-workgroup partial images for the fused kernels; for
@@ -356,21 +463,27 @@ def enqueue_step_pair(actor, critic, n_local, adv_stats, actor_info, critic_info
     actor.enqueue_clip(n_global, actor.stop_flag_ptr())
     critic.enqueue_clip(n_global)
     p = _lib.ptr
-    _lib.check(actor.lib.tonic_adam_step_pair(
+    # (`plain` is the rule; a schedule on either network keeps the ONE launch, through the scheduled pair)
+    entry, schedules = 'tonic_adam_step_pair', ()
+    if actor.schedule is not None or critic.schedule is not None:
+        entry = 'tonic_scheduled_adam_step_pair'
+        schedules = tuple(ctypes.byref(u.schedule) if u.schedule is not None else None for u in (actor, critic))
+    _lib.check(getattr(actor.lib, entry)(
         p(actor.flat.flat), p(actor.grad_sums), p(actor.exp_avg), p(actor.exp_avg_sq),
         p(actor.state), actor.count, ha['lr'], actor.stats_kind, float(actor.kl_threshold),
         float(actor.entropy_coeff), p(adv_stats), p(actor_info), actor.stop_flag_ptr(),
         p(critic.flat.flat), p(critic.grad_sums), p(critic.exp_avg), p(critic.exp_avg_sq),
         p(critic.state), critic.count, hc['lr'], critic.stats_kind, p(critic_info),
-        1.0 / (n_local * actor.world_size), ha['betas'][0], ha['betas'][1], ha['eps'],
-        _lib.current_stream()), 'tonic_adam_step_pair')
+        1.0 / (n_local * actor.world_size), ha['betas'][0], ha['betas'][1], ha['eps'], *schedules,
+        _lib.current_stream()), entry)
 
 
 class ClippedRatio(_FlatUpdater):
     stats_kind = 1
 
     def __init__(self, optimizer=None, ratio_clip=0.2, kl_threshold=0.015, entropy_coeff=0,
-                 gradient_clip=0):
+                 gradient_clip=0, lr_scheduler=None):
+        self.lr_scheduler = lr_scheduler
         self.optimizer = optimizer
         self.ratio_clip = ratio_clip
         self.kl_threshold = kl_threshold
@@ -498,9 +611,9 @@ class StochasticPolicyGradient(ClippedRatio):
     Adam step.  Same fused kernel as ClippedRatio in its plain mode (`ratio_clip < 0` in the C ABI:
     the gradient of -adv * logp is -adv, nothing to clip) and no KL stop."""
 
-    def __init__(self, optimizer=None, entropy_coeff=0, gradient_clip=0):
+    def __init__(self, optimizer=None, entropy_coeff=0, gradient_clip=0, lr_scheduler=None):
         super().__init__(optimizer=optimizer, ratio_clip=-1.0, kl_threshold=float('inf'),
-                         entropy_coeff=entropy_coeff, gradient_clip=gradient_clip)
+                         entropy_coeff=entropy_coeff, gradient_clip=gradient_clip, lr_scheduler=lr_scheduler)
 
     def __call__(self, observations, actions, advantages, log_probs):
         out = super().__call__(observations, actions, advantages, log_probs)
@@ -818,7 +931,8 @@ class TrustRegionPolicyGradient:
 class VRegression(_FlatUpdater):
     stats_kind = 2
 
-    def __init__(self, loss=None, optimizer=None, gradient_clip=0):
+    def __init__(self, loss=None, optimizer=None, gradient_clip=0, lr_scheduler=None):
+        self.lr_scheduler = lr_scheduler
         if loss is not None and not isinstance(loss, torch.nn.MSELoss):
             raise NotImplementedError('only the default MSE loss is fused')
         self.loss = loss
@@ -1231,9 +1345,7 @@ class _TwinCriticQLearning(_QUpdater):
                 torch.distributed.all_reduce(p.grad)
         if self.gradient_clip > 0:
             torch.nn.utils.clip_grad_norm_(self.variables, self.gradient_clip)
-        self.torch_optimizer.step()
-        self.steps_enqueued += 1
-        self.state[0] += 1
+        self._stock_optimizer_step()
         info_row[:row.numel()] = row
         info_row[6] = 1.0
 
@@ -1276,7 +1388,8 @@ class DeterministicQLearning(_TwinCriticQLearning):
     """critics.py:56-86 (DDPG): ONE critic, target actor, no target noise."""
     kind, default_lr = 2, 1e-3
 
-    def __init__(self, loss=None, optimizer=None, gradient_clip=0):
+    def __init__(self, loss=None, optimizer=None, gradient_clip=0, lr_scheduler=None):
+        self.lr_scheduler = lr_scheduler
         self.loss = loss
         self.optimizer = optimizer
         self.gradient_clip = gradient_clip
@@ -1303,6 +1416,10 @@ class QRegression(_TwinCriticQLearning):
     arithmetic as stock torch operators.  ``__call__`` returns dict(loss=, q=) with `q` the batch mean, as
     `DeterministicQLearning` here does."""
     default_lr = 1e-3
+
+    # (the constructor is the reference's, critics.py:33, argument for argument: a scheduler is the attribute
+    #  `lr_scheduler`, assigned before `initialize`, which reads it like every other updater's)
+    lr_scheduler = None
 
     def __init__(self, loss=None, optimizer=None, gradient_clip=0):
         self.loss = loss
@@ -1389,7 +1506,8 @@ class TwinCriticDeterministicQLearning(_TwinCriticQLearning):
     """critics.py:137-182 (TD3): target actor + clipped target-action noise."""
     kind, default_lr = 0, 1e-3
 
-    def __init__(self, loss=None, optimizer=None, target_action_noise=None, gradient_clip=0):
+    def __init__(self, loss=None, optimizer=None, target_action_noise=None, gradient_clip=0, lr_scheduler=None):
+        self.lr_scheduler = lr_scheduler
         self.loss = loss
         self.optimizer = optimizer
         self.gradient_clip = gradient_clip
@@ -1404,7 +1522,8 @@ class TwinCriticSoftQLearning(_TwinCriticQLearning):
     kind, default_lr = 1, 3e-4
     head_family = 'sac'
 
-    def __init__(self, loss=None, optimizer=None, entropy_coeff=0.2, gradient_clip=0):
+    def __init__(self, loss=None, optimizer=None, entropy_coeff=0.2, gradient_clip=0, lr_scheduler=None):
+        self.lr_scheduler = lr_scheduler
         self.loss = loss
         self.optimizer = optimizer
         self.gradient_clip = gradient_clip
@@ -1460,7 +1579,8 @@ class DistributionalDeterministicQLearning(_DistributionalQLearning):
     stats_kind = 4          # {loss}
     entries = ('tonic_distributional_q_grad', 'tonic_weighted_distributional_q_grad')
 
-    def __init__(self, optimizer=None, gradient_clip=0):
+    def __init__(self, optimizer=None, gradient_clip=0, lr_scheduler=None):
+        self.lr_scheduler = lr_scheduler
         self.optimizer = optimizer
         self.gradient_clip = gradient_clip
 
@@ -1488,7 +1608,8 @@ class TwinCriticDistributionalDeterministicQLearning(_DistributionalQLearning):
     stats_kind = 3          # {loss, q1 mean, q2 mean}
     entries = ('tonic_twin_distributional_q_grad', 'tonic_weighted_twin_distributional_q_grad')
 
-    def __init__(self, optimizer=None, target_action_noise=None, gradient_clip=0):
+    def __init__(self, optimizer=None, target_action_noise=None, gradient_clip=0, lr_scheduler=None):
+        self.lr_scheduler = lr_scheduler
         self.optimizer = optimizer
         self.gradient_clip = gradient_clip
         self.target_action_noise = target_action_noise or TargetActionNoise(scale=0.2, clip=0.5)
@@ -1523,7 +1644,8 @@ class ExpectedSARSA(_TwinCriticQLearning):
     stock_capable = False
     head_family = 'mpo'
 
-    def __init__(self, num_samples=20, loss=None, optimizer=None, gradient_clip=0):
+    def __init__(self, num_samples=20, loss=None, optimizer=None, gradient_clip=0, lr_scheduler=None):
+        self.lr_scheduler = lr_scheduler
         _check_num_samples('ExpectedSARSA', num_samples)
         self.loss = loss
         self.num_samples = num_samples
@@ -1597,9 +1719,7 @@ class _ActorQGradient(_QUpdater):
                 torch.distributed.all_reduce(p.grad)
         if self.gradient_clip > 0:
             torch.nn.utils.clip_grad_norm_(self.variables, self.gradient_clip)
-        self.torch_optimizer.step()
-        self.steps_enqueued += 1
-        self.state[0] += 1
+        self._stock_optimizer_step()
         info_row[0] = row[0]
         info_row[6] = 1.0
         if targets is not None:                         # update_targets right after (ddpg.py:112)
@@ -1638,7 +1758,8 @@ class DeterministicPolicyGradient(_ActorQGradient):
     """actors.py:159-189 on `model.critic` (= critic_1 for TD3, td3.py:36)."""
     kind, default_lr = 0, 1e-3
 
-    def __init__(self, optimizer=None, gradient_clip=0):
+    def __init__(self, optimizer=None, gradient_clip=0, lr_scheduler=None):
+        self.lr_scheduler = lr_scheduler
         self.optimizer = optimizer
         self.gradient_clip = gradient_clip
 
@@ -1648,7 +1769,8 @@ class DistributionalDeterministicPolicyGradient(_ActorQGradient):
     (tonic_distributional_actor_grad)."""
     stock_capable = False
 
-    def __init__(self, optimizer=None, gradient_clip=0):
+    def __init__(self, optimizer=None, gradient_clip=0, lr_scheduler=None):
+        self.lr_scheduler = lr_scheduler
         self.optimizer = optimizer
         self.gradient_clip = gradient_clip
 
@@ -1699,7 +1821,7 @@ class MaximumAPosterioriPolicyOptimization(_ActorQGradient):
                  epsilon_std=1e-6, initial_log_temperature=1., initial_log_alpha_mean=1.,
                  initial_log_alpha_std=10., min_log_dual=-18., per_dim_constraining=True,
                  action_penalization=True, actor_optimizer=None, dual_optimizer=None,
-                 gradient_clip=0):
+                 gradient_clip=0, actor_lr_scheduler=None, dual_lr_scheduler=None):
         _check_num_samples('MaximumAPosterioriPolicyOptimization', num_samples)
         self.num_samples = num_samples
         self.per_dim_constraining = per_dim_constraining
@@ -1713,6 +1835,8 @@ class MaximumAPosterioriPolicyOptimization(_ActorQGradient):
         self.optimizer = actor_optimizer
         self.dual_hyper = optimizer_hyperparameters(actor_optimizer, 1e-2)      # actors.py:291-292
         self.gradient_clip = gradient_clip
+        self.lr_scheduler, self.dual_lr_scheduler = actor_lr_scheduler, dual_lr_scheduler
+        self.dual_schedule = lr_schedule_rule(dual_lr_scheduler, actor_optimizer, 1e-2)   # (the duals' own count)
 
     def initialize(self, model, action_space=None):
         super().initialize(model)
@@ -1722,7 +1846,7 @@ class MaximumAPosterioriPolicyOptimization(_ActorQGradient):
             [self.initial_log_alpha_std] * K + [self.initial_log_temperature]
         self.duals = torch.tensor(duals, dtype=torch.float32, device=device)
         self.dual_grads = torch.zeros(2 * K + 2 + INFO_WIDTH, dtype=torch.float32, device=device)
-        self.dual_optim = _OptimizerState(self.lib, self.dual_hyper, 2 * K + 2, device)
+        self.dual_optim = _OptimizerState(self.lib, self.dual_hyper, 2 * K + 2, device, self.dual_schedule)
         self.dual_slots, self.dual_state = self.dual_optim.slots, self.dual_optim.state
         self.dual_exp_avg, self.dual_exp_avg_sq = self.dual_optim.exp_avg, self.dual_optim.exp_avg_sq
         self.mpo_stats = torch.zeros(9 + 2 * K, dtype=torch.float32, device=device)
@@ -1817,7 +1941,8 @@ class TwinCriticSoftDeterministicPolicyGradient(_ActorQGradient):
     kind, default_lr = 1, 3e-4
     head_family = 'sac'
 
-    def __init__(self, optimizer=None, entropy_coeff=0.2, gradient_clip=0):
+    def __init__(self, optimizer=None, entropy_coeff=0.2, gradient_clip=0, lr_scheduler=None):
+        self.lr_scheduler = lr_scheduler
         self.optimizer = optimizer
         self.gradient_clip = gradient_clip
         self.entropy_coeff = entropy_coeff
@@ -1840,7 +1965,8 @@ class EntropyCoeffTuning(_FlatUpdater):
     default_lr = 3e-4
     INFO = ('loss', 'log_prob', 'value')
 
-    def __init__(self, target_entropy=None, initial_entropy_coeff=1.0, optimizer=None):
+    def __init__(self, target_entropy=None, initial_entropy_coeff=1.0, optimizer=None, lr_scheduler=None):
+        self.lr_scheduler = lr_scheduler
         initial = float(initial_entropy_coeff)
         if not (math.isfinite(initial) and initial > 0):
             raise ValueError(f'initial_entropy_coeff={initial_entropy_coeff!r}: the coefficient is exp(log_entropy_coeff), '
@@ -1851,6 +1977,7 @@ class EntropyCoeffTuning(_FlatUpdater):
         self.initial_entropy_coeff = initial
         self.optimizer = optimizer
         self.hyper = optimizer_hyperparameters(optimizer, self.default_lr)      # (the refusals, by name, right here)
+        lr_schedule_rule(lr_scheduler, optimizer, self.default_lr)
         self.log_entropy_coeff = None
 
     def initialize(self, model, action_size=None):
