@@ -1350,6 +1350,54 @@ int tonic_mpo_dual_step_joint(const double* d_column_sums, float* d_duals, doubl
                               double epsilon_penalty, double epsilon_mean, double epsilon_std,
                               int32_t action_penalization, int32_t joint_kl, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * DMPO: MPO on a categorical critic (additive under ABI 22).  The critic has D4PG's layout,
+ *   tonic_mlp_actor_param_count(O + A, H, NA, 1), d_values [NA] is its support (float32, ascending,
+ *   2 <= NA <= 64); S, H, the tiling of the rows (s * B + m) and d_eps [S, B, A] as in the MPO entries above.
+ *   No reference line states the critic step: MPO's ExpectedSARSA (updaters/critics.py:238-282) with D4PG's
+ *   categorical loss (critics.py:100-122) in place of the regression.
+ *
+ * tonic_distributional_mpo_workspace_bytes — a function of its arguments alone (no GPU, no tuning switch), never
+ *   below tonic_mpo_workspace_bytes(B, O, A, H, S).  All three entries take a workspace of this size.
+ * tonic_distributional_expected_sarsa_grad — per row m: a'_s = loc_t(s') + sigma_t(s') eps_s;
+ *   p_bar = (1 / S) sum_s softmax(target_critic(s', a'_s)), the mixture of the S target distributions;
+ *   T = CategoricalWithSupport.project(r + discount z, p_bar) (linear in p: the mixture is projected, once);
+ *   loss_m = -sum_i T_i log_softmax(critic(s, a))_i.  Output: gradient SUMS of the critic +
+ *   {sum loss_m, sum q_m, 0, 0, 0, B, 0, 0}, q_m = sum_i softmax(critic(s, a))_i z_i (float64, fixed order).
+ * tonic_distributional_mpo_actor_grad(_shard) — tonic_mpo_actor_grad_joint / tonic_mpo_actor_grad_shard_joint with
+ *   the E-step's q[s * B + m] = sum_i softmax(target_critic(s_m, a_s))_i z_i; everything else, and the second half
+ *   tonic_mpo_dual_step_joint, as there.
+ * TONIC_ERR_INVALID_ARGUMENT: a NULL pointer, B <= 0, NA outside 2 .. 64, S outside 1 .. 256, an unknown H,
+ *   joint_kl not 0 / 1; then TONIC_ERR_WORKSPACE: a workspace below the query's answer. */
+int64_t tonic_distributional_mpo_workspace_bytes(int32_t B, int32_t O, int32_t A, int32_t H, int32_t S,
+                                                 int32_t NA);
+int tonic_distributional_expected_sarsa_grad(const float* d_target_actor, const float* d_target_critic,
+                                             const float* d_critic, const float* d_norm_mean,
+                                             const float* d_norm_std, double norm_clip,
+                                             const float* d_observations, const float* d_actions,
+                                             const float* d_next_observations, const float* d_rewards,
+                                             const float* d_discounts, const float* d_eps, const float* d_values,
+                                             float* d_grad_sums, int32_t B, int32_t O, int32_t H, int32_t A,
+                                             int32_t S, int32_t NA, void* d_workspace, int64_t workspace_bytes,
+                                             void* stream);
+int tonic_distributional_mpo_actor_grad(const float* d_actor_params, const float* d_target_actor,
+                                        const float* d_target_critic, float* d_duals, double min_log_dual,
+                                        const float* d_norm_mean, const float* d_norm_std, double norm_clip,
+                                        const float* d_observations, const float* d_eps, const float* d_values,
+                                        float* d_grad_sums, float* d_dual_grads, float* d_stats, int32_t B,
+                                        int32_t O, int32_t H, int32_t A, int32_t S, int32_t NA, double epsilon,
+                                        double epsilon_penalty, double epsilon_mean, double epsilon_std,
+                                        int32_t action_penalization, int32_t joint_kl, void* d_workspace,
+                                        int64_t workspace_bytes, void* stream);
+int tonic_distributional_mpo_actor_grad_shard(const float* d_actor_params, const float* d_target_actor,
+                                              const float* d_target_critic, float* d_duals, double min_log_dual,
+                                              const float* d_norm_mean, const float* d_norm_std, double norm_clip,
+                                              const float* d_observations, const float* d_eps,
+                                              const float* d_values, float* d_grad_sums, double* d_column_sums,
+                                              int32_t B, int32_t O, int32_t H, int32_t A, int32_t S, int32_t NA,
+                                              int32_t action_penalization, int32_t joint_kl, void* d_workspace,
+                                              int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

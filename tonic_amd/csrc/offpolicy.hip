@@ -491,6 +491,60 @@ __global__ void loss_stats_kernel(const float* loss_m, float* stats, int B) {
   }
 }
 
+// ---- DMPO: MPO's sampled actions on the categorical critic.  The target critic's logits on the S * B tiled rows
+// (row s * B + m), one wave per row, lane = atom: the row's mean value sum_i softmax(logits)_i z_i -> tq — what the
+// E-step reads where the scalar critic leaves its output — and, log_norm != null, the row's log-normaliser
+// max + log(sum_i exp(logit_i - max)), which the mixture kernel below turns logits into probabilities with.
+__global__ __launch_bounds__(256) void distributional_value_kernel(const float* logits, int ld, const float* values,
+                                                                   int NA, float* tq, float* log_norm, int rows) {
+  AtomRow r;
+  if (!atom_row(values, NA, rows, r)) return;
+  float ln;
+  const float p = wave_softmax(logits[(int64_t)r.m * ld + r.i], r.live, &ln);
+  const float value = wave_sum(r.live ? p * r.z : 0.f);
+  if (r.lane == 0) {
+    tq[r.m] = value;
+    if (log_norm != nullptr) log_norm[r.m] = ln;
+  }
+}
+
+// The distributional Expected-SARSA loss, one wave per state m, lane = atom:
+//   p_bar = (1 / S) sum_s softmax(target_logits[s * B + m])   (the mixture of the S sampled actions' distributions;
+//                                                              the projection is linear in p: it runs once, on p_bar)
+//   T = project(r + disc * z, p_bar) ; loss = -sum_i T_i log_softmax(logits)_i ; dlogits_i = softmax_i sum T - T_i
+// The loop over s reads each row's log-normaliser from distributional_value_kernel, exp(logit - log_norm), so it
+// holds no cross-lane step however many samples there are.  sample_m [2][Bp] = {loss, q} per state,
+// q = sum_i softmax(logits)_i z_i the ONLINE critic's mean (the logged critic/q).
+__global__ __launch_bounds__(256) void mixture_critic_loss_kernel(
+    const float* target_logits, const float* target_log_norm, const float* logits, int ld, const float* rewards,
+    const float* discounts, const float* values, int NA, float* dlogits, float* sample_m, int B, int Bp, int S) {
+  AtomRow r;
+  if (!atom_row(values, NA, B, r)) return;
+  float mix = 0.f;
+  for (int s = 0; s < S; ++s) {
+    const int64_t row = (int64_t)s * B + r.m;
+    mix += expf(target_logits[row * ld + r.i] - target_log_norm[row]);
+  }
+  const float p_next = r.live ? mix / (float)S : 0.f;
+  const float target = projected_target(r, values, NA, rewards[r.m], discounts[r.m], p_next);
+  const CriticRow c = critic_row(r, logits[(int64_t)r.m * ld + r.i], target, wave_sum(target));
+  const float q = wave_sum(r.live ? c.p * r.z : 0.f);
+  if (r.lane < ld) dlogits[(int64_t)r.m * ld + r.lane] = c.grad;
+  if (r.lane == 0) { sample_m[r.m] = c.loss; sample_m[Bp + r.m] = q; }
+}
+
+// the 8 statistics {sum loss, sum q, 0, 0, 0, B, 0, 0} (ExpectedSARSA's row) from sample_m [2][Bp] (fixed order,
+// float64)
+__global__ void mixture_loss_stats_kernel(const float* sample_m, float* stats, int B, int Bp) {
+  double a = 0, b = 0, unused = 0;
+  for (int m = threadIdx.x; m < B; m += blockDim.x) { a += sample_m[m]; b += sample_m[Bp + m]; }
+  block_sum3(a, b, unused);
+  if (threadIdx.x == 0) {
+    stats[0] = (float)a; stats[1] = (float)b;
+    for (int i = 2; i < 8; ++i) stats[i] = i == 5 ? (float)B : 0.f;
+  }
+}
+
 // ---- MPO (agents/mpo.py; updaters/critics.py:238-282, updaters/actors.py:270-464)
 // GaussianPolicyHead (models/actors.py:69-98): loc = tanh(.) (applied by the forward), sigma =
 // clamp(softplus(spre), scale_lo, scale_hi).
@@ -2603,11 +2657,30 @@ struct MpoBuffers {
   }
 };
 
-// target_actor(obs) -> S sampled actions per state -> target_critic on the tiled rows: tq [S * B]
+// DMPO: MPO's arrays as they are, and behind them the categorical critic's — the target logits of the S * B tiled
+// rows with their log-normalisers, the online critic's logits and their gradient, and sample_m [2][Bp].  The
+// critics' hidden regions (t_h1, c_h1, dh2) are MPO's: a D4PG-shaped critic has the scalar critic's torso.
+// NA == 0 (mpo_actor_grad on the scalar critic): MPO's arrays and nothing more.
+struct DmpoBuffers : MpoBuffers {
+  float *t_logits = nullptr, *t_log_norm = nullptr, *logits = nullptr, *dlogits = nullptr, *sample_m = nullptr;
+  DmpoBuffers(Workspace& ws, int B, int O, int A, int32_t H, int S, int NA) : MpoBuffers(ws, B, O, A, H, S) {
+    if (NA == 0) return;
+    const int64_t Bp = pad16(B), Rp = pad16(S * B), ldl = pad16(NA);
+    t_logits = ws.take(Rp * ldl); t_log_norm = ws.take(Rp);
+    logits = ws.take(Bp * ldl); dlogits = ws.take(Bp * ldl); sample_m = ws.take(2 * Bp);
+  }
+};
+
+// The categorical critic of a DMPO entry: its support, and where the tiled rows' logits and (null: not wanted)
+// log-normalisers go.
+struct SampledDistribution { const float* values; int NA; float* t_logits; float* t_log_norm; };
+
+// target_actor(obs) -> S sampled actions per state -> target_critic on the tiled rows: tq [S * B].  dist != null:
+// the critic is categorical — its logits on the tiled rows, then each row's mean into tq.
 int mpo_sampled_values(const float* d_target_actor, const float* d_target_critic,
                        const float* d_norm_mean, const float* d_norm_std, double norm_clip,
                        const float* d_obs, const float* d_eps, int B, int O, int H, int A, int S,
-                       const MpoBuffers& w, hipStream_t st) {
+                       const MpoBuffers& w, hipStream_t st, const SampledDistribution* dist = nullptr) {
   const int ldx = pitch16(O + A), ldh = pad16(A), threads = 256;
   const ActorShape as = actor_shape(O, H, A, 2);
   TRY(actor_forward(d_target_actor, as, d_obs, B, w.a_h1, w.a_h2, w.loc_t, w.spre_t, ldh, true, st));
@@ -2615,14 +2688,26 @@ int mpo_sampled_values(const float* d_target_actor, const float* d_target_critic
   hipLaunchKernelGGL(gaussian_tile_kernel, dim3((unsigned)((items + threads - 1) / threads)),
                      dim3(threads), 0, st, d_obs, w.loc_t, w.spre_t, d_eps, ldh, d_norm_mean,
                      d_norm_std, clip_bound(norm_clip), w.act, w.X, B, O, A, S, ldx, as.scale_lo, as.scale_hi);
-  return critics_forward(d_target_critic, critic_shape(O, A, H), 1, w.X, ldx, S * B, pad16(S * B),
-                         w.t_h1, w.t_h2, w.tq, st);
+  if (dist == nullptr)
+    return critics_forward(d_target_critic, critic_shape(O, A, H), 1, w.X, ldx, S * B, pad16(S * B),
+                           w.t_h1, w.t_h2, w.tq, st);
+  const int ldl = pad16(dist->NA), rows = S * B;
+  TRY(actor_forward(d_target_critic, actor_shape(O + A, H, dist->NA, 1), w.X, rows, w.t_h1, w.t_h2, dist->t_logits,
+                    dist->t_logits, ldl, false, st, nullptr, nullptr, ldx));
+  hipLaunchKernelGGL(distributional_value_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, dist->t_logits, ldl,
+                     dist->values, dist->NA, w.tq, dist->t_log_norm, rows);
+  return TONIC_OK;
 }
 
 }  // namespace
 
 extern "C" int64_t tonic_mpo_workspace_bytes(int32_t B, int32_t O, int32_t A, int32_t H, int32_t S) {
   return measure<MpoBuffers>(B, O, A, H, S);
+}
+
+extern "C" int64_t tonic_distributional_mpo_workspace_bytes(int32_t B, int32_t O, int32_t A, int32_t H, int32_t S,
+                                                            int32_t NA) {
+  return measure<DmpoBuffers>(B, O, A, H, S, NA);
 }
 
 namespace {
@@ -2688,6 +2773,47 @@ extern "C" int tonic_expected_sarsa_grad_loss(
                              d_grad_sums, B, O, H, A, S, loss, d_workspace, workspace_bytes, stream);
 }
 
+// DMPO's critic step: Expected SARSA on the categorical critic (D4PG's layout, tonic_mlp_actor_param_count(O + A, H,
+// NA, 1)).  The target is the projection of the MIXTURE of the target critic's distributions at the S sampled next
+// actions; the online critic takes the cross-entropy against it, as in tonic_distributional_q_grad.
+extern "C" int tonic_distributional_expected_sarsa_grad(
+    const float* d_target_actor, const float* d_target_critic, const float* d_critic,
+    const float* d_norm_mean, const float* d_norm_std, double norm_clip,
+    const float* d_observations, const float* d_actions, const float* d_next_observations,
+    const float* d_rewards, const float* d_discounts, const float* d_eps, const float* d_values,
+    float* d_grad_sums, int32_t B, int32_t O, int32_t H, int32_t A, int32_t S, int32_t NA, void* d_workspace,
+    int64_t workspace_bytes, void* stream) {
+  TONIC_REQUIRE(d_target_actor && d_target_critic && d_critic && d_norm_mean && d_norm_std &&
+                    d_observations && d_actions && d_next_observations && d_rewards &&
+                    d_discounts && d_eps && d_values && d_grad_sums && d_workspace && B > 0 && S >= 1 &&
+                    S <= kMpoMaxSamples && NA >= 2 && NA <= 64 && hidden_known(H),
+                TONIC_ERR_INVALID_ARGUMENT,
+                "tonic_distributional_expected_sarsa_grad: bad argument (1 <= samples <= 256, 2 <= atoms <= 64)");
+  TONIC_REQUIRE(workspace_bytes >= tonic_distributional_mpo_workspace_bytes(B, O, A, H, S, NA), TONIC_ERR_WORKSPACE,
+                "tonic_distributional_expected_sarsa_grad: workspace too small");
+  hipStream_t st = as_stream(stream);
+  const int Bp = pad16(B), ldx = pitch16(O + A), ldl = pad16(NA), threads = 256;
+  Workspace ws{static_cast<char*>(d_workspace), 0};
+  const DmpoBuffers w(ws, B, O, A, H, S, NA);
+  const ActorShape cs = actor_shape(O + A, H, NA, 1);
+  const SampledDistribution dist{d_values, NA, w.t_logits, w.t_log_norm};
+  TRY(mpo_sampled_values(d_target_actor, d_target_critic, d_norm_mean, d_norm_std, norm_clip,
+                         d_next_observations, d_eps, B, O, H, A, S, w, st, &dist));
+  hipLaunchKernelGGL(encode_kernel, dim3((B * (O + A) + threads - 1) / threads), dim3(threads), 0,
+                     st, d_observations, d_actions, d_norm_mean, d_norm_std, clip_bound(norm_clip),
+                     w.X2, B, O, A, ldx);
+  TRY(actor_forward(d_critic, cs, w.X2, B, w.c_h1, w.c_h2, w.logits, w.logits, ldl, false, st, nullptr, nullptr,
+                    ldx));
+  hipLaunchKernelGGL(mixture_critic_loss_kernel, dim3((B + 3) / 4), dim3(256), 0, st, w.t_logits, w.t_log_norm,
+                     w.logits, ldl, d_rewards, d_discounts, d_values, NA, w.dlogits, w.sample_m, B, Bp, S);
+  hipLaunchKernelGGL(mixture_loss_stats_kernel, dim3(1), dim3(1024), 0, st, w.sample_m,
+                     d_grad_sums + actor_count(cs), B, Bp);
+  TRY(actor_shaped_backward(d_critic, cs, w.X2, ldx, B, w.c_h1, w.c_h2, w.dlogits, nullptr, ldl, w.dh2, w.dh1,
+                            d_grad_sums, nullptr, 0, 0, st));
+  TONIC_CHECK_LAUNCH("tonic_distributional_expected_sarsa_grad");
+  return TONIC_OK;
+}
+
 namespace {
 static_assert(kMpoMaxSamples == 256, "the messages of the MPO entries name the bound");
 
@@ -2714,7 +2840,10 @@ int mpo_actor_grad(
     const float* d_observations, const float* d_eps, float* d_grad_sums, float* d_dual_grads,
     float* d_stats, int32_t B, int32_t O, int32_t H, int32_t A, int32_t S, double epsilon,
     double epsilon_penalty, double epsilon_mean, double epsilon_std, int32_t action_penalization,
-    int32_t joint_kl, void* d_workspace, int64_t workspace_bytes, void* stream, double* d_column_sums, bool shard) {
+    int32_t joint_kl, void* d_workspace, int64_t workspace_bytes, void* stream, double* d_column_sums, bool shard,
+    const float* d_values = nullptr, int32_t NA = 0) {
+  // NA != 0 (the tonic_distributional_mpo_* entries, which check the pair): the E-step's q are the means of the
+  // categorical target critic's distributions over the support d_values; nothing else differs
   // (a rank's shard of the batch: only the column sums leave, the duals' half follows the all-reduce — mpo_dual_step)
   TONIC_REQUIRE(!shard || d_column_sums != nullptr, TONIC_ERR_INVALID_ARGUMENT,
                 "tonic_mpo_actor_grad_shard: null column sums");
@@ -2724,15 +2853,16 @@ int mpo_actor_grad(
                     d_workspace && B > 0 && S >= 1 && S <= kMpoMaxSamples && A >= 1 && A <= 64 &&
                     (joint_kl == 0 || joint_kl == 1) && hidden_known(H),
                 TONIC_ERR_INVALID_ARGUMENT, "tonic_mpo_actor_grad: bad argument (1 <= samples <= 256, A <= 64)");
-  TONIC_REQUIRE(workspace_bytes >= tonic_mpo_workspace_bytes(B, O, A, H, S), TONIC_ERR_WORKSPACE,
+  TONIC_REQUIRE(workspace_bytes >= measure<DmpoBuffers>(B, O, A, H, S, NA), TONIC_ERR_WORKSPACE,
                 "tonic_mpo_actor_grad: workspace too small");
   hipStream_t st = as_stream(stream);
   const int ldh = pad16(A);
   Workspace ws{static_cast<char*>(d_workspace), 0};
-  const MpoBuffers w(ws, B, O, A, H, S);
+  const DmpoBuffers w(ws, B, O, A, H, S, NA);
   const ActorShape as = actor_shape(O, H, A, 2);
+  const SampledDistribution dist{d_values, NA, w.t_logits, nullptr};       // (the E-step needs the rows' means alone)
   TRY(mpo_sampled_values(d_target_actor, d_target_critic, d_norm_mean, d_norm_std, norm_clip,
-                         d_observations, d_eps, B, O, H, A, S, w, st));
+                         d_observations, d_eps, B, O, H, A, S, w, st, NA != 0 ? &dist : nullptr));
   TRY(actor_forward(d_actor_params, as, d_observations, B, w.o_h1, w.o_h2, w.loc, w.spre, ldh, true,
                     st));
   launch_mpo_state((S + 63) / 64, dim3((B + 3) / 4), st, w.tq, w.act, w.loc_t, w.spre_t, w.loc, w.spre, ldh, d_duals,
@@ -2816,6 +2946,38 @@ extern "C" int tonic_mpo_actor_grad_shard_joint(
                         d_norm_std, norm_clip, d_observations, d_eps, d_grad_sums, nullptr, nullptr, B, O, H, A, S,
                         0.0, 0.0, 0.0, 0.0, action_penalization, joint_kl, d_workspace, workspace_bytes, stream,
                         d_column_sums, true);
+}
+
+// DMPO's actor step: tonic_mpo_actor_grad_joint and its shard form on a categorical target critic (D4PG's layout) —
+// the E-step's q[s * B + m] = sum_i softmax(target_critic(s_m, a_s))_i z_i; the dual half is tonic_mpo_dual_step_joint
+extern "C" int tonic_distributional_mpo_actor_grad(
+    const float* d_actor_params, const float* d_target_actor, const float* d_target_critic,
+    float* d_duals, double min_log_dual, const float* d_norm_mean, const float* d_norm_std, double norm_clip,
+    const float* d_observations, const float* d_eps, const float* d_values, float* d_grad_sums, float* d_dual_grads,
+    float* d_stats, int32_t B, int32_t O, int32_t H, int32_t A, int32_t S, int32_t NA, double epsilon,
+    double epsilon_penalty, double epsilon_mean, double epsilon_std, int32_t action_penalization,
+    int32_t joint_kl, void* d_workspace, int64_t workspace_bytes, void* stream) {
+  TONIC_REQUIRE(d_values != nullptr && NA >= 2 && NA <= 64, TONIC_ERR_INVALID_ARGUMENT,
+                "tonic_distributional_mpo_actor_grad: bad argument (2 <= atoms <= 64)");
+  return mpo_actor_grad(d_actor_params, d_target_actor, d_target_critic, d_duals, min_log_dual, d_norm_mean,
+                        d_norm_std, norm_clip, d_observations, d_eps, d_grad_sums, d_dual_grads,
+                        d_stats, B, O, H, A, S, epsilon, epsilon_penalty, epsilon_mean, epsilon_std,
+                        action_penalization, joint_kl, d_workspace, workspace_bytes, stream, nullptr, false, d_values,
+                        NA);
+}
+
+extern "C" int tonic_distributional_mpo_actor_grad_shard(
+    const float* d_actor_params, const float* d_target_actor, const float* d_target_critic,
+    float* d_duals, double min_log_dual, const float* d_norm_mean, const float* d_norm_std, double norm_clip,
+    const float* d_observations, const float* d_eps, const float* d_values, float* d_grad_sums,
+    double* d_column_sums, int32_t B, int32_t O, int32_t H, int32_t A, int32_t S, int32_t NA,
+    int32_t action_penalization, int32_t joint_kl, void* d_workspace, int64_t workspace_bytes, void* stream) {
+  TONIC_REQUIRE(d_values != nullptr && NA >= 2 && NA <= 64, TONIC_ERR_INVALID_ARGUMENT,
+                "tonic_distributional_mpo_actor_grad_shard: bad argument (2 <= atoms <= 64)");
+  return mpo_actor_grad(d_actor_params, d_target_actor, d_target_critic, d_duals, min_log_dual, d_norm_mean,
+                        d_norm_std, norm_clip, d_observations, d_eps, d_grad_sums, nullptr, nullptr, B, O, H, A, S,
+                        0.0, 0.0, 0.0, 0.0, action_penalization, joint_kl, d_workspace, workspace_bytes, stream,
+                        d_column_sums, true, d_values, NA);
 }
 
 extern "C" int tonic_mpo_dual_step(const double* d_column_sums, float* d_duals, double min_log_dual,

@@ -1,4 +1,4 @@
-"""A2C / PPO / TRPO / DDPG / TD3 / SAC / D4PG / MPO on the HIP engine — API of ``tonic/torch/agents/*.py``.
+"""A2C / PPO / TRPO / DDPG / TD3 / SAC / D4PG / MPO / TD4 / DMPO on the HIP engine — API of ``tonic/torch/agents/*.py``.
 
 ``step`` / ``update`` keep the reference signatures (NumPy in, NumPy out) so
 ``tonic.Trainer`` drives the agents unchanged.  The on-policy agents talk to the GPU through
@@ -1639,6 +1639,28 @@ class MPO(DDPG):
         self.last_infos, self.last_actor_infos = infos, stats
         log_learning_rate('actor', self.actor_updater, self)
         log_learning_rate('critic', self.critic_updater, self)
+
+
+def _dmpo_model():
+    """MPO's model with the categorical critic head D4PG and TD4 default to."""
+    model = _mpo_model()
+    return models.ActorCriticWithTargets(
+        actor=model.actor,
+        critic=models.Critic(
+            encoder=models.ObservationActionEncoder(), torso=model.critic.torso,
+            head=models.DistributionalValueHead(-150., 150., 51)),
+        observation_normalizer=model.observation_normalizer)
+
+
+class DMPO(MPO):
+    """Distributional MPO, an agent the library does not have: MPO's acting, actor and dual step on D4PG's
+    categorical critic.  The critic step is DistributionalExpectedSARSA; the E-step reads the means of the target
+    critic's distributions (MaximumAPosterioriPolicyOptimization on a critic with atoms).  Everything else — the
+    noise draws, 5-step returns, scheduling, graph capture, several ranks — is MPO's."""
+
+    def __init__(self, model=None, replay=None, actor_updater=None, critic_updater=None):
+        super().__init__(model or _dmpo_model(), replay, actor_updater,
+                         critic_updater or updaters.DistributionalExpectedSARSA())
 
 
 class TD3(DDPG):

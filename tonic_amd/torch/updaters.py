@@ -1652,6 +1652,14 @@ class ExpectedSARSA(_TwinCriticQLearning):
         self.optimizer = optimizer
         self.gradient_clip = gradient_clip
 
+    def initialize(self, model):
+        critic = model.critic_1 if hasattr(model, 'critic_1') else model.critic
+        if getattr(critic.head, 'num_atoms', 0):
+            # (the scalar entry would walk the categorical critic's block by a scalar critic's offsets)
+            raise NotImplementedError('ExpectedSARSA regresses a scalar critic: a critic with a '
+                                      'DistributionalValueHead takes DistributionalExpectedSARSA')
+        super().initialize(model)
+
     def _workspace_bytes(self, batch):
         return self.lib.tonic_mpo_workspace_bytes(batch, self.observation_size, self.action_size, self.hidden,
                                                   self.num_samples)
@@ -1669,6 +1677,65 @@ class ExpectedSARSA(_TwinCriticQLearning):
             p(batch['discounts']), p(eps), p(self.grad_sums), B, self.observation_size, self.hidden,
             self.action_size, self.num_samples, ctypes.addressof(self.loss_rule), p(ws), ws.numel(),
             _lib.current_stream()), 'tonic_expected_sarsa_grad_loss')
+        self._step(n_global or B, info_row)
+
+    def __call__(self, observations, actions, next_observations, rewards, discounts):
+        batch = dict(observations=observations, actions=actions,
+                     next_observations=next_observations, rewards=rewards, discounts=discounts)
+        eps = torch.randn(self.num_samples * observations.shape[0], self.action_size).to(
+            observations.device)
+        return self._info(lambda row: self.enqueue(batch, eps, row), ('loss', 'q'))
+
+
+class DistributionalExpectedSARSA(_TwinCriticQLearning):
+    """DMPO's critic step, which no reference line states: ExpectedSARSA on D4PG's categorical critic.  Per row the
+    target is the MIXTURE of the target critic's distributions at `num_samples` actions drawn from the target actor,
+    projected onto the support at r + discount * z (CategoricalWithSupport.project is linear in the distribution, so
+    the mixture is projected once); the online critic takes the cross-entropy against it
+    (tonic_distributional_expected_sarsa_grad).  Logs ExpectedSARSA's row: loss, and the online critic's mean value q."""
+    default_lr = 3e-4
+    stock_capable = False
+    head_family = 'mpo'
+    stats_kind = 3          # {loss, q mean}
+
+    def __init__(self, num_samples=20, optimizer=None, gradient_clip=0, lr_scheduler=None):
+        self.lr_scheduler = lr_scheduler
+        _check_num_samples('DistributionalExpectedSARSA', num_samples)
+        self.num_samples = num_samples
+        self.optimizer = optimizer
+        self.gradient_clip = gradient_clip
+
+    def initialize(self, model):
+        name = type(self).__name__
+        if hasattr(model, 'critic_1'):
+            raise NotImplementedError(f'{name} serves one critic with its target (ActorCriticWithTargets), not twin '
+                                      'critics')
+        if not getattr(model.critic.head, 'num_atoms', 0):
+            raise NotImplementedError(f'{name} needs a critic with a DistributionalValueHead')
+        online, target = model.critic.head.values, model.target_critic.head.values
+        if online.shape != target.shape or not torch.equal(online.cpu(), target.cpu()):
+            # one support for the projection and the logged values (the target is a copy made at construction:
+            # unequal only when somebody changed one head afterwards)
+            raise NotImplementedError(f'{name} needs the same support in the online and the target critic\'s heads')
+        super().initialize(model)
+
+    def _workspace_bytes(self, batch):
+        return self.lib.tonic_distributional_mpo_workspace_bytes(
+            batch, self.observation_size, self.action_size, self.hidden, self.num_samples, self.atoms)
+
+    def enqueue(self, batch, eps, info_row, n_global=None):
+        """eps: the [num_samples * B, A] standard-normal draws of the target actor's `rsample((num_samples,))`."""
+        B = batch['observations'].shape[0]
+        ws = self._offpolicy_workspace(B)
+        mean, std = self.norm_tensors()
+        p = _lib.ptr
+        _lib.check(self.lib.tonic_distributional_expected_sarsa_grad(
+            p(self.model.flat_target_actor.flat), p(self.model.flat_target_critics.flat),
+            p(self.flat.flat), p(mean), p(std), self.norm_clip(), p(batch['observations']),
+            p(batch['actions']), p(batch['next_observations']), p(batch['rewards']),
+            p(batch['discounts']), p(eps), p(self.target_values), p(self.grad_sums), B, self.observation_size,
+            self.hidden, self.action_size, self.num_samples, self.atoms, p(ws), ws.numel(),
+            _lib.current_stream()), 'tonic_distributional_expected_sarsa_grad')
         self._step(n_global or B, info_row)
 
     def __call__(self, observations, actions, next_observations, rewards, discounts):
@@ -1812,7 +1879,9 @@ class MaximumAPosterioriPolicyOptimization(_ActorQGradient):
     {log_temperature, log_alpha_mean[K], log_alpha_std[K], log_penalty_temperature} — K = A with per-dimension
     KL constraints, K = 1 with `per_dim_constraining=False` (one alpha pair on the KLs summed over the action
     dimensions) — one flat device vector with its own Adam state (actors.py:289-316; like the reference, the
-    dual optimizer is Adam(lr=1e-2) unless `actor_optimizer` is given)."""
+    dual optimizer is Adam(lr=1e-2) unless `actor_optimizer` is given).  On a critic with a DistributionalValueHead
+    (DMPO) the E-step's values are the means of the target critic's distributions
+    (tonic_distributional_mpo_actor_grad); everything else is the same step."""
     default_lr = 3e-4
     stock_capable = False
     head_family = 'mpo'
@@ -1856,12 +1925,21 @@ class MaximumAPosterioriPolicyOptimization(_ActorQGradient):
             self.lib.tonic_clip_workspace_bytes(2 * K + 2), dtype=torch.uint8, device=device)
 
     def _workspace_bytes(self, batch):
-        return self.lib.tonic_mpo_workspace_bytes(batch, self.observation_size, self.action_size, self.hidden,
-                                                  self.num_samples)
+        shape = (batch, self.observation_size, self.action_size, self.hidden, self.num_samples)
+        if self.atoms:
+            return self.lib.tonic_distributional_mpo_workspace_bytes(*shape, self.atoms)
+        return self.lib.tonic_mpo_workspace_bytes(*shape)
 
     def enqueue(self, observations, eps, info_row, n_global=None, targets=None, stats_row=None):
         from tonic_amd import parallel
         p = _lib.ptr
+        # a categorical target critic (DMPO): the tonic_distributional_mpo_* entries, which take the TARGET head's
+        # support (`_shapes`) behind eps and the number of atoms behind the samples; else the calls as they were
+        whole, shard = 'tonic_mpo_actor_grad_joint', 'tonic_mpo_actor_grad_shard_joint'
+        support, atoms = (), ()
+        if self.atoms:
+            whole, shard = 'tonic_distributional_mpo_actor_grad', 'tonic_distributional_mpo_actor_grad_shard'
+            support, atoms = (p(self.target_values),), (self.atoms,)
         # (actors.py:347-356 floors the log-duals in place at the head of the call: the kernels read them
         #  through the floor and write the floored values back ahead of the duals' optimizer step)
         floor, joint = float(self.min_log_dual), int(not self.per_dim_constraining)
@@ -1874,13 +1952,13 @@ class MaximumAPosterioriPolicyOptimization(_ActorQGradient):
             if B > 0:
                 ws = self._offpolicy_workspace(B)
                 mean, std = self.norm_tensors()
-                _lib.check(self.lib.tonic_mpo_actor_grad_shard_joint(
+                _lib.check(getattr(self.lib, shard)(
                     p(self.flat.flat), p(self.model.flat_target_actor.flat),
                     p(self.model.flat_target_critics.flat), p(self.duals), floor, p(mean), p(std),
-                    self.norm_clip(), p(observations), p(eps), p(self.grad_sums),
+                    self.norm_clip(), p(observations), p(eps), *support, p(self.grad_sums),
                     p(self.column_sums), B, self.observation_size, self.hidden, self.action_size,
-                    self.num_samples, int(bool(self.action_penalization)), joint, p(ws), ws.numel(),
-                    _lib.current_stream()), 'tonic_mpo_actor_grad_shard_joint')
+                    self.num_samples, *atoms, int(bool(self.action_penalization)), joint, p(ws), ws.numel(),
+                    _lib.current_stream()), shard)
             else:
                 self.grad_sums.zero_()
                 self.column_sums.zero_()
@@ -1894,15 +1972,15 @@ class MaximumAPosterioriPolicyOptimization(_ActorQGradient):
         else:
             ws = self._offpolicy_workspace(B)
             mean, std = self.norm_tensors()
-            _lib.check(self.lib.tonic_mpo_actor_grad_joint(
+            _lib.check(getattr(self.lib, whole)(
                 p(self.flat.flat), p(self.model.flat_target_actor.flat),
                 p(self.model.flat_target_critics.flat), p(self.duals), floor, p(mean), p(std),
-                self.norm_clip(), p(observations), p(eps), p(self.grad_sums), p(self.dual_grads),
+                self.norm_clip(), p(observations), p(eps), *support, p(self.grad_sums), p(self.dual_grads),
                 p(stats), B, self.observation_size, self.hidden, self.action_size,
-                self.num_samples, float(self.epsilon), float(self.epsilon_penalty),
+                self.num_samples, *atoms, float(self.epsilon), float(self.epsilon_penalty),
                 float(self.epsilon_mean), float(self.epsilon_std),
                 int(bool(self.action_penalization)), joint, p(ws), ws.numel(), _lib.current_stream()),
-                'tonic_mpo_actor_grad_joint')
+                whole)
         self._step(n_global or B, info_row, targets=targets)
         if self.gradient_clip > 0:
             # actors.py:441-445 clips the dual variables' gradient norm as well (the penalty
