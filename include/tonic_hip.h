@@ -66,7 +66,8 @@ const char* tonic_last_error(void);
  * earlier entry keeps its signature), 20 = tonic_twin_distributional_q_grad / _workspace_bytes (TD4; additive),
  * 21 = tonic_q_regression_grad / tonic_q_regression_workspace_bytes (QRegression; additive),
  * 22 = tonic_tempered_twin_q_grad / tonic_tempered_actor_q_grad (SAC's learned entropy coefficient; additive)
- * (still 22, purely additive: the tonic_priority_* entries and the tonic_weighted_* distributional critic steps — prioritized replay)
+ * (still 22, purely additive: the tonic_priority_* entries and the tonic_weighted_* distributional critic steps — prioritized replay;
+ * tonic_quantile_workspace_bytes / tonic_truncated_quantile_q_grad / tonic_truncated_quantile_actor_grad — TQC)
  * and the gfx target the kernels were built for.  TONIC_ABI_VERSION is what a binding was compiled against:
  * tonic_amd/_fastcall (csrc/fastcall.c) and tonic_amd/_lib.py compare it with the loaded library's answer. */
 #define TONIC_ABI_VERSION 22
@@ -1397,6 +1398,46 @@ int tonic_distributional_mpo_actor_grad_shard(const float* d_actor_params, const
                                               int32_t B, int32_t O, int32_t H, int32_t A, int32_t S, int32_t NA,
                                               int32_t action_penalization, int32_t joint_kl, void* d_workspace,
                                               int64_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * TQC: SAC on truncated quantile critics (Kuznetsov et al. 2020; additive under ABI 22).  No reference line states
+ *   it: SAC's steps (updaters/critics.py:202-235, actors.py:238-267) with two critics of M quantile outputs each.
+ *   A critic has D4PG's layout, tonic_mlp_actor_param_count(O + A, H, M, 1) — one linear head of M outputs — and
+ *   the flat blocks are [critic_1 | critic_2]; the actor is SAC's (two heads), H any code the SAC entries take.
+ *   1 <= M <= 32, so that the 2 M pooled target values fit one wave.
+ *
+ * tonic_quantile_workspace_bytes — a function of its arguments alone (no GPU, no tuning switch); both entries take
+ *   a workspace of this size.
+ * tonic_truncated_quantile_q_grad — per row m: a' = the ONLINE actor's rsample at s' from d_eps [B, A] with logp';
+ *   Z = the two TARGET critics' 2 M values at (s', a') sorted ascending, the K = 2 (M - drop_per_net) smallest kept;
+ *   y_j = r + discount (Z_j - alpha logp'); for each online critic z and quantile i (tau_i = (2 i + 1) / (2 M)),
+ *   u = y_j - theta_zi, rho = |tau_i - 1{u < 0}| huber_1(u); loss_m = sum_z (1 / (M K)) sum_i sum_j rho.
+ *   alpha = entropy_coeff, or expf(*d_log_entropy_coeff) read on the device when that pointer is given.
+ *   Output: gradient SUMS of [critic_1 | critic_2] + {sum loss_m, sum q1, sum q2, 0, 0, B, 0, 0}, q_z = mean_i theta_zi
+ *   of the online critics (float64, fixed order).
+ * tonic_truncated_quantile_actor_grad — a = the actor's rsample at s with logp; Q = the mean of the two (frozen)
+ *   online critics' 2 M quantiles at (s, a); loss_m = alpha logp - Q.  Output: gradient SUMS of the actor +
+ *   {sum loss_m, 0, 0, 0, 0, B, 0, 0}; with d_log_entropy_coeff / d_entropy_coeff_sums (both or neither) the
+ *   coefficient's block [1 + 8] as tonic_tempered_actor_q_grad writes it, in no launch more.
+ * TONIC_ERR_INVALID_ARGUMENT, each with its own message, before anything touches the device: a NULL pointer; one of
+ *   the tuner's pair without the other; target_entropy not finite; drop_per_net outside 0 .. M - 1; B, O or A below 1;
+ *   an unknown H; M outside 1 .. 32; then TONIC_ERR_WORKSPACE: a workspace below the query's answer. */
+int64_t tonic_quantile_workspace_bytes(int32_t B, int32_t O, int32_t A, int32_t H, int32_t M);
+int tonic_truncated_quantile_q_grad(const float* d_actor, const float* d_target_critics, const float* d_critics,
+                                    const float* d_norm_mean, const float* d_norm_std, double norm_clip,
+                                    const float* d_observations, const float* d_actions,
+                                    const float* d_next_observations, const float* d_rewards,
+                                    const float* d_discounts, const float* d_eps, float* d_grad_sums, int32_t B,
+                                    int32_t O, int32_t H, int32_t A, int32_t M, int32_t drop_per_net,
+                                    double entropy_coeff, const float* d_log_entropy_coeff, void* d_workspace,
+                                    int64_t workspace_bytes, void* stream);
+int tonic_truncated_quantile_actor_grad(const float* d_actor, const float* d_critics, const float* d_norm_mean,
+                                        const float* d_norm_std, double norm_clip, const float* d_observations,
+                                        const float* d_eps, float* d_grad_sums, int32_t B, int32_t O, int32_t H,
+                                        int32_t A, int32_t M, double entropy_coeff,
+                                        const float* d_log_entropy_coeff, float* d_entropy_coeff_sums,
+                                        double target_entropy, void* d_workspace, int64_t workspace_bytes,
+                                        void* stream);
 
 #ifdef __cplusplus
 }

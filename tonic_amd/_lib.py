@@ -303,6 +303,14 @@ SIGNATURES = {
     'tonic_debug_occupy': (ctypes.c_int, [c_i32, c_f64, c_vp]),
     'tonic_gemm_f32': (ctypes.c_int, [ctypes.c_char_p] + [c_vp] * 6 + [c_i32] * 8 + [c_f64, c_vp]),
     'tonic_gemm_group_f32': (ctypes.c_int, [ctypes.c_char_p, c_vp, c_i32, c_i32, c_vp]),
+    # TQC: SAC on truncated quantile critics (additive under ABI 22), and the loss kernel's test entry
+    'tonic_quantile_workspace_bytes': (c_i64, [c_i32] * 5),
+    'tonic_truncated_quantile_q_grad': (ctypes.c_int, [c_vp] * 5 + [c_f64] + [c_vp] * 7 + [c_i32] * 6 +
+                                        [c_f64, c_vp] + [c_vp, c_i64, c_vp]),
+    'tonic_truncated_quantile_actor_grad': (ctypes.c_int, [c_vp] * 4 + [c_f64] + [c_vp] * 3 + [c_i32] * 5 +
+                                            [c_f64, c_vp, c_vp, c_f64] + [c_vp, c_i64, c_vp]),
+    'tonic_debug_truncated_quantile_loss': (ctypes.c_int, [c_vp] * 4 + [c_i32] + [c_vp] * 3 + [c_i32] * 2 +
+                                            [c_f64, c_vp] + [c_vp] * 3 + [c_i32] * 2 + [c_vp]),
 }
 
 

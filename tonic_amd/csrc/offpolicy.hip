@@ -491,6 +491,100 @@ __global__ void loss_stats_kernel(const float* loss_m, float* stats, int B) {
   }
 }
 
+// ---- TQC (Kuznetsov et al. 2020, truncated quantile critics): SAC on two critics of M <= 32 quantile outputs each,
+// one wave per sample.  The online critics share the wave: critic z = lane / 32, quantile i = lane % 32 (live: i < M),
+// so a [B, ld] array's columns (ld = pad16(M) <= 32) are one half of the wave.  False: no row for this wave.
+constexpr int kMaxQuantiles = 32;
+struct QuantileRow { int lane, m, z, i; bool live; };
+__device__ __forceinline__ bool quantile_row(int M, int B, QuantileRow& r) {
+  r.lane = threadIdx.x & 63;
+  r.m = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  r.z = r.lane >> 5;
+  r.i = r.lane & 31;
+  r.live = r.i < M;
+  return r.m < B;
+}
+
+// One value per lane, ascending over the wave's 64 lanes: the bitonic network, 21 compare-exchange steps on
+// __shfl_xor — a fixed sequence whatever the values are (a NaN may displace a value; it cannot stop the network).
+__device__ __forceinline__ float wave_sort(float v, int lane) {
+#pragma unroll
+  for (int k = 2; k <= 64; k <<= 1) {
+#pragma unroll
+    for (int j = k >> 1; j >= 1; j >>= 1) {
+      const float other = __shfl_xor(v, j, 64);
+      const bool ascending = (lane & k) == 0, lower = (lane & j) == 0;
+      v = ascending == lower ? fminf(v, other) : fmaxf(v, other);
+    }
+  }
+  return v;
+}
+
+// TruncatedQuantileQLearning: the two TARGET critics' 2 M values at (s', a') pooled one per lane (+inf behind them),
+// sorted, the K = 2 (M - drop) smallest kept: y_j = r + disc (Z_j - alpha logp'), j < K (lane j holds y_j).  Each
+// online quantile theta_zi (tau_i = (2 i + 1) / (2 M)) walks the kept targets in ascending j, u = y_j - theta:
+//   rho = |tau - 1{u < 0}| huber_1(u) ;  d rho / d theta = -|tau - 1{u < 0}| clamp(u, -1, 1)
+// loss_m = sum_z (1 / (M K)) sum_i sum_j rho (the twin convention loss_1 + loss_2); dlogits: its gradient (0 on a
+// padded column); sample_m [3][Bp] = {loss_m, q1, q2}, q_z = mean_i theta_zi.  y_j is read from a wave-uniform lane.
+// alpha = expf(*log_alpha) when that pointer is given, read once at entry like M and drop.
+// The targets, the errors and the two sums over j are float64: a quantile's gradient is a sum of terms of both signs
+// (with M = 1, +1/2 clamp(u_0) + 1/2 clamp(u_1)), and float32 targets of magnitude ~10 leave it an error of 1e-6 of
+// a term however far the terms cancel.  At most 64 steps per row: the cost does not show beside the networks' passes.
+__global__ __launch_bounds__(256) void truncated_quantile_critic_loss_kernel(
+    const float* target_1, const float* target_2, const float* theta_1, const float* theta_2, int ld,
+    const float* rewards, const float* discounts, const float* logp_next, int M, int drop, float alpha,
+    const float* log_alpha, float* dlogits_1, float* dlogits_2, float* sample_m, int B, int Bp) {
+  if (log_alpha != nullptr) alpha = expf(*log_alpha);
+  QuantileRow r;
+  if (!quantile_row(M, B, r)) return;
+  const int K = 2 * (M - drop);
+  const int64_t row = (int64_t)r.m * ld;
+  float pooled = INFINITY;
+  if (r.lane < M) pooled = target_1[row + r.lane];
+  else if (r.lane < 2 * M) pooled = target_2[row + (r.lane - M)];
+  const double theta = r.live ? (double)(r.z ? theta_2 : theta_1)[row + r.i] : 0.0;
+  const double y = (double)rewards[r.m] +
+                   (double)discounts[r.m] * ((double)wave_sort(pooled, r.lane) - (double)alpha * (double)logp_next[r.m]);
+  const int y_hi = __double2hiint(y), y_lo = __double2loint(y);
+  const double tau = (double)(2 * r.i + 1) / (double)(2 * M);
+  double loss = 0.0, grad = 0.0;
+  for (int j = 0; j < K; ++j) {
+    const double u = __hiloint2double(__builtin_amdgcn_readlane(y_hi, j), __builtin_amdgcn_readlane(y_lo, j)) - theta;
+    const double weight = u < 0.0 ? 1.0 - tau : tau;
+    const double a = fabs(u);
+    loss += weight * (a <= 1.0 ? 0.5 * (u * u) : a - 0.5);
+    grad += weight * fmin(fmax(u, -1.0), 1.0);
+  }
+  const double scale = 1.0 / (double)(M * K);
+  const double row_loss = wave_sum(r.live ? loss : 0.0) * scale;
+  const double q1 = wave_sum(r.live && r.z == 0 ? theta : 0.0) / (double)M;
+  const double q2 = wave_sum(r.live && r.z == 1 ? theta : 0.0) / (double)M;
+  if (r.i < ld) (r.z ? dlogits_2 : dlogits_1)[row + r.i] = r.live ? (float)-(grad * scale) : 0.f;
+  if (r.lane == 0) {
+    sample_m[r.m] = (float)row_loss; sample_m[Bp + r.m] = (float)q1; sample_m[2 * Bp + r.m] = (float)q2;
+  }
+}
+
+// TwinCriticQuantileSoftPolicyGradient: Q = (1 / (2 M)) sum_z sum_i theta_zi(s, a) on the (frozen) online critics,
+// loss_m = alpha logp - Q: dlogits = -1 / (2 M) on the live columns of both critics, 0 on the padding.  With a tuner
+// (temper.sums) workgroup 0, whole, also forms the coefficient's block as actor_loss_tempered_kernel does.
+__global__ __launch_bounds__(256) void quantile_actor_loss_kernel(
+    const float* theta_1, const float* theta_2, int ld, const float* logp, int M, float alpha, TemperArg temper,
+    float* dlogits_1, float* dlogits_2, float* loss_m, int B) {
+  float log_alpha = 0.f;
+  if (temper.log_alpha != nullptr) { log_alpha = *temper.log_alpha; alpha = expf(log_alpha); }
+  QuantileRow r;
+  if (quantile_row(M, B, r)) {
+    const int64_t row = (int64_t)r.m * ld;
+    const float theta = r.live ? (r.z ? theta_2 : theta_1)[row + r.i] : 0.f;
+    const float q = wave_sum(theta) / (float)(2 * M);
+    if (r.i < ld) (r.z ? dlogits_2 : dlogits_1)[row + r.i] = r.live ? -1.f / (float)(2 * M) : 0.f;
+    if (r.lane == 0) loss_m[r.m] = alpha * logp[r.m] - q;
+  }
+  if (temper.sums != nullptr && blockIdx.x == 0)
+    entropy_coeff_sums(logp, B, log_alpha, alpha, temper.target_entropy, temper.sums);
+}
+
 // ---- DMPO: MPO's sampled actions on the categorical critic.  The target critic's logits on the S * B tiled rows
 // (row s * B + m), one wave per row, lane = atom: the row's mean value sum_i softmax(logits)_i z_i -> tq — what the
 // E-step reads where the scalar critic leaves its output — and, log_norm != null, the row's log-normaliser
@@ -2632,6 +2726,170 @@ extern "C" int tonic_weighted_twin_distributional_q_grad(
                                d_next_observations, d_rewards, d_discounts, d_eps, d_values, d_grad_sums, B, O, H, A, NA,
                                noise_scale, noise_clip, d_weights, d_sample_losses, d_workspace, workspace_bytes,
                                stream);
+}
+
+// ------------------------------------------------------------------ TQC (truncated quantile critics)
+// SAC's frame on two quantile critics: each an actor-shaped network with ONE linear head of M quantiles (D4PG's
+// layout, tonic_mlp_actor_param_count(O + A, H, M, 1)); the flat blocks are [critic_1 | critic_2].
+
+namespace {
+
+// Both entries' arrays (one query): SAC's policy pass with its sample, the critics' inputs, per critic the target and
+// online regions and outputs (DistributionalCritic), the rows' values, one chain (dz2, dz1) the backward passes use one
+// after the other, and the actor step's action columns, head gradients and chain.
+struct QuantileBuffers {
+  float *a_h1, *a_h2, *head0, *head1, *act, *sigma, *logp, *X, *X2, *sample_m, *loss_m, *dz2, *dz1, *dxa, *dloc, *dspre,
+      *da_h2, *da_h1;
+  DistributionalCritic k[2];
+  QuantileBuffers(Workspace& ws, int B, int O, int A, int32_t H, int M) : k{} {
+    const int64_t Bp = pad16(B), ldx = pitch16(O + A), ldh = pad16(A), ldl = pad16(M);
+    const int64_t hid = Bp * hidden_pitch(H), region = hid * hidden_layers(H);
+    a_h1 = ws.take(region); a_h2 = behind(a_h1, hid);
+    head0 = ws.take(Bp * ldh); head1 = ws.take(Bp * ldh);
+    act = ws.take(Bp * A); sigma = ws.take(Bp * A); logp = ws.take(Bp);
+    X = ws.take(Bp * ldx); X2 = ws.take(Bp * ldx);
+    for (int z = 0; z < 2; ++z) k[z].take(ws, hid, region, Bp * ldl);
+    sample_m = ws.take(3 * Bp); loss_m = ws.take(Bp);
+    dz2 = ws.take(region); dz1 = behind(dz2, hid);
+    dxa = ws.take(2 * Bp * ldh);
+    dloc = ws.take(Bp * ldh); dspre = ws.take(Bp * ldh);
+    da_h2 = ws.take(region); da_h1 = behind(da_h2, hid);
+  }
+};
+
+// what both entries ask of M and the workspace, after their own pointer checks
+int quantile_check(const char* what, int32_t B, int32_t O, int32_t A, int32_t H, int32_t M, int64_t workspace_bytes) {
+  TONIC_REQUIRE(B > 0 && O > 0 && A > 0, TONIC_ERR_INVALID_ARGUMENT, "%s: B %d, O %d, A %d (each >= 1)", what, B, O, A);
+  TONIC_REQUIRE(hidden_known(H), TONIC_ERR_INVALID_ARGUMENT, "%s: H %d is not a torso this library knows", what, H);
+  TONIC_REQUIRE(M >= 1 && M <= kMaxQuantiles, TONIC_ERR_INVALID_ARGUMENT, "%s: %d quantiles (1 <= M <= %d)", what, M,
+                kMaxQuantiles);
+  TONIC_REQUIRE(workspace_bytes >= measure<QuantileBuffers>(B, O, A, H, M), TONIC_ERR_WORKSPACE,
+                "%s: workspace too small", what);
+  return TONIC_OK;
+}
+
+}  // namespace
+
+extern "C" int64_t tonic_quantile_workspace_bytes(int32_t B, int32_t O, int32_t A, int32_t H, int32_t M) {
+  return measure<QuantileBuffers>(B, O, A, H, M);
+}
+
+extern "C" int tonic_truncated_quantile_q_grad(
+    const float* d_actor, const float* d_target_critics, const float* d_critics, const float* d_norm_mean,
+    const float* d_norm_std, double norm_clip, const float* d_observations, const float* d_actions,
+    const float* d_next_observations, const float* d_rewards, const float* d_discounts, const float* d_eps,
+    float* d_grad_sums, int32_t B, int32_t O, int32_t H, int32_t A, int32_t M, int32_t drop_per_net,
+    double entropy_coeff, const float* d_log_entropy_coeff, void* d_workspace, int64_t workspace_bytes, void* stream) {
+  const char* what = "tonic_truncated_quantile_q_grad";
+  TONIC_REQUIRE(d_actor && d_target_critics && d_critics && d_norm_mean && d_norm_std && d_observations && d_actions &&
+                    d_next_observations && d_rewards && d_discounts && d_eps && d_grad_sums && d_workspace,
+                TONIC_ERR_INVALID_ARGUMENT, "%s: a NULL pointer (only d_log_entropy_coeff may be NULL)", what);
+  TONIC_REQUIRE(M < 1 || M > kMaxQuantiles || (drop_per_net >= 0 && drop_per_net < M), TONIC_ERR_INVALID_ARGUMENT,
+                "%s: %d quantiles dropped per critic (0 <= drop_per_net < M = %d)", what, drop_per_net, M);
+  TRY(quantile_check(what, B, O, A, H, M, workspace_bytes));
+  hipStream_t st = as_stream(stream);
+  const int Bp = pad16(B), ldx = pitch16(O + A), ldh = pad16(A), ldl = pad16(M);
+  Workspace ws{static_cast<char*>(d_workspace), 0};
+  const QuantileBuffers w(ws, B, O, A, H, M);
+  const ActorShape as = actor_shape(O, H, A, 2), cs = actor_shape(O + A, torso_code(H), M, 1);
+  const int64_t Pc = actor_count(cs);
+  // 1  a' = rsample of the ONLINE actor at s' with logp' (as tonic_twin_q_grad, kind 1); the tail encodes (s', a') -> X
+  //    and the stored (s, a) -> X2
+  PolicyTail tail{};
+  tail.post = POST_SQUASHED_SAMPLE; tail.eps = d_eps; tail.actions = w.act; tail.logp = w.logp;
+  tail.enc_obs = d_next_observations; tail.enc_obs2 = d_observations; tail.enc_act2 = d_actions;
+  tail.enc_mean = d_norm_mean; tail.enc_std = d_norm_std; tail.enc_clip = clip_bound(norm_clip);
+  tail.enc_out = w.X; tail.enc_out2 = w.X2; tail.enc_ld = ldx;
+  TRY(policy_pass(d_actor, as, d_next_observations, B, w.a_h1, w.a_h2, w.head0, w.head1, ldh, false, st, tail));
+  // 2  the target critics on (s', a'), then  3  the online critics on (s, a)
+  for (int z = 0; z < 2; ++z)
+    TRY(actor_forward(d_target_critics + z * Pc, cs, w.X, B, w.k[z].t_h1, w.k[z].t_h2, w.k[z].t_logits,
+                      w.k[z].t_logits, ldl, false, st, nullptr, nullptr, ldx));
+  for (int z = 0; z < 2; ++z)
+    TRY(actor_forward(d_critics + z * Pc, cs, w.X2, B, w.k[z].c_h1, w.k[z].c_h2, w.k[z].logits, w.k[z].logits, ldl,
+                      false, st, nullptr, nullptr, ldx));
+  // 4 + 5  the truncated quantile loss and the statistics behind the gradient blocks
+  hipLaunchKernelGGL(truncated_quantile_critic_loss_kernel, dim3((B + 3) / 4), dim3(256), 0, st, w.k[0].t_logits,
+                     w.k[1].t_logits, w.k[0].logits, w.k[1].logits, ldl, d_rewards, d_discounts, w.logp, M, drop_per_net,
+                     (float)entropy_coeff, d_log_entropy_coeff, w.k[0].dlogits, w.k[1].dlogits, w.sample_m, B, Bp);
+  hipLaunchKernelGGL(twin_loss_stats_kernel, dim3(1), dim3(1024), 0, st, w.sample_m, d_grad_sums + 2 * Pc, B, Bp);
+  // 6  each online critic's backward into its own block of the sums
+  for (int z = 0; z < 2; ++z)
+    TRY(actor_shaped_backward(d_critics + z * Pc, cs, w.X2, ldx, B, w.k[z].c_h1, w.k[z].c_h2, w.k[z].dlogits, nullptr,
+                              ldl, w.dz2, w.dz1, d_grad_sums + z * Pc, nullptr, 0, 0, st));
+  TONIC_CHECK_LAUNCH(what);
+  return TONIC_OK;
+}
+
+extern "C" int tonic_truncated_quantile_actor_grad(
+    const float* d_actor, const float* d_critics, const float* d_norm_mean, const float* d_norm_std, double norm_clip,
+    const float* d_observations, const float* d_eps, float* d_grad_sums, int32_t B, int32_t O, int32_t H, int32_t A,
+    int32_t M, double entropy_coeff, const float* d_log_entropy_coeff, float* d_entropy_coeff_sums,
+    double target_entropy, void* d_workspace, int64_t workspace_bytes, void* stream) {
+  const char* what = "tonic_truncated_quantile_actor_grad";
+  TONIC_REQUIRE(d_actor && d_critics && d_norm_mean && d_norm_std && d_observations && d_eps && d_grad_sums &&
+                    d_workspace,
+                TONIC_ERR_INVALID_ARGUMENT, "%s: a NULL pointer (only the tuner's pair may be NULL)", what);
+  TONIC_REQUIRE((d_log_entropy_coeff == nullptr) == (d_entropy_coeff_sums == nullptr), TONIC_ERR_INVALID_ARGUMENT,
+                "%s: %s is NULL and the other is not (both or neither)", what,
+                d_log_entropy_coeff == nullptr ? "d_log_entropy_coeff" : "d_entropy_coeff_sums");
+  TONIC_REQUIRE(std::isfinite(target_entropy), TONIC_ERR_INVALID_ARGUMENT, "%s: target_entropy is not finite", what);
+  TRY(quantile_check(what, B, O, A, H, M, workspace_bytes));
+  hipStream_t st = as_stream(stream);
+  const int Bp = pad16(B), ldx = pitch16(O + A), ldh = pad16(A), ldl = pad16(M), threads = 256;
+  Workspace ws{static_cast<char*>(d_workspace), 0};
+  const QuantileBuffers w(ws, B, O, A, H, M);
+  const ActorShape as = actor_shape(O, H, A, 2), cs = actor_shape(O + A, torso_code(H), M, 1);
+  const int64_t Pa = actor_count(as), Pc = actor_count(cs);
+  const TemperArg temper{d_log_entropy_coeff, d_entropy_coeff_sums, (float)target_entropy};
+  PolicyTail tail{};                              // a = rsample of the actor at s with logp; the tail encodes (s, a) -> X
+  tail.post = POST_SQUASHED_SAMPLE; tail.eps = d_eps; tail.actions = w.act; tail.sigma = w.sigma; tail.logp = w.logp;
+  tail.enc_obs = d_observations; tail.enc_mean = d_norm_mean; tail.enc_std = d_norm_std;
+  tail.enc_clip = clip_bound(norm_clip); tail.enc_out = w.X; tail.enc_ld = ldx;
+  TRY(policy_pass(d_actor, as, d_observations, B, w.a_h1, w.a_h2, w.head0, w.head1, ldh, false, st, tail));
+  for (int z = 0; z < 2; ++z)
+    TRY(actor_forward(d_critics + z * Pc, cs, w.X, B, w.k[z].c_h1, w.k[z].c_h2, w.k[z].logits, w.k[z].logits, ldl,
+                      false, st, nullptr, nullptr, ldx));
+  hipLaunchKernelGGL(quantile_actor_loss_kernel, dim3((B + 3) / 4), dim3(256), 0, st, w.k[0].logits, w.k[1].logits, ldl,
+                     w.logp, M, (float)entropy_coeff, temper, w.k[0].dlogits, w.k[1].dlogits, w.loss_m, B);
+  hipLaunchKernelGGL(loss_stats_kernel, dim3(1), dim3(1024), 0, st, w.loss_m, d_grad_sums + Pa, B);
+  // through each frozen critic to the action columns of its input, then SAC's head (which adds the two) and the actor
+  for (int z = 0; z < 2; ++z)
+    TRY(actor_shaped_backward(d_critics + z * Pc, cs, w.X, ldx, B, w.k[z].c_h1, w.k[z].c_h2, w.k[z].dlogits, nullptr,
+                              ldl, w.dz2, w.dz1, nullptr, w.dxa + (int64_t)z * Bp * ldh, O, A, st));
+  if (temper.log_alpha != nullptr)
+    hipLaunchKernelGGL(actor_head_backward_tempered_kernel, dim3((B * A + threads - 1) / threads), dim3(threads), 0, st,
+                       w.dxa, w.dxa + (int64_t)Bp * ldh, ldh, w.act, d_eps, w.sigma, w.head1, ldh, temper.log_alpha,
+                       w.dloc, w.dspre, B, A, as.scale_lo, as.scale_hi);
+  else hipLaunchKernelGGL(actor_head_backward_kernel, dim3((B * A + threads - 1) / threads), dim3(threads), 0, st, w.dxa,
+                     w.dxa + (int64_t)Bp * ldh, ldh, w.act, d_eps, w.sigma, w.head1, ldh, (float)entropy_coeff, 1, w.dloc,
+                     w.dspre, B, A, as.scale_lo, as.scale_hi);
+  TRY(actor_shaped_backward(d_actor, as, d_observations, O, B, w.a_h1, w.a_h2, w.dloc, w.dspre, ldh, w.da_h2, w.da_h1,
+                            d_grad_sums, nullptr, 0, 0, st));
+  TONIC_CHECK_LAUNCH(what);
+  return TONIC_OK;
+}
+
+// Test entry (include/tonic_hip_dev.h): truncated_quantile_critic_loss_kernel alone on given rows.
+extern "C" int tonic_debug_truncated_quantile_loss(
+    const float* d_target_1, const float* d_target_2, const float* d_theta_1, const float* d_theta_2, int32_t ld,
+    const float* d_rewards, const float* d_discounts, const float* d_logp, int32_t M, int32_t drop_per_net,
+    double entropy_coeff, const float* d_log_entropy_coeff, float* d_dlogits_1, float* d_dlogits_2, float* d_sample_m,
+    int32_t B, int32_t Bp, void* stream) {
+  const char* what = "tonic_debug_truncated_quantile_loss";
+  TONIC_REQUIRE(d_target_1 && d_target_2 && d_theta_1 && d_theta_2 && d_rewards && d_discounts && d_logp &&
+                    d_dlogits_1 && d_dlogits_2 && d_sample_m,
+                TONIC_ERR_INVALID_ARGUMENT, "%s: a NULL pointer", what);
+  TONIC_REQUIRE(M >= 1 && M <= kMaxQuantiles && drop_per_net >= 0 && drop_per_net < M && ld >= M &&
+                    ld <= kMaxQuantiles && B > 0 && Bp >= B,
+                TONIC_ERR_INVALID_ARGUMENT,
+                "%s: M %d, drop_per_net %d, ld %d, B %d, Bp %d (1 <= M <= %d, 0 <= drop < M, M <= ld <= %d, 0 < B <= Bp)",
+                what, M, drop_per_net, ld, B, Bp, kMaxQuantiles, kMaxQuantiles);
+  hipLaunchKernelGGL(truncated_quantile_critic_loss_kernel, dim3((B + 3) / 4), dim3(256), 0, as_stream(stream),
+                     d_target_1, d_target_2, d_theta_1, d_theta_2, ld, d_rewards, d_discounts, d_logp, M, drop_per_net,
+                     (float)entropy_coeff, d_log_entropy_coeff, d_dlogits_1, d_dlogits_2, d_sample_m, B, Bp);
+  TONIC_CHECK_LAUNCH(what);
+  return TONIC_OK;
 }
 
 

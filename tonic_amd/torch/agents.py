@@ -1732,16 +1732,18 @@ class SAC(DDPG):
         return np.stack([np.stack([torch.randn(B, A).numpy(), torch.randn(B, A).numpy()])
                          for _ in range(iterations)])
 
+    # the updaters whose entries read a learned coefficient on the device: (critic, actor)
+    _TEMPERED = (updaters.TwinCriticSoftQLearning, updaters.TwinCriticSoftDeterministicPolicyGradient)
+
     def initialize(self, observation_space, action_space, seed=None):
         tuner = self.entropy_coeff_updater
         if tuner is not None:       # (before anything is built: the tempered entries are these two updaters')
-            for role, updater, served in (('critic_updater', self.critic_updater, updaters.TwinCriticSoftQLearning),
-                                          ('actor_updater', self.actor_updater,
-                                           updaters.TwinCriticSoftDeterministicPolicyGradient)):
+            for role, updater, served in (('critic_updater', self.critic_updater, self._TEMPERED[0]),
+                                          ('actor_updater', self.actor_updater, self._TEMPERED[1])):
                 if type(updater) is not served:
                     raise NotImplementedError(
-                        f'SAC(entropy_coeff_updater=...) with {role}={type(updater).__name__}: a learned entropy '
-                        f'coefficient is read on the device by {served.__name__} only')
+                        f'{type(self).__name__}(entropy_coeff_updater=...) with {role}={type(updater).__name__}: a '
+                        f'learned entropy coefficient is read on the device by {served.__name__} only')
         super().initialize(observation_space, action_space, seed=seed)
         if tuner is not None:
             tuner.initialize(self.model, self.action_size)
@@ -1781,3 +1783,25 @@ class SAC(DDPG):
         sibling = path + '.entropy_coeff.pt'
         if self.entropy_coeff_updater is not None and os.path.exists(sibling):   # (absent: the initial value stays)
             self.entropy_coeff_updater.load_state_dict(torch.load(sibling, map_location='cpu'))
+
+
+class TQC(SAC):
+    """Truncated quantile critics (Kuznetsov et al. 2020; the reference has no such agent): SAC — acting, noise
+    draws, scheduling, checkpoints, log keys and the optional `entropy_coeff_updater` — on two critics of 25 quantiles
+    each, whose pooled target quantiles are sorted and truncated at the top (updaters.TruncatedQuantileQLearning,
+    updaters.TwinCriticQuantileSoftPolicyGradient).  The updaters run the split route."""
+
+    _TEMPERED = (updaters.TruncatedQuantileQLearning, updaters.TwinCriticQuantileSoftPolicyGradient)
+
+    def __init__(self, model=None, replay=None, exploration=None, actor_updater=None,
+                 critic_updater=None, entropy_coeff_updater=None):
+        head = models.GaussianPolicyHead(loc_activation=torch.nn.Identity,
+                                         distribution=models.SquashedMultivariateNormalDiag)
+        super().__init__(
+            model=model or _twin_model(head, models.QuantileValueHead(25)), replay=replay, exploration=exploration,
+            actor_updater=actor_updater or updaters.TwinCriticQuantileSoftPolicyGradient(),
+            critic_updater=critic_updater or updaters.TruncatedQuantileQLearning(),
+            entropy_coeff_updater=entropy_coeff_updater)
+
+    def _graph_signature(self):
+        return super()._graph_signature() + (getattr(self.critic_updater, 'top_quantiles_to_drop_per_net', None),)

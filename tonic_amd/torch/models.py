@@ -231,6 +231,28 @@ class DistributionalValueHead(torch.nn.Module):
         return CategoricalWithSupport(values=self.values.to(logits.device), logits=logits)
 
 
+class QuantileValueHead(torch.nn.Module):
+    """TQC's critic head (Kuznetsov et al. 2020; the reference has none): one linear layer of `num_quantiles`
+    outputs, the locations of the quantiles at the midpoints tau_i = (2 i + 1) / (2 M) of the return distribution.
+    Packed like DistributionalValueHead — one head of M outputs.  It has no `num_atoms`: the quantiles carry no
+    support, and the categorical updaters do not take it for one of theirs.  A Return normaliser is kept as given
+    and refused by the TQC updaters, which have no form for it."""
+
+    def __init__(self, num_quantiles=25, fn=None):
+        super().__init__()
+        self.num_quantiles = num_quantiles
+        self.fn = fn
+
+    def initialize(self, input_size, return_normalizer=None):
+        self.return_normalizer = return_normalizer
+        self.quantile_layer = torch.nn.Linear(input_size, self.num_quantiles)
+        if self.fn:
+            self.quantile_layer.apply(self.fn)
+
+    def forward(self, inputs):
+        return self.quantile_layer(inputs)          # [B, M]
+
+
 class _Network(torch.nn.Module):
     """encoder -> torso -> head (actors.py:118-137, critics.py:70-90)."""
 

@@ -1136,6 +1136,16 @@ def _actor_code(torso, bounds, generic=False):
     return code
 
 
+def _refuse_quantile_head(name, model):
+    """The scalar and categorical updaters on a critic with a QuantileValueHead: refused by name (its block has
+    neither a scalar critic's nor, without a support, a categorical critic's meaning)."""
+    critic = model.critic_1 if hasattr(model, 'critic_1') else model.critic
+    if hasattr(critic.head, 'num_quantiles'):
+        raise NotImplementedError(
+            f'{name} does not serve a critic with a QuantileValueHead: its quantiles are trained by '
+            'TruncatedQuantileQLearning and TwinCriticQuantileSoftPolicyGradient (TQC)')
+
+
 class _QUpdater(_FlatUpdater):
     """Shared plumbing of the four off-policy updaters: shapes, normaliser tensors, workspace."""
 
@@ -1145,10 +1155,16 @@ class _QUpdater(_FlatUpdater):
     # outside the fused kernels
     stock_capable = False
 
+    # TQC's two updaters: the critics are QuantileValueHead networks (the others refuse such a head by name)
+    quantile_critic = False
+
     def _shapes(self, model):
         self.model = model
         self.observation_size = model.actor.torso.model[0].in_features
         critic = model.critic_1 if hasattr(model, 'critic_1') else model.critic
+        self.quantiles = int(getattr(critic.head, 'num_quantiles', 0)) if self.quantile_critic else 0
+        if not self.quantile_critic:
+            _refuse_quantile_head(type(self).__name__, model)
         try:
             self.hidden = _torso_width(model.actor.torso, self.stock_capable)
             if _torso_width(critic.torso, self.stock_capable) != self.hidden:
@@ -1197,6 +1213,9 @@ class _QUpdater(_FlatUpdater):
                 raise NotImplementedError('online and target critic with different numbers of atoms')
             self.target_values = target.head.values.to(device=device,
                                                        dtype=torch.float32).contiguous()
+        elif self.quantiles:
+            want_critic = lib.tonic_mlp_actor_param_count(
+                self.observation_size + self.action_size, self.hidden, self.quantiles, 1)
         else:
             want_critic = lib.tonic_q_critic_param_count(
                 self.observation_size, self.action_size, self.hidden)
@@ -1433,6 +1452,7 @@ class QRegression(_TwinCriticQLearning):
             raise NotImplementedError('QRegression regresses model.critic (critics.py:40,45): a model with critic_1 / '
                                       'critic_2 is not served, twin regression is no updater of the reference')
         critic = model.critic
+        _refuse_quantile_head('QRegression', model)
         if isinstance(critic.head, models.DistributionalValueHead) or getattr(critic.head, 'num_atoms', 0):
             raise NotImplementedError('QRegression on a DistributionalValueHead is not served: the loss of '
                                       'critics.py:46 cannot take a distribution for its values')
@@ -1618,6 +1638,7 @@ class TwinCriticDistributionalDeterministicQLearning(_DistributionalQLearning):
         name = type(self).__name__
         if not hasattr(model, 'critic_2'):
             raise NotImplementedError(f'{name} needs a model with twin critics (ActorTwinCriticWithTargets)')
+        _refuse_quantile_head(name, model)
         critics = (model.critic_1, model.critic_2, model.target_critic_1, model.target_critic_2)
         if not all(getattr(critic.head, 'num_atoms', 0) for critic in critics):
             raise NotImplementedError(f'{name} needs critics with a DistributionalValueHead')
@@ -1635,6 +1656,83 @@ class TwinCriticDistributionalDeterministicQLearning(_DistributionalQLearning):
     def _workspace_bytes(self, batch):
         return self.lib.tonic_twin_distributional_workspace_bytes(
             batch, self.observation_size, self.action_size, self.hidden, self.atoms)
+
+
+QUANTILES_MAX = 32         # csrc/offpolicy.hip kMaxQuantiles: the two critics' pooled target values fill one wave
+
+
+def _quantile_model(name, model):
+    """What TQC's two updaters ask of the model, refused by name: twin critics, a QuantileValueHead of one size in
+    all four, 1 .. 32 quantiles, no Return normaliser.  Returns the number of quantiles."""
+    from tonic_amd.torch import models
+    if not hasattr(model, 'critic_2'):
+        raise NotImplementedError(f'{name} needs a model with twin critics (ActorTwinCriticWithTargets)')
+    critics = (model.critic_1, model.critic_2, model.target_critic_1, model.target_critic_2)
+    if not all(isinstance(critic.head, models.QuantileValueHead) for critic in critics):
+        raise NotImplementedError(f'{name} needs critics with a QuantileValueHead')
+    counts = [int(critic.head.num_quantiles) for critic in critics]
+    if len(set(counts)) != 1:
+        raise NotImplementedError(f'{name} needs the same num_quantiles in all four critics\' heads, got {counts}')
+    if not 1 <= counts[0] <= QUANTILES_MAX:
+        raise NotImplementedError(f'{name}: the quantile kernels serve num_quantiles = 1 .. {QUANTILES_MAX}, got '
+                                  f'{counts[0]}')
+    if getattr(model, 'return_normalizer', None):
+        raise NotImplementedError(f'{name} does not serve a Return normaliser (return_normalizer): the quantile '
+                                  'critics have no squashed head')
+    return counts[0]
+
+
+class TruncatedQuantileQLearning(_TwinCriticQLearning):
+    """TQC's critic step (Kuznetsov et al. 2020; the reference has none): SAC's — the ONLINE actor's sample at s' and
+    its entropy bonus in the target — on two critics of M quantiles each.  Per row the two target critics' 2 M values
+    are pooled and sorted and the `top_quantiles_to_drop_per_net` largest per critic dropped, K = 2 (M - d) kept:
+    y_j = r + discount (Z_j - alpha logp'); each online critic takes the quantile Huber loss (kappa = 1) of its M
+    quantiles at tau_i = (2 i + 1) / (2 M) against the K targets, loss_1 + loss_2 (tonic_truncated_quantile_q_grad).
+    Logs the row of SAC: loss, and the online critics' mean quantiles q1, q2."""
+    kind, default_lr = 1, 3e-4
+    head_family = 'sac'
+    stock_capable = False
+    quantile_critic = True
+
+    def __init__(self, optimizer=None, entropy_coeff=0.2, top_quantiles_to_drop_per_net=2, gradient_clip=0,
+                 lr_scheduler=None):
+        self.lr_scheduler = lr_scheduler
+        self.optimizer = optimizer
+        self.entropy_coeff = entropy_coeff
+        self.top_quantiles_to_drop_per_net = top_quantiles_to_drop_per_net
+        self.gradient_clip = gradient_clip
+
+    def initialize(self, model):
+        name = type(self).__name__
+        quantiles = _quantile_model(name, model)
+        drop = self.top_quantiles_to_drop_per_net
+        if int(drop) != drop or not 0 <= drop < quantiles:
+            raise NotImplementedError(f'{name}: top_quantiles_to_drop_per_net = 0 .. num_quantiles - 1 = '
+                                      f'{quantiles - 1}, got {drop!r}')
+        super().initialize(model)
+
+    def _policy_params(self):
+        return self.model.flat_actor.flat
+
+    def _workspace_bytes(self, batch):
+        return self.lib.tonic_quantile_workspace_bytes(batch, self.observation_size, self.action_size, self.hidden,
+                                                       self.quantiles)
+
+    def enqueue(self, batch, eps, info_row, n_global=None):
+        """eps: the [B, A] standard-normal draw of the next action's rsample."""
+        B = batch['observations'].shape[0]
+        ws = self._offpolicy_workspace(B)
+        mean, std = self.norm_tensors()
+        p = _lib.ptr
+        tuner = self.entropy_coeff_updater         # (the coefficient is then read on the device)
+        _lib.check(self.lib.tonic_truncated_quantile_q_grad(
+            p(self._policy_params()), p(self.model.flat_target_critics.flat), p(self.flat.flat), p(mean), p(std),
+            self.norm_clip(), p(batch['observations']), p(batch['actions']), p(batch['next_observations']),
+            p(batch['rewards']), p(batch['discounts']), p(eps), p(self.grad_sums), B, self.observation_size,
+            self.hidden, self.action_size, self.quantiles, int(self.top_quantiles_to_drop_per_net),
+            float(self.entropy_coeff), p(tuner.log_entropy_coeff) if tuner is not None else None, p(ws), ws.numel(),
+            _lib.current_stream()), 'tonic_truncated_quantile_q_grad')
+        self._step(n_global or B * self.world_size, info_row)
 
 
 class ExpectedSARSA(_TwinCriticQLearning):
@@ -1710,6 +1808,7 @@ class DistributionalExpectedSARSA(_TwinCriticQLearning):
         if hasattr(model, 'critic_1'):
             raise NotImplementedError(f'{name} serves one critic with its target (ActorCriticWithTargets), not twin '
                                       'critics')
+        _refuse_quantile_head(name, model)
         if not getattr(model.critic.head, 'num_atoms', 0):
             raise NotImplementedError(f'{name} needs a critic with a DistributionalValueHead')
         online, target = model.critic.head.values, model.target_critic.head.values
@@ -2024,6 +2123,45 @@ class TwinCriticSoftDeterministicPolicyGradient(_ActorQGradient):
         self.optimizer = optimizer
         self.gradient_clip = gradient_clip
         self.entropy_coeff = entropy_coeff
+
+
+class TwinCriticQuantileSoftPolicyGradient(_ActorQGradient):
+    """TQC's actor step: SAC's (actors.py:226-267) with the mean of the two online critics' 2 M quantiles in the place
+    of min(q1, q2): loss = mean(alpha logp - Q) (tonic_truncated_quantile_actor_grad).  With a tuner the entry also
+    writes the coefficient's block, as SAC's tempered entry does."""
+    kind, default_lr = 1, 3e-4
+    head_family = 'sac'
+    stock_capable = False
+    quantile_critic = True
+
+    def __init__(self, optimizer=None, entropy_coeff=0.2, gradient_clip=0, lr_scheduler=None):
+        self.lr_scheduler = lr_scheduler
+        self.optimizer = optimizer
+        self.gradient_clip = gradient_clip
+        self.entropy_coeff = entropy_coeff
+
+    def initialize(self, model):
+        _quantile_model(type(self).__name__, model)
+        super().initialize(model)
+
+    def _workspace_bytes(self, batch):
+        return self.lib.tonic_quantile_workspace_bytes(batch, self.observation_size, self.action_size, self.hidden,
+                                                       self.quantiles)
+
+    def enqueue(self, observations, eps, info_row, n_global=None, targets=None):
+        B = observations.shape[0]
+        ws = self._offpolicy_workspace(B)
+        mean, std = self.norm_tensors()
+        p = _lib.ptr
+        tuner = self.entropy_coeff_updater
+        temper = (None, None, 0.0) if tuner is None else (p(tuner.log_entropy_coeff), p(tuner.grad_sums),
+                                                          float(tuner.target_entropy))
+        _lib.check(self.lib.tonic_truncated_quantile_actor_grad(
+            p(self.flat.flat), p(self.model.flat_critics.flat), p(mean), p(std), self.norm_clip(), p(observations),
+            p(eps), p(self.grad_sums), B, self.observation_size, self.hidden, self.action_size, self.quantiles,
+            float(self.entropy_coeff), *temper, p(ws), ws.numel(), _lib.current_stream()),
+            'tonic_truncated_quantile_actor_grad')
+        self._step(n_global or B * self.world_size, info_row, targets=targets)
 
 
 class EntropyCoeffTuning(_FlatUpdater):
