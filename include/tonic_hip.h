@@ -67,7 +67,9 @@ const char* tonic_last_error(void);
  * 21 = tonic_q_regression_grad / tonic_q_regression_workspace_bytes (QRegression; additive),
  * 22 = tonic_tempered_twin_q_grad / tonic_tempered_actor_q_grad (SAC's learned entropy coefficient; additive)
  * (still 22, purely additive: the tonic_priority_* entries and the tonic_weighted_* distributional critic steps — prioritized replay;
- * tonic_quantile_workspace_bytes / tonic_truncated_quantile_q_grad / tonic_truncated_quantile_actor_grad — TQC)
+ * tonic_quantile_workspace_bytes / tonic_truncated_quantile_q_grad / tonic_truncated_quantile_actor_grad — TQC;
+ * tonic_ensemble_quantile_workspace_bytes / tonic_ensemble_quantile_q_grad / tonic_ensemble_quantile_actor_grad — TQC on
+ * 2 .. 8 critics)
  * and the gfx target the kernels were built for.  TONIC_ABI_VERSION is what a binding was compiled against:
  * tonic_amd/_fastcall (csrc/fastcall.c) and tonic_amd/_lib.py compare it with the loaded library's answer. */
 #define TONIC_ABI_VERSION 22
@@ -1438,6 +1440,36 @@ int tonic_truncated_quantile_actor_grad(const float* d_actor, const float* d_cri
                                         const float* d_log_entropy_coeff, float* d_entropy_coeff_sums,
                                         double target_entropy, void* d_workspace, int64_t workspace_bytes,
                                         void* stream);
+
+/* TQC on an ensemble of 2 <= N <= 8 critics (the paper's default: 5 critics of 25 quantiles, 2 dropped per critic;
+ *   additive under ABI 22).  The three entries above with `int32_t N` behind M and the same statement with 2 -> N:
+ *   the flat blocks are [critic_1 | ... | critic_N], the pool is the N TARGET critics' N M <= 256 values, the
+ *   K = N (M - drop_per_net) smallest kept, loss_m = sum_z (1 / (M K)) sum_i sum_j rho over the N online critics.
+ * tonic_ensemble_quantile_workspace_bytes — a function of its arguments alone; both entries take a workspace of this
+ *   size (0 for an N outside 2 .. 8).  tonic_quantile_workspace_bytes answers what it answered.
+ * tonic_ensemble_quantile_q_grad — Output: gradient SUMS of [critic_1 | ... | critic_N] (N Pc floats) +
+ *   {sum loss_m, sum q, 0, 0, 0, B, 0, 0}, q = (1 / N) sum_z mean_i theta_zi of the online critics.
+ * tonic_ensemble_quantile_actor_grad — Q = the mean of the N (frozen) online critics' N M quantiles at (s, a),
+ *   loss_m = alpha logp - Q; the N critics' action-column gradients are summed into SAC's head backward.  Output and
+ *   the tuner's pair as tonic_truncated_quantile_actor_grad.
+ * TONIC_ERR_INVALID_ARGUMENT as above, each message with its numbers, and: N outside 2 .. 8; N M > 256; then
+ *   TONIC_ERR_WORKSPACE. */
+int64_t tonic_ensemble_quantile_workspace_bytes(int32_t B, int32_t O, int32_t A, int32_t H, int32_t M, int32_t N);
+int tonic_ensemble_quantile_q_grad(const float* d_actor, const float* d_target_critics, const float* d_critics,
+                                   const float* d_norm_mean, const float* d_norm_std, double norm_clip,
+                                   const float* d_observations, const float* d_actions,
+                                   const float* d_next_observations, const float* d_rewards,
+                                   const float* d_discounts, const float* d_eps, float* d_grad_sums, int32_t B,
+                                   int32_t O, int32_t H, int32_t A, int32_t M, int32_t N, int32_t drop_per_net,
+                                   double entropy_coeff, const float* d_log_entropy_coeff, void* d_workspace,
+                                   int64_t workspace_bytes, void* stream);
+int tonic_ensemble_quantile_actor_grad(const float* d_actor, const float* d_critics, const float* d_norm_mean,
+                                       const float* d_norm_std, double norm_clip, const float* d_observations,
+                                       const float* d_eps, float* d_grad_sums, int32_t B, int32_t O, int32_t H,
+                                       int32_t A, int32_t M, int32_t N, double entropy_coeff,
+                                       const float* d_log_entropy_coeff, float* d_entropy_coeff_sums,
+                                       double target_entropy, void* d_workspace, int64_t workspace_bytes,
+                                       void* stream);
 
 #ifdef __cplusplus
 }

@@ -94,6 +94,15 @@ int tonic_debug_truncated_quantile_loss(const float* d_target_1, const float* d_
                                         const float* d_log_entropy_coeff, float* d_dlogits_1, float* d_dlogits_2,
                                         float* d_sample_m, int32_t B, int32_t Bp, void* stream);
 
+/* Test entry: the ensemble critic loss kernel of TQC alone (tonic_ensemble_quantile_q_grad's step 4) on given rows.
+ * d_targets / d_thetas [N][B][ld] (M <= ld <= 32, columns past M ignored; 2 <= N <= 8, N M <= 256), the rest as above.
+ * Out: d_dlogits [N][B][ld] (0 on the columns past M) and d_sample_m [2][Bp] = {loss_m, (1 / N) sum_z mean_i theta_zi}. */
+int tonic_debug_ensemble_quantile_loss(const float* d_targets, const float* d_thetas, int32_t ld,
+                                       const float* d_rewards, const float* d_discounts, const float* d_logp,
+                                       int32_t M, int32_t N, int32_t drop_per_net, double entropy_coeff,
+                                       const float* d_log_entropy_coeff, float* d_dlogits, float* d_sample_m,
+                                       int32_t B, int32_t Bp, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1499,7 +1499,8 @@ class DDPG(Agent):
             self.model.return_normalizer.update()
 
     def _log_update(self, infos, stats):
-        twin = hasattr(self.model, 'critic_2')
+        # (an ensemble of N critics logs one q, the mean over its critics: models.ActorCriticEnsembleWithTargets)
+        twin = hasattr(self.model, 'critic_2') and not hasattr(self.model, 'num_critics')
         for row in infos[0]:
             logger.store('critic/loss', row[0])
             if twin:
@@ -1789,7 +1790,9 @@ class TQC(SAC):
     """Truncated quantile critics (Kuznetsov et al. 2020; the reference has no such agent): SAC — acting, noise
     draws, scheduling, checkpoints, log keys and the optional `entropy_coeff_updater` — on two critics of 25 quantiles
     each, whose pooled target quantiles are sorted and truncated at the top (updaters.TruncatedQuantileQLearning,
-    updaters.TwinCriticQuantileSoftPolicyGradient).  The updaters run the split route."""
+    updaters.TwinCriticQuantileSoftPolicyGradient).  The updaters run the split route.  The paper's 5 critics:
+    `model=models.ActorCriticEnsembleWithTargets(actor, critic, num_critics=5, ...)`, 2 .. 8 critics with
+    num_critics x num_quantiles <= 256; the log then carries critic/q, the mean over the critics, for critic/q1, q2."""
 
     _TEMPERED = (updaters.TruncatedQuantileQLearning, updaters.TwinCriticQuantileSoftPolicyGradient)
 

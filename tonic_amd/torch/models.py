@@ -455,3 +455,38 @@ class ActorTwinCriticWithTargets(ActorCriticWithTargets):
                 (self.target_actor, False), (self.target_critic_1, True),
                 (self.target_critic_2, True)]
 
+
+CRITICS_MAX = 8            # csrc/offpolicy.hip kMaxCritics: N critics of M <= 32 quantiles pool at most 256 values
+
+
+class ActorCriticEnsembleWithTargets(ActorCriticWithTargets):
+    """TQC's ensemble (Kuznetsov et al. 2020; the reference has none): ActorTwinCriticWithTargets with `num_critics`
+    critics, critic_1 .. critic_N and target_critic_1 .. target_critic_N, every one a deep copy of `critic`.  The flat
+    critics are N consecutive blocks; initialize, assign_targets, pack and update_targets are the inherited ones."""
+
+    def __init__(self, actor, critic, num_critics=5, observation_normalizer=None, return_normalizer=None,
+                 target_coeff=0.005):
+        whole = isinstance(num_critics, (int, float)) and not isinstance(num_critics, bool) and \
+            int(num_critics) == num_critics
+        if not whole or not 2 <= num_critics <= CRITICS_MAX:
+            raise ValueError(f'ActorCriticEnsembleWithTargets: num_critics is a whole number with 2 <= num_critics <= '
+                             f'{CRITICS_MAX}, got {num_critics!r}')
+        torch.nn.Module.__init__(self)
+        self.num_critics = int(num_critics)
+        self.actor = actor
+        self.target_actor = copy.deepcopy(actor)
+        for z in range(1, self.num_critics + 1):
+            setattr(self, f'critic_{z}', critic if z == 1 else copy.deepcopy(critic))
+        for z in range(1, self.num_critics + 1):
+            setattr(self, f'target_critic_{z}', copy.deepcopy(critic))
+        self.observation_normalizer = observation_normalizer
+        self.return_normalizer = return_normalizer
+        self.target_coeff = target_coeff
+
+    def critics(self, target=False):
+        prefix = 'target_critic_' if target else 'critic_'
+        return [getattr(self, f'{prefix}{z}') for z in range(1, self.num_critics + 1)]
+
+    def _networks(self):
+        return [(self.actor, False)] + [(critic, True) for critic in self.critics()] + \
+            [(self.target_actor, False)] + [(critic, True) for critic in self.critics(target=True)]

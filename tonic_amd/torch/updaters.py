@@ -1136,9 +1136,26 @@ def _actor_code(torso, bounds, generic=False):
     return code
 
 
+def _critic_count(model):
+    """How many online critics the model packs: an ensemble's num_critics, 2 for twin critics, else 1."""
+    if hasattr(model, 'num_critics'):
+        return int(model.num_critics)
+    return 2 if hasattr(model, 'critic_1') else 1
+
+
+def _refuse_ensemble(name, model):
+    """Every updater but TQC's two on a model of N critics (models.ActorCriticEnsembleWithTargets): refused by name
+    (its entries would walk N critic blocks by their own one or two)."""
+    if hasattr(model, 'num_critics'):
+        raise NotImplementedError(
+            f'{name} does not serve a {type(model).__name__} of {model.num_critics} critics: an ensemble is trained '
+            'by TQC\'s updaters, TruncatedQuantileQLearning and TwinCriticQuantileSoftPolicyGradient')
+
+
 def _refuse_quantile_head(name, model):
     """The scalar and categorical updaters on a critic with a QuantileValueHead: refused by name (its block has
     neither a scalar critic's nor, without a support, a categorical critic's meaning)."""
+    _refuse_ensemble(name, model)
     critic = model.critic_1 if hasattr(model, 'critic_1') else model.critic
     if hasattr(critic.head, 'num_quantiles'):
         raise NotImplementedError(
@@ -1219,7 +1236,7 @@ class _QUpdater(_FlatUpdater):
         else:
             want_critic = lib.tonic_q_critic_param_count(
                 self.observation_size, self.action_size, self.hidden)
-        n_critics = 2 if hasattr(model, 'critic_1') else 1
+        n_critics = _critic_count(model)
         if (model.flat_actor.count, model.flat_critics.count) != (want_actor,
                                                                    n_critics * want_critic):
             raise NotImplementedError(
@@ -1448,6 +1465,7 @@ class QRegression(_TwinCriticQLearning):
     def _shapes(self, model):
         from tonic_amd.torch import models
         self.model = model
+        _refuse_ensemble('QRegression', model)
         if hasattr(model, 'critic_1'):
             raise NotImplementedError('QRegression regresses model.critic (critics.py:40,45): a model with critic_1 / '
                                       'critic_2 is not served, twin regression is no updater of the reference')
@@ -1659,27 +1677,51 @@ class TwinCriticDistributionalDeterministicQLearning(_DistributionalQLearning):
 
 
 QUANTILES_MAX = 32         # csrc/offpolicy.hip kMaxQuantiles: the two critics' pooled target values fill one wave
+POOLED_MAX = 256           # csrc/offpolicy.hip kMaxPooled: an ensemble's pooled target values, four per lane
 
 
 def _quantile_model(name, model):
-    """What TQC's two updaters ask of the model, refused by name: twin critics, a QuantileValueHead of one size in
-    all four, 1 .. 32 quantiles, no Return normaliser.  Returns the number of quantiles."""
+    """What TQC's two updaters ask of the model, refused by name: twin critics or an ensemble of N, a
+    QuantileValueHead of one size in all 2 N critics, 1 .. 32 quantiles, N M <= 256, no Return normaliser.  Returns
+    the number of quantiles."""
     from tonic_amd.torch import models
     if not hasattr(model, 'critic_2'):
-        raise NotImplementedError(f'{name} needs a model with twin critics (ActorTwinCriticWithTargets)')
-    critics = (model.critic_1, model.critic_2, model.target_critic_1, model.target_critic_2)
+        raise NotImplementedError(f'{name} needs a model with twin critics (ActorTwinCriticWithTargets) or an '
+                                  'ensemble of them (ActorCriticEnsembleWithTargets)')
+    ensemble = hasattr(model, 'num_critics')
+    N = _critic_count(model)
+    critics = [getattr(model, f'{prefix}{z}') for prefix in ('critic_', 'target_critic_') for z in range(1, N + 1)]
     if not all(isinstance(critic.head, models.QuantileValueHead) for critic in critics):
         raise NotImplementedError(f'{name} needs critics with a QuantileValueHead')
     counts = [int(critic.head.num_quantiles) for critic in critics]
     if len(set(counts)) != 1:
-        raise NotImplementedError(f'{name} needs the same num_quantiles in all four critics\' heads, got {counts}')
+        heads = f'all {2 * N}' if ensemble else 'all four'
+        raise NotImplementedError(f'{name} needs the same num_quantiles in {heads} critics\' heads, got {counts}')
     if not 1 <= counts[0] <= QUANTILES_MAX:
         raise NotImplementedError(f'{name}: the quantile kernels serve num_quantiles = 1 .. {QUANTILES_MAX}, got '
                                   f'{counts[0]}')
+    if ensemble and N * counts[0] > POOLED_MAX:
+        raise NotImplementedError(f'{name}: the ensemble kernels pool num_critics x num_quantiles <= {POOLED_MAX} '
+                                  f'values, got {N} x {counts[0]} = {N * counts[0]}')
     if getattr(model, 'return_normalizer', None):
         raise NotImplementedError(f'{name} does not serve a Return normaliser (return_normalizer): the quantile '
                                   'critics have no squashed head')
     return counts[0]
+
+
+def _quantile_entry(model, step):
+    """TQC's entry for `step` ('q_grad' / 'actor_grad') and what it takes behind M: a twin model keeps the twin
+    entries, an ensemble (models.ActorCriticEnsembleWithTargets) takes the ensemble's with N = num_critics."""
+    if hasattr(model, 'num_critics'):
+        return f'tonic_ensemble_quantile_{step}', (int(model.num_critics),)
+    return f'tonic_truncated_quantile_{step}', ()
+
+
+def _quantile_workspace_bytes(updater, batch):
+    shape = (batch, updater.observation_size, updater.action_size, updater.hidden, updater.quantiles)
+    if hasattr(updater.model, 'num_critics'):
+        return updater.lib.tonic_ensemble_quantile_workspace_bytes(*shape, int(updater.model.num_critics))
+    return updater.lib.tonic_quantile_workspace_bytes(*shape)
 
 
 class TruncatedQuantileQLearning(_TwinCriticQLearning):
@@ -1688,7 +1730,9 @@ class TruncatedQuantileQLearning(_TwinCriticQLearning):
     are pooled and sorted and the `top_quantiles_to_drop_per_net` largest per critic dropped, K = 2 (M - d) kept:
     y_j = r + discount (Z_j - alpha logp'); each online critic takes the quantile Huber loss (kappa = 1) of its M
     quantiles at tau_i = (2 i + 1) / (2 M) against the K targets, loss_1 + loss_2 (tonic_truncated_quantile_q_grad).
-    Logs the row of SAC: loss, and the online critics' mean quantiles q1, q2."""
+    Logs the row of SAC: loss, and the online critics' mean quantiles q1, q2.
+    On an ensemble of N critics (models.ActorCriticEnsembleWithTargets): the same with 2 -> N, N M <= 256
+    (tonic_ensemble_quantile_q_grad); the row is then loss and q, the mean over the critics."""
     kind, default_lr = 1, 3e-4
     head_family = 'sac'
     stock_capable = False
@@ -1715,8 +1759,7 @@ class TruncatedQuantileQLearning(_TwinCriticQLearning):
         return self.model.flat_actor.flat
 
     def _workspace_bytes(self, batch):
-        return self.lib.tonic_quantile_workspace_bytes(batch, self.observation_size, self.action_size, self.hidden,
-                                                       self.quantiles)
+        return _quantile_workspace_bytes(self, batch)
 
     def enqueue(self, batch, eps, info_row, n_global=None):
         """eps: the [B, A] standard-normal draw of the next action's rsample."""
@@ -1725,14 +1768,21 @@ class TruncatedQuantileQLearning(_TwinCriticQLearning):
         mean, std = self.norm_tensors()
         p = _lib.ptr
         tuner = self.entropy_coeff_updater         # (the coefficient is then read on the device)
-        _lib.check(self.lib.tonic_truncated_quantile_q_grad(
+        entry, ensemble = _quantile_entry(self.model, 'q_grad')
+        _lib.check(getattr(self.lib, entry)(
             p(self._policy_params()), p(self.model.flat_target_critics.flat), p(self.flat.flat), p(mean), p(std),
             self.norm_clip(), p(batch['observations']), p(batch['actions']), p(batch['next_observations']),
             p(batch['rewards']), p(batch['discounts']), p(eps), p(self.grad_sums), B, self.observation_size,
-            self.hidden, self.action_size, self.quantiles, int(self.top_quantiles_to_drop_per_net),
+            self.hidden, self.action_size, self.quantiles, *ensemble, int(self.top_quantiles_to_drop_per_net),
             float(self.entropy_coeff), p(tuner.log_entropy_coeff) if tuner is not None else None, p(ws), ws.numel(),
-            _lib.current_stream()), 'tonic_truncated_quantile_q_grad')
+            _lib.current_stream()), entry)
         self._step(n_global or B * self.world_size, info_row)
+
+    def __call__(self, observations, actions, next_observations, rewards, discounts):
+        out = super().__call__(observations, actions, next_observations, rewards, discounts)
+        if hasattr(self.model, 'num_critics'):       # (an ensemble's row: loss and the mean q over its critics)
+            out = {'loss': out['loss'], 'q': out['q1']}
+        return out
 
 
 class ExpectedSARSA(_TwinCriticQLearning):
@@ -1751,6 +1801,7 @@ class ExpectedSARSA(_TwinCriticQLearning):
         self.gradient_clip = gradient_clip
 
     def initialize(self, model):
+        _refuse_ensemble(type(self).__name__, model)
         critic = model.critic_1 if hasattr(model, 'critic_1') else model.critic
         if getattr(critic.head, 'num_atoms', 0):
             # (the scalar entry would walk the categorical critic's block by a scalar critic's offsets)
@@ -1805,6 +1856,7 @@ class DistributionalExpectedSARSA(_TwinCriticQLearning):
 
     def initialize(self, model):
         name = type(self).__name__
+        _refuse_ensemble(name, model)
         if hasattr(model, 'critic_1'):
             raise NotImplementedError(f'{name} serves one critic with its target (ActorCriticWithTargets), not twin '
                                       'critics')
@@ -2128,7 +2180,8 @@ class TwinCriticSoftDeterministicPolicyGradient(_ActorQGradient):
 class TwinCriticQuantileSoftPolicyGradient(_ActorQGradient):
     """TQC's actor step: SAC's (actors.py:226-267) with the mean of the two online critics' 2 M quantiles in the place
     of min(q1, q2): loss = mean(alpha logp - Q) (tonic_truncated_quantile_actor_grad).  With a tuner the entry also
-    writes the coefficient's block, as SAC's tempered entry does."""
+    writes the coefficient's block, as SAC's tempered entry does.  On an ensemble of N critics: the mean of their N M
+    quantiles (tonic_ensemble_quantile_actor_grad)."""
     kind, default_lr = 1, 3e-4
     head_family = 'sac'
     stock_capable = False
@@ -2145,8 +2198,7 @@ class TwinCriticQuantileSoftPolicyGradient(_ActorQGradient):
         super().initialize(model)
 
     def _workspace_bytes(self, batch):
-        return self.lib.tonic_quantile_workspace_bytes(batch, self.observation_size, self.action_size, self.hidden,
-                                                       self.quantiles)
+        return _quantile_workspace_bytes(self, batch)
 
     def enqueue(self, observations, eps, info_row, n_global=None, targets=None):
         B = observations.shape[0]
@@ -2156,11 +2208,11 @@ class TwinCriticQuantileSoftPolicyGradient(_ActorQGradient):
         tuner = self.entropy_coeff_updater
         temper = (None, None, 0.0) if tuner is None else (p(tuner.log_entropy_coeff), p(tuner.grad_sums),
                                                           float(tuner.target_entropy))
-        _lib.check(self.lib.tonic_truncated_quantile_actor_grad(
+        entry, ensemble = _quantile_entry(self.model, 'actor_grad')
+        _lib.check(getattr(self.lib, entry)(
             p(self.flat.flat), p(self.model.flat_critics.flat), p(mean), p(std), self.norm_clip(), p(observations),
             p(eps), p(self.grad_sums), B, self.observation_size, self.hidden, self.action_size, self.quantiles,
-            float(self.entropy_coeff), *temper, p(ws), ws.numel(), _lib.current_stream()),
-            'tonic_truncated_quantile_actor_grad')
+            *ensemble, float(self.entropy_coeff), *temper, p(ws), ws.numel(), _lib.current_stream()), entry)
         self._step(n_global or B * self.world_size, info_row, targets=targets)
 
 
