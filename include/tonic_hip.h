@@ -1403,27 +1403,35 @@ int tonic_distributional_mpo_actor_grad_shard(const float* d_actor_params, const
 
 /* ---------------------------------------------------------------------------------------------
  * TQC: SAC on truncated quantile critics (Kuznetsov et al. 2020; additive under ABI 22).  No reference line states
- *   it: SAC's steps (updaters/critics.py:202-235, actors.py:238-267) with two critics of M quantile outputs each.
- *   A critic has D4PG's layout, tonic_mlp_actor_param_count(O + A, H, M, 1) — one linear head of M outputs — and
- *   the flat blocks are [critic_1 | critic_2]; the actor is SAC's (two heads), H any code the SAC entries take.
- *   1 <= M <= 32, so that the 2 M pooled target values fit one wave.
+ *   it: SAC's steps (updaters/critics.py:202-235, actors.py:238-267) with 2 <= N <= 8 critics of M quantile outputs
+ *   each (the paper's default: 5 critics of 25 quantiles, 2 dropped per critic).  A critic has D4PG's layout,
+ *   tonic_mlp_actor_param_count(O + A, H, M, 1) — one linear head of M outputs — and the flat blocks are
+ *   [critic_1 | ... | critic_N]; the actor is SAC's (two heads), H any code the SAC entries take.  1 <= M <= 32 and
+ *   N M <= 256, so that the pooled target values fit one wave at up to four values per lane.
+ *   The tonic_ensemble_* entries take N behind M.  The twin entries (tonic_quantile_workspace_bytes,
+ *   tonic_truncated_quantile_q_grad, tonic_truncated_quantile_actor_grad) are the same steps at N = 2; the twin
+ *   critic entry writes the twin model's statistics row {loss, q1, q2}.
  *
- * tonic_quantile_workspace_bytes — a function of its arguments alone (no GPU, no tuning switch); both entries take
- *   a workspace of this size.
- * tonic_truncated_quantile_q_grad — per row m: a' = the ONLINE actor's rsample at s' from d_eps [B, A] with logp';
- *   Z = the two TARGET critics' 2 M values at (s', a') sorted ascending, the K = 2 (M - drop_per_net) smallest kept;
+ * tonic_ensemble_quantile_workspace_bytes — a function of its arguments alone (no GPU, no tuning switch); both
+ *   entries take a workspace of this size (0 for an N outside 2 .. 8).  tonic_quantile_workspace_bytes equals the
+ *   ensemble query at N = 2.
+ * tonic_ensemble_quantile_q_grad — per row m: a' = the ONLINE actor's rsample at s' from d_eps [B, A] with logp';
+ *   Z = the N TARGET critics' N M values at (s', a') sorted ascending, the K = N (M - drop_per_net) smallest kept;
  *   y_j = r + discount (Z_j - alpha logp'); for each online critic z and quantile i (tau_i = (2 i + 1) / (2 M)),
  *   u = y_j - theta_zi, rho = |tau_i - 1{u < 0}| huber_1(u); loss_m = sum_z (1 / (M K)) sum_i sum_j rho.
  *   alpha = entropy_coeff, or expf(*d_log_entropy_coeff) read on the device when that pointer is given.
- *   Output: gradient SUMS of [critic_1 | critic_2] + {sum loss_m, sum q1, sum q2, 0, 0, B, 0, 0}, q_z = mean_i theta_zi
- *   of the online critics (float64, fixed order).
- * tonic_truncated_quantile_actor_grad — a = the actor's rsample at s with logp; Q = the mean of the two (frozen)
- *   online critics' 2 M quantiles at (s, a); loss_m = alpha logp - Q.  Output: gradient SUMS of the actor +
- *   {sum loss_m, 0, 0, 0, 0, B, 0, 0}; with d_log_entropy_coeff / d_entropy_coeff_sums (both or neither) the
- *   coefficient's block [1 + 8] as tonic_tempered_actor_q_grad writes it, in no launch more.
- * TONIC_ERR_INVALID_ARGUMENT, each with its own message, before anything touches the device: a NULL pointer; one of
- *   the tuner's pair without the other; target_entropy not finite; drop_per_net outside 0 .. M - 1; B, O or A below 1;
- *   an unknown H; M outside 1 .. 32; then TONIC_ERR_WORKSPACE: a workspace below the query's answer. */
+ *   Output: gradient SUMS of [critic_1 | ... | critic_N] (N Pc floats) + {sum loss_m, sum q, 0, 0, 0, B, 0, 0},
+ *   q = (1 / N) sum_z mean_i theta_zi of the online critics (float64, fixed order).
+ *   tonic_truncated_quantile_q_grad (N = 2): + {sum loss_m, sum q1, sum q2, 0, 0, B, 0, 0}, q_z = mean_i theta_zi.
+ * tonic_ensemble_quantile_actor_grad — a = the actor's rsample at s with logp; Q = the mean of the N (frozen) online
+ *   critics' N M quantiles at (s, a); loss_m = alpha logp - Q; the N critics' action-column gradients are summed
+ *   into SAC's head backward.  Output: gradient SUMS of the actor + {sum loss_m, 0, 0, 0, 0, B, 0, 0}; with
+ *   d_log_entropy_coeff / d_entropy_coeff_sums (both or neither) the coefficient's block [1 + 8] as
+ *   tonic_tempered_actor_q_grad writes it, in no launch more.  tonic_truncated_quantile_actor_grad: the same, N = 2.
+ * TONIC_ERR_INVALID_ARGUMENT, each with its own message and its numbers, before anything touches the device: a NULL
+ *   pointer; one of the tuner's pair without the other; target_entropy not finite; drop_per_net outside 0 .. M - 1;
+ *   B, O or A below 1; an unknown H; N outside 2 .. 8; M outside 1 .. 32; N M > 256; then TONIC_ERR_WORKSPACE: a
+ *   workspace below the query's answer ("workspace of … bytes, … needed"). */
 int64_t tonic_quantile_workspace_bytes(int32_t B, int32_t O, int32_t A, int32_t H, int32_t M);
 int tonic_truncated_quantile_q_grad(const float* d_actor, const float* d_target_critics, const float* d_critics,
                                     const float* d_norm_mean, const float* d_norm_std, double norm_clip,
@@ -1441,19 +1449,6 @@ int tonic_truncated_quantile_actor_grad(const float* d_actor, const float* d_cri
                                         double target_entropy, void* d_workspace, int64_t workspace_bytes,
                                         void* stream);
 
-/* TQC on an ensemble of 2 <= N <= 8 critics (the paper's default: 5 critics of 25 quantiles, 2 dropped per critic;
- *   additive under ABI 22).  The three entries above with `int32_t N` behind M and the same statement with 2 -> N:
- *   the flat blocks are [critic_1 | ... | critic_N], the pool is the N TARGET critics' N M <= 256 values, the
- *   K = N (M - drop_per_net) smallest kept, loss_m = sum_z (1 / (M K)) sum_i sum_j rho over the N online critics.
- * tonic_ensemble_quantile_workspace_bytes — a function of its arguments alone; both entries take a workspace of this
- *   size (0 for an N outside 2 .. 8).  tonic_quantile_workspace_bytes answers what it answered.
- * tonic_ensemble_quantile_q_grad — Output: gradient SUMS of [critic_1 | ... | critic_N] (N Pc floats) +
- *   {sum loss_m, sum q, 0, 0, 0, B, 0, 0}, q = (1 / N) sum_z mean_i theta_zi of the online critics.
- * tonic_ensemble_quantile_actor_grad — Q = the mean of the N (frozen) online critics' N M quantiles at (s, a),
- *   loss_m = alpha logp - Q; the N critics' action-column gradients are summed into SAC's head backward.  Output and
- *   the tuner's pair as tonic_truncated_quantile_actor_grad.
- * TONIC_ERR_INVALID_ARGUMENT as above, each message with its numbers, and: N outside 2 .. 8; N M > 256; then
- *   TONIC_ERR_WORKSPACE. */
 int64_t tonic_ensemble_quantile_workspace_bytes(int32_t B, int32_t O, int32_t A, int32_t H, int32_t M, int32_t N);
 int tonic_ensemble_quantile_q_grad(const float* d_actor, const float* d_target_critics, const float* d_critics,
                                    const float* d_norm_mean, const float* d_norm_std, double norm_clip,

@@ -82,26 +82,18 @@ int tonic_gemm_group_f32(const char* mode, const tonic_gemm_problem* problems,
  * resident collect kernel does when not all of its workgroups find a compute unit. */
 int tonic_debug_occupy(int32_t workgroups, double milliseconds, void* stream);
 
-/* Test entry: the truncated quantile critic loss kernel of TQC alone (tonic_truncated_quantile_q_grad's step 4,
- * include/tonic_hip.h) on given rows.  d_target_1 / d_target_2 / d_theta_1 / d_theta_2 [B, ld] (M <= ld <= 32: the
- * target and the online critics' quantiles, columns past M ignored), d_rewards / d_discounts / d_logp [B]; alpha =
- * entropy_coeff, or expf(*d_log_entropy_coeff) when given.  Out: d_dlogits_1 / d_dlogits_2 [B, ld] (the row losses'
- * gradients, 0 on the columns past M) and d_sample_m [3][Bp] = {loss_m, q1, q2}. */
-int tonic_debug_truncated_quantile_loss(const float* d_target_1, const float* d_target_2, const float* d_theta_1,
-                                        const float* d_theta_2, int32_t ld, const float* d_rewards,
-                                        const float* d_discounts, const float* d_logp, int32_t M,
-                                        int32_t drop_per_net, double entropy_coeff,
-                                        const float* d_log_entropy_coeff, float* d_dlogits_1, float* d_dlogits_2,
-                                        float* d_sample_m, int32_t B, int32_t Bp, void* stream);
-
-/* Test entry: the ensemble critic loss kernel of TQC alone (tonic_ensemble_quantile_q_grad's step 4) on given rows.
- * d_targets / d_thetas [N][B][ld] (M <= ld <= 32, columns past M ignored; 2 <= N <= 8, N M <= 256), the rest as above.
- * Out: d_dlogits [N][B][ld] (0 on the columns past M) and d_sample_m [2][Bp] = {loss_m, (1 / N) sum_z mean_i theta_zi}. */
+/* Test entry: the critic loss kernel of TQC alone (step 4 of tonic_ensemble_quantile_q_grad and, at N = 2 with
+ * twin_row, of tonic_truncated_quantile_q_grad; include/tonic_hip.h) on given rows.  d_targets / d_thetas [N][B][ld]
+ * (the target and the online critics' quantiles; M <= ld <= 32, columns past M ignored; 2 <= N <= 8, N M <= 256),
+ * d_rewards / d_discounts / d_logp [B]; alpha = entropy_coeff, or expf(*d_log_entropy_coeff) when given.
+ * Out: d_dlogits [N][B][ld] (the row losses' gradients, 0 on the columns past M) and d_sample_m [3][Bp] =
+ * {loss_m, (1 / N) sum_z mean_i theta_zi, 0}, or with twin_row != 0 (N = 2 only: TONIC_ERR_INVALID_ARGUMENT
+ * otherwise) the twin row {loss_m, q1, q2}, q_z = mean_i theta_zi. */
 int tonic_debug_ensemble_quantile_loss(const float* d_targets, const float* d_thetas, int32_t ld,
                                        const float* d_rewards, const float* d_discounts, const float* d_logp,
                                        int32_t M, int32_t N, int32_t drop_per_net, double entropy_coeff,
                                        const float* d_log_entropy_coeff, float* d_dlogits, float* d_sample_m,
-                                       int32_t B, int32_t Bp, void* stream);
+                                       int32_t B, int32_t Bp, int32_t twin_row, void* stream);
 
 #ifdef __cplusplus
 }

@@ -7,12 +7,15 @@ scripts/tqc_timing.py does:
   e2  this commit's ensemble entries at N = 2 (models.ActorCriticEnsembleWithTargets, the same 25 / 2);
   e5  the ensemble at N = 5: the paper's configuration;
   k   the ensemble critic loss kernel alone (tonic_debug_ensemble_quantile_loss) at B = 256 and N M = 50 (2 x 25, one
-      value per lane), 125 (5 x 25, two) and 256 (8 x 32, four), 2 dropped per critic.
+      value per lane), 125 (5 x 25, two) and 256 (8 x 32, four), 2 dropped per critic;
+  pe2, pe5, pk   e2, e5 and k on the parent commit, by the parent's own copy of this script (its developer entry may
+      take other arguments).
 
 a .. e5: the agent's default (256, 256) torso, O = 17, A = 6, B = 256, one update call of 200 iterations captured as a
 hipGraph; device events round 7 replays (new indices and draws each), microseconds per iteration, the median of the 7.
 k: 200 launches captured as one graph, device events round 7 replays, microseconds per launch.  Checked when the figures
-are written: b's median inside the parent's own spread between its two processes.  The rest is reported, not judged.
+are written: b's median inside the range of the parent's own windows, and inside the spread between its two processes;
+each kernel figure inside the range of the parent's windows.  The rest is reported, not judged.
 
     python scripts/tqc_ensemble_timing.py --parent <built checkout of the parent commit> [--rounds 2] [--out FILE]
 
@@ -99,12 +102,12 @@ def one_kernel():
         targets, thetas = (5 + 3 * torch.randn(N, B, ld, device='cuda', generator=generator) for _ in range(2))
         rewards, logp = (torch.randn(B, device='cuda', generator=generator) for _ in range(2))
         discounts = torch.full((B,), 0.99, device='cuda')
-        dlogits, sample_m = torch.empty_like(thetas), torch.empty(2, B, device='cuda')
+        dlogits, sample_m = torch.empty_like(thetas), torch.empty(3, B, device='cuda')
 
         def launch():
             _lib.check(lib.tonic_debug_ensemble_quantile_loss(
                 p(targets), p(thetas), ld, p(rewards), p(discounts), p(logp), quantiles, N, DROP, 0.2, None, p(dlogits),
-                p(sample_m), B, B, _lib.current_stream()), 'tonic_debug_ensemble_quantile_loss')
+                p(sample_m), B, B, 0, _lib.current_stream()), 'tonic_debug_ensemble_quantile_loss')
         stream = torch.cuda.Stream()
         with torch.cuda.stream(stream):
             launch()                             # (outside the capture first)
@@ -129,7 +132,7 @@ def one_kernel():
     print('RESULT ' + json.dumps(dict(kernel=out, launches_per_window=ITERATIONS)))
 
 
-FIGURES = {'a': 0, 'b': 0, 'e2': 2, 'e5': 5}
+FIGURES = {'a': 0, 'b': 0, 'e2': 2, 'e5': 5, 'pe2': 2, 'pe5': 5}
 
 
 def main():
@@ -147,11 +150,13 @@ def main():
     parent = os.path.abspath(args.parent)
 
     def run(figure):
-        command = [sys.executable, os.path.abspath(__file__), '--one']
-        command += ['kernel'] if figure == 'k' else ['time', '--critics', str(FIGURES[figure])]
+        theirs = figure.startswith('p')
+        script = os.path.join(parent, 'scripts', os.path.basename(__file__)) if theirs else os.path.abspath(__file__)
+        command = [sys.executable, script, '--one']
+        command += ['kernel'] if figure in ('k', 'pk') else ['time', '--critics', str(FIGURES[figure])]
         env = dict(os.environ)
         env.pop('TONIC_AMD_NO_GRAPH', None)
-        done = subprocess.run(command, cwd=parent if figure == 'a' else ROOT, env=env, capture_output=True, text=True,
+        done = subprocess.run(command, cwd=parent if figure == 'a' or theirs else ROOT, env=env, capture_output=True, text=True,
                               timeout=300)
         if done.returncode != 0:
             sys.stderr.write(done.stdout[-2000:] + done.stderr[-4000:])
@@ -165,7 +170,7 @@ def main():
             what='TQC learner iterations, (256, 256) torso, O = 17, A = 6, B = 256, 25 quantiles per critic, 2 dropped '
                  'per critic, one MI355X, one fresh process per run, the order reversed in the second round: a = the '
                  'parent commit\'s twin TQC, b = this commit\'s twin TQC, e2 = the ensemble entries at N = 2, e5 = at '
-                 'N = 5; microseconds per iteration, device events round 7 replays of a captured update call of '
+                 'N = 5, pe2 / pe5 / pk = e2 / e5 / k on the parent commit; microseconds per iteration, device events round 7 replays of a captured update call of '
                  f'{ITERATIONS} iterations, the median of the 7 per run.  k = the ensemble critic loss kernel alone at '
                  f'B = 256 and N M = 50, 125, 256: microseconds per launch, 7 replays of {ITERATIONS} captured launches',
             runs=runs, summary=summary)
@@ -173,7 +178,7 @@ def main():
         with open(args.out, 'w') as out:
             json.dump(result, out, indent=1)
 
-    order = ('a', 'b', 'e2', 'e5', 'k')
+    order = ('a', 'b', 'e2', 'e5', 'k', 'pe2', 'pe5', 'pk')
     for round_ in range(1, args.rounds + 1):
         for figure in (order if round_ % 2 else order[::-1]):
             runs.append({**run(figure), 'figure': figure, 'round': round_})
@@ -182,14 +187,21 @@ def main():
     windows = {f: [w for r in runs if r['figure'] == f for w in r['us_per_iteration_windows']] for f in FIGURES}
     medians = {f: statistics.median(w) for f, w in windows.items()}
     per_process = [r['us_per_iteration'] for r in runs if r['figure'] == 'a']
-    alone = [r['kernel'] for r in runs if r['figure'] == 'k']
-    kernel = {pool: statistics.median([w for r in alone for w in r[pool]['us_per_launch_windows']]) for pool in alone[0]}
+    alone = {f: [r['kernel'] for r in runs if r['figure'] == f] for f in ('k', 'pk')}
+    launches = {f: {pool: [w for r in alone[f] for w in r[pool]['us_per_launch_windows']] for pool in alone[f][0]}
+                for f in alone}
+    kernel = {f: {pool: round(statistics.median(w), 3) for pool, w in launches[f].items()} for f in launches}
     summary.update(
         a_median=round(medians['a'], 3), a_min=round(min(windows['a']), 3), a_max=round(max(windows['a']), 3),
         a_process_medians=per_process, b_median=round(medians['b'], 3), e2_median=round(medians['e2'], 3),
         e5_median=round(medians['e5'], 3), b_minus_a=round(medians['b'] - medians['a'], 3),
         e2_minus_b=round(medians['e2'] - medians['b'], 3), e5_over_b=round(medians['e5'] / medians['b'], 4),
-        loss_kernel_us={pool: round(v, 3) for pool, v in kernel.items()},
+        pe2_median=round(medians['pe2'], 3), pe5_median=round(medians['pe5'], 3),
+        loss_kernel_us=kernel['k'], parent_loss_kernel_us=kernel['pk'],
+        parent_loss_kernel_us_range={pool: [min(w), max(w)] for pool, w in launches['pk'].items()},
+        loss_kernel_within_parent_windows={pool: bool(min(launches['pk'][pool]) <= kernel['k'][pool]
+                                                      <= max(launches['pk'][pool])) for pool in kernel['k']},
+        b_within_a_windows=bool(min(windows['a']) <= medians['b'] <= max(windows['a'])),
         b_within_a_process_medians=bool(min(per_process) <= medians['b'] <= max(per_process)))
     write()
     print(json.dumps(summary))

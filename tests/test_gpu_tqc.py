@@ -1,9 +1,10 @@
 """GPU tests of TQC (truncated quantile critics) against the float64 restatement tests/tqc_ref.py.
 
-1. truncated_quantile_critic_loss_kernel alone (tonic_debug_truncated_quantile_loss) on crafted rows: unsorted targets
-   whose pooled order interleaves the two critics, identical target critics, rows with discount 0, errors on both
+1. the critic loss kernel alone in the twin form (tonic_debug_ensemble_quantile_loss at N = 2 with the twin row
+   {loss, q1, q2}) on crafted rows: unsorted targets whose pooled order interleaves the two critics, identical target critics, rows with discount 0, errors on both
    sides of |u| = 1; a lone wave, a ragged workgroup and a general batch; K = 2 at both ends of M, no truncation,
-   2 M = 64 and a row wider than 2 M.  Bit-identical launches.
+   2 M = 64 and a row wider than 2 M.  Bit-identical launches; the bits of the twin kernel this one replaced
+   (tests/golden/tqc_twin_loss_parent.npz, scripts/tqc_twin_rows_record.py).
 2. tonic_truncated_quantile_q_grad / _actor_grad: gradient sums per tensor and the logged statistics against float64
    autograd (the conventions and bounds of tests/test_gpu_offpolicy_grads.py), with the float coefficient and with
    the coefficient read on the device, whose own block is checked as well.
@@ -11,6 +12,7 @@
    with a tuner; save / load; two ranks against one; gradient clipping.
 
 Every check prints the largest error it saw before it asserts."""
+import hashlib
 import math
 import os
 
@@ -101,16 +103,16 @@ def launch_loss(lib, rows, M, d, alpha=ALPHA, log_alpha=None):
         out = torch.full((B, ld), fill, dtype=torch.float32)
         out[:, :M] = x
         return out.cuda()
-    t1, t2 = padded(rows['target_1'], 777.0), padded(rows['target_2'], -777.0)
-    th1, th2 = padded(rows['theta_1'], float('nan')), padded(rows['theta_2'], 555.0)
+    targets = torch.stack([padded(rows['target_1'], 777.0), padded(rows['target_2'], -777.0)])       # [2][B, ld]
+    thetas = torch.stack([padded(rows['theta_1'], float('nan')), padded(rows['theta_2'], 555.0)])
     r, disc, logp = rows['rewards'].cuda(), rows['discounts'].cuda(), rows['logp'].cuda()
-    g1, g2 = (torch.full((B, ld), float('nan'), device='cuda') for _ in range(2))
+    dlogits = torch.full((2, B, ld), float('nan'), device='cuda')
     sample_m = torch.full((3, Bp), float('nan'), device='cuda')
-    _lib.check(lib.tonic_debug_truncated_quantile_loss(
-        p(t1), p(t2), p(th1), p(th2), ld, p(r), p(disc), p(logp), M, d, float(alpha), p(log_alpha), p(g1), p(g2),
-        p(sample_m), B, Bp, _lib.current_stream()), 'tonic_debug_truncated_quantile_loss')
+    _lib.check(lib.tonic_debug_ensemble_quantile_loss(
+        p(targets), p(thetas), ld, p(r), p(disc), p(logp), M, 2, d, float(alpha), p(log_alpha), p(dlogits),
+        p(sample_m), B, Bp, 1, _lib.current_stream()), 'tonic_debug_ensemble_quantile_loss')
     torch.cuda.synchronize()
-    return g1.cpu(), g2.cpu(), sample_m[:, :B].cpu()
+    return dlogits[0].cpu(), dlogits[1].cpu(), sample_m[:, :B].cpu()
 
 
 def loss_errors(got, want, M):
@@ -151,6 +153,45 @@ def test_loss_kernel_vs_float64_on_crafted_rows(lib, M, d, B):
     for a, b in zip(got, again):
         assert np.array_equal(bits(a), bits(b)), 'two launches on the same inputs differ'
     assert gradient <= DLOGITS_BOUND and value <= VALUE_BOUND, (gradient, value)
+
+
+def rows_digest(rows):
+    """sha256 of a case's input rows, in the order crafted_rows names them."""
+    digest = hashlib.sha256()
+    for name in ('target_1', 'target_2', 'theta_1', 'theta_2', 'rewards', 'discounts', 'logp'):
+        digest.update(rows[name].contiguous().numpy().tobytes())
+    return digest.hexdigest()
+
+
+def ulps_apart(a, b):
+    """How many float32 values lie between a and b, elementwise (finite values)."""
+    def ordered(x):
+        i = x.contiguous().view(torch.int32).to(torch.int64)
+        return torch.where(i < 0, -(i & 0x7FFFFFFF), i)
+    return (ordered(a) - ordered(b)).abs()
+
+
+def test_loss_kernel_equals_the_retired_twin_kernel(lib):
+    """tests/golden/tqc_twin_loss_parent.npz holds what the twin kernel of the commit before the fold
+    (truncated_quantile_critic_loss_kernel: critic z = lane / 32, one wave_sum over that placement) wrote on
+    crafted_rows for LOSS_CASES x LOSS_BATCHES, recorded by scripts/tqc_twin_rows_record.py.  The kernel kept gives
+    the same dlogits bit for bit, padding included; loss_m, q1 and q2 are float64 sums over another lane placement
+    cast once: within 1 float32 ulp."""
+    golden = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'tqc_twin_loss_parent.npz'))
+    worst = 0
+    for M, d in LOSS_CASES:
+        for B in LOSS_BATCHES:
+            key = f'M{M}_d{d}_B{B}'
+            rows, _ = crafted_rows(B, M)
+            assert rows_digest(rows) == str(golden[key + '_inputs_sha256']), f'{key}: the crafted rows changed'
+            g1, g2, sample_m = launch_loss(lib, rows, M, d)
+            assert np.array_equal(bits(g1), golden[key + '_dlogits_1'].view(np.int32)), key
+            assert np.array_equal(bits(g2), golden[key + '_dlogits_2'].view(np.int32)), key
+            apart = ulps_apart(sample_m, torch.as_tensor(golden[key + '_sample_m']))
+            print(f'{key}: sample_m differs from the recording in {int((apart > 0).sum())} of {apart.numel()} values, '
+                  f'by at most {int(apart.max())} ulp')
+            worst = max(worst, int(apart.max()))
+    assert worst <= 1, worst
 
 
 def test_loss_kernel_does_not_care_which_twin_is_dropped(lib):

@@ -117,12 +117,13 @@ def test_entries_answer_before_any_gpu_work(lib, entry):
             expect(call(lib, entry, target_entropy=bad), INVALID, b'target_entropy is not finite')
             expect(call(lib, entry, target_entropy=bad, d_log_entropy_coeff=FAKE, d_entropy_coeff_sums=FAKE), INVALID,
                    b'target_entropy is not finite')
-    expect(call(lib, entry, workspace_bytes=16), WORKSPACE, name + b': workspace too small')
+    expect(call(lib, entry, workspace_bytes=16), WORKSPACE,
+           name + b': workspace of 16 bytes, %d needed' % query(lib, DEFAULTS))
     for H in (64, 256, lib.tonic_mlp_hidden(40, 24, 2), torso_code(lib, 'relu32x3'), torso_code(lib, 'one256')):
         for B, M in ((1, 1), (17, 25), (37, 32)):
             need = query(lib, dict(DEFAULTS, B=B, H=H, M=M))
             expect(call(lib, entry, B=B, H=H, M=M, drop_per_net=0, workspace_bytes=need - 1), WORKSPACE,
-                   b'workspace too small')
+                   name + b': workspace of %d bytes, %d needed' % (need - 1, need))
 
 
 @pytest.mark.parametrize('torso', TORSOS)
@@ -157,18 +158,23 @@ def test_query_is_a_function_of_its_arguments(lib):
 
 
 def test_loss_kernel_entry_refuses_before_a_launch(lib):
-    entry = lib.tonic_debug_truncated_quantile_loss
+    """The developer entry in the twin form: N = 2 and the twin row {loss, q1, q2}."""
+    entry = lib.tonic_debug_ensemble_quantile_loss
 
-    def run(ld=32, M=25, drop=2, B=5, Bp=16, **null):
+    def run(ld=32, M=25, N=2, drop=2, B=5, Bp=16, twin_row=1, **null):
         p = lambda name: None if name in null else FAKE                    # noqa: E731
-        status = entry(p('t1'), p('t2'), p('th1'), p('th2'), ld, p('r'), p('d'), p('logp'), M, drop, 0.2, None,
-                       p('g1'), p('g2'), p('sample_m'), B, Bp, None)
+        status = entry(p('targets'), p('thetas'), ld, p('r'), p('d'), p('logp'), M, N, drop, 0.2, None, p('dlogits'),
+                       p('sample_m'), B, Bp, twin_row, None)
         return status, lib.tonic_last_error()
-    for name in ('t1', 't2', 'th1', 'th2', 'r', 'd', 'logp', 'g1', 'g2', 'sample_m'):
+    for name in ('targets', 'thetas', 'r', 'd', 'logp', 'dlogits', 'sample_m'):
         expect(run(**{name: True}), INVALID, b'a NULL pointer')
-    for bad in (dict(M=0), dict(M=33), dict(drop=25), dict(drop=-1), dict(ld=24), dict(ld=48), dict(B=0),
-                dict(B=17, Bp=16)):
-        expect(run(**bad), INVALID, b'1 <= M <= 32, 0 <= drop < M, M <= ld <= 32, 0 < B <= Bp')
+    for M in (0, 33):
+        expect(run(M=M), INVALID, b'%d quantiles (1 <= M <= 32)' % M)
+    for bad in (dict(drop=25), dict(drop=-1), dict(ld=24), dict(ld=48), dict(B=0), dict(B=17, Bp=16)):
+        expect(run(**bad), INVALID, b'0 <= drop < M, M <= ld <= 32, 0 < B <= Bp')
+    for N in (3, 8):
+        expect(run(N=N), INVALID, b'the twin row {loss, q1, q2} is that of 2 critics, not of %d' % N)
+    expect(run(N=3, twin_row=0, sample_m=True), INVALID, b'a NULL pointer')    # (N = 3 itself is served)
 
 
 # ---------------------------------------------------------------- 3. the head, the updaters and the agent

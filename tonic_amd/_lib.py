@@ -303,22 +303,21 @@ SIGNATURES = {
     'tonic_debug_occupy': (ctypes.c_int, [c_i32, c_f64, c_vp]),
     'tonic_gemm_f32': (ctypes.c_int, [ctypes.c_char_p] + [c_vp] * 6 + [c_i32] * 8 + [c_f64, c_vp]),
     'tonic_gemm_group_f32': (ctypes.c_int, [ctypes.c_char_p, c_vp, c_i32, c_i32, c_vp]),
-    # TQC: SAC on truncated quantile critics (additive under ABI 22), and the loss kernel's test entry
+    # TQC: SAC on truncated quantile critics (additive under ABI 22): the twin entries are the ensemble's at N = 2
     'tonic_quantile_workspace_bytes': (c_i64, [c_i32] * 5),
     'tonic_truncated_quantile_q_grad': (ctypes.c_int, [c_vp] * 5 + [c_f64] + [c_vp] * 7 + [c_i32] * 6 +
                                         [c_f64, c_vp] + [c_vp, c_i64, c_vp]),
     'tonic_truncated_quantile_actor_grad': (ctypes.c_int, [c_vp] * 4 + [c_f64] + [c_vp] * 3 + [c_i32] * 5 +
                                             [c_f64, c_vp, c_vp, c_f64] + [c_vp, c_i64, c_vp]),
-    'tonic_debug_truncated_quantile_loss': (ctypes.c_int, [c_vp] * 4 + [c_i32] + [c_vp] * 3 + [c_i32] * 2 +
-                                            [c_f64, c_vp] + [c_vp] * 3 + [c_i32] * 2 + [c_vp]),
-    # TQC on an ensemble of 2 .. 8 critics: the entries above with N behind M (additive under ABI 22)
+    # TQC on an ensemble of 2 .. 8 critics: the entries above with N behind M (additive under ABI 22), and the loss
+    # kernel's test entry
     'tonic_ensemble_quantile_workspace_bytes': (c_i64, [c_i32] * 6),
     'tonic_ensemble_quantile_q_grad': (ctypes.c_int, [c_vp] * 5 + [c_f64] + [c_vp] * 7 + [c_i32] * 7 +
                                        [c_f64, c_vp] + [c_vp, c_i64, c_vp]),
     'tonic_ensemble_quantile_actor_grad': (ctypes.c_int, [c_vp] * 4 + [c_f64] + [c_vp] * 3 + [c_i32] * 6 +
                                            [c_f64, c_vp, c_vp, c_f64] + [c_vp, c_i64, c_vp]),
     'tonic_debug_ensemble_quantile_loss': (ctypes.c_int, [c_vp] * 2 + [c_i32] + [c_vp] * 3 + [c_i32] * 3 +
-                                           [c_f64, c_vp] + [c_vp] * 2 + [c_i32] * 2 + [c_vp]),
+                                           [c_f64, c_vp] + [c_vp] * 2 + [c_i32] * 3 + [c_vp]),
 }
 
 

@@ -456,7 +456,8 @@ __global__ __launch_bounds__(256) void twin_distributional_critic_loss_kernel(
 }
 
 // the 8 statistics {sum loss_1 + loss_2, sum q1, sum q2, 0, 0, B, 0, 0} (the stats_kind 3 row) from the per-sample
-// values sample_m [3][Bp] (fixed order, float64)
+// values sample_m [3][Bp] (fixed order, float64); TQC's {sum loss, sum q, 0, ...} row is the same sums over a third
+// row of zeros
 __global__ void twin_loss_stats_kernel(const float* sample_m, float* stats, int B, int Bp) {
   double a = 0, b = 0, c = 0;
   for (int m = threadIdx.x; m < B; m += blockDim.x) { a += sample_m[m]; b += sample_m[Bp + m]; c += sample_m[2 * Bp + m]; }
@@ -491,111 +492,18 @@ __global__ void loss_stats_kernel(const float* loss_m, float* stats, int B) {
   }
 }
 
-// ---- TQC (Kuznetsov et al. 2020, truncated quantile critics): SAC on two critics of M <= 32 quantile outputs each,
-// one wave per sample.  The online critics share the wave: critic z = lane / 32, quantile i = lane % 32 (live: i < M),
-// so a [B, ld] array's columns (ld = pad16(M) <= 32) are one half of the wave.  False: no row for this wave.
-constexpr int kMaxQuantiles = 32;
-struct QuantileRow { int lane, m, z, i; bool live; };
-__device__ __forceinline__ bool quantile_row(int M, int B, QuantileRow& r) {
-  r.lane = threadIdx.x & 63;
-  r.m = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  r.z = r.lane >> 5;
-  r.i = r.lane & 31;
-  r.live = r.i < M;
-  return r.m < B;
-}
+// ---- TQC (Kuznetsov et al. 2020, truncated quantile critics): SAC on 2 <= N <= 8 critics (the paper's default is 5;
+// the twin model is N = 2) of M <= 32 quantile outputs each, one wave per sample.  The pool of P = N M <= 256 values
+// need not fit one value per lane: a lane holds R = 1, 2 or 4 values, element e = 64 r + lane in register r.  The N
+// critics' [B, ld] arrays (ld = pad16(M)) lie `stride` floats apart (critic z at base + z stride).
+constexpr int kMaxQuantiles = 32, kMaxCritics = 8, kMaxPooled = 64 * 4;
 
-// One value per lane, ascending over the wave's 64 lanes: the bitonic network, 21 compare-exchange steps on
-// __shfl_xor — a fixed sequence whatever the values are (a NaN may displace a value; it cannot stop the network).
-__device__ __forceinline__ float wave_sort(float v, int lane) {
-#pragma unroll
-  for (int k = 2; k <= 64; k <<= 1) {
-#pragma unroll
-    for (int j = k >> 1; j >= 1; j >>= 1) {
-      const float other = __shfl_xor(v, j, 64);
-      const bool ascending = (lane & k) == 0, lower = (lane & j) == 0;
-      v = ascending == lower ? fminf(v, other) : fmaxf(v, other);
-    }
-  }
-  return v;
-}
-
-// TruncatedQuantileQLearning: the two TARGET critics' 2 M values at (s', a') pooled one per lane (+inf behind them),
-// sorted, the K = 2 (M - drop) smallest kept: y_j = r + disc (Z_j - alpha logp'), j < K (lane j holds y_j).  Each
-// online quantile theta_zi (tau_i = (2 i + 1) / (2 M)) walks the kept targets in ascending j, u = y_j - theta:
-//   rho = |tau - 1{u < 0}| huber_1(u) ;  d rho / d theta = -|tau - 1{u < 0}| clamp(u, -1, 1)
-// loss_m = sum_z (1 / (M K)) sum_i sum_j rho (the twin convention loss_1 + loss_2); dlogits: its gradient (0 on a
-// padded column); sample_m [3][Bp] = {loss_m, q1, q2}, q_z = mean_i theta_zi.  y_j is read from a wave-uniform lane.
-// alpha = expf(*log_alpha) when that pointer is given, read once at entry like M and drop.
-// The targets, the errors and the two sums over j are float64: a quantile's gradient is a sum of terms of both signs
-// (with M = 1, +1/2 clamp(u_0) + 1/2 clamp(u_1)), and float32 targets of magnitude ~10 leave it an error of 1e-6 of
-// a term however far the terms cancel.  At most 64 steps per row: the cost does not show beside the networks' passes.
-__global__ __launch_bounds__(256) void truncated_quantile_critic_loss_kernel(
-    const float* target_1, const float* target_2, const float* theta_1, const float* theta_2, int ld,
-    const float* rewards, const float* discounts, const float* logp_next, int M, int drop, float alpha,
-    const float* log_alpha, float* dlogits_1, float* dlogits_2, float* sample_m, int B, int Bp) {
-  if (log_alpha != nullptr) alpha = expf(*log_alpha);
-  QuantileRow r;
-  if (!quantile_row(M, B, r)) return;
-  const int K = 2 * (M - drop);
-  const int64_t row = (int64_t)r.m * ld;
-  float pooled = INFINITY;
-  if (r.lane < M) pooled = target_1[row + r.lane];
-  else if (r.lane < 2 * M) pooled = target_2[row + (r.lane - M)];
-  const double theta = r.live ? (double)(r.z ? theta_2 : theta_1)[row + r.i] : 0.0;
-  const double y = (double)rewards[r.m] +
-                   (double)discounts[r.m] * ((double)wave_sort(pooled, r.lane) - (double)alpha * (double)logp_next[r.m]);
-  const int y_hi = __double2hiint(y), y_lo = __double2loint(y);
-  const double tau = (double)(2 * r.i + 1) / (double)(2 * M);
-  double loss = 0.0, grad = 0.0;
-  for (int j = 0; j < K; ++j) {
-    const double u = __hiloint2double(__builtin_amdgcn_readlane(y_hi, j), __builtin_amdgcn_readlane(y_lo, j)) - theta;
-    const double weight = u < 0.0 ? 1.0 - tau : tau;
-    const double a = fabs(u);
-    loss += weight * (a <= 1.0 ? 0.5 * (u * u) : a - 0.5);
-    grad += weight * fmin(fmax(u, -1.0), 1.0);
-  }
-  const double scale = 1.0 / (double)(M * K);
-  const double row_loss = wave_sum(r.live ? loss : 0.0) * scale;
-  const double q1 = wave_sum(r.live && r.z == 0 ? theta : 0.0) / (double)M;
-  const double q2 = wave_sum(r.live && r.z == 1 ? theta : 0.0) / (double)M;
-  if (r.i < ld) (r.z ? dlogits_2 : dlogits_1)[row + r.i] = r.live ? (float)-(grad * scale) : 0.f;
-  if (r.lane == 0) {
-    sample_m[r.m] = (float)row_loss; sample_m[Bp + r.m] = (float)q1; sample_m[2 * Bp + r.m] = (float)q2;
-  }
-}
-
-// TwinCriticQuantileSoftPolicyGradient: Q = (1 / (2 M)) sum_z sum_i theta_zi(s, a) on the (frozen) online critics,
-// loss_m = alpha logp - Q: dlogits = -1 / (2 M) on the live columns of both critics, 0 on the padding.  With a tuner
-// (temper.sums) workgroup 0, whole, also forms the coefficient's block as actor_loss_tempered_kernel does.
-__global__ __launch_bounds__(256) void quantile_actor_loss_kernel(
-    const float* theta_1, const float* theta_2, int ld, const float* logp, int M, float alpha, TemperArg temper,
-    float* dlogits_1, float* dlogits_2, float* loss_m, int B) {
-  float log_alpha = 0.f;
-  if (temper.log_alpha != nullptr) { log_alpha = *temper.log_alpha; alpha = expf(log_alpha); }
-  QuantileRow r;
-  if (quantile_row(M, B, r)) {
-    const int64_t row = (int64_t)r.m * ld;
-    const float theta = r.live ? (r.z ? theta_2 : theta_1)[row + r.i] : 0.f;
-    const float q = wave_sum(theta) / (float)(2 * M);
-    if (r.i < ld) (r.z ? dlogits_2 : dlogits_1)[row + r.i] = r.live ? -1.f / (float)(2 * M) : 0.f;
-    if (r.lane == 0) loss_m[r.m] = alpha * logp[r.m] - q;
-  }
-  if (temper.sums != nullptr && blockIdx.x == 0)
-    entropy_coeff_sums(logp, B, log_alpha, alpha, temper.target_entropy, temper.sums);
-}
-
-// ---- TQC on an ensemble of 2 <= N <= 8 critics (the paper's default is 5): the pool of P = N M <= 256 target values
-// no longer fits one value per lane.  One wave per sample still; a lane holds R = 1, 2 or 4 values, element
-// e = 64 r + lane in register r.  The N critics' [B, ld] arrays lie `stride` floats apart (critic z at base + z stride).
-constexpr int kMaxCritics = 8, kMaxPooled = 64 * 4;
-
-// 64 R values ascending in e: the bitonic network of wave_sort continued over the registers.  A step of partner
-// distance below 64 is a __shfl_xor on each register, one of distance 64 d an exchange between registers r and r + d of
-// the same lane: 21 steps at R = 1 (wave_sort's own), 28 at 2, 36 at 4, fully unrolled — a fixed sequence whatever the
-// values are (a NaN may displace a value; it cannot stop or lengthen the network).
+// 64 R values ascending in e: the bitonic network over the wave's lanes, continued over the registers.  A step of
+// partner distance below 64 is a __shfl_xor on each register, one of distance 64 d an exchange between registers r and
+// r + d of the same lane: 21 steps at R = 1, 28 at 2, 36 at 4, fully unrolled — a fixed sequence whatever the values
+// are (a NaN may displace a value; it cannot stop or lengthen the network).
 template <int R>
-__device__ __forceinline__ void wave_sort_wide(float (&v)[R], int lane) {
+__device__ __forceinline__ void wave_sort(float (&v)[R], int lane) {
 #pragma unroll
   for (int k = 2; k <= 64 * R; k <<= 1) {
 #pragma unroll
@@ -623,19 +531,25 @@ __device__ __forceinline__ void wave_sort_wide(float (&v)[R], int lane) {
   }
 }
 
-// TruncatedQuantileQLearning on N critics: truncated_quantile_critic_loss_kernel's statement with 2 -> N.  The N TARGET
-// critics' values pooled in critic order (element e = z M + i, +inf behind them), sorted, the K = N (M - drop) smallest
-// kept: rank j sits in register j / 64 of lane j % 64, y_j = r + disc (Z_j - alpha logp').  A lane owns the online
-// quantiles e = 64 r + lane < P (critic e / M, quantile e % M) and walks the K targets in ascending j, each read from
-// a wave-uniform lane of a compile-time register; the trip counts depend on K alone.
-//   loss_m = sum_z (1 / (M K)) sum_i sum_j rho ; dlogits: its gradient, 0 on a padded column ;
-//   sample_m [2][Bp] = {loss_m, (1 / N) sum_z mean_i theta_zi}.
-// float64 targets, errors and sums, for the reason given above the twin kernel.
+// TruncatedQuantileQLearning on N critics.  The N TARGET critics' values at (s', a') pooled in critic order (element
+// e = z M + i, +inf behind them), sorted, the K = N (M - drop) smallest kept: rank j sits in register j / 64 of lane
+// j % 64, y_j = r + disc (Z_j - alpha logp').  A lane owns the online quantiles e = 64 r + lane < P (critic e / M,
+// quantile i = e % M, tau_i = (2 i + 1) / (2 M)) and walks the K targets in ascending j, u = y_j - theta, each y_j read
+// from a wave-uniform lane of a compile-time register; the trip counts depend on K alone:
+//   rho = |tau - 1{u < 0}| huber_1(u) ;  d rho / d theta = -|tau - 1{u < 0}| clamp(u, -1, 1)
+//   loss_m = sum_z (1 / (M K)) sum_i sum_j rho (at N = 2 the twin convention loss_1 + loss_2) ;
+//   dlogits: its gradient, 0 on a padded column ;
+//   sample_m [3][Bp] = {loss_m, (1 / N) sum_z mean_i theta_zi, 0}, or with twin_row (wave-uniform; N = 2, so R = 1)
+//   the twin row {loss_m, q1, q2}, q_z = mean_i theta_zi, each from a wave_sum of its own over critic z's quantiles.
+// alpha = expf(*log_alpha) when that pointer is given, read once at entry like M and drop.
+// The targets, the errors and the two sums over j are float64: a quantile's gradient is a sum of terms of both signs
+// (with M = 1, +1/2 clamp(u_0) + 1/2 clamp(u_1)), and float32 targets of magnitude ~10 leave it an error of 1e-6 of
+// a term however far the terms cancel.  At most 256 steps per row: the cost does not show beside the networks' passes.
 template <int R>
-__global__ __launch_bounds__(256) void ensemble_quantile_critic_loss_kernel(
+__global__ __launch_bounds__(256) void quantile_critic_loss_kernel(
     const float* targets, const float* thetas, int64_t stride, int ld, const float* rewards, const float* discounts,
     const float* logp_next, int M, int N, int drop, float alpha, const float* log_alpha, float* dlogits,
-    float* sample_m, int B, int Bp) {
+    float* sample_m, int twin_row, int B, int Bp) {
   if (log_alpha != nullptr) alpha = expf(*log_alpha);
   const int lane = threadIdx.x & 63, m = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (m >= B) return;
@@ -655,7 +569,7 @@ __global__ __launch_bounds__(256) void ensemble_quantile_critic_loss_kernel(
     tau[r] = (double)(2 * i + 1) / (double)(2 * M);
     loss[r] = 0.0; grad[r] = 0.0;
   }
-  wave_sort_wide<R>(pooled, lane);
+  wave_sort<R>(pooled, lane);
   const double reward = (double)rewards[m], discount = (double)discounts[m];
   const double bonus = (double)alpha * (double)logp_next[m];
 #pragma unroll
@@ -689,37 +603,35 @@ __global__ __launch_bounds__(256) void ensemble_quantile_critic_loss_kernel(
     const int z = t / pad;
     dlogits[z * stride + row + M + (t - z * pad)] = 0.f;
   }
+  // each form's sums in one block of its own, so that their cross-lane steps overlap
+  if (twin_row) {                                                // (theta[0] is 0.0 on a lane past the pool)
+    const double q1 = wave_sum(lane < M ? theta[0] : 0.0) / (double)M;
+    const double q2 = wave_sum(lane >= M ? theta[0] : 0.0) / (double)M;
+    const double row_loss = wave_sum(lane_loss) * scale;
+    if (lane == 0) { sample_m[m] = (float)row_loss; sample_m[Bp + m] = (float)q1; sample_m[2 * Bp + m] = (float)q2; }
+    return;
+  }
   const double row_loss = wave_sum(lane_loss) * scale, q = wave_sum(lane_theta) / (double)P;
-  if (lane == 0) { sample_m[m] = (float)row_loss; sample_m[Bp + m] = (float)q; }
+  if (lane == 0) { sample_m[m] = (float)row_loss; sample_m[Bp + m] = (float)q; sample_m[2 * Bp + m] = 0.f; }
 }
 
 // the launch for a pool of P = N M values: as many registers per lane as the pool needs
-static void launch_ensemble_quantile_critic_loss(hipStream_t st, const float* targets, const float* thetas, int64_t stride,
-                                          int ld, const float* rewards, const float* discounts, const float* logp_next,
-                                          int M, int N, int drop, float alpha, const float* log_alpha, float* dlogits,
-                                          float* sample_m, int B, int Bp) {
+static void launch_quantile_critic_loss(hipStream_t st, const float* targets, const float* thetas, int64_t stride, int ld,
+                                        const float* rewards, const float* discounts, const float* logp_next, int M,
+                                        int N, int drop, float alpha, const float* log_alpha, float* dlogits,
+                                        float* sample_m, int twin_row, int B, int Bp) {
   const int P = N * M;
-  auto kernel = P <= 64 ? ensemble_quantile_critic_loss_kernel<1>
-                        : P <= 128 ? ensemble_quantile_critic_loss_kernel<2> : ensemble_quantile_critic_loss_kernel<4>;
+  auto kernel = P <= 64 ? quantile_critic_loss_kernel<1>
+                        : P <= 128 ? quantile_critic_loss_kernel<2> : quantile_critic_loss_kernel<4>;
   hipLaunchKernelGGL(kernel, dim3((B + 3) / 4), dim3(256), 0, st, targets, thetas, stride, ld, rewards, discounts,
-                     logp_next, M, N, drop, alpha, log_alpha, dlogits, sample_m, B, Bp);
+                     logp_next, M, N, drop, alpha, log_alpha, dlogits, sample_m, twin_row, B, Bp);
 }
 
-// the 8 statistics {sum loss_m, sum q, 0, 0, 0, B, 0, 0} from sample_m [2][Bp] (fixed order, float64)
-__global__ void ensemble_loss_stats_kernel(const float* sample_m, float* stats, int B, int Bp) {
-  double a = 0, b = 0, unused = 0;
-  for (int m = threadIdx.x; m < B; m += blockDim.x) { a += sample_m[m]; b += sample_m[Bp + m]; }
-  block_sum3(a, b, unused);
-  if (threadIdx.x == 0) {
-    stats[0] = (float)a; stats[1] = (float)b;
-    for (int i = 2; i < 8; ++i) stats[i] = i == 5 ? (float)B : 0.f;
-  }
-}
-
-// TwinCriticQuantileSoftPolicyGradient on N critics: Q = (1 / (N M)) sum_z sum_i theta_zi(s, a), loss_m = alpha logp - Q:
-// dlogits = -1 / (N M) on the live columns, 0 on the padding; the wave walks the N rows' N ld columns.  With a tuner
-// workgroup 0, whole, also forms the coefficient's block, as quantile_actor_loss_kernel does.
-__global__ __launch_bounds__(256) void ensemble_quantile_actor_loss_kernel(
+// TwinCriticQuantileSoftPolicyGradient on N critics: Q = (1 / (N M)) sum_z sum_i theta_zi(s, a) on the (frozen) online
+// critics, loss_m = alpha logp - Q: dlogits = -1 / (N M) on the live columns, 0 on the padding; the wave walks the N
+// rows' N ld columns.  With a tuner (temper.sums) workgroup 0, whole, also forms the coefficient's block, as
+// actor_loss_tempered_kernel does.
+__global__ __launch_bounds__(256) void quantile_actor_loss_kernel(
     const float* thetas, int64_t stride, int ld, const float* logp, int M, int N, float alpha, TemperArg temper,
     float* dlogits, float* loss_m, int B) {
   float log_alpha = 0.f;
@@ -2895,183 +2807,22 @@ extern "C" int tonic_weighted_twin_distributional_q_grad(
 }
 
 // ------------------------------------------------------------------ TQC (truncated quantile critics)
-// SAC's frame on two quantile critics: each an actor-shaped network with ONE linear head of M quantiles (D4PG's
-// layout, tonic_mlp_actor_param_count(O + A, H, M, 1)); the flat blocks are [critic_1 | critic_2].
+// SAC's frame on 2 <= N <= 8 quantile critics: each an actor-shaped network with ONE linear head of M quantiles (D4PG's
+// layout, tonic_mlp_actor_param_count(O + A, H, M, 1)); the flat blocks are [critic_1 | ... | critic_N].  Every critic's
+// passes are launches of their own and only the loss kernels see the ensemble whole.  The twin entries are N = 2.
 
 namespace {
 
-// Both entries' arrays (one query): SAC's policy pass with its sample, the critics' inputs, per critic the target and
-// online regions and outputs (DistributionalCritic), the rows' values, one chain (dz2, dz1) the backward passes use one
-// after the other, and the actor step's action columns, head gradients and chain.
+// Both steps' arrays (one query): SAC's policy pass with its sample, the critics' inputs, the critics' hidden regions,
+// the rows' values, one chain (dz2, dz1) the backward passes use one after the other, and the actor step's action
+// columns, head gradients and chain.  The N critics' target outputs, online outputs and their gradients are three
+// arrays of N consecutive [Bp, ldl] blocks (the loss kernels address critic z at base + z `rows`); an online critic
+// keeps its hidden region for its backward pass, the target critics, consumed one after the other, share one.
 struct QuantileBuffers {
-  float *a_h1, *a_h2, *head0, *head1, *act, *sigma, *logp, *X, *X2, *sample_m, *loss_m, *dz2, *dz1, *dxa, *dloc, *dspre,
-      *da_h2, *da_h1;
-  DistributionalCritic k[2];
-  QuantileBuffers(Workspace& ws, int B, int O, int A, int32_t H, int M) : k{} {
-    const int64_t Bp = pad16(B), ldx = pitch16(O + A), ldh = pad16(A), ldl = pad16(M);
-    const int64_t hid = Bp * hidden_pitch(H), region = hid * hidden_layers(H);
-    a_h1 = ws.take(region); a_h2 = behind(a_h1, hid);
-    head0 = ws.take(Bp * ldh); head1 = ws.take(Bp * ldh);
-    act = ws.take(Bp * A); sigma = ws.take(Bp * A); logp = ws.take(Bp);
-    X = ws.take(Bp * ldx); X2 = ws.take(Bp * ldx);
-    for (int z = 0; z < 2; ++z) k[z].take(ws, hid, region, Bp * ldl);
-    sample_m = ws.take(3 * Bp); loss_m = ws.take(Bp);
-    dz2 = ws.take(region); dz1 = behind(dz2, hid);
-    dxa = ws.take(2 * Bp * ldh);
-    dloc = ws.take(Bp * ldh); dspre = ws.take(Bp * ldh);
-    da_h2 = ws.take(region); da_h1 = behind(da_h2, hid);
-  }
-};
-
-// what both entries ask of M and the workspace, after their own pointer checks
-int quantile_check(const char* what, int32_t B, int32_t O, int32_t A, int32_t H, int32_t M, int64_t workspace_bytes) {
-  TONIC_REQUIRE(B > 0 && O > 0 && A > 0, TONIC_ERR_INVALID_ARGUMENT, "%s: B %d, O %d, A %d (each >= 1)", what, B, O, A);
-  TONIC_REQUIRE(hidden_known(H), TONIC_ERR_INVALID_ARGUMENT, "%s: H %d is not a torso this library knows", what, H);
-  TONIC_REQUIRE(M >= 1 && M <= kMaxQuantiles, TONIC_ERR_INVALID_ARGUMENT, "%s: %d quantiles (1 <= M <= %d)", what, M,
-                kMaxQuantiles);
-  TONIC_REQUIRE(workspace_bytes >= measure<QuantileBuffers>(B, O, A, H, M), TONIC_ERR_WORKSPACE,
-                "%s: workspace too small", what);
-  return TONIC_OK;
-}
-
-}  // namespace
-
-extern "C" int64_t tonic_quantile_workspace_bytes(int32_t B, int32_t O, int32_t A, int32_t H, int32_t M) {
-  return measure<QuantileBuffers>(B, O, A, H, M);
-}
-
-extern "C" int tonic_truncated_quantile_q_grad(
-    const float* d_actor, const float* d_target_critics, const float* d_critics, const float* d_norm_mean,
-    const float* d_norm_std, double norm_clip, const float* d_observations, const float* d_actions,
-    const float* d_next_observations, const float* d_rewards, const float* d_discounts, const float* d_eps,
-    float* d_grad_sums, int32_t B, int32_t O, int32_t H, int32_t A, int32_t M, int32_t drop_per_net,
-    double entropy_coeff, const float* d_log_entropy_coeff, void* d_workspace, int64_t workspace_bytes, void* stream) {
-  const char* what = "tonic_truncated_quantile_q_grad";
-  TONIC_REQUIRE(d_actor && d_target_critics && d_critics && d_norm_mean && d_norm_std && d_observations && d_actions &&
-                    d_next_observations && d_rewards && d_discounts && d_eps && d_grad_sums && d_workspace,
-                TONIC_ERR_INVALID_ARGUMENT, "%s: a NULL pointer (only d_log_entropy_coeff may be NULL)", what);
-  TONIC_REQUIRE(M < 1 || M > kMaxQuantiles || (drop_per_net >= 0 && drop_per_net < M), TONIC_ERR_INVALID_ARGUMENT,
-                "%s: %d quantiles dropped per critic (0 <= drop_per_net < M = %d)", what, drop_per_net, M);
-  TRY(quantile_check(what, B, O, A, H, M, workspace_bytes));
-  hipStream_t st = as_stream(stream);
-  const int Bp = pad16(B), ldx = pitch16(O + A), ldh = pad16(A), ldl = pad16(M);
-  Workspace ws{static_cast<char*>(d_workspace), 0};
-  const QuantileBuffers w(ws, B, O, A, H, M);
-  const ActorShape as = actor_shape(O, H, A, 2), cs = actor_shape(O + A, torso_code(H), M, 1);
-  const int64_t Pc = actor_count(cs);
-  // 1  a' = rsample of the ONLINE actor at s' with logp' (as tonic_twin_q_grad, kind 1); the tail encodes (s', a') -> X
-  //    and the stored (s, a) -> X2
-  PolicyTail tail{};
-  tail.post = POST_SQUASHED_SAMPLE; tail.eps = d_eps; tail.actions = w.act; tail.logp = w.logp;
-  tail.enc_obs = d_next_observations; tail.enc_obs2 = d_observations; tail.enc_act2 = d_actions;
-  tail.enc_mean = d_norm_mean; tail.enc_std = d_norm_std; tail.enc_clip = clip_bound(norm_clip);
-  tail.enc_out = w.X; tail.enc_out2 = w.X2; tail.enc_ld = ldx;
-  TRY(policy_pass(d_actor, as, d_next_observations, B, w.a_h1, w.a_h2, w.head0, w.head1, ldh, false, st, tail));
-  // 2  the target critics on (s', a'), then  3  the online critics on (s, a)
-  for (int z = 0; z < 2; ++z)
-    TRY(actor_forward(d_target_critics + z * Pc, cs, w.X, B, w.k[z].t_h1, w.k[z].t_h2, w.k[z].t_logits,
-                      w.k[z].t_logits, ldl, false, st, nullptr, nullptr, ldx));
-  for (int z = 0; z < 2; ++z)
-    TRY(actor_forward(d_critics + z * Pc, cs, w.X2, B, w.k[z].c_h1, w.k[z].c_h2, w.k[z].logits, w.k[z].logits, ldl,
-                      false, st, nullptr, nullptr, ldx));
-  // 4 + 5  the truncated quantile loss and the statistics behind the gradient blocks
-  hipLaunchKernelGGL(truncated_quantile_critic_loss_kernel, dim3((B + 3) / 4), dim3(256), 0, st, w.k[0].t_logits,
-                     w.k[1].t_logits, w.k[0].logits, w.k[1].logits, ldl, d_rewards, d_discounts, w.logp, M, drop_per_net,
-                     (float)entropy_coeff, d_log_entropy_coeff, w.k[0].dlogits, w.k[1].dlogits, w.sample_m, B, Bp);
-  hipLaunchKernelGGL(twin_loss_stats_kernel, dim3(1), dim3(1024), 0, st, w.sample_m, d_grad_sums + 2 * Pc, B, Bp);
-  // 6  each online critic's backward into its own block of the sums
-  for (int z = 0; z < 2; ++z)
-    TRY(actor_shaped_backward(d_critics + z * Pc, cs, w.X2, ldx, B, w.k[z].c_h1, w.k[z].c_h2, w.k[z].dlogits, nullptr,
-                              ldl, w.dz2, w.dz1, d_grad_sums + z * Pc, nullptr, 0, 0, st));
-  TONIC_CHECK_LAUNCH(what);
-  return TONIC_OK;
-}
-
-extern "C" int tonic_truncated_quantile_actor_grad(
-    const float* d_actor, const float* d_critics, const float* d_norm_mean, const float* d_norm_std, double norm_clip,
-    const float* d_observations, const float* d_eps, float* d_grad_sums, int32_t B, int32_t O, int32_t H, int32_t A,
-    int32_t M, double entropy_coeff, const float* d_log_entropy_coeff, float* d_entropy_coeff_sums,
-    double target_entropy, void* d_workspace, int64_t workspace_bytes, void* stream) {
-  const char* what = "tonic_truncated_quantile_actor_grad";
-  TONIC_REQUIRE(d_actor && d_critics && d_norm_mean && d_norm_std && d_observations && d_eps && d_grad_sums &&
-                    d_workspace,
-                TONIC_ERR_INVALID_ARGUMENT, "%s: a NULL pointer (only the tuner's pair may be NULL)", what);
-  TONIC_REQUIRE((d_log_entropy_coeff == nullptr) == (d_entropy_coeff_sums == nullptr), TONIC_ERR_INVALID_ARGUMENT,
-                "%s: %s is NULL and the other is not (both or neither)", what,
-                d_log_entropy_coeff == nullptr ? "d_log_entropy_coeff" : "d_entropy_coeff_sums");
-  TONIC_REQUIRE(std::isfinite(target_entropy), TONIC_ERR_INVALID_ARGUMENT, "%s: target_entropy is not finite", what);
-  TRY(quantile_check(what, B, O, A, H, M, workspace_bytes));
-  hipStream_t st = as_stream(stream);
-  const int Bp = pad16(B), ldx = pitch16(O + A), ldh = pad16(A), ldl = pad16(M), threads = 256;
-  Workspace ws{static_cast<char*>(d_workspace), 0};
-  const QuantileBuffers w(ws, B, O, A, H, M);
-  const ActorShape as = actor_shape(O, H, A, 2), cs = actor_shape(O + A, torso_code(H), M, 1);
-  const int64_t Pa = actor_count(as), Pc = actor_count(cs);
-  const TemperArg temper{d_log_entropy_coeff, d_entropy_coeff_sums, (float)target_entropy};
-  PolicyTail tail{};                              // a = rsample of the actor at s with logp; the tail encodes (s, a) -> X
-  tail.post = POST_SQUASHED_SAMPLE; tail.eps = d_eps; tail.actions = w.act; tail.sigma = w.sigma; tail.logp = w.logp;
-  tail.enc_obs = d_observations; tail.enc_mean = d_norm_mean; tail.enc_std = d_norm_std;
-  tail.enc_clip = clip_bound(norm_clip); tail.enc_out = w.X; tail.enc_ld = ldx;
-  TRY(policy_pass(d_actor, as, d_observations, B, w.a_h1, w.a_h2, w.head0, w.head1, ldh, false, st, tail));
-  for (int z = 0; z < 2; ++z)
-    TRY(actor_forward(d_critics + z * Pc, cs, w.X, B, w.k[z].c_h1, w.k[z].c_h2, w.k[z].logits, w.k[z].logits, ldl,
-                      false, st, nullptr, nullptr, ldx));
-  hipLaunchKernelGGL(quantile_actor_loss_kernel, dim3((B + 3) / 4), dim3(256), 0, st, w.k[0].logits, w.k[1].logits, ldl,
-                     w.logp, M, (float)entropy_coeff, temper, w.k[0].dlogits, w.k[1].dlogits, w.loss_m, B);
-  hipLaunchKernelGGL(loss_stats_kernel, dim3(1), dim3(1024), 0, st, w.loss_m, d_grad_sums + Pa, B);
-  // through each frozen critic to the action columns of its input, then SAC's head (which adds the two) and the actor
-  for (int z = 0; z < 2; ++z)
-    TRY(actor_shaped_backward(d_critics + z * Pc, cs, w.X, ldx, B, w.k[z].c_h1, w.k[z].c_h2, w.k[z].dlogits, nullptr,
-                              ldl, w.dz2, w.dz1, nullptr, w.dxa + (int64_t)z * Bp * ldh, O, A, st));
-  if (temper.log_alpha != nullptr)
-    hipLaunchKernelGGL(actor_head_backward_tempered_kernel, dim3((B * A + threads - 1) / threads), dim3(threads), 0, st,
-                       w.dxa, w.dxa + (int64_t)Bp * ldh, ldh, w.act, d_eps, w.sigma, w.head1, ldh, temper.log_alpha,
-                       w.dloc, w.dspre, B, A, as.scale_lo, as.scale_hi);
-  else hipLaunchKernelGGL(actor_head_backward_kernel, dim3((B * A + threads - 1) / threads), dim3(threads), 0, st, w.dxa,
-                     w.dxa + (int64_t)Bp * ldh, ldh, w.act, d_eps, w.sigma, w.head1, ldh, (float)entropy_coeff, 1, w.dloc,
-                     w.dspre, B, A, as.scale_lo, as.scale_hi);
-  TRY(actor_shaped_backward(d_actor, as, d_observations, O, B, w.a_h1, w.a_h2, w.dloc, w.dspre, ldh, w.da_h2, w.da_h1,
-                            d_grad_sums, nullptr, 0, 0, st));
-  TONIC_CHECK_LAUNCH(what);
-  return TONIC_OK;
-}
-
-// Test entry (include/tonic_hip_dev.h): truncated_quantile_critic_loss_kernel alone on given rows.
-extern "C" int tonic_debug_truncated_quantile_loss(
-    const float* d_target_1, const float* d_target_2, const float* d_theta_1, const float* d_theta_2, int32_t ld,
-    const float* d_rewards, const float* d_discounts, const float* d_logp, int32_t M, int32_t drop_per_net,
-    double entropy_coeff, const float* d_log_entropy_coeff, float* d_dlogits_1, float* d_dlogits_2, float* d_sample_m,
-    int32_t B, int32_t Bp, void* stream) {
-  const char* what = "tonic_debug_truncated_quantile_loss";
-  TONIC_REQUIRE(d_target_1 && d_target_2 && d_theta_1 && d_theta_2 && d_rewards && d_discounts && d_logp &&
-                    d_dlogits_1 && d_dlogits_2 && d_sample_m,
-                TONIC_ERR_INVALID_ARGUMENT, "%s: a NULL pointer", what);
-  TONIC_REQUIRE(M >= 1 && M <= kMaxQuantiles && drop_per_net >= 0 && drop_per_net < M && ld >= M &&
-                    ld <= kMaxQuantiles && B > 0 && Bp >= B,
-                TONIC_ERR_INVALID_ARGUMENT,
-                "%s: M %d, drop_per_net %d, ld %d, B %d, Bp %d (1 <= M <= %d, 0 <= drop < M, M <= ld <= %d, 0 < B <= Bp)",
-                what, M, drop_per_net, ld, B, Bp, kMaxQuantiles, kMaxQuantiles);
-  hipLaunchKernelGGL(truncated_quantile_critic_loss_kernel, dim3((B + 3) / 4), dim3(256), 0, as_stream(stream),
-                     d_target_1, d_target_2, d_theta_1, d_theta_2, ld, d_rewards, d_discounts, d_logp, M, drop_per_net,
-                     (float)entropy_coeff, d_log_entropy_coeff, d_dlogits_1, d_dlogits_2, d_sample_m, B, Bp);
-  TONIC_CHECK_LAUNCH(what);
-  return TONIC_OK;
-}
-
-// ------------------------------------------------------------------ TQC on an ensemble of 2 .. 8 critics
-// The same frame on N critics: the flat blocks are [critic_1 | ... | critic_N]; every critic's passes are launches of
-// their own, as above, and only the loss kernels see the ensemble whole.
-
-namespace {
-
-// QuantileBuffers for N critics.  The N critics' target outputs, online outputs and their gradients are three arrays
-// of N consecutive [Bp, ldl] blocks (the loss kernels address critic z at base + z `rows`); an online critic keeps its
-// hidden region for its backward pass, the target critics, consumed one after the other, share one.
-struct EnsembleQuantileBuffers {
   float *a_h1, *a_h2, *head0, *head1, *act, *sigma, *logp, *X, *X2, *t_h1, *t_h2, *c_h1[kMaxCritics], *c_h2[kMaxCritics],
       *t_logits, *logits, *dlogits, *sample_m, *loss_m, *dz2, *dz1, *dxa, *dloc, *dspre, *da_h2, *da_h1;
   int64_t rows, action_rows;
-  EnsembleQuantileBuffers(Workspace& ws, int B, int O, int A, int32_t H, int M, int N) : c_h1{}, c_h2{} {
+  QuantileBuffers(Workspace& ws, int B, int O, int A, int32_t H, int M, int N) : c_h1{}, c_h2{} {
     const int64_t Bp = pad16(B), ldx = pitch16(O + A), ldh = pad16(A), ldl = pad16(M);
     const int64_t hid = Bp * hidden_pitch(H), region = hid * hidden_layers(H);
     rows = Bp * ldl; action_rows = Bp * ldh;
@@ -3082,7 +2833,7 @@ struct EnsembleQuantileBuffers {
     t_h1 = ws.take(region); t_h2 = behind(t_h1, hid);
     for (int z = 0; z < N; ++z) { c_h1[z] = ws.take(region); c_h2[z] = behind(c_h1[z], hid); }
     t_logits = ws.take(N * rows); logits = ws.take(N * rows); dlogits = ws.take(N * rows);
-    sample_m = ws.take(2 * Bp); loss_m = ws.take(Bp);
+    sample_m = ws.take(3 * Bp); loss_m = ws.take(Bp);
     dz2 = ws.take(region); dz1 = behind(dz2, hid);
     dxa = ws.take(N * action_rows);
     dloc = ws.take(Bp * ldh); dspre = ws.take(Bp * ldh);
@@ -3090,8 +2841,8 @@ struct EnsembleQuantileBuffers {
   }
 };
 
-// what the ensemble asks of N and M, with the numbers
-int ensemble_counts_check(const char* what, int32_t M, int32_t N) {
+// what TQC asks of N and M, with the numbers
+int quantile_counts_check(const char* what, int32_t M, int32_t N) {
   TONIC_REQUIRE(N >= 2 && N <= kMaxCritics, TONIC_ERR_INVALID_ARGUMENT, "%s: %d critics (2 <= N <= %d)", what, N,
                 kMaxCritics);
   TONIC_REQUIRE(M >= 1 && M <= kMaxQuantiles, TONIC_ERR_INVALID_ARGUMENT, "%s: %d quantiles (1 <= M <= %d)", what, M,
@@ -3101,46 +2852,39 @@ int ensemble_counts_check(const char* what, int32_t M, int32_t N) {
   return TONIC_OK;
 }
 
-// ... and both entries of the shapes and the workspace, after their own pointer checks
-int ensemble_quantile_check(const char* what, int32_t B, int32_t O, int32_t A, int32_t H, int32_t M, int32_t N,
-                            int64_t workspace_bytes) {
+// ... and both steps of the shapes and the workspace, after their own pointer checks
+int quantile_check(const char* what, int32_t B, int32_t O, int32_t A, int32_t H, int32_t M, int32_t N,
+                   int64_t workspace_bytes) {
   TONIC_REQUIRE(B > 0 && O > 0 && A > 0, TONIC_ERR_INVALID_ARGUMENT, "%s: B %d, O %d, A %d (each >= 1)", what, B, O, A);
   TONIC_REQUIRE(hidden_known(H), TONIC_ERR_INVALID_ARGUMENT, "%s: H %d is not a torso this library knows", what, H);
-  TRY(ensemble_counts_check(what, M, N));
-  const int64_t need = measure<EnsembleQuantileBuffers>(B, O, A, H, M, N);
+  TRY(quantile_counts_check(what, M, N));
+  const int64_t need = measure<QuantileBuffers>(B, O, A, H, M, N);
   TONIC_REQUIRE(workspace_bytes >= need, TONIC_ERR_WORKSPACE, "%s: workspace of %lld bytes, %lld needed", what,
                 (long long)workspace_bytes, (long long)need);
   return TONIC_OK;
 }
 
-}  // namespace
-
-extern "C" int64_t tonic_ensemble_quantile_workspace_bytes(int32_t B, int32_t O, int32_t A, int32_t H, int32_t M,
-                                                           int32_t N) {
-  if (N < 2 || N > kMaxCritics) return 0;                  // (the entries refuse such an N before they ask for a byte)
-  return measure<EnsembleQuantileBuffers>(B, O, A, H, M, N);
-}
-
-extern "C" int tonic_ensemble_quantile_q_grad(
-    const float* d_actor, const float* d_target_critics, const float* d_critics, const float* d_norm_mean,
-    const float* d_norm_std, double norm_clip, const float* d_observations, const float* d_actions,
-    const float* d_next_observations, const float* d_rewards, const float* d_discounts, const float* d_eps,
-    float* d_grad_sums, int32_t B, int32_t O, int32_t H, int32_t A, int32_t M, int32_t N, int32_t drop_per_net,
-    double entropy_coeff, const float* d_log_entropy_coeff, void* d_workspace, int64_t workspace_bytes, void* stream) {
-  const char* what = "tonic_ensemble_quantile_q_grad";
+// The critic step.  twin_row: the statistics row is the twin model's {loss, q1, q2} (N = 2), not {loss, q}.
+int quantile_q_grad(const char* what, int32_t N, int twin_row, const float* d_actor, const float* d_target_critics,
+                    const float* d_critics, const float* d_norm_mean, const float* d_norm_std, double norm_clip,
+                    const float* d_observations, const float* d_actions, const float* d_next_observations,
+                    const float* d_rewards, const float* d_discounts, const float* d_eps, float* d_grad_sums, int32_t B,
+                    int32_t O, int32_t H, int32_t A, int32_t M, int32_t drop_per_net, double entropy_coeff,
+                    const float* d_log_entropy_coeff, void* d_workspace, int64_t workspace_bytes, void* stream) {
   TONIC_REQUIRE(d_actor && d_target_critics && d_critics && d_norm_mean && d_norm_std && d_observations && d_actions &&
                     d_next_observations && d_rewards && d_discounts && d_eps && d_grad_sums && d_workspace,
                 TONIC_ERR_INVALID_ARGUMENT, "%s: a NULL pointer (only d_log_entropy_coeff may be NULL)", what);
   TONIC_REQUIRE(M < 1 || M > kMaxQuantiles || (drop_per_net >= 0 && drop_per_net < M), TONIC_ERR_INVALID_ARGUMENT,
                 "%s: %d quantiles dropped per critic (0 <= drop_per_net < M = %d)", what, drop_per_net, M);
-  TRY(ensemble_quantile_check(what, B, O, A, H, M, N, workspace_bytes));
+  TRY(quantile_check(what, B, O, A, H, M, N, workspace_bytes));
   hipStream_t st = as_stream(stream);
   const int Bp = pad16(B), ldx = pitch16(O + A), ldh = pad16(A), ldl = pad16(M);
   Workspace ws{static_cast<char*>(d_workspace), 0};
-  const EnsembleQuantileBuffers w(ws, B, O, A, H, M, N);
+  const QuantileBuffers w(ws, B, O, A, H, M, N);
   const ActorShape as = actor_shape(O, H, A, 2), cs = actor_shape(O + A, torso_code(H), M, 1);
   const int64_t Pc = actor_count(cs);
-  // 1  a' = rsample of the ONLINE actor at s' with logp'; the tail encodes (s', a') -> X and the stored (s, a) -> X2
+  // 1  a' = rsample of the ONLINE actor at s' with logp' (as tonic_twin_q_grad, kind 1); the tail encodes (s', a') -> X
+  //    and the stored (s, a) -> X2
   PolicyTail tail{};
   tail.post = POST_SQUASHED_SAMPLE; tail.eps = d_eps; tail.actions = w.act; tail.logp = w.logp;
   tail.enc_obs = d_next_observations; tail.enc_obs2 = d_observations; tail.enc_act2 = d_actions;
@@ -3155,10 +2899,9 @@ extern "C" int tonic_ensemble_quantile_q_grad(
     TRY(actor_forward(d_critics + z * Pc, cs, w.X2, B, w.c_h1[z], w.c_h2[z], w.logits + z * w.rows,
                       w.logits + z * w.rows, ldl, false, st, nullptr, nullptr, ldx));
   // 4 + 5  the truncated quantile loss over the pool of N M and the statistics behind the gradient blocks
-  launch_ensemble_quantile_critic_loss(st, w.t_logits, w.logits, w.rows, ldl, d_rewards, d_discounts, w.logp, M, N,
-                                       drop_per_net, (float)entropy_coeff, d_log_entropy_coeff, w.dlogits, w.sample_m, B,
-                                       Bp);
-  hipLaunchKernelGGL(ensemble_loss_stats_kernel, dim3(1), dim3(1024), 0, st, w.sample_m, d_grad_sums + N * Pc, B, Bp);
+  launch_quantile_critic_loss(st, w.t_logits, w.logits, w.rows, ldl, d_rewards, d_discounts, w.logp, M, N, drop_per_net,
+                              (float)entropy_coeff, d_log_entropy_coeff, w.dlogits, w.sample_m, twin_row, B, Bp);
+  hipLaunchKernelGGL(twin_loss_stats_kernel, dim3(1), dim3(1024), 0, st, w.sample_m, d_grad_sums + N * Pc, B, Bp);
   // 6  each online critic's backward into its own block of the sums
   for (int z = 0; z < N; ++z)
     TRY(actor_shaped_backward(d_critics + z * Pc, cs, w.X2, ldx, B, w.c_h1[z], w.c_h2[z], w.dlogits + z * w.rows,
@@ -3167,12 +2910,12 @@ extern "C" int tonic_ensemble_quantile_q_grad(
   return TONIC_OK;
 }
 
-extern "C" int tonic_ensemble_quantile_actor_grad(
-    const float* d_actor, const float* d_critics, const float* d_norm_mean, const float* d_norm_std, double norm_clip,
-    const float* d_observations, const float* d_eps, float* d_grad_sums, int32_t B, int32_t O, int32_t H, int32_t A,
-    int32_t M, int32_t N, double entropy_coeff, const float* d_log_entropy_coeff, float* d_entropy_coeff_sums,
-    double target_entropy, void* d_workspace, int64_t workspace_bytes, void* stream) {
-  const char* what = "tonic_ensemble_quantile_actor_grad";
+// The actor step.
+int quantile_actor_grad(const char* what, int32_t N, const float* d_actor, const float* d_critics,
+                        const float* d_norm_mean, const float* d_norm_std, double norm_clip, const float* d_observations,
+                        const float* d_eps, float* d_grad_sums, int32_t B, int32_t O, int32_t H, int32_t A, int32_t M,
+                        double entropy_coeff, const float* d_log_entropy_coeff, float* d_entropy_coeff_sums,
+                        double target_entropy, void* d_workspace, int64_t workspace_bytes, void* stream) {
   TONIC_REQUIRE(d_actor && d_critics && d_norm_mean && d_norm_std && d_observations && d_eps && d_grad_sums &&
                     d_workspace,
                 TONIC_ERR_INVALID_ARGUMENT, "%s: a NULL pointer (only the tuner's pair may be NULL)", what);
@@ -3180,11 +2923,11 @@ extern "C" int tonic_ensemble_quantile_actor_grad(
                 "%s: %s is NULL and the other is not (both or neither)", what,
                 d_log_entropy_coeff == nullptr ? "d_log_entropy_coeff" : "d_entropy_coeff_sums");
   TONIC_REQUIRE(std::isfinite(target_entropy), TONIC_ERR_INVALID_ARGUMENT, "%s: target_entropy is not finite", what);
-  TRY(ensemble_quantile_check(what, B, O, A, H, M, N, workspace_bytes));
+  TRY(quantile_check(what, B, O, A, H, M, N, workspace_bytes));
   hipStream_t st = as_stream(stream);
   const int ldx = pitch16(O + A), ldh = pad16(A), ldl = pad16(M), threads = 256;
   Workspace ws{static_cast<char*>(d_workspace), 0};
-  const EnsembleQuantileBuffers w(ws, B, O, A, H, M, N);
+  const QuantileBuffers w(ws, B, O, A, H, M, N);
   const ActorShape as = actor_shape(O, H, A, 2), cs = actor_shape(O + A, torso_code(H), M, 1);
   const int64_t Pa = actor_count(as), Pc = actor_count(cs);
   const TemperArg temper{d_log_entropy_coeff, d_entropy_coeff_sums, (float)target_entropy};
@@ -3196,8 +2939,8 @@ extern "C" int tonic_ensemble_quantile_actor_grad(
   for (int z = 0; z < N; ++z)
     TRY(actor_forward(d_critics + z * Pc, cs, w.X, B, w.c_h1[z], w.c_h2[z], w.logits + z * w.rows,
                       w.logits + z * w.rows, ldl, false, st, nullptr, nullptr, ldx));
-  hipLaunchKernelGGL(ensemble_quantile_actor_loss_kernel, dim3((B + 3) / 4), dim3(256), 0, st, w.logits, w.rows, ldl,
-                     w.logp, M, N, (float)entropy_coeff, temper, w.dlogits, w.loss_m, B);
+  hipLaunchKernelGGL(quantile_actor_loss_kernel, dim3((B + 3) / 4), dim3(256), 0, st, w.logits, w.rows, ldl, w.logp, M,
+                     N, (float)entropy_coeff, temper, w.dlogits, w.loss_m, B);
   hipLaunchKernelGGL(loss_stats_kernel, dim3(1), dim3(1024), 0, st, w.loss_m, d_grad_sums + Pa, B);
   // through each frozen critic to the action columns of its input; critics 2 .. N added up, then SAC's head (which adds
   // the two blocks left) and the actor
@@ -3220,23 +2963,84 @@ extern "C" int tonic_ensemble_quantile_actor_grad(
   return TONIC_OK;
 }
 
-// Test entry (include/tonic_hip_dev.h): the ensemble critic loss kernel alone on given rows, critic z's [B, ld] block
-// at z B ld of each array.
+}  // namespace
+
+extern "C" int64_t tonic_ensemble_quantile_workspace_bytes(int32_t B, int32_t O, int32_t A, int32_t H, int32_t M,
+                                                           int32_t N) {
+  if (N < 2 || N > kMaxCritics) return 0;                  // (the entries refuse such an N before they ask for a byte)
+  return measure<QuantileBuffers>(B, O, A, H, M, N);
+}
+
+extern "C" int64_t tonic_quantile_workspace_bytes(int32_t B, int32_t O, int32_t A, int32_t H, int32_t M) {
+  return measure<QuantileBuffers>(B, O, A, H, M, 2);
+}
+
+extern "C" int tonic_truncated_quantile_q_grad(
+    const float* d_actor, const float* d_target_critics, const float* d_critics, const float* d_norm_mean,
+    const float* d_norm_std, double norm_clip, const float* d_observations, const float* d_actions,
+    const float* d_next_observations, const float* d_rewards, const float* d_discounts, const float* d_eps,
+    float* d_grad_sums, int32_t B, int32_t O, int32_t H, int32_t A, int32_t M, int32_t drop_per_net,
+    double entropy_coeff, const float* d_log_entropy_coeff, void* d_workspace, int64_t workspace_bytes, void* stream) {
+  return quantile_q_grad("tonic_truncated_quantile_q_grad", 2, 1, d_actor, d_target_critics, d_critics, d_norm_mean,
+                         d_norm_std, norm_clip, d_observations, d_actions, d_next_observations, d_rewards, d_discounts,
+                         d_eps, d_grad_sums, B, O, H, A, M, drop_per_net, entropy_coeff, d_log_entropy_coeff, d_workspace,
+                         workspace_bytes, stream);
+}
+
+extern "C" int tonic_ensemble_quantile_q_grad(
+    const float* d_actor, const float* d_target_critics, const float* d_critics, const float* d_norm_mean,
+    const float* d_norm_std, double norm_clip, const float* d_observations, const float* d_actions,
+    const float* d_next_observations, const float* d_rewards, const float* d_discounts, const float* d_eps,
+    float* d_grad_sums, int32_t B, int32_t O, int32_t H, int32_t A, int32_t M, int32_t N, int32_t drop_per_net,
+    double entropy_coeff, const float* d_log_entropy_coeff, void* d_workspace, int64_t workspace_bytes, void* stream) {
+  return quantile_q_grad("tonic_ensemble_quantile_q_grad", N, 0, d_actor, d_target_critics, d_critics, d_norm_mean,
+                         d_norm_std, norm_clip, d_observations, d_actions, d_next_observations, d_rewards, d_discounts,
+                         d_eps, d_grad_sums, B, O, H, A, M, drop_per_net, entropy_coeff, d_log_entropy_coeff, d_workspace,
+                         workspace_bytes, stream);
+}
+
+extern "C" int tonic_truncated_quantile_actor_grad(
+    const float* d_actor, const float* d_critics, const float* d_norm_mean, const float* d_norm_std, double norm_clip,
+    const float* d_observations, const float* d_eps, float* d_grad_sums, int32_t B, int32_t O, int32_t H, int32_t A,
+    int32_t M, double entropy_coeff, const float* d_log_entropy_coeff, float* d_entropy_coeff_sums,
+    double target_entropy, void* d_workspace, int64_t workspace_bytes, void* stream) {
+  return quantile_actor_grad("tonic_truncated_quantile_actor_grad", 2, d_actor, d_critics, d_norm_mean, d_norm_std,
+                             norm_clip, d_observations, d_eps, d_grad_sums, B, O, H, A, M, entropy_coeff,
+                             d_log_entropy_coeff, d_entropy_coeff_sums, target_entropy, d_workspace, workspace_bytes,
+                             stream);
+}
+
+extern "C" int tonic_ensemble_quantile_actor_grad(
+    const float* d_actor, const float* d_critics, const float* d_norm_mean, const float* d_norm_std, double norm_clip,
+    const float* d_observations, const float* d_eps, float* d_grad_sums, int32_t B, int32_t O, int32_t H, int32_t A,
+    int32_t M, int32_t N, double entropy_coeff, const float* d_log_entropy_coeff, float* d_entropy_coeff_sums,
+    double target_entropy, void* d_workspace, int64_t workspace_bytes, void* stream) {
+  return quantile_actor_grad("tonic_ensemble_quantile_actor_grad", N, d_actor, d_critics, d_norm_mean, d_norm_std,
+                             norm_clip, d_observations, d_eps, d_grad_sums, B, O, H, A, M, entropy_coeff,
+                             d_log_entropy_coeff, d_entropy_coeff_sums, target_entropy, d_workspace, workspace_bytes,
+                             stream);
+}
+
+// Test entry (include/tonic_hip_dev.h): the critic loss kernel alone on given rows, critic z's [B, ld] block at z B ld
+// of each array; sample_m [3][Bp].
 extern "C" int tonic_debug_ensemble_quantile_loss(
     const float* d_targets, const float* d_thetas, int32_t ld, const float* d_rewards, const float* d_discounts,
     const float* d_logp, int32_t M, int32_t N, int32_t drop_per_net, double entropy_coeff,
-    const float* d_log_entropy_coeff, float* d_dlogits, float* d_sample_m, int32_t B, int32_t Bp, void* stream) {
+    const float* d_log_entropy_coeff, float* d_dlogits, float* d_sample_m, int32_t B, int32_t Bp, int32_t twin_row,
+    void* stream) {
   const char* what = "tonic_debug_ensemble_quantile_loss";
   TONIC_REQUIRE(d_targets && d_thetas && d_rewards && d_discounts && d_logp && d_dlogits && d_sample_m,
                 TONIC_ERR_INVALID_ARGUMENT, "%s: a NULL pointer (only d_log_entropy_coeff may be NULL)", what);
-  TRY(ensemble_counts_check(what, M, N));
+  TRY(quantile_counts_check(what, M, N));
   TONIC_REQUIRE(drop_per_net >= 0 && drop_per_net < M && ld >= M && ld <= kMaxQuantiles && B > 0 && Bp >= B,
                 TONIC_ERR_INVALID_ARGUMENT,
                 "%s: M %d, drop_per_net %d, ld %d, B %d, Bp %d (0 <= drop < M, M <= ld <= %d, 0 < B <= Bp)", what, M,
                 drop_per_net, ld, B, Bp, kMaxQuantiles);
-  launch_ensemble_quantile_critic_loss(as_stream(stream), d_targets, d_thetas, (int64_t)B * ld, ld, d_rewards,
-                                       d_discounts, d_logp, M, N, drop_per_net, (float)entropy_coeff,
-                                       d_log_entropy_coeff, d_dlogits, d_sample_m, B, Bp);
+  TONIC_REQUIRE(twin_row == 0 || N == 2, TONIC_ERR_INVALID_ARGUMENT,
+                "%s: the twin row {loss, q1, q2} is that of 2 critics, not of %d", what, N);
+  launch_quantile_critic_loss(as_stream(stream), d_targets, d_thetas, (int64_t)B * ld, ld, d_rewards, d_discounts, d_logp,
+                              M, N, drop_per_net, (float)entropy_coeff, d_log_entropy_coeff, d_dlogits, d_sample_m,
+                              twin_row != 0, B, Bp);
   TONIC_CHECK_LAUNCH(what);
   return TONIC_OK;
 }

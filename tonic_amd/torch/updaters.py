@@ -1718,10 +1718,9 @@ def _quantile_entry(model, step):
 
 
 def _quantile_workspace_bytes(updater, batch):
-    shape = (batch, updater.observation_size, updater.action_size, updater.hidden, updater.quantiles)
-    if hasattr(updater.model, 'num_critics'):
-        return updater.lib.tonic_ensemble_quantile_workspace_bytes(*shape, int(updater.model.num_critics))
-    return updater.lib.tonic_quantile_workspace_bytes(*shape)
+    return updater.lib.tonic_ensemble_quantile_workspace_bytes(    # (one layout: the twin model's is that of N = 2)
+        batch, updater.observation_size, updater.action_size, updater.hidden, updater.quantiles,
+        _critic_count(updater.model))
 
 
 class TruncatedQuantileQLearning(_TwinCriticQLearning):
