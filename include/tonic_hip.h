@@ -69,7 +69,7 @@ const char* tonic_last_error(void);
  * (still 22, purely additive: the tonic_priority_* entries and the tonic_weighted_* distributional critic steps — prioritized replay;
  * tonic_quantile_workspace_bytes / tonic_truncated_quantile_q_grad / tonic_truncated_quantile_actor_grad — TQC;
  * tonic_ensemble_quantile_workspace_bytes / tonic_ensemble_quantile_q_grad / tonic_ensemble_quantile_actor_grad — TQC on
- * 2 .. 8 critics)
+ * 2 .. 8 critics; tonic_ensemble_q_workspace_bytes / tonic_ensemble_subset_q_grad — REDQ)
  * and the gfx target the kernels were built for.  TONIC_ABI_VERSION is what a binding was compiled against:
  * tonic_amd/_fastcall (csrc/fastcall.c) and tonic_amd/_lib.py compare it with the loaded library's answer. */
 #define TONIC_ABI_VERSION 22
@@ -1465,6 +1465,45 @@ int tonic_ensemble_quantile_actor_grad(const float* d_actor, const float* d_crit
                                        const float* d_log_entropy_coeff, float* d_entropy_coeff_sums,
                                        double target_entropy, void* d_workspace, int64_t workspace_bytes,
                                        void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * REDQ: SAC on an ensemble of scalar critics with a random-subset minimum in the target (Chen et al. 2021, randomized
+ *   ensembled double Q-learning; additive under ABI 22).  No reference line states it: SAC's steps with 2 <= N <= 8
+ *   critics of ONE output each.  A critic has TQC's layout at one output, tonic_mlp_actor_param_count(O + A, H, 1, 1)
+ *   — what a Critic with a ValueHead packs to — and the flat blocks are [critic_1 | ... | critic_N]; the actor is
+ *   SAC's (two heads), H any code the SAC entries take.
+ *
+ * tonic_ensemble_q_workspace_bytes — a function of its arguments alone (no GPU, no tuning switch): TQC's layout at
+ *   M = 1, tonic_ensemble_quantile_workspace_bytes(B, O, A, H, 1, N); 0 for an N outside 2 .. 8.  Both steps take a
+ *   workspace of this size.
+ * tonic_ensemble_subset_q_grad — per row m: a' = the ONLINE actor's rsample at s' from d_eps [B, A] with logp'; the
+ *   N TARGET critics at (s', a') and the N online critics at (s, a); over the subset S,
+ *   y = r + discount (min_{z in S} Qt_z(s', a') - alpha logp'), loss_m = sum_z l(Q_z(s, a) - y) over ALL N online
+ *   critics, l the per-sample term of `loss` (tonic_critic_loss_t, NULL: MSE — as tonic_twin_q_grad_loss takes it).
+ *   The minimum keeps a NaN as torch.min does.  alpha = entropy_coeff, or expf(*d_log_entropy_coeff) read on the
+ *   device when that pointer is given.
+ *   d_subset points at ONE int32 on the device, bit z set: target critic z + 1 is in S.  The loss kernel reads it, so
+ *   a captured graph follows a new subset without re-capture.  The host cannot validate device data: bits at and
+ *   above N are ignored, and a word with none of the low N bits set means all N critics — no value of the word
+ *   indexes outside the N blocks.  A target critic outside S is evaluated and not read by the loss.
+ *   Output: gradient SUMS of [critic_1 | ... | critic_N] (N Pc floats) + {sum loss_m, sum q, 0, 0, 0, B, 0, 0},
+ *   q = (1 / N) sum_z Q_z of the online critics (float64, fixed order): the row of tonic_ensemble_quantile_q_grad.
+ * The actor step — the mean of the N online critics in the place of SAC's minimum, the tuner's block included — is
+ *   tonic_ensemble_quantile_actor_grad at M = 1: there is no entry of its own.
+ * TONIC_ERR_INVALID_ARGUMENT, each with its own message and its numbers, before anything touches the device: a NULL
+ *   pointer (only d_log_entropy_coeff and loss may be NULL); an unknown loss kind or a parameter that is not finite
+ *   (tonic_critic_loss_check); B, O or A below 1; an unknown H; N outside 2 .. 8; then TONIC_ERR_WORKSPACE: a
+ *   workspace below the query's answer ("workspace of … bytes, … needed"). */
+int64_t tonic_ensemble_q_workspace_bytes(int32_t B, int32_t O, int32_t A, int32_t H, int32_t N);
+int tonic_ensemble_subset_q_grad(const float* d_actor, const float* d_target_critics, const float* d_critics,
+                                 const float* d_norm_mean, const float* d_norm_std, double norm_clip,
+                                 const float* d_observations, const float* d_actions,
+                                 const float* d_next_observations, const float* d_rewards,
+                                 const float* d_discounts, const float* d_eps, float* d_grad_sums, int32_t B,
+                                 int32_t O, int32_t H, int32_t A, int32_t N, const int32_t* d_subset,
+                                 double entropy_coeff, const float* d_log_entropy_coeff,
+                                 const tonic_critic_loss_t* loss, void* d_workspace, int64_t workspace_bytes,
+                                 void* stream);
 
 #ifdef __cplusplus
 }

@@ -10,6 +10,8 @@
 
 #include <stdint.h>
 
+#include "tonic_hip.h" /* tonic_critic_loss_t */
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -94,6 +96,19 @@ int tonic_debug_ensemble_quantile_loss(const float* d_targets, const float* d_th
                                        int32_t M, int32_t N, int32_t drop_per_net, double entropy_coeff,
                                        const float* d_log_entropy_coeff, float* d_dlogits, float* d_sample_m,
                                        int32_t B, int32_t Bp, int32_t twin_row, void* stream);
+
+/* Test entry: the critic loss kernel of REDQ alone (step 4 of tonic_ensemble_subset_q_grad; include/tonic_hip.h) on
+ * given rows.  d_targets / d_qs [N][Bp][ld] (the target and the online critics' values in column 0; 1 <= ld <= 32,
+ * the columns behind it ignored; 2 <= N <= 8), d_rewards / d_discounts / d_logp [B]; d_subset: ONE int32 on the
+ * device, bit z = target critic z in the minimum (bits at and above N ignored, none of the low N set: all N);
+ * alpha = entropy_coeff, or expf(*d_log_entropy_coeff) when given; loss: the rule (NULL: MSE).
+ * Out: d_dq [N][Bp][ld] (rows below B: column 0 the row losses' gradients, 0 behind it; rows from B on untouched) and
+ * d_sample_m [3][Bp] = {loss_m, (1 / N) sum_z Q_z, 0}. */
+int tonic_debug_ensemble_subset_loss(const float* d_targets, const float* d_qs, int32_t ld, const float* d_rewards,
+                                     const float* d_discounts, const float* d_logp, int32_t N,
+                                     const int32_t* d_subset, double entropy_coeff,
+                                     const float* d_log_entropy_coeff, const tonic_critic_loss_t* loss, float* d_dq,
+                                     float* d_sample_m, int32_t B, int32_t Bp, void* stream);
 
 #ifdef __cplusplus
 }

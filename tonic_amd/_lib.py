@@ -318,6 +318,13 @@ SIGNATURES = {
                                            [c_f64, c_vp, c_vp, c_f64] + [c_vp, c_i64, c_vp]),
     'tonic_debug_ensemble_quantile_loss': (ctypes.c_int, [c_vp] * 2 + [c_i32] + [c_vp] * 3 + [c_i32] * 3 +
                                            [c_f64, c_vp] + [c_vp] * 2 + [c_i32] * 3 + [c_vp]),
+    # REDQ: SAC on 2 .. 8 scalar critics, the target's minimum over the subset one device word names (additive under
+    # ABI 22); the actor step is tonic_ensemble_quantile_actor_grad at M = 1
+    'tonic_ensemble_q_workspace_bytes': (c_i64, [c_i32] * 5),
+    'tonic_ensemble_subset_q_grad': (ctypes.c_int, [c_vp] * 5 + [c_f64] + [c_vp] * 7 + [c_i32] * 5 + [c_vp] +
+                                     [c_f64, c_vp, c_vp] + [c_vp, c_i64, c_vp]),
+    'tonic_debug_ensemble_subset_loss': (ctypes.c_int, [c_vp] * 2 + [c_i32] + [c_vp] * 3 + [c_i32, c_vp] +
+                                         [c_f64, c_vp, c_vp] + [c_vp] * 2 + [c_i32] * 2 + [c_vp]),
 }
 
 

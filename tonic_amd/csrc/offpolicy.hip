@@ -663,6 +663,62 @@ __global__ void ensemble_action_grad_sum_kernel(float* blocks, int N, int64_t co
   blocks[count + idx] = sum;
 }
 
+// ---- REDQ (Chen et al. 2021, randomized ensembled double Q-learning): SAC on 2 <= N <= 8 SCALAR critics — TQC's
+// layout at one output, so the value of critic z at row m is column 0 of its [Bp, ld] block — one wave per sample.
+// EnsembleSoftQLearning: S = the target critics whose bit is set in the ONE device word *subset (read here, so a
+// captured graph follows a new draw; bits at and above N ignored; none of the low N set: all N — no value of the word
+// reaches a block outside the N):
+//   y = r + disc (min_{z in S} Qt_z(s', a') - alpha logp') ;  loss_m = sum_z l(Q_z(s, a) - y) over ALL N online critics ;
+//   dq: column 0 = l'(Q_z - y) (critic_loss_term / critic_loss_dq, mlpfwd.h), 0 on every column behind it ;
+//   sample_m [3][Bp] = {loss_m, (1 / N) sum_z Q_z, 0}: the ensemble row of quantile_critic_loss_kernel.
+// The minimum walks S in ascending z on every lane (wave-uniform loads, N <= 8) and keeps a NaN once it meets one, as
+// torch.min does (fminf would drop it); a target critic outside S is never read.  y and the errors are float64 (a
+// float32 y of magnitude ~10 would leave a small error 1e-6 / |e| of itself); lane z < N owns online critic z, and
+// the two sums over the critics are wave_sums of float64: no atomics, the same inputs give the same bits.
+// alpha = expf(*log_alpha) when that pointer is given, read once at entry.
+__global__ __launch_bounds__(256) void ensemble_subset_critic_loss_kernel(
+    const float* targets, const float* qs, int64_t stride, int ld, const float* rewards, const float* discounts,
+    const float* logp_next, int N, const int32_t* subset, float alpha, const float* log_alpha, CriticLoss loss,
+    float* dq, float* sample_m, int B, int Bp) {
+  if (log_alpha != nullptr) alpha = expf(*log_alpha);
+  const int all = (1 << N) - 1;
+  int mask = *subset & all;
+  if (mask == 0) mask = all;
+  const int lane = threadIdx.x & 63, m = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (m >= B) return;
+  const int64_t row = (int64_t)m * ld;
+  float low = INFINITY;
+  for (int z = 0; z < N; ++z) {
+    if (((mask >> z) & 1) == 0) continue;
+    const float t = targets[z * stride + row];
+    low = (t < low || t != t) ? t : low;                         // (a NaN `low` fails both tests: it stays)
+  }
+  const double y = (double)rewards[m] + (double)discounts[m] * ((double)low - (double)alpha * (double)logp_next[m]);
+  const bool live = lane < N;
+  const float q = live ? qs[lane * stride + row] : 0.f;
+  const float e = (float)((double)q - y);
+  if (live) dq[lane * stride + row] = critic_loss_dq(e, loss.kind, loss.param);
+  const int pad = ld - 1;                                        // the padded columns of the N rows: exact 0
+  for (int t = lane; t < N * pad; t += 64) {
+    const int z = t / pad;
+    dq[z * stride + row + 1 + (t - z * pad)] = 0.f;
+  }
+  const double row_loss = wave_sum(live ? (double)critic_loss_term(e, loss.kind, loss.param) : 0.0);
+  const double q_mean = wave_sum(live ? (double)q : 0.0) / (double)N;
+  if (lane == 0) { sample_m[m] = (float)row_loss; sample_m[Bp + m] = (float)q_mean; sample_m[2 * Bp + m] = 0.f; }
+}
+
+// what REDQ's critic step adds to TQC's: where the subset's word lies and the rule of `loss=`
+struct SubsetLoss { const int32_t* subset; CriticLoss rule; };
+
+static void launch_subset_critic_loss(hipStream_t st, const float* targets, const float* qs, int64_t stride, int ld,
+                                      const float* rewards, const float* discounts, const float* logp_next, int N,
+                                      const SubsetLoss& s, float alpha, const float* log_alpha, float* dq,
+                                      float* sample_m, int B, int Bp) {
+  hipLaunchKernelGGL(ensemble_subset_critic_loss_kernel, dim3((B + 3) / 4), dim3(256), 0, st, targets, qs, stride, ld,
+                     rewards, discounts, logp_next, N, s.subset, alpha, log_alpha, s.rule, dq, sample_m, B, Bp);
+}
+
 // ---- DMPO: MPO's sampled actions on the categorical critic.  The target critic's logits on the S * B tiled rows
 // (row s * B + m), one wave per row, lane = atom: the row's mean value sum_i softmax(logits)_i z_i -> tq — what the
 // E-step reads where the scalar critic leaves its output — and, log_norm != null, the row's log-normaliser
@@ -2865,7 +2921,9 @@ int quantile_check(const char* what, int32_t B, int32_t O, int32_t A, int32_t H,
 }
 
 // The critic step.  twin_row: the statistics row is the twin model's {loss, q1, q2} (N = 2), not {loss, q}.
-int quantile_q_grad(const char* what, int32_t N, int twin_row, const float* d_actor, const float* d_target_critics,
+// subset: REDQ's step — the same passes at M = 1 around the subset minimum's loss kernel; null: TQC's.
+int quantile_q_grad(const char* what, int32_t N, int twin_row, const SubsetLoss* subset, const float* d_actor,
+                    const float* d_target_critics,
                     const float* d_critics, const float* d_norm_mean, const float* d_norm_std, double norm_clip,
                     const float* d_observations, const float* d_actions, const float* d_next_observations,
                     const float* d_rewards, const float* d_discounts, const float* d_eps, float* d_grad_sums, int32_t B,
@@ -2898,9 +2956,15 @@ int quantile_q_grad(const char* what, int32_t N, int twin_row, const float* d_ac
   for (int z = 0; z < N; ++z)
     TRY(actor_forward(d_critics + z * Pc, cs, w.X2, B, w.c_h1[z], w.c_h2[z], w.logits + z * w.rows,
                       w.logits + z * w.rows, ldl, false, st, nullptr, nullptr, ldx));
-  // 4 + 5  the truncated quantile loss over the pool of N M and the statistics behind the gradient blocks
-  launch_quantile_critic_loss(st, w.t_logits, w.logits, w.rows, ldl, d_rewards, d_discounts, w.logp, M, N, drop_per_net,
-                              (float)entropy_coeff, d_log_entropy_coeff, w.dlogits, w.sample_m, twin_row, B, Bp);
+  // 4 + 5  the truncated quantile loss over the pool of N M (REDQ: the loss against the subset's minimum) and the
+  //        statistics behind the gradient blocks
+  if (subset != nullptr)
+    launch_subset_critic_loss(st, w.t_logits, w.logits, w.rows, ldl, d_rewards, d_discounts, w.logp, N, *subset,
+                              (float)entropy_coeff, d_log_entropy_coeff, w.dlogits, w.sample_m, B, Bp);
+  else
+    launch_quantile_critic_loss(st, w.t_logits, w.logits, w.rows, ldl, d_rewards, d_discounts, w.logp, M, N,
+                                drop_per_net, (float)entropy_coeff, d_log_entropy_coeff, w.dlogits, w.sample_m,
+                                twin_row, B, Bp);
   hipLaunchKernelGGL(twin_loss_stats_kernel, dim3(1), dim3(1024), 0, st, w.sample_m, d_grad_sums + N * Pc, B, Bp);
   // 6  each online critic's backward into its own block of the sums
   for (int z = 0; z < N; ++z)
@@ -2981,10 +3045,10 @@ extern "C" int tonic_truncated_quantile_q_grad(
     const float* d_next_observations, const float* d_rewards, const float* d_discounts, const float* d_eps,
     float* d_grad_sums, int32_t B, int32_t O, int32_t H, int32_t A, int32_t M, int32_t drop_per_net,
     double entropy_coeff, const float* d_log_entropy_coeff, void* d_workspace, int64_t workspace_bytes, void* stream) {
-  return quantile_q_grad("tonic_truncated_quantile_q_grad", 2, 1, d_actor, d_target_critics, d_critics, d_norm_mean,
-                         d_norm_std, norm_clip, d_observations, d_actions, d_next_observations, d_rewards, d_discounts,
-                         d_eps, d_grad_sums, B, O, H, A, M, drop_per_net, entropy_coeff, d_log_entropy_coeff, d_workspace,
-                         workspace_bytes, stream);
+  return quantile_q_grad("tonic_truncated_quantile_q_grad", 2, 1, nullptr, d_actor, d_target_critics, d_critics,
+                         d_norm_mean, d_norm_std, norm_clip, d_observations, d_actions, d_next_observations, d_rewards,
+                         d_discounts, d_eps, d_grad_sums, B, O, H, A, M, drop_per_net, entropy_coeff,
+                         d_log_entropy_coeff, d_workspace, workspace_bytes, stream);
 }
 
 extern "C" int tonic_ensemble_quantile_q_grad(
@@ -2993,10 +3057,10 @@ extern "C" int tonic_ensemble_quantile_q_grad(
     const float* d_next_observations, const float* d_rewards, const float* d_discounts, const float* d_eps,
     float* d_grad_sums, int32_t B, int32_t O, int32_t H, int32_t A, int32_t M, int32_t N, int32_t drop_per_net,
     double entropy_coeff, const float* d_log_entropy_coeff, void* d_workspace, int64_t workspace_bytes, void* stream) {
-  return quantile_q_grad("tonic_ensemble_quantile_q_grad", N, 0, d_actor, d_target_critics, d_critics, d_norm_mean,
-                         d_norm_std, norm_clip, d_observations, d_actions, d_next_observations, d_rewards, d_discounts,
-                         d_eps, d_grad_sums, B, O, H, A, M, drop_per_net, entropy_coeff, d_log_entropy_coeff, d_workspace,
-                         workspace_bytes, stream);
+  return quantile_q_grad("tonic_ensemble_quantile_q_grad", N, 0, nullptr, d_actor, d_target_critics, d_critics,
+                         d_norm_mean, d_norm_std, norm_clip, d_observations, d_actions, d_next_observations, d_rewards,
+                         d_discounts, d_eps, d_grad_sums, B, O, H, A, M, drop_per_net, entropy_coeff,
+                         d_log_entropy_coeff, d_workspace, workspace_bytes, stream);
 }
 
 extern "C" int tonic_truncated_quantile_actor_grad(
@@ -3041,6 +3105,51 @@ extern "C" int tonic_debug_ensemble_quantile_loss(
   launch_quantile_critic_loss(as_stream(stream), d_targets, d_thetas, (int64_t)B * ld, ld, d_rewards, d_discounts, d_logp,
                               M, N, drop_per_net, (float)entropy_coeff, d_log_entropy_coeff, d_dlogits, d_sample_m,
                               twin_row != 0, B, Bp);
+  TONIC_CHECK_LAUNCH(what);
+  return TONIC_OK;
+}
+
+// ------------------------------------------------------------------ REDQ (random-subset ensemble Q-learning)
+// SAC on N scalar critics in TQC's layout at M = 1: the critic step is quantile_q_grad with the subset loss launch,
+// the actor step tonic_ensemble_quantile_actor_grad at M = 1 as it stands, and the workspace TQC's layout at M = 1.
+extern "C" int64_t tonic_ensemble_q_workspace_bytes(int32_t B, int32_t O, int32_t A, int32_t H, int32_t N) {
+  return tonic_ensemble_quantile_workspace_bytes(B, O, A, H, 1, N);
+}
+
+extern "C" int tonic_ensemble_subset_q_grad(
+    const float* d_actor, const float* d_target_critics, const float* d_critics, const float* d_norm_mean,
+    const float* d_norm_std, double norm_clip, const float* d_observations, const float* d_actions,
+    const float* d_next_observations, const float* d_rewards, const float* d_discounts, const float* d_eps,
+    float* d_grad_sums, int32_t B, int32_t O, int32_t H, int32_t A, int32_t N, const int32_t* d_subset,
+    double entropy_coeff, const float* d_log_entropy_coeff, const tonic_critic_loss_t* loss, void* d_workspace,
+    int64_t workspace_bytes, void* stream) {
+  const char* what = "tonic_ensemble_subset_q_grad";
+  TONIC_REQUIRE(d_subset != nullptr, TONIC_ERR_INVALID_ARGUMENT,
+                "%s: a NULL pointer (d_subset; only d_log_entropy_coeff may be NULL)", what);
+  TRY(tonic_critic_loss_check(loss));
+  const SubsetLoss subset{d_subset, critic_loss_rule(loss)};
+  return quantile_q_grad(what, N, 0, &subset, d_actor, d_target_critics, d_critics, d_norm_mean, d_norm_std, norm_clip,
+                         d_observations, d_actions, d_next_observations, d_rewards, d_discounts, d_eps, d_grad_sums, B,
+                         O, H, A, 1, 0, entropy_coeff, d_log_entropy_coeff, d_workspace, workspace_bytes, stream);
+}
+
+// Test entry (include/tonic_hip_dev.h): REDQ's critic loss kernel alone on given rows, critic z's [Bp, ld] block at
+// z Bp ld of each array; sample_m [3][Bp].
+extern "C" int tonic_debug_ensemble_subset_loss(
+    const float* d_targets, const float* d_qs, int32_t ld, const float* d_rewards, const float* d_discounts,
+    const float* d_logp, int32_t N, const int32_t* d_subset, double entropy_coeff, const float* d_log_entropy_coeff,
+    const tonic_critic_loss_t* loss, float* d_dq, float* d_sample_m, int32_t B, int32_t Bp, void* stream) {
+  const char* what = "tonic_debug_ensemble_subset_loss";
+  TONIC_REQUIRE(d_targets && d_qs && d_rewards && d_discounts && d_logp && d_subset && d_dq && d_sample_m,
+                TONIC_ERR_INVALID_ARGUMENT, "%s: a NULL pointer (only d_log_entropy_coeff and loss may be NULL)", what);
+  TONIC_REQUIRE(N >= 2 && N <= kMaxCritics, TONIC_ERR_INVALID_ARGUMENT, "%s: %d critics (2 <= N <= %d)", what, N,
+                kMaxCritics);
+  TONIC_REQUIRE(ld >= 1 && ld <= kMaxQuantiles && B > 0 && Bp >= B, TONIC_ERR_INVALID_ARGUMENT,
+                "%s: ld %d, B %d, Bp %d (1 <= ld <= %d, 0 < B <= Bp)", what, ld, B, Bp, kMaxQuantiles);
+  TRY(tonic_critic_loss_check(loss));
+  launch_subset_critic_loss(as_stream(stream), d_targets, d_qs, (int64_t)Bp * ld, ld, d_rewards, d_discounts, d_logp, N,
+                            SubsetLoss{d_subset, critic_loss_rule(loss)}, (float)entropy_coeff, d_log_entropy_coeff,
+                            d_dq, d_sample_m, B, Bp);
   TONIC_CHECK_LAUNCH(what);
   return TONIC_OK;
 }

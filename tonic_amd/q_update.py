@@ -127,17 +127,21 @@ class Slot:
     infos    float32 [2, iterations, INFO_WIDTH]: the critic's and the actor's statistics rows
     stats    float32 [iterations, width] or None: the agent's `_stats_width()` more per iteration (MPO; SAC with
              a learned entropy coefficient: the coefficient's statistics rows)
+    subsets  int32 [iterations] or None: one word per iteration that the critic step reads on the device (REDQ: the
+             mask of the target critics in the minimum), uploaded with the noise; iteration `it`'s step gets the
+             pointer to element `it`
     graph    the captured hipGraph; None: the next call through a graph captures
     With a PrioritizedBuffer `indices` is an OUTPUT of the graph, and there are three more:
     uniforms       float64 [iterations, B]: the host's draws, uploaded like `indices` otherwise
     weights        float32 [iterations, B]: the batches' importance weights
     sample_losses  float32 [iterations, B]: the rows' unweighted critic losses, the next priorities"""
 
-    __slots__ = ('key', 'indices', 'eps', 'adam', 'infos', 'stats', 'graph', 'uniforms', 'weights', 'sample_losses')
+    __slots__ = ('key', 'indices', 'eps', 'adam', 'infos', 'stats', 'graph', 'uniforms', 'weights', 'sample_losses',
+                 'subsets')
 
     def __init__(self):
         self.key = self.indices = self.eps = self.adam = self.infos = self.stats = self.graph = None
-        self.uniforms = self.weights = self.sample_losses = None
+        self.uniforms = self.weights = self.sample_losses = self.subsets = None
 
 
 class QUpdate:
@@ -220,12 +224,15 @@ class QUpdate:
             raise
         return infos, stats
 
-    def enqueue(self, indices, eps, graph=None, route=None):
+    def enqueue(self, indices, eps, graph=None, route=None, subsets=None):
         """`agent.enqueue_update`: shard, fill the current slot, issue the iterations or replay their graph.
-        With a PrioritizedBuffer `indices` are its uniforms (float64 [iterations, B])."""
+        With a PrioritizedBuffer `indices` are its uniforms (float64 [iterations, B]).  subsets: the iterations'
+        words of a critic step that reads one (REDQ), int [iterations]; None: the agent draws them — from a stream
+        of its own, the same on every rank, so neither the chunks nor the shards move it."""
         agent = self.agent
         prioritized = self.prioritized
         iterations, global_batch = indices.shape
+        subsets = self._subsets(subsets, iterations)
         agent._q.parameters_changed()
         counts = None
         if agent.critic_updater.world_size > 1:
@@ -235,7 +242,7 @@ class QUpdate:
             # single-process one on the global buffer.
             indices, positions, counts = agent.replay.shard_indices(indices)
             eps = shard_noise(eps, positions, counts, global_batch, agent._noise_samples(eps.shape[1]))
-        slot = self._prepare(indices, eps)
+        slot = self._prepare(indices, eps, subsets)
         if graph is None:
             graph = os.environ.get('TONIC_AMD_NO_GRAPH', '0') != '1'
         route = route or self.route()
@@ -269,7 +276,23 @@ class QUpdate:
         self.mirror_valid = route.fused_kind is not None and not route.phased
         return slot.infos
 
-    def _prepare(self, indices, eps):
+    def _subsets(self, subsets, iterations):
+        """The iterations' words as int32 [iterations]: those given, else the agent's draw (None: it has none)."""
+        agent = self.agent
+        if not getattr(agent.critic_updater, 'takes_subset', False):
+            if subsets is not None:
+                raise ValueError(f'subsets= goes with a critic updater that reads one per iteration (REDQ\'s '
+                                 f'EnsembleSoftQLearning), not with {type(agent.critic_updater).__name__}')
+            return None
+        if subsets is None:
+            return agent._draw_subsets(iterations)
+        given = np.asarray(subsets)
+        if given.shape != (iterations,) or given.dtype.kind not in 'iu':
+            raise ValueError(f'subsets: an int array of one mask per iteration, shape ({iterations},), got '
+                             f'{given.dtype} {given.shape}')
+        return given.astype(np.int32)
+
+    def _prepare(self, indices, eps, subsets=None):
         agent, slot, iterations = self.agent, self.slot, indices.shape[0]
         # everything a captured graph bakes in: shapes, the replay's storage, the updaters'
         # hyper-parameters and schedules — a change of any of them re-captures
@@ -285,6 +308,7 @@ class QUpdate:
             slot.infos = torch.zeros(2, iterations, INFO_WIDTH, device=agent.device)
             slot.graph = None
             slot.uniforms = slot.weights = slot.sample_losses = None
+            slot.subsets = None if subsets is None else torch.zeros(iterations, dtype=torch.int32, device=agent.device)
             if prioritized:
                 slot.uniforms = torch.zeros(indices.shape, dtype=torch.float64, device=agent.device)
                 slot.weights = torch.zeros(indices.shape, dtype=torch.float32, device=agent.device)
@@ -295,6 +319,8 @@ class QUpdate:
             slot.graph = None
         (slot.uniforms if prioritized else slot.indices).copy_(torch.as_tensor(indices), non_blocking=True)
         slot.eps.copy_(torch.as_tensor(eps), non_blocking=True)
+        if subsets is not None:
+            slot.subsets.copy_(torch.as_tensor(subsets), non_blocking=True)
         return slot
 
     def _upload_adam_table(self, slot, due):
@@ -354,7 +380,8 @@ class QUpdate:
             c = global_batch if counts is None else int(counts[it])
             if c > 0:
                 batch = {k: v[it, :c] for k, v in batches.items()}
-                critic.enqueue(batch, slot.eps[it, 0, :c * samples[0]], slot.infos[0, it], n_global)
+                more = {} if slot.subsets is None else {'subset': slot.subsets[it:it + 1]}
+                critic.enqueue(batch, slot.eps[it, 0, :c * samples[0]], slot.infos[0, it], n_global, **more)
             else:
                 critic.enqueue_empty(slot.infos[0, it], n_global)
             if due[it]:

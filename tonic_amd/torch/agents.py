@@ -1413,15 +1413,22 @@ class DDPG(Agent):
     def _actor_due(self, iteration):
         return True                       # ddpg.py:105-112: actor + targets every iteration
 
-    def enqueue_update(self, indices, eps, graph=None):
+    def _draw_subsets(self, iterations):
+        """int32 [iterations]: one word per learner iteration for a critic step that reads one (REDQ's subset
+        masks); None: this agent's critic step reads none."""
+        return None
+
+    def enqueue_update(self, indices, eps, graph=None, subsets=None):
         """Enqueues `indices.shape[0]` learner iterations (no host sync).  indices: int64
         [iterations, B] host array (with a PrioritizedBuffer: its `sample_uniforms`, float64 [iterations, B] — the
         indices are drawn on the device between the critic steps); eps: float32 [iterations, draws, B, A] host array with the
         standard-normal draws in the order the reference consumes them.  With `graph` (default:
         on unless TONIC_AMD_NO_GRAPH=1) the launch sequence — gather, the fused forward / backward /
         grouped weight-gradient launches, Adam + polyak: 13 per SAC iteration — is captured once into a hipGraph
-        reading fixed index / noise buffers and replayed on later calls (tonic_amd.q_update)."""
-        return self._u.enqueue(indices, eps, graph)
+        reading fixed index / noise buffers and replayed on later calls (tonic_amd.q_update).
+        subsets: int [iterations], REDQ's subset masks (bit z: target critic z + 1 is in the minimum), one per
+        iteration; None: drawn by `_draw_subsets`."""
+        return self._u.enqueue(indices, eps, graph, subsets=subsets)
 
     # -- the whole iteration through tonic_q_iteration (5 launches instead of 13)
     _FUSED = {updaters.DeterministicQLearning: (2, updaters.DeterministicPolicyGradient),
@@ -1808,3 +1815,65 @@ class TQC(SAC):
 
     def _graph_signature(self):
         return super()._graph_signature() + (getattr(self.critic_updater, 'top_quantiles_to_drop_per_net', None),)
+
+
+def _redq_model(head):
+    """SAC's default networks with 5 scalar critics."""
+    return models.ActorCriticEnsembleWithTargets(
+        actor=models.Actor(
+            encoder=models.ObservationEncoder(),
+            torso=models.MLP((256, 256), torch.nn.ReLU), head=head),
+        critic=models.Critic(
+            encoder=models.ObservationActionEncoder(),
+            torso=models.MLP((256, 256), torch.nn.ReLU), head=models.ValueHead()),
+        num_critics=5, observation_normalizer=normalizers.MeanStd())
+
+
+class REDQ(SAC):
+    """Randomized ensembled double Q-learning (Chen et al. 2021; the reference has no such agent): SAC — acting, noise
+    draws, scheduling, checkpoints and the optional `entropy_coeff_updater` — on an ensemble of 5 scalar critics
+    (models.ActorCriticEnsembleWithTargets, 2 .. 8 critics).  Every learner iteration draws `subset_size` (2) of the
+    target critics, whose minimum forms the TD target of ALL the online critics (updaters.EnsembleSoftQLearning); the
+    actor ascends the mean of all of them (updaters.EnsembleSoftPolicyGradient).  The default replay runs 20 learner
+    iterations per environment step (an update-to-data ratio of 20).  The updaters run the split route.
+
+    The subsets come from a generator of the agent's own, seeded from `initialize(seed=...)` — not torch's global
+    stream, not the replay's — one draw per iteration: chunked updates and SAC's noise order cannot move it, and every
+    rank of several holds the same subsets (equal seeds, like the index stream).  They reach the GPU as one int32 per
+    iteration in the update's Slot, uploaded with the noise; the critic step's loss kernel reads its word, so one
+    captured graph serves every draw.  The log carries critic/loss, critic/q (the mean over the critics) and
+    actor/loss."""
+
+    _TEMPERED = (updaters.EnsembleSoftQLearning, updaters.EnsembleSoftPolicyGradient)
+
+    def __init__(self, model=None, replay=None, exploration=None, actor_updater=None,
+                 critic_updater=None, entropy_coeff_updater=None):
+        head = models.GaussianPolicyHead(loc_activation=torch.nn.Identity,
+                                         distribution=models.SquashedMultivariateNormalDiag)
+        super().__init__(
+            model=model or _redq_model(head),
+            replay=replay or replays.Buffer(batch_size=256, batch_iterations=20, steps_between_batches=1),
+            exploration=exploration,
+            actor_updater=actor_updater or updaters.EnsembleSoftPolicyGradient(),
+            critic_updater=critic_updater or updaters.EnsembleSoftQLearning(),
+            entropy_coeff_updater=entropy_coeff_updater)
+
+    SUBSET_STREAM = 0x52454451       # what the subsets' seed adds to the agent's, apart from the replay's index stream
+
+    def initialize(self, observation_space, action_space, seed=None):
+        super().initialize(observation_space, action_space, seed=seed)
+        self._seed_subsets(seed)
+
+    def _seed_subsets(self, seed):
+        self._subset_generator = np.random.RandomState(None if seed is None else (seed + self.SUBSET_STREAM) % 2 ** 32)
+
+    def _draw_subsets(self, iterations):
+        critic = self.critic_updater
+        if not getattr(critic, 'takes_subset', False):
+            return None
+        return updaters.draw_subset_masks(self._subset_generator, iterations, self.model.num_critics,
+                                          critic.subset_size)
+
+    def _graph_signature(self):
+        return super()._graph_signature() + ((getattr(self.model, 'num_critics', None),
+                                              getattr(self.critic_updater, 'subset_size', None)),)

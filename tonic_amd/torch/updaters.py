@@ -1144,8 +1144,8 @@ def _critic_count(model):
 
 
 def _refuse_ensemble(name, model):
-    """Every updater but TQC's two on a model of N critics (models.ActorCriticEnsembleWithTargets): refused by name
-    (its entries would walk N critic blocks by their own one or two)."""
+    """Every updater but TQC's two and REDQ's two on a model of N critics (models.ActorCriticEnsembleWithTargets):
+    refused by name (its entries would walk N critic blocks by their own one or two)."""
     if hasattr(model, 'num_critics'):
         raise NotImplementedError(
             f'{name} does not serve a {type(model).__name__} of {model.num_critics} critics: an ensemble is trained '
@@ -1175,12 +1175,16 @@ class _QUpdater(_FlatUpdater):
     # TQC's two updaters: the critics are QuantileValueHead networks (the others refuse such a head by name)
     quantile_critic = False
 
+    # REDQ's two updaters: an ensemble of scalar (ValueHead) critics, packed and walked as TQC's layout at ONE output
+    scalar_ensemble = False
+
     def _shapes(self, model):
         self.model = model
         self.observation_size = model.actor.torso.model[0].in_features
         critic = model.critic_1 if hasattr(model, 'critic_1') else model.critic
-        self.quantiles = int(getattr(critic.head, 'num_quantiles', 0)) if self.quantile_critic else 0
-        if not self.quantile_critic:
+        self.quantiles = int(getattr(critic.head, 'num_quantiles', 0)) if self.quantile_critic else \
+            int(self.scalar_ensemble)
+        if not (self.quantile_critic or self.scalar_ensemble):
             _refuse_quantile_head(type(self).__name__, model)
         try:
             self.hidden = _torso_width(model.actor.torso, self.stock_capable)
@@ -1784,6 +1788,123 @@ class TruncatedQuantileQLearning(_TwinCriticQLearning):
         return out
 
 
+def _ensemble_model(name, model):
+    """What REDQ's two updaters ask of the model, refused by name: an ensemble (models.ActorCriticEnsembleWithTargets)
+    whose 2 N critics all have a plain ValueHead, no Return normaliser, and torsos the kernels run."""
+    from tonic_amd.torch import models
+    if not isinstance(model, models.ActorCriticEnsembleWithTargets):
+        raise NotImplementedError(f'{name} needs an ensemble of critics (models.ActorCriticEnsembleWithTargets), got a '
+                                  f'{type(model).__name__}')
+    heads = [type(critic.head) for critic in model.critics() + model.critics(target=True)]
+    if any(head is not models.ValueHead for head in heads):       # (a subclass may compute anything in its forward)
+        raise NotImplementedError(f'{name} needs critics with a ValueHead (one value each), all {len(heads)} of them, '
+                                  f'got {[head.__name__ for head in heads]}')
+    if getattr(model, 'return_normalizer', None):
+        raise NotImplementedError(f'{name} does not serve a Return normaliser (return_normalizer='
+                                  f'{type(model.return_normalizer).__name__}): the ensemble kernels have no squashed head')
+    for role, network in (('actor', model.actor), ('critic', model.critic_1)):
+        try:
+            _torso_width(network.torso)
+        except NotImplementedError as error:
+            raise NotImplementedError(f'{name}: the {role}\'s torso: {error}') from None
+
+
+def subset_mask(critics):
+    """The device word of a subset: bit z set for every critic index z (0-based) in `critics`."""
+    mask = 0
+    for z in critics:
+        mask |= 1 << int(z)
+    return mask
+
+
+def draw_subset_masks(generator, iterations, num_critics, subset_size):
+    """REDQ's subset stream: int32 [iterations], one mask per learner iteration with `subset_size` distinct critics of
+    `num_critics`, uniform over the subsets, each iteration one draw of `generator` (a numpy RandomState) — the stream
+    is the same however the iterations are split into calls.  subset_size == num_critics: the minimum over all
+    critics, which draws nothing."""
+    if subset_size == num_critics:
+        return np.full(iterations, (1 << num_critics) - 1, np.int32)
+    return np.array([subset_mask(generator.choice(num_critics, size=subset_size, replace=False))
+                     for _ in range(iterations)], np.int32).reshape(iterations)
+
+
+class EnsembleSoftQLearning(_TwinCriticQLearning):
+    """REDQ's critic step (Chen et al. 2021, randomized ensembled double Q-learning; the reference has none): SAC's —
+    the ONLINE actor's sample at s' and its entropy bonus in the target — on an ensemble of N scalar critics
+    (models.ActorCriticEnsembleWithTargets with ValueHead critics).  Per update a subset S of `subset_size` target
+    critics is named by one int32 on the device (bit z: critic z + 1), y = r + discount (min_{z in S} Qt_z(s', a') -
+    alpha logp'), and ALL N online critics regress on y with `loss` (tonic_ensemble_subset_q_grad).  The agent draws
+    the subsets (`draw_subset_masks`); the kernel reads the word, so a captured update graph follows them.
+    subset_size == num_critics is the minimum over all critics.  Logs the ensemble's row: loss, and q, the mean over
+    the critics."""
+    kind, default_lr = 1, 3e-4
+    head_family = 'sac'
+    stock_capable = False
+    scalar_ensemble = True
+    takes_subset = True          # (`QUpdate`: enqueue takes the pointer of the iteration's word)
+
+    def __init__(self, loss=None, optimizer=None, entropy_coeff=0.2, subset_size=2, gradient_clip=0,
+                 lr_scheduler=None):
+        self.lr_scheduler = lr_scheduler
+        try:
+            self.loss = loss
+        except NotImplementedError as error:
+            raise NotImplementedError(f'{type(self).__name__}: {error}') from None
+        self.optimizer = optimizer
+        self.entropy_coeff = entropy_coeff
+        self.subset_size = subset_size
+        self.gradient_clip = gradient_clip
+
+    def initialize(self, model):
+        name = type(self).__name__
+        _ensemble_model(name, model)
+        size, N = self.subset_size, model.num_critics
+        whole = isinstance(size, (int, float)) and not isinstance(size, bool) and int(size) == size
+        if not whole or not 1 <= size <= N:
+            raise NotImplementedError(f'{name}: subset_size is a whole number in 1 .. num_critics = {N}, got {size!r}')
+        self.subset_size = int(size)
+        try:
+            self.loss = self._loss         # (anew: whoever assigned `_loss` directly is told here)
+        except NotImplementedError as error:
+            raise NotImplementedError(f'{name}: {error}') from None
+        super().initialize(model)
+        self._subset = torch.zeros(1, dtype=torch.int32, device=model.flat_online.device)
+
+    def _policy_params(self):
+        return self.model.flat_actor.flat
+
+    def _workspace_bytes(self, batch):
+        return self.lib.tonic_ensemble_q_workspace_bytes(batch, self.observation_size, self.action_size, self.hidden,
+                                                         _critic_count(self.model))
+
+    def enqueue(self, batch, eps, info_row, n_global=None, subset=None):
+        """eps: the [B, A] standard-normal draw of the next action's rsample; subset: an int32 device tensor whose
+        first element is the subset's mask (None: the word `__call__` filled)."""
+        B = batch['observations'].shape[0]
+        ws = self._offpolicy_workspace(B)
+        mean, std = self.norm_tensors()
+        p = _lib.ptr
+        tuner = self.entropy_coeff_updater         # (the coefficient is then read on the device)
+        entry = 'tonic_ensemble_subset_q_grad'
+        _lib.check(getattr(self.lib, entry)(
+            p(self._policy_params()), p(self.model.flat_target_critics.flat), p(self.flat.flat), p(mean), p(std),
+            self.norm_clip(), p(batch['observations']), p(batch['actions']), p(batch['next_observations']),
+            p(batch['rewards']), p(batch['discounts']), p(eps), p(self.grad_sums), B, self.observation_size,
+            self.hidden, self.action_size, _critic_count(self.model), p(self._subset if subset is None else subset),
+            float(self.entropy_coeff), p(tuner.log_entropy_coeff) if tuner is not None else None,
+            ctypes.addressof(self.loss_rule), p(ws), ws.numel(), _lib.current_stream()), entry)
+        self._step(n_global or B * self.world_size, info_row)
+
+    def __call__(self, observations, actions, next_observations, rewards, discounts, subset=None):
+        """Drop-in form: draws its own noise from the torch CPU generator and, unless `subset` (a mask) is given, its
+        subset from numpy's global RandomState."""
+        if subset is None:
+            subset = draw_subset_masks(np.random, 1, _critic_count(self.model), self.subset_size)[0]
+        self._subset.fill_(int(subset))
+        out = super().__call__(observations, actions, next_observations, rewards, discounts)
+        return {'loss': out['loss'], 'q': out['q1']}
+
+
 class ExpectedSARSA(_TwinCriticQLearning):
     """critics.py:238-282 (MPO): one critic regressed on r + discount * the mean target value of
     `num_samples` actions drawn from the target actor (tonic_expected_sarsa_grad)."""
@@ -2213,6 +2334,18 @@ class TwinCriticQuantileSoftPolicyGradient(_ActorQGradient):
             p(eps), p(self.grad_sums), B, self.observation_size, self.hidden, self.action_size, self.quantiles,
             *ensemble, float(self.entropy_coeff), *temper, p(ws), ws.numel(), _lib.current_stream()), entry)
         self._step(n_global or B * self.world_size, info_row, targets=targets)
+
+
+class EnsembleSoftPolicyGradient(TwinCriticQuantileSoftPolicyGradient):
+    """REDQ's actor step: SAC's (actors.py:226-267) with the mean of ALL N online critics in the place of
+    min(q1, q2): loss = mean(alpha logp - (1 / N) sum_z Q_z).  N critics of one output each are TQC's ensemble at
+    M = 1, so the step is tonic_ensemble_quantile_actor_grad at M = 1, the tuner's block included."""
+    quantile_critic = False
+    scalar_ensemble = True
+
+    def initialize(self, model):
+        _ensemble_model(type(self).__name__, model)
+        _ActorQGradient.initialize(self, model)
 
 
 class EntropyCoeffTuning(_FlatUpdater):
