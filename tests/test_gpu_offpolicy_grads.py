@@ -110,7 +110,9 @@ class Ref:
     observation normaliser of mean_stds.py on the critics' inputs only: the reference's Actor.initialize hands its
     normaliser to the encoder's `action_space` slot (actors.py:128-129 vs encoders.py:5-8), so its actors read raw
     observations, and so do the kernels.  `record`: a list that receives (W1, first-layer pre-activation, input) of
-    every forward with gradients, for the column-wise bound of dW1."""
+    every forward with gradients, for the column-wise bound of dW1.  `trace`: a list that receives every torso layer's
+    pre-activation of every forward (detached), `scales`: one that receives the Gaussian heads' softplus before its
+    clamp: what a test's preconditions on its inputs read.  `agent`: anything with `.model.observation_normalizer`."""
 
     def __init__(self, agent, kind, layers, activation):
         self.kind, self.L = kind, layers
@@ -120,6 +122,7 @@ class Ref:
         self.std = norm._std.detach().cpu().double()
         self.clip = norm.clip
         self.record = None
+        self.trace = self.scales = None
 
     def norm(self, obs):
         x = (obs - self.mean) / self.std
@@ -131,6 +134,8 @@ class Ref:
             if layer == 0 and self.record is not None and z.requires_grad:
                 z.retain_grad()
                 self.record.append((params[0], z, x.detach()))
+            if self.trace is not None:
+                self.trace.append(z.detach())
             x = self.act(z)
         return x
 
@@ -142,7 +147,10 @@ class Ref:
         h, L = self._torso(params, obs), self.L
         if self.kind in ('sac', 'mpo'):
             loc = self._linear(params, h, 2 * L)
-            scale = torch.clamp(torch.nn.functional.softplus(self._linear(params, h, 2 * L + 2)), 1e-4, 1.0)
+            raw = torch.nn.functional.softplus(self._linear(params, h, 2 * L + 2))
+            if self.scales is not None:
+                self.scales.append(raw.detach())
+            scale = torch.clamp(raw, 1e-4, 1.0)
             return (torch.tanh(loc) if self.kind == 'mpo' else loc), scale
         return torch.tanh(self._linear(params, h, 2 * L)), None
 
@@ -206,76 +214,129 @@ def _batch(rng, B, O, A):
 
 # ---------------------------------------------------------------- 1 + 2. SAC / TD3 / DDPG
 
-def _q_steps(agent, kind, batch, eps, eps_actor, ref, bound=1e-5, dw1_columns=False):
+Q_HYPER = dict(entropy_coeff=0.2, noise_scale=0.2, noise_clip=0.5)     # the updaters' defaults (critics.py, actors.py)
+
+
+def _q_hyper(agent, kind):
+    """What the float64 restatement reads of the updaters: SAC's coefficient, TD3's target-action noise."""
+    critic_u, actor_u = agent.critic_updater, agent.actor_updater
+    hyper = {}
+    if kind == 'sac':
+        hyper.update(entropy_coeff=critic_u.entropy_coeff, actor_entropy_coeff=actor_u.entropy_coeff)
+    if kind == 'td3':
+        noise = critic_u.target_action_noise
+        hyper.update(noise_scale=noise.scale, noise_clip=noise.clip)
+    return hyper
+
+
+def _q_leaves(model, kind):
+    """float64 leaves of a model's networks: dict(actor, target_actor, online = [critics], frozen = [targets])."""
+    twin = kind in ('sac', 'td3')
+    critics = [model.critic_1, model.critic_2] if twin else [model.critic]
+    targets = [model.target_critic_1, model.target_critic_2] if twin else [model.target_critic]
+    return dict(actor=_f64(model.actor), target_actor=_f64(model.target_actor),
+                online=[_f64(c) for c in critics], frozen=[_f64(c) for c in targets])
+
+
+def _q_critic_reference(ref, kind, nets, d, eps, hyper):
+    """The critic step's loss in float64 (critics.py), backward into nets['online']: dict(loss, qs, returns, targets
+    — each target critic's value of (s', a') — and for TD3 loc / noise, the target action's terms before their
+    clamps)."""
+    out = {}
+    with torch.no_grad():
+        if kind == 'sac':                                                   # critics.py:202-235
+            loc, scale = ref.policy(nets['actor'], d['next_observations'])
+            a, logp = _squashed(loc, scale, eps.to(loc.dtype))
+            out['targets'] = [ref.critic(p, d['next_observations'], a) for p in nets['frozen']]
+            nxt = torch.min(*out['targets']) - hyper['entropy_coeff'] * logp
+        else:
+            a = ref.policy(nets['target_actor'], d['next_observations'])[0]
+            if kind == 'td3':                                               # critics.py:125-134, :156-182
+                out['loc'], out['noise'] = a, hyper['noise_scale'] * eps.to(a.dtype)
+                a = torch.clamp(a + torch.clamp(out['noise'], -hyper['noise_clip'], hyper['noise_clip']), -1, 1)
+                out['targets'] = [ref.critic(p, d['next_observations'], a) for p in nets['frozen']]
+                nxt = torch.min(*out['targets'])
+            else:                                                           # critics.py:68-86 (DDPG)
+                nxt = ref.critic(nets['frozen'][0], d['next_observations'], a)
+                out['targets'] = [nxt]
+        returns = d['rewards'] + d['discounts'] * nxt
+    qs = [ref.critic(p, d['observations'], d['actions']) for p in nets['online']]
+    loss = sum(((q - returns) ** 2).mean() for q in qs)
+    loss.backward()
+    out.update(loss=loss.detach(), qs=[q.detach() for q in qs], returns=returns)
+    return out
+
+
+def _q_actor_reference(ref, kind, actor, online, d, eps_actor, hyper):
+    """The actor step's loss in float64 (actors.py) through the critics `online`, backward into `actor`:
+    dict(terms — the rows' losses —, qs — each critic's value of (s, actor(s)))."""
+    if kind == 'sac':                                                       # actors.py:238-267
+        loc, scale = ref.policy(actor, d['observations'])
+        a, logp = _squashed(loc, scale, eps_actor.to(loc.dtype))
+        qs = [ref.critic(p, d['observations'], a) for p in online]
+        terms = hyper.get('actor_entropy_coeff', hyper['entropy_coeff']) * logp - torch.min(*qs)
+    else:                                                                   # actors.py:170-189 (critic_1)
+        qs = [ref.critic(online[0], d['observations'], ref.policy(actor, d['observations'])[0])]
+        terms = -qs[0]
+    terms.mean().backward()
+    return dict(terms=terms.detach(), qs=[q.detach() for q in qs])
+
+
+def _q_steps(agent, kind, batch, eps, eps_actor, ref, bound=1e-5, dw1_columns=False, restore=False):
     """One critic step and one actor step of the HIP entries against float64; returns {'critic': err, 'actor': err}
-    (largest relative error of the tensors) and, with bound = None, checks nothing but the statistic slots."""
+    (largest relative error of the tensors) and, with bound = None, checks nothing but the statistic slots.
+    restore: the online parameters are put back behind the critic step's optimizer, so that the actor step runs
+    from the parameters the critic step ran from (else: through the critics the critic step has just moved).
+    Also returned: grads / actor_grads, the two gradient-sum blocks as left for the optimizer, and critic_stats /
+    actor_stats, their eight statistic slots."""
     m, B = agent.model, batch['observations'].shape[0]
     critic_u, actor_u = agent.critic_updater, agent.actor_updater
     twin = kind in ('sac', 'td3')
     critics = [m.critic_1, m.critic_2] if twin else [m.critic]
-    targets = [m.target_critic_1, m.target_critic_2] if twin else [m.target_critic]
-    actor, target_actor = _f64(m.actor), _f64(m.target_actor)
-    online, frozen = [_f64(c) for c in critics], [_f64(c) for c in targets]
+    hyper = _q_hyper(agent, kind)
+    nets = _q_leaves(m, kind)
+    actor, online = nets['actor'], nets['online']
     d = {k: v.double() for k, v in batch.items()}
     gpu = {k: v.cuda() for k, v in batch.items()}
-    with torch.no_grad():
-        if kind == 'sac':                                                   # critics.py:202-235
-            loc, scale = ref.policy(actor, d['next_observations'])
-            a, logp = _squashed(loc, scale, eps.double())
-            nxt = torch.min(*[ref.critic(p, d['next_observations'], a) for p in frozen]) - \
-                critic_u.entropy_coeff * logp
-        else:
-            a = ref.policy(target_actor, d['next_observations'])[0]
-            if kind == 'td3':                                               # critics.py:125-134, :156-182
-                noise = critic_u.target_action_noise
-                a = torch.clamp(a + torch.clamp(noise.scale * eps.double(), -noise.clip, noise.clip), -1, 1)
-                nxt = torch.min(*[ref.critic(p, d['next_observations'], a) for p in frozen])
-            else:                                                           # critics.py:68-86 (DDPG)
-                nxt = ref.critic(frozen[0], d['next_observations'], a)
-        returns = d['rewards'] + d['discounts'] * nxt
     ref.record = [] if dw1_columns else None
-    qs = [ref.critic(p, d['observations'], d['actions']) for p in online]
-    loss = sum(((q - returns) ** 2).mean() for q in qs)
-    loss.backward()
+    want = _q_critic_reference(ref, kind, nets, d, eps, hyper)
+    qs, returns, loss = want['qs'], want['returns'], want['loss']
     records = ref.record
     info = torch.zeros(8, device='cuda')
+    before = m.flat_online.clone() if restore else None
     critic_u.enqueue(gpu, eps.cuda() if eps is not None else None, info)
     stats = _stats(critic_u)
     got = _grad_sums(critics, critic_u.grad_sums, B)
-    out = dict(grads=critic_u.grad_sums[:critic_u.count].cpu().numpy())
+    out = dict(grads=critic_u.grad_sums[:critic_u.count].cpu().numpy(), critic_stats=stats)
     assert stats[5] == B, stats
     leaves = [leaf for p in online for leaf in p]
     out['critic'] = _check(got, leaves, [f'critic {i}' for i in range(len(got))], bound)
     out['critic_net'] = _network_error(got, leaves)
     if bound is not None:
-        sq = sum((q.detach() - returns) ** 2 for q in qs)
-        _check_stat(stats[0] / B, loss.detach(), sq, 'critic loss')
+        sq = sum((q - returns) ** 2 for q in qs)
+        _check_stat(stats[0] / B, loss, sq, 'critic loss')
         for i, q in enumerate(qs):
-            _check_stat(stats[1 + i] / B, q.detach().mean(), q.detach(), f'q{i + 1}')
+            _check_stat(stats[1 + i] / B, q.mean(), q, f'q{i + 1}')
     if dw1_columns:
-        conditions = [((q.detach().abs() + returns.abs()) / (q.detach() - returns).abs().clamp_min(1e-300)).numpy()
-                      for q in qs]
+        conditions = [((q.abs() + returns.abs()) / (q - returns).abs().clamp_min(1e-300)).numpy() for q in qs]
         out['columns'] = _columns(got, leaves, records, len(online[0]), conditions)
-    # the actor step (actors.py), through the critics the critic step has just moved
+    # the actor step (actors.py), through the critics the critic step has just moved (restore: has left as they were)
+    if restore:
+        m.flat_online.copy_(before)
     online = [_f64(c) for c in critics]
     ref.record = [] if dw1_columns else None
-    if kind == 'sac':                                                       # actors.py:238-267
-        loc, scale = ref.policy(actor, d['observations'])
-        a, logp = _squashed(loc, scale, eps_actor.double())
-        terms = actor_u.entropy_coeff * logp - torch.min(*[ref.critic(p, d['observations'], a) for p in online])
-    else:                                                                   # actors.py:170-189 (critic_1)
-        terms = -ref.critic(online[0], d['observations'], ref.policy(actor, d['observations'])[0])
+    terms = _q_actor_reference(ref, kind, actor, online, d, eps_actor, hyper)['terms']
     records = [r for r in ref.record if r[0] is actor[0]] if dw1_columns else None
     ref.record = None
-    terms.mean().backward()
     actor_u.enqueue(gpu['observations'], eps_actor.cuda() if kind == 'sac' else None, info)
     stats = _stats(actor_u)
     assert stats[5] == B, stats
     got = _grad_sums([m.actor], actor_u.grad_sums, B)
+    out.update(actor_grads=actor_u.grad_sums[:actor_u.count].cpu().numpy(), actor_stats=stats)
     out['actor'] = _check(got, actor, [f'actor {i}' for i in range(len(actor))], bound)
     out['actor_net'] = _network_error(got, actor)
     if bound is not None:
-        _check_stat(stats[0] / B, terms.detach().mean(), terms.detach(), 'actor loss')
+        _check_stat(stats[0] / B, terms.mean(), terms, 'actor loss')
     if dw1_columns:
         out['columns'] = max(out['columns'], _columns(got, actor, records, len(actor), [np.ones(B)]))
     return out
@@ -447,6 +508,80 @@ def test_a_weight_beyond_the_image_range_is_loud(lib):
 
 # ---------------------------------------------------------------- 3. D4PG
 
+def _d4pg_returns(rng, B, NA, returns):
+    """(atoms, rewards, discounts) of test_d4pg_grads_vs_float64's two generators."""
+    if returns == 'edges':
+        atoms = (-10.0, 10.0, NA)
+        pushed = rng.uniform(size=B) < 0.8
+        pushed[0] = True
+        rewards = rng.choice([-1.0, 1.0], B) * rng.uniform(25, 40, B) * pushed + rng.normal(size=B)
+        discounts = np.where(rng.uniform(size=B) < 0.25, 0.0, 0.99)
+    else:
+        atoms = ((1 - NA) / 2, (NA - 1) / 2, NA)
+        rewards = rng.randint(-3, 4, B).astype(np.float64)
+        discounts = np.ones(B)
+    return atoms, rewards, discounts
+
+
+def _d4pg_critic_reference(ref, target_actor, frozen, online, d, values):
+    """critics.py:100-122 in float64, backward into `online`: dict(terms, ret, delta)."""
+    with torch.no_grad():
+        a = ref.policy(target_actor, d['next_observations'])[0]
+        p_next = torch.softmax(ref.critic(frozen, d['next_observations'], a), -1)
+        ret = d['rewards'][:, None] + d['discounts'][:, None] * values[None]
+        above = (torch.cat([values[1:], values[:1]]) - values)[None, :, None]
+        below = (values - torch.cat([values[-1:], values[:-1]]))[None, :, None]
+        delta = torch.clamp(ret, values[0], values[-1])[:, None] - values[None, :, None]
+        up = (delta >= 0).double()
+        hat = (up * delta / above) - ((1 - up) * delta / below)
+        target = (torch.clamp(1 - hat, 0, 1) * p_next[:, None]).sum(2)
+    terms = -(target * torch.log_softmax(ref.critic(online, d['observations'], d['actions']), -1)).sum(-1)
+    terms.mean().backward()
+    return dict(terms=terms.detach(), ret=ret, delta=delta)
+
+
+def _d4pg_actor_reference(ref, actor, online, d, values):
+    """actors.py:203-224 in float64, backward into `actor`: (the rows' losses, the rows' sum_i p_i |z_i| — the size of
+    the terms a row's loss is the sum of)."""
+    logits = ref.critic(online, d['observations'], ref.policy(actor, d['observations'])[0])
+    terms = -(torch.softmax(logits, -1) * values).sum(-1)
+    terms.mean().backward()
+    return terms.detach(), (torch.softmax(logits, -1) * values.abs()).sum(-1).detach()
+
+
+def _d4pg_steps(agent, batch, ref, restore=False):
+    """One critic step and one actor step of the D4PG entries against float64 (see _q_steps): the references, the
+    gradient blocks and statistic slots as left for the optimizer, and the largest relative errors."""
+    m, B = agent.model, batch['observations'].shape[0]
+    critic_u, actor_u = agent.critic_updater, agent.actor_updater
+    values = m.target_critic.head.values.double()
+    target_actor, frozen, online, actor = _f64(m.target_actor), _f64(m.target_critic), _f64(m.critic), _f64(m.actor)
+    d = {k: v.double() for k, v in batch.items()}
+    out = _d4pg_critic_reference(ref, target_actor, frozen, online, d, values)
+    terms = out['terms']
+    info = torch.zeros(8, device='cuda')
+    gpu = {k: v.cuda() for k, v in batch.items()}
+    before = m.flat_online.clone() if restore else None
+    critic_u.enqueue(gpu, None, info)
+    stats = _stats(critic_u)
+    assert stats[5] == B, stats
+    out.update(grads=critic_u.grad_sums[:critic_u.count].cpu().numpy(), critic_stats=stats)
+    out['critic'] = _check(_grad_sums([m.critic], critic_u.grad_sums, B), online,
+                           [f'critic {i}' for i in range(len(online))])
+    _check_stat(stats[0] / B, terms.mean(), terms, 'critic loss')
+    if restore:
+        m.flat_online.copy_(before)
+    online = _f64(m.critic)                                                 # actors.py:203-224, the moved critic
+    terms = _d4pg_actor_reference(ref, actor, online, d, agent.actor_updater.values.double().cpu())[0]
+    actor_u.enqueue(gpu['observations'], None, info)
+    stats = _stats(actor_u)
+    assert stats[5] == B, stats
+    out.update(actor_grads=actor_u.grad_sums[:actor_u.count].cpu().numpy(), actor_stats=stats)
+    out['actor'] = _check(_grad_sums([m.actor], actor_u.grad_sums, B), actor, [f'actor {i}' for i in range(len(actor))])
+    _check_stat(stats[0] / B, terms.mean(), terms, 'actor loss')
+    return out
+
+
 @pytest.mark.parametrize('torso', ['plain', 'uneven'])
 @pytest.mark.parametrize('NA', [2, 16, 17, 51, 64])
 @pytest.mark.parametrize('B', [1, 37, 256])
@@ -460,19 +595,9 @@ def test_d4pg_grads_vs_float64(lib, torso, NA, B, returns):
     O, A = 17, 6
     sizes = (256, 256) if torso == 'plain' else (96, 64)
     rng = np.random.RandomState(NA * 31 + B)
-    if returns == 'edges':
-        atoms = (-10.0, 10.0, NA)
-        pushed = rng.uniform(size=B) < 0.8
-        pushed[0] = True
-        rewards = rng.choice([-1.0, 1.0], B) * rng.uniform(25, 40, B) * pushed + rng.normal(size=B)
-        discounts = np.where(rng.uniform(size=B) < 0.25, 0.0, 0.99)
-    else:
-        atoms = ((1 - NA) / 2, (NA - 1) / 2, NA)
-        rewards = rng.randint(-3, 4, B).astype(np.float64)
-        discounts = np.ones(B)
+    atoms, rewards, discounts = _d4pg_returns(rng, B, NA, returns)
     agent = _agent('d4pg', O, A, B, sizes=sizes, atoms=atoms)
-    critic_u, actor_u = agent.critic_updater, agent.actor_updater
-    assert (critic_u.hidden == 256) == (torso == 'plain')
+    assert (agent.critic_updater.hidden == 256) == (torso == 'plain')
     values = agent.model.target_critic.head.values.double()
     if returns == 'on_atoms':
         assert np.array_equal(values.numpy(), np.arange(NA) + (1 - NA) / 2)
@@ -480,49 +605,48 @@ def test_d4pg_grads_vs_float64(lib, torso, NA, B, returns):
     batch = _batch(rng, B, O, A)
     batch['rewards'] = torch.as_tensor(rewards, dtype=torch.float32)
     batch['discounts'] = torch.as_tensor(discounts, dtype=torch.float32)
-    m = agent.model
-    ref = Ref(agent, 'd4pg', len(sizes), 'ReLU')
-    target_actor, frozen, online, actor = _f64(m.target_actor), _f64(m.target_critic), _f64(m.critic), _f64(m.actor)
-    d = {k: v.double() for k, v in batch.items()}
-    with torch.no_grad():                                                    # critics.py:100-122
-        a = ref.policy(target_actor, d['next_observations'])[0]
-        p_next = torch.softmax(ref.critic(frozen, d['next_observations'], a), -1)
-        ret = d['rewards'][:, None] + d['discounts'][:, None] * values[None]
-        above = (torch.cat([values[1:], values[:1]]) - values)[None, :, None]
-        below = (values - torch.cat([values[-1:], values[:-1]]))[None, :, None]
-        delta = torch.clamp(ret, values[0], values[-1])[:, None] - values[None, :, None]
-        up = (delta >= 0).double()
-        hat = (up * delta / above) - ((1 - up) * delta / below)
-        target = (torch.clamp(1 - hat, 0, 1) * p_next[:, None]).sum(2)
+    ret = batch['rewards'].double()[:, None] + batch['discounts'].double()[:, None] * values[None]
     if returns == 'edges':
         assert (ret[:, 0] < values[0]).any() or B == 1
         assert ((ret < values[0]) | (ret > values[-1])).double().mean() > 0.5
-    else:
-        assert (delta == 0).any()
-    terms = -(target * torch.log_softmax(ref.critic(online, d['observations'], d['actions']), -1)).sum(-1)
-    terms.mean().backward()
-    info = torch.zeros(8, device='cuda')
-    gpu = {k: v.cuda() for k, v in batch.items()}
-    critic_u.enqueue(gpu, None, info)
-    stats = _stats(critic_u)
-    assert stats[5] == B, stats
-    errs = [_check(_grad_sums([m.critic], critic_u.grad_sums, B), online, [f'critic {i}' for i in range(len(online))])]
-    _check_stat(stats[0] / B, terms.detach().mean(), terms.detach(), 'critic loss')
-    online = _f64(m.critic)                                                 # actors.py:203-224, the moved critic
-    logits = ref.critic(online, d['observations'], ref.policy(actor, d['observations'])[0])
-    terms = -(torch.softmax(logits, -1) * agent.actor_updater.values.double().cpu()).sum(-1)
-    terms.mean().backward()
-    actor_u.enqueue(gpu['observations'], None, info)
-    stats = _stats(actor_u)
-    assert stats[5] == B, stats
-    errs.append(_check(_grad_sums([m.actor], actor_u.grad_sums, B), actor, [f'actor {i}' for i in range(len(actor))]))
-    _check_stat(stats[0] / B, terms.detach().mean(), terms.detach(), 'actor loss')
-    print(f'd4pg {torso} NA={NA} B={B} {returns}: largest relative error critic {errs[0]:.2e} actor {errs[1]:.2e}')
+    out = _d4pg_steps(agent, batch, Ref(agent, 'd4pg', len(sizes), 'ReLU'))
+    if returns == 'on_atoms':
+        assert (out['delta'] == 0).any()
+    print(f'd4pg {torso} NA={NA} B={B} {returns}: largest relative error critic {out["critic"]:.2e} '
+          f'actor {out["actor"]:.2e}')
 
 
 # ---------------------------------------------------------------- 4. MPO
 
 MPO_TORSOS = {'plain': ((256, 256), 'ReLU'), 'elu3': ((64, 48, 40), 'ELU')}
+
+
+def _sarsa_reference(ref, target_actor, frozen, online, d, eps, S):
+    """critics.py:238-282 at S samples in float64, backward into `online`: (the rows' squared errors, q)."""
+    B, A = d['observations'].shape[0], eps.shape[-1]
+    with torch.no_grad():
+        loc, scale = ref.policy(target_actor, d['next_observations'])
+        a = (loc[None] + scale[None] * eps.to(loc.dtype).view(S, B, A)).reshape(S * B, A)
+        nxt = ref.critic(frozen, d['next_observations'].repeat(S, 1), a).view(S, B).mean(0)
+        returns = d['rewards'] + d['discounts'] * nxt
+    q = ref.critic(online, d['observations'], d['actions'])
+    sq = (q - returns) ** 2
+    sq.mean().backward()
+    return sq.detach(), q.detach()
+
+
+def _sarsa_step(agent, batch, eps, ref, S):
+    """tonic_expected_sarsa_grad against float64: dict(critic, the largest relative error; grads, critic_stats)."""
+    m, u, B = agent.model, agent.critic_updater, batch['observations'].shape[0]
+    target_actor, frozen, online = _f64(m.target_actor), _f64(m.target_critic), _f64(m.critic)
+    sq, q = _sarsa_reference(ref, target_actor, frozen, online, {k: v.double() for k, v in batch.items()}, eps, S)
+    u.enqueue({k: v.cuda() for k, v in batch.items()}, eps.cuda(), torch.zeros(8, device='cuda'))
+    stats = _stats(u)
+    assert stats[5] == B, stats
+    err = _check(_grad_sums([m.critic], u.grad_sums, B), online, [f'critic {i}' for i in range(len(online))])
+    _check_stat(stats[0] / B, sq.mean(), sq, 'loss')
+    _check_stat(stats[1] / B, q.mean(), q, 'q')
+    return dict(critic=err, grads=u.grad_sums[:u.count].cpu().numpy(), critic_stats=stats)
 
 
 @pytest.mark.parametrize('torso', ['plain', 'elu3'])
@@ -536,24 +660,7 @@ def test_expected_sarsa_grads_vs_float64(lib, torso, S):
     _set_normalizer(agent, rng.normal(size=O) * 0.3, np.exp(rng.uniform(-0.5, 0.5, O)))
     batch = _batch(rng, B, O, A)
     eps = torch.as_tensor(rng.normal(size=(S * B, A)), dtype=torch.float32)
-    m, u = agent.model, agent.critic_updater
-    ref = Ref(agent, 'mpo', len(sizes), activation)
-    target_actor, frozen, online = _f64(m.target_actor), _f64(m.target_critic), _f64(m.critic)
-    d = {k: v.double() for k, v in batch.items()}
-    with torch.no_grad():
-        loc, scale = ref.policy(target_actor, d['next_observations'])
-        a = (loc[None] + scale[None] * eps.double().view(S, B, A)).reshape(S * B, A)
-        nxt = ref.critic(frozen, d['next_observations'].repeat(S, 1), a).view(S, B).mean(0)
-        returns = d['rewards'] + d['discounts'] * nxt
-    q = ref.critic(online, d['observations'], d['actions'])
-    sq = (q - returns) ** 2
-    sq.mean().backward()
-    u.enqueue({k: v.cuda() for k, v in batch.items()}, eps.cuda(), torch.zeros(8, device='cuda'))
-    stats = _stats(u)
-    assert stats[5] == B, stats
-    err = _check(_grad_sums([m.critic], u.grad_sums, B), online, [f'critic {i}' for i in range(len(online))])
-    _check_stat(stats[0] / B, sq.detach().mean(), sq.detach(), 'loss')
-    _check_stat(stats[1] / B, q.detach().mean(), q.detach(), 'q')
+    err = _sarsa_step(agent, batch, eps, Ref(agent, 'mpo', len(sizes), activation), S)['critic']
     print(f'mpo critic {torso} S={S}: largest relative error {err:.2e}')
 
 
@@ -614,9 +721,16 @@ def _mpo_reference(ref, actor, target_actor, frozen, obs, eps, duals, floor, u, 
     return (log_t, log_am, log_as, log_p), stats, actor_loss, floored.numpy(), actions, sum(scales), tempering
 
 
+def _mpo_duals(A, log_temperature=-5.0):
+    """[log T | log alpha_mean | log alpha_std | log penalty T]: duals below the floor, T cold unless given."""
+    return np.concatenate([[log_temperature], np.where(np.arange(A) % 2, -25.0, 1.0),
+                           np.where(np.arange(A) % 2, 10.0, -30.0), [-20.0]]).astype(np.float32)
+
+
 def _mpo_setup(lib, A, B, torso, penalization, floor, S=20, seed=0):
+    """torso: a name of MPO_TORSOS, or (sizes, activation)."""
     O = 17
-    sizes, activation = MPO_TORSOS[torso]
+    sizes, activation = MPO_TORSOS[torso] if isinstance(torso, str) else torso
     rng = np.random.RandomState(seed + A * 13 + B)
     agent = _agent('mpo', O, A, B, sizes=sizes, activation=activation, S=S, action_penalization=penalization,
                    min_log_dual=floor)
@@ -633,8 +747,7 @@ def _mpo_setup(lib, A, B, torso, penalization, floor, S=20, seed=0):
         for p in _variables(m.actor):
             p += torch.as_tensor(rng.normal(size=tuple(p.shape)) * 0.02, dtype=torch.float32, device='cuda')
     u = agent.actor_updater
-    duals = np.concatenate([[-5.0], np.where(np.arange(A) % 2, -25.0, 1.0), np.where(np.arange(A) % 2, 10.0, -30.0),
-                            [-20.0]]).astype(np.float32)           # a cold temperature, duals below the floor
+    duals = _mpo_duals(A)                                          # a cold temperature, duals below the floor
     obs = torch.as_tensor(rng.normal(size=(B, O)), dtype=torch.float32)
     eps = torch.as_tensor(rng.normal(size=(S * B, A)), dtype=torch.float32)
     return agent, u, duals, obs, eps, Ref(agent, 'mpo', len(sizes), activation)
@@ -684,7 +797,7 @@ def _mpo_call(lib, agent, u, duals, obs, eps, shard=None):
     return (grads.cpu().numpy(), dual_grads.cpu().numpy(), stats.cpu().numpy(), d_duals.cpu().numpy())
 
 
-def _mpo_compare(agent, u, got, duals, obs, eps, ref, label):
+def _mpo_compare(agent, u, got, duals, obs, eps, ref, label, bound=None):
     grads, dual_grads, stats, written = got
     m, A, S, B = agent.model, u.action_size, u.num_samples, obs.shape[0]
     actor, target_actor, frozen = _f64(m.actor), _f64(m.target_actor), _f64(m.target_critic)
@@ -697,7 +810,8 @@ def _mpo_compare(agent, u, got, duals, obs, eps, ref, label):
     # 2^-24 max |Q| / T relative, 150x more at log T = -5 than at T = 1.  The actor's gradients are held to
     # max(1e-5, 64 x that) of each tensor's largest element (seen: up to 5.2e-5 at A = 1, B = 37, log T = -5, where
     # 16 x would give 2.5e-5; a gradient scaled by 1.001 is still 1e-3 off).
-    bound = max(1e-5, 64 * 2.0 ** -24 * tempering)
+    # (bound given: the caller's, for inputs whose temperature leaves the weights well conditioned)
+    bound = max(1e-5, 64 * 2.0 ** -24 * tempering) if bound is None else bound
     err = _check(_grad_sums([m.actor], torch.as_tensor(grads), B), actor, [f'actor {i}' for i in range(len(actor))],
                  bound)
     names = ('log_temperature', 'log_alpha_mean', 'log_alpha_std', 'log_penalty_temperature')
@@ -731,6 +845,7 @@ def _mpo_compare(agent, u, got, duals, obs, eps, ref, label):
     stat_err = max(_check_stat(stats[i], want_stats[i], torch.tensor([temperature_scale]) if i == 6 else None,
                                f'stat {i}') for i in range(n))
     print(f'mpo actor {label}: largest relative error actor {err:.2e} (bound {bound:.1e}) duals {dual_err:.2e} stats {stat_err:.2e}')
+    return err, dual_err, stat_err
 
 
 @pytest.mark.parametrize('torso', ['plain', 'elu3'])
