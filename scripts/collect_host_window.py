@@ -33,7 +33,7 @@ for r in range(rounds):
     loop.run(2048)
     times.append((time.perf_counter() - t0) / 2048 * 1e6)
 between_rollouts(agent, loop)
-collector, blocked = agent._collector, [0.0]
+collector, blocked = agent._rollout.collector, [0.0]
 wait = collector._wait
 
 

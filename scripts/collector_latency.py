@@ -78,7 +78,7 @@ def agent_loop(W, O, A, transport, steps=3000, pool=64):
         t3 = clock()
         parts += (t1 - t0, t2 - t1, t3 - t2)
     total = clock() - begin
-    agent._collector.end_rollout(agent.replay.index - 1)
+    agent._rollout.collector.end_rollout(agent.replay.index - 1)
     torch.cuda.synchronize()
     return dict(transport=transport, us_per_step=round(total / steps * 1e6, 2),
                 agent_step_us=round(parts[0] / steps * 1e6, 2),

@@ -20,7 +20,7 @@ loop.run(bench.T)                                # one whole rollout + update: e
 agent.settle()
 torch.cuda.synchronize()
 loop.run(64)
-collector, noise = agent._collector, agent._noise
+collector, noise = agent._rollout.collector, agent._rollout.noise
 clock = time.perf_counter
 spent = dict(wait=0.0, arm=0.0, claim=0.0, take=0.0)
 

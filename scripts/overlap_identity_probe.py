@@ -34,7 +34,7 @@ def run(overlap, sleeps=True):
     real_update = agent._update
 
     def snapshotting_update():
-        agent._collector  # (the rollout has ended: end_rollout ran before _update)
+        # (the rollout has ended: PolicyBlock.update ran end_rollout before _update)
         torch.cuda.synchronize()
         snap = {k: v.cpu().numpy().copy() for k, v in agent.replay.buffers.items()
                 if k in ('observations', 'actions', 'next_observations', 'rewards', 'resets',
@@ -51,9 +51,8 @@ def run(overlap, sleeps=True):
             kept = {k: v.clone() for k, v in agent.replay.buffers.items()}
         observations, infos = env.step(actions)
         if t >= T and t % 16 == 0:
-            pending = getattr(agent, '_critic_pending', None)
-            in_flight += (pending is not None and pending['done'] is not None
-                          and not pending['done'].query())
+            done = agent._chain.done
+            in_flight += done is not None and not done.query()
         if T <= t < T + 30 or 2 * T <= t < 2 * T + 30:
             if sleeps:
                 time.sleep(0.0003)

@@ -11,9 +11,9 @@ for _ in range(200):
     actions = agent.step(obs, steps)
     obs, infos = loop.env.step(actions)
     agent.update(**infos, steps=steps)
-    early += bool(agent._speculated)
+    early += bool(agent._rollout.speculated)
     steps += bench.W
-print('issued early', early, 'of 200; fed', agent._block_fed, 'eps_ahead', agent._eps_ahead)
+print('issued early', early, 'of 200; fed', agent._rollout.fed, 'eps_ahead', agent._rollout.eps_ahead)
 loop.observations, loop.steps = obs, steps
 t0 = time.perf_counter(); loop.run(2000); dt = time.perf_counter() - t0
 print('us per env step', dt / 2000 * 1e6)

@@ -521,7 +521,7 @@ def test_critic_chain_under_a_running_rollout_is_bit_identical_at_size(lib, monk
     (TONIC_AMD_CRITIC_OVERLAP=0) is BIT FOR BIT — every logged row of the first and the last update
     (80 actor rows, 80 critic rows each), every parameter and the normaliser after three rollouts +
     updates.  (From the second update on a gate holds the chain back so that it ends a margin before
-    the rollout does: PPO._arm_gate.)  A race
+    the rollout does: CriticChain.arm_gate.)  A race
     on the spare observation buffer, the normaliser snapshot or the Segment cannot hide behind a
     tolerance here."""
     if _in_a_process_of_its_own(request):

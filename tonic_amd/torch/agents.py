@@ -20,14 +20,14 @@ generator, a2c.py:87-90) first rewinds the generator to where the reference woul
 """
 import os
 import random
-import time
 import weakref
 
 import numpy as np
 import torch
 
 from tonic_amd import _lib, agents, explorations, logger, parallel, replays
-from tonic_amd.collector import Block, Collector
+from tonic_amd.critic_chain import CriticChain
+from tonic_amd.policy_block import PolicyBlock
 from tonic_amd.q_block import QBlocks
 from tonic_amd.q_update import QUpdate, _check_chain, chunk_size, shard_noise      # noqa: F401 (for their importers)
 from tonic_amd.torch import models, normalizers, updaters
@@ -45,21 +45,6 @@ def default_model():
             torso=models.MLP((64, 64), torch.nn.Tanh),
             head=models.ValueHead()),
         observation_normalizer=normalizers.MeanStd())
-
-
-_SIDE_STREAMS = {}
-_ARMED_GATES = weakref.WeakSet()      # agents whose critic chain waits behind a tonic_stream_gate
-
-
-def _side_stream(name):
-    """One stream per purpose and device for the whole process, not one per agent: HIP maps the
-    streams of a process onto a handful of hardware queues in creation order, and two streams on one
-    queue run one after the other — an agent whose critic stream landed on its collector's queue
-    would get no overlap at all (seen in a process that had built a dozen agents before)."""
-    key = (name, torch.cuda.current_device())
-    if key not in _SIDE_STREAMS:
-        _SIDE_STREAMS[key] = torch.cuda.Stream()
-    return _SIDE_STREAMS[key]
 
 
 def _device():
@@ -368,17 +353,36 @@ class A2C(Agent):
         self.observation_size = observation_space.shape[0]
         self.action_size = action_space.shape[0]
         self._replicate([self.model.flat_actor.flat, self.model.flat_critic.flat], own_noise=True)
-        self._collector = self._block = None
-        self._speculated = self._eps_ahead = self._block_fed = self._armed = False
-        self._critic_pending = self._rollout_behind = None       # (PPO: see _update)
-        self._host_rollout = False
+        self._staged_workers = self._test_workers = self._act_workspace = None       # (the staged path)
         # 3 (default): the act kernel stays RESIDENT for a rollout and the host pushes each step's
         # command, observation and noise rows into a device window (the collector falls back to 2 where
         # it cannot or should not: see tonic_collector_create); 2: resident, the kernel pulls everything
         # from the page-locked block over PCIe; 0: the same kernel launched once per step;
         # 1: hipMemcpyAsync around it (profiles/r02_collector_latency.md: 10.4 / 13.9 / 28.4 us per
         # round trip for 2 / 0 / 1)
-        self.transport = int(os.environ.get('TONIC_AMD_COLLECTOR_TRANSPORT', '3'))
+        transport = int(os.environ.get('TONIC_AMD_COLLECTOR_TRANSPORT', '3'))
+        if self._rollout is None:
+            self._rollout = PolicyBlock(self, transport)
+        else:
+            self._rollout.reset(transport)
+
+    # the rollout on the environment's collector block: all of its state (tonic_amd.policy_block)
+    _rollout = None
+    _chain = None            # (PPO: the critic's iterations under the next rollout, tonic_amd.critic_chain)
+    transport = property(lambda self: self._rollout.transport,
+                         lambda self, value: setattr(self._rollout, 'transport', value))
+    transport_in_effect = property(lambda self: self._rollout.transport_in_effect)       # (absent until bound)
+    steps_issued_by_environment = property(lambda self: self._rollout.issued_by_environment)
+    # (what the GPU tests read of the rollout, under the names it had on the agent)
+    _block = property(lambda self: self._rollout.block)
+    _collector = property(lambda self: self._rollout.collector)
+    _speculated = property(lambda self: self._rollout.speculated)
+
+    def _settle(self):
+        self._rollout.settle()
+
+    def _draws_ahead(self, workers, width):
+        return _NoiseAhead(self, workers, width)
 
     # ------------------------------------------------------------------ acting
     def _io(self, workers):
@@ -420,7 +424,7 @@ class A2C(Agent):
         else:
             prefix, name = (), 'tonic_ppo_act_wide'
             need = self.lib.tonic_ppo_workspace_bytes(W, self.observation_size, A, 1)
-        if getattr(self, '_act_workspace', None) is None or self._act_workspace.numel() < need:
+        if self._act_workspace is None or self._act_workspace.numel() < need:
             self._act_workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=self.device)
         _lib.check(getattr(self.lib, name)(
             *prefix, p(self.model.flat_actor.flat), p(stage_in.device_view('observations')),
@@ -429,34 +433,6 @@ class A2C(Agent):
             W, self.observation_size, A, p(self._act_workspace), self._act_workspace.numel(),
             _lib.current_stream()), name)
         return _read_back_actions(stage_in, stage_out)
-
-    def _bind(self, observations):
-        """First step (or a new worker count): find the environment's block — the arrays of
-        tonic_amd.environments ARE views of one — or make a private one, page-lock it and point
-        the collector at the Segment."""
-        W, O, A = observations.shape[0], self.observation_size, self.action_size
-        block = Block.owner_of(observations) or Block(W, O, A)
-        self._block = block
-        self._collector = Collector.for_block(block, self.transport)
-        self.transport_in_effect = self._collector.transport
-        replay = self.replay
-        if replay.buffers is None or replay.num_workers != W:
-            replay._allocate(W, O, A)
-        self._eps = (torch.from_numpy(block.eps[0]), torch.from_numpy(block.eps[1]))
-        noise = getattr(self, '_noise', None)
-        if noise is None or (noise.workers, noise.width) != (W, A):
-            if noise is not None:
-                noise.rewind(0)
-            self._noise = _NoiseAhead(self, W, A)
-        self._slot, self._eps_ahead, self._pending, self._rollout_open = 0, False, False, False
-        # update() may issue the NEXT step's launch itself (see there): whether it did, and whether
-        # the caller has been handing over the block's own arrays so far
-        self._speculated, self._block_fed = False, False
-        self._speculate = os.environ.get('TONIC_AMD_SPECULATE', '1') != '0'
-        # step() may leave the next command with the environment (Block.ring issues it)
-        self._armed = False
-        self.steps_issued_by_environment = 0
-        self._arm_steps = self._speculate and os.environ.get('TONIC_AMD_ARM', '1') != '0'
 
     # -- shapes beyond the fused act kernel (O > 32 or A > 8): staged copies + separate launches
     def _wide(self):
@@ -474,7 +450,7 @@ class A2C(Agent):
     def _step_staged(self, observations):
         observations = np.asarray(observations, np.float32)
         W, O = observations.shape[0], self.observation_size
-        if getattr(self, '_staged_workers', None) != W:
+        if self._staged_workers != W:
             self._staged_workers = W
             self._in, self._out = self._io(W)
             self._outcome = _Staging([('next_observations', (W, O)), ('rewards', (W,)),
@@ -504,231 +480,48 @@ class A2C(Agent):
             self._update()
 
     def step(self, observations, steps):
-        # The steady state of a block-fed loop first (every attribute lookup of this call is host
-        # time between the simulator's step and the next command to the GPU): update() has issued
-        # this step with the block's own observations and the noise drawn ahead.
-        if self._speculated and self._eps_ahead and observations is self._block.out_observations:
-            block, slot = self._block, self._slot
-            self._speculated = False
-            self._noise.take(block.eps[slot ^ 1])      # the step after this one
-            self._slot = slot ^ 1
-            # ... whose command is left with the ENVIRONMENT: it issues it the moment its step
-            # record is complete (Block.ring), update() only confirms (see there)
-            replay = self.replay
-            if self._arm_steps and replay.index + 2 < replay.max_size:
-                self._armed = self._collector.arm(replay.index + 1, slot ^ 1, True)
-            self._collector.wait_actions()
-            self._block_fed = True
-            self.last_observations = observations
-            self.last_actions = actions = block.out_actions
-            return actions
-        if self._wide():
-            return self._step_staged(observations)
-        self._claim()
-        block = getattr(self, '_block', None)
-        if self._collector is None or block.workers != len(observations):
-            self._settle()
-            self._bind(observations)
-            block = self._block
-        fed = observations is block.out_observations or observations is block.observations
-        if not fed and self.replay.index == 0 and not self._rollout_open:
-            # between two rollouts: another environment of tonic_amd.environments took over (its
-            # observations are the view of ANOTHER live block) -> adopt that block, stay zero-copy
-            owner = Block.owner_of(observations)
-            if owner is not None and owner is not block:
-                self._settle()
-                eps_ahead = self._eps_ahead and self._eps[self._slot].clone()
-                self._bind(observations)
-                block, fed = self._block, True
-                if eps_ahead is not False:        # the noise drawn ahead moves along (same stream)
-                    self._eps[self._slot].copy_(eps_ahead)
-                    self._eps_ahead = True
-        if not fed:
-            np.copyto(block.observations, observations)
-        collector = self._collector
-        launched = False
-        if self._speculated:
-            # update() already issued this step with the block's contents and the noise drawn
-            # ahead.  Still what the reference would compute?  (Other observations, or a test
-            # episode in between whose draws come first in the generator's order: no.)
-            self._speculated = False
-            if fed and self._eps_ahead:
-                launched = True
-            else:
-                collector.wait_actions()          # discard; a step is idempotent (collector.hip)
-        if not launched:
-            if not self._rollout_open:
-                norm = self.model.observation_normalizer
-                behind = None
-                if getattr(self, '_rollout_behind', None) is not None:
-                    # PPO._update left the critic's iterations running: this rollout writes its
-                    # observations to the spare buffer and is ordered behind what it depends on
-                    # (the actor, the normaliser) — the current stream waits for the critic as well
-                    behind, self._rollout_behind = self._rollout_behind.cuda_stream, None
-                    buffers = self.replay.buffers
-                    spare = getattr(self, '_spare_observations', None)
-                    if spare is None or spare.shape != buffers['observations'].shape:
-                        spare = torch.empty_like(buffers['observations'])
-                    self._spare_observations, buffers['observations'] = buffers['observations'], spare
-                collector.bind_segment(self.replay.buffers,
-                                       norm.device_sums if norm is not None else None,
-                                       self.replay.max_size)
-                collector.begin_rollout(self.model.flat_actor.flat, behind)
-                self._rollout_open = True
-            if not self._eps_ahead:
-                self._noise.take(block.eps[self._slot])                                # a2c.py:81
-            collector.ppo_step(self.replay.index, self._slot, self._pending)
-            self._pending = False
-        slot = self._slot
-        # The next step's noise goes into the other slot while the GPU works on this one (drawn
-        # ahead by _NoiseAhead; test_step rewinds the generator: its own draws come first in the
-        # reference's stream order).
-        self._noise.take(block.eps[slot ^ 1])
-        self._slot, self._eps_ahead = slot ^ 1, True
-        collector.wait_actions()
-        # An environment that lives in the block consumes the actions at once (and may take them
-        # from the block itself): it gets the block's read-only view; anybody else a fresh array.
-        actions = block.out_actions if fed else block.actions.copy()
-        self._block_fed = fed
+        # (once per environment step: the steady state of a block-fed loop first, PolicyBlock.step_ahead)
+        rollout = self._rollout
+        actions = rollout.step_ahead(observations)
+        if actions is None:
+            if self._wide():
+                return self._step_staged(observations)
+            actions = rollout.step(observations)
         self.last_observations = observations
         self.last_actions = actions
         return actions
 
-    def _settle(self):
-        """Waits out a step that update() issued early and nobody asked for yet (the Segment row it
-        wrote lies beyond the rows stored so far and is rewritten by the real step)."""
-        self._claim()
-        if getattr(self, '_speculated', False):
-            self._collector.wait_actions()
-            self._speculated = False
-
-    def _claim(self):
-        """Takes back a command that step() left with the environment: issued meanwhile = a step
-        in flight like one update() issued early; not issued = withdrawn."""
-        if getattr(self, '_armed', False):
-            self._armed = False
-            if self._collector.claim():
-                self._speculated = True
-
     def close(self):
-        """Releases what a live agent holds beyond its tensors: waits out a step issued ahead,
-        puts the generator back where the reference's stream is, ends the noise helper thread and
-        destroys the collector (its stream, its resident kernel, the page-lock on the
-        environment's block).  The agent can be initialised again afterwards."""
-        if getattr(self, '_collector', None) is not None:
-            self._settle()
-            noise = getattr(self, '_noise', None)
-            if noise is not None:
-                noise.rewind(1 if self._eps_ahead else 0)
-                noise.close()
-                self._noise = None
-            self._collector.close()
-            self._block._collectors.pop(self._collector.requested, None)
-            self._collector = self._block = None
-            self._speculated = self._eps_ahead = self._block_fed = False
-            self._rollout_behind = None
+        """Releases what a live agent holds beyond its tensors (PolicyBlock.close: a step issued ahead, the
+        generator, the noise helper thread, the collector).  The agent can be initialised again afterwards."""
+        if self._rollout is not None:
+            self._rollout.close()
         if getattr(self, '_holds_affinity', False):
             self._holds_affinity = False
             parallel.release_affinity()            # (bind_near_gpu: the last agent to close restores the CPU mask)
 
     def test_step(self, observations, steps):
-        self._open_gate()       # (the current stream waits for the critic's iterations: let them start)
-        noise = getattr(self, '_noise', None)
-        if noise is not None:
-            self._settle()          # (a step issued ahead reads the slot: let it finish first)
-            noise.rewind(1 if self._eps_ahead else 0)
-            self._eps_ahead = False
+        self._open_gates()      # (the current stream waits for the critic's iterations: let them start)
+        self._rollout.rewind()
         observations = np.asarray(observations, np.float32)
-        if getattr(self, '_test_workers', None) != observations.shape[0]:
+        if self._test_workers != observations.shape[0]:
             self._test_workers = observations.shape[0]
             self._test_in, self._test_out = self._io(observations.shape[0])
         return self._act(observations, self._test_in, self._test_out, False)
 
+    def _open_gates(self):
+        """(PPO: the gates in front of critic chains, CriticChain.open_gates)"""
+
     # ---------------------------------------------------------------- learning
     def update(self, observations, rewards, resets, terminations, steps):
-        """a2c.py:58-73.  The outcome stays in the block; the NEXT step's launch (or
-        end_rollout) moves it into the Segment row of the step it belongs to."""
-        block, replay = self._block, self.replay
-        if self._block_fed and observations is block.out_next_observations \
-                and rewards is block.out_rewards and resets is block.out_resets \
-                and terminations is block.out_terminations and self._eps_ahead and self._speculate \
-                and replay.index + 2 < replay.max_size:
-            # the steady state of a block-fed loop (the general form is below): the next step's
-            # command goes out first, the bookkeeping runs while the GPU works
-            index = replay.index
-            if self._armed:
-                # step() left this command with the environment, which normally has issued it
-                # from inside its own step call, before the trainer's loop even got here
-                self._armed = False
-                if self._collector.claim():
-                    self.steps_issued_by_environment += 1
-                else:
-                    self._collector.ppo_step(index + 1, self._slot, True)
-            else:
-                self._collector.ppo_step(index + 1, self._slot, True)
-            self._speculated = True
-            replay.index = index + 1
-            gate = self._gate_row
-            if gate is not None and index >= gate:
-                self._open_gate()
-            normalizer = self.model.observation_normalizer
-            if normalizer:
-                normalizer.new_count += block.workers             # (note_device_rows)
-            self._pending = False
+        """a2c.py:58-73 (PolicyBlock.update_ahead: the steady state; PolicyBlock.update ends the rollout with
+        `self._update()`)."""
+        rollout = self._rollout
+        if rollout.update_ahead(observations, rewards, resets, terminations):
             return
         if self._wide():
             return self._update_staged(observations, rewards, resets, terminations)
-        self._claim()
-        # (identity: the arrays tonic_amd.environments hand out ARE the block's fields)
-        if (self._block_fed and observations is block.out_next_observations
-                and rewards is block.out_rewards and resets is block.out_resets
-                and terminations is block.out_terminations):
-            # The environment lives in the block: the outcome is in place and so are the next
-            # step's observations (distributed.py:136-155 returns them with these infos).  With
-            # its noise drawn ahead, the next step's launch goes out FIRST — the rest of this call,
-            # the trainer's bookkeeping and the head of the next agent.step run while the GPU
-            # works.  step() issues it again if it turns out to be obsolete.
-            if (self._eps_ahead and self._speculate and replay.index + 2 <= replay.max_size
-                    and not self._speculated):
-                self._collector.ppo_step(replay.index + 1, self._slot, True)
-                self._speculated = True
-        else:
-            self._settle()      # (a step the environment issued reads the block: not under it)
-            if (observations is not block.out_next_observations
-                    and observations is not block.next_observations):
-                np.copyto(block.next_observations, observations)
-            if rewards is not block.out_rewards and rewards is not block.rewards:
-                np.copyto(block.rewards, rewards)
-            if resets is not block.out_resets and resets is not block.resets_bool:
-                np.copyto(block.resets, resets)             # bool -> float32 (segments.py:33)
-            if terminations is not block.out_terminations and \
-                    terminations is not block.terminations_bool:
-                np.copyto(block.terminations, terminations)
-        replay.index += 1
-        if self._gate_row is not None and replay.index > self._gate_row:
-            self._open_gate()
-        if self.model.observation_normalizer:
-            self.model.observation_normalizer.note_device_rows(block.workers)
-        self._pending = not self._speculated
-        if replay.ready():
-            started = getattr(self, '_rollout_started', None)
-            if started is not None:          # host time per environment step of the rollout that ends here
-                self._rollout_step_us = (time.perf_counter() - started) * 1e6 / replay.max_size
-            self._collector.end_rollout(replay.index - 1)
-            self._pending, self._rollout_open = False, False
-            # (this rollout came through the collector, which binds the Segment's buffers anew at
-            #  every rollout: the update may swap them — see PPO._update)
-            self._host_rollout = True
-            try:
-                self._update()
-            finally:
-                self._host_rollout = False
-
-    # (PPO: the row of the running rollout at which the gate in front of the critic's iterations opens)
-    _gate_row = None
-
-    def _open_gate(self):
-        self._gate_row = None
+        rollout.update(observations, rewards, resets, terminations)
 
     # -- the Return normaliser (a2c.py:68-69 records every step's rewards, :126-127 updates it)
     def _range_rewards(self):
@@ -774,19 +567,33 @@ class A2C(Agent):
                               b['next_values'].view(-1))
         return b['values'], b['next_values']
 
+    def _form_returns(self):
+        """Evaluate, lambda-returns (a2c.py:101-106); returns how many iterations one pass over the Segment yields."""
+        values, next_values = self._evaluate()
+        self.replay.compute_returns(values, next_values)
+        return self.replay.updates_per_get()
+
+    def _begin_update(self, fresh=False):
+        """The head of a kernel update: the returns formed, the statistic rows [2, updates, INFO_WIDTH] zeroed — the
+        agent's own, or `fresh` ones for a critic chain that outlives the update and keeps them — and the actor's KL
+        stop reset.  Returns the rows."""
+        updates = self._form_returns()
+        if fresh:
+            infos = torch.zeros(2, updates, updaters.INFO_WIDTH, device=self.device)
+        else:
+            if getattr(self, '_infos', None) is None or self._infos.shape[1] != updates:
+                self._infos = torch.zeros(2, updates, updaters.INFO_WIDTH, device=self.device)
+            self._infos.zero_()
+            infos = self._infos
+        self.actor_updater.reset_stop()
+        return infos
 
     def enqueue_update(self):
         """a2c.py:101-127 without a host sync: evaluate, lambda-returns, ONE actor step on the
         full batch, then the critic over `replay.get` (full batch `batch_iterations` times, or
         minibatches).  Returns the statistic rows: [0, 0] the actor's, [1, :] the critic's."""
         replay, actor, critic = self.replay, self.actor_updater, self.critic_updater
-        values, next_values = self._evaluate()
-        replay.compute_returns(values, next_values)
-        updates = replay.updates_per_get()
-        if getattr(self, '_infos', None) is None or self._infos.shape[1] != updates:
-            self._infos = torch.zeros(2, updates, updaters.INFO_WIDTH, device=self.device)
-        self._infos.zero_()
-        actor.reset_stop()
+        self._begin_update()
         full = tuple(replays.flatten_batch(replay.buffers[k]) for k in replays.segments.LEARNER_KEYS)
         obs, act, raw_adv, log_probs, _ = full
         actor.enqueue(obs, act, raw_adv, replay.adv_stats, log_probs, self._infos[0, 0])
@@ -825,12 +632,11 @@ class TRPO(A2C):
     def _update(self):
         replay, critic = self.replay, self.critic_updater
         self._range_rewards()
-        values, next_values = self._evaluate()
-        replay.compute_returns(values, next_values)
+        updates = self._form_returns()
         batch = replay.get_full('observations', 'actions', 'log_probs', 'advantages')
         for key, value in self.actor_updater(**batch).items():
             logger.store('actor/' + key, value.numpy())
-        updates = replay.updates_per_get()
+        # (the actor's step is the updater's own: no KL stop to reset, and the critic's rows alone, behind it)
         infos = torch.zeros(updates, updaters.INFO_WIDTH, device=self.device)
         for it, (obs, _, _, _, returns) in enumerate(replay.learner_batches()):
             critic.enqueue(obs, returns, infos[it])
@@ -853,33 +659,29 @@ class PPO(A2C):
                          actor_updater=actor_updater or updaters.ClippedRatio(),
                          critic_updater=critic_updater)
 
+    def initialize(self, observation_space, action_space, seed=None):
+        super().initialize(observation_space, action_space, seed=seed)
+        if self._chain is None:
+            self._chain = CriticChain(self)
+
+    def _form_returns(self):
+        self.critic_updater.max_workgroups = self._critic_width()
+        return super()._form_returns()
+
     def enqueue_update(self):
         """Enqueues one whole learner update on the current stream (no host sync)."""
         self.settle()
         replay, actor, critic = self.replay, self.actor_updater, self.critic_updater
-        critic.max_workgroups = self._critic_width()
-        values, next_values = self._evaluate()
-        replay.compute_returns(values, next_values)
-        updates = replay.updates_per_get()
-        if getattr(self, '_infos', None) is None or self._infos.shape[1] != updates:
-            self._infos = torch.zeros(2, updates, updaters.INFO_WIDTH, device=self.device)
-        self._infos.zero_()
-        actor.reset_stop()
-        world = actor.world_size
+        infos = self._begin_update()
         # Full batch (ppo.py:40-47 over segments.py:55-57) or shuffled minibatches
         # (segments.py:58-65); the advantages stay raw and are normalised in-register with the
         # GLOBAL statistics, exactly what get_full computes before the reference slices.
-        if not parallel.exchanging():
-            for it, (obs, act, raw_adv, log_probs, returns) in enumerate(replay.learner_batches()):
-                actor.enqueue_grad(obs, act, raw_adv, replay.adv_stats, log_probs)
-                critic.enqueue_grad(obs, returns)
-                updaters.enqueue_step_pair(actor, critic, obs.shape[0], replay.adv_stats,
-                                           self._infos[0, it], self._infos[1, it])
-            return self._infos
         # Several ranks: every iteration exchanges [gradient sums | 8 statistics] of both networks
         # (RCCL over xGMI).  After the KL stop the actor half is zero-filled on every rank alike and
-        # its step is skipped by the same device flag everywhere.  Two schedules
+        # its step is skipped by the same device flag everywhere.  The schedules
         # (TONIC_AMD_EXCHANGE), A/B-measured through RCCL with a one-rank group (DESIGN.md §6):
+        #   one-shot         tonic_allreduce_f32 behind each grad launch: one ~10 us launch per exchange,
+        #                    nothing to hide it behind
         #   joint (default)  one all-reduce of both halves per iteration, both Adam steps in one
         #                    launch: +8.6 ms per 80-iteration update over the exchange-free path;
         #   overlap          one asynchronous all-reduce per network, each hidden behind the OTHER
@@ -888,33 +690,43 @@ class PPO(A2C):
         #                      critic grad i | AR(critic i) over Adam(actor i) + actor grad i+1 | Adam(critic i)
         #                    : +12.4 ms — the stream hand-overs of 160 collectives cost more than
         #                    the latency of 80 they hide when there is no link latency to hide.
-        one_shot = parallel.one_shot(max(actor.count, critic.count) + updaters.INFO_WIDTH)
-        if one_shot is not None:
-            # tonic_allreduce_f32: one ~10 us launch per exchange, nothing to hide it behind
-            for it, (obs, act, raw_adv, log_probs, returns) in enumerate(replay.learner_batches()):
-                actor.enqueue_grad(obs, act, raw_adv, replay.adv_stats, log_probs)
-                one_shot.all_reduce(actor.grad_sums)
-                critic.enqueue_grad(obs, returns)
-                one_shot.all_reduce(critic.grad_sums)
-                updaters.enqueue_step_pair(actor, critic, obs.shape[0], replay.adv_stats,
-                                           self._infos[0, it], self._infos[1, it])
-            return self._infos
+        # The first three are ONE loop: what follows the actor's grad launch, what the critic's.
+        after_actor = after_critic = None
+        if parallel.exchanging():
+            one_shot = parallel.one_shot(max(actor.count, critic.count) + updaters.INFO_WIDTH)
+            if one_shot is not None:
+                def after_actor():
+                    one_shot.all_reduce(actor.grad_sums)
+
+                def after_critic():
+                    one_shot.all_reduce(critic.grad_sums)
+            elif os.environ.get('TONIC_AMD_EXCHANGE', 'joint') == 'joint':
+                # ONE synchronous all-reduce of [actor sums | 8 | critic sums | 8] per iteration, both
+                # optimizer steps in one launch (half the collectives, none of them hidden)
+                if getattr(self, '_joint_grads', None) is None:
+                    na, nc = actor.count + updaters.INFO_WIDTH, critic.count + updaters.INFO_WIDTH
+                    self._joint_grads = torch.zeros(na + nc, device=self.device)
+                    actor.share_gradient_buffer(self._joint_grads[:na])
+                    critic.share_gradient_buffer(self._joint_grads[na:])
+
+                def after_critic():
+                    torch.distributed.all_reduce(self._joint_grads)
+            else:
+                return self._enqueue_overlapped_exchange(infos)
+        for it, (obs, act, raw_adv, log_probs, returns) in enumerate(replay.learner_batches()):
+            actor.enqueue_grad(obs, act, raw_adv, replay.adv_stats, log_probs)
+            if after_actor is not None:
+                after_actor()
+            critic.enqueue_grad(obs, returns)
+            if after_critic is not None:
+                after_critic()
+            updaters.enqueue_step_pair(actor, critic, obs.shape[0], replay.adv_stats, infos[0, it], infos[1, it])
+        return infos
+
+    def _enqueue_overlapped_exchange(self, infos):
+        """TONIC_AMD_EXCHANGE=overlap (see enqueue_update): its pipelining is a loop of its own."""
+        replay, actor, critic = self.replay, self.actor_updater, self.critic_updater
         all_reduce = torch.distributed.all_reduce
-        if os.environ.get('TONIC_AMD_EXCHANGE', 'joint') == 'joint':
-            # ONE synchronous all-reduce of [actor sums | 8 | critic sums | 8] per iteration, both
-            # optimizer steps in one launch (half the collectives, none of them hidden)
-            if getattr(self, '_joint_grads', None) is None:
-                na, nc = actor.count + updaters.INFO_WIDTH, critic.count + updaters.INFO_WIDTH
-                self._joint_grads = torch.zeros(na + nc, device=self.device)
-                actor.share_gradient_buffer(self._joint_grads[:na])
-                critic.share_gradient_buffer(self._joint_grads[na:])
-            for it, (obs, act, raw_adv, log_probs, returns) in enumerate(replay.learner_batches()):
-                actor.enqueue_grad(obs, act, raw_adv, replay.adv_stats, log_probs)
-                critic.enqueue_grad(obs, returns)
-                all_reduce(self._joint_grads)
-                updaters.enqueue_step_pair(actor, critic, obs.shape[0], replay.adv_stats,
-                                           self._infos[0, it], self._infos[1, it])
-            return self._infos
         pending = None                           # (work handle, rows, info row) of the critic
         for it, (obs, act, raw_adv, log_probs, returns) in enumerate(replay.learner_batches()):
             n = obs.shape[0]
@@ -924,29 +736,25 @@ class PPO(A2C):
                 pending[0].wait()
                 critic.enqueue_step(pending[1], pending[2], allreduce=False)
             critic.enqueue_grad(obs, returns)
-            pending = (all_reduce(critic.grad_sums, async_op=True), n, self._infos[1, it])
+            pending = (all_reduce(critic.grad_sums, async_op=True), n, infos[1, it])
             actor_sums.wait()
-            actor.enqueue_step(n, replay.adv_stats, self._infos[0, it], allreduce=False)
+            actor.enqueue_step(n, replay.adv_stats, infos[0, it], allreduce=False)
         if pending is not None:
             pending[0].wait()
             critic.enqueue_step(pending[1], pending[2], allreduce=False)
-        return self._infos
+        return infos
 
-    # -- the critic's iterations under the next rollout ---------------------------------------
-    # The two networks of an update share nothing (ppo.py:33-46: advantages and returns are formed
-    # before the first iteration), and a rollout needs the ACTOR only — the critic is not asked
-    # again before the next update's evaluation.  So on one GPU with full-batch iterations update()
-    # runs the actor's 80 iterations, hands the critic's 80 to a second HIP stream BEHIND them and
-    # returns: the critic's kernels (on the compute units the resident collect kernel leaves, less 16
-    # to spare: 219 of 256 at 256 workers) run while the host drives the next rollout, whose collect loop is latency-
-    # bound and leaves the GPU idle.  Everything that reads the critic waits first (settle():
-    # the next update, save / load, close, `last_infos`, the logger's dump — and the current stream
-    # itself waits, so parameters read through torch are final), and what the critic still reads is
-    # kept out of the rollout's way: the next rollout writes its observations to a spare buffer
-    # (swapped in when it starts), the normaliser's mean / std (updated in place after the update,
-    # a2c.py:126-127) are snapshot.  TONIC_AMD_CRITIC_OVERLAP=0: the interleaved launches of enqueue_update.
+    # -- the critic's iterations under the next rollout (tonic_amd.critic_chain) --------------
+    # On one GPU with full-batch iterations update() runs the actor's 80 iterations, hands the critic's 80
+    # to a second HIP stream BEHIND them and returns (on the compute units the resident collect kernel
+    # leaves, less 16 to spare: 219 of 256 at 256 workers).  Everything that reads the critic waits first
+    # (settle(): the next update, save / load, close, `last_infos`, the logger's dump — and the current
+    # stream itself waits, so parameters read through torch are final).
+    # TONIC_AMD_CRITIC_OVERLAP=0: the interleaved launches of enqueue_update.
     OVERLAP_BLOCKS = None       # (developer override of the critic's workgroups per launch)
     MIN_OVERLAP_BLOCKS = 128    # below this width the critic's chain does not go under a rollout
+    GATE_MARGIN_MS = 1.0        # (CriticChain.arm_gate: the chain ends this long before the rollout does)
+    GATE_ROLLOUT_US = 100e3     # (... and no gate in a rollout longer than this)
 
     def _critic_blocks(self):
         """Workgroups of the critic's launches while a rollout is collected: what the resident
@@ -982,11 +790,22 @@ class PPO(A2C):
                 # few units left over would run many times longer than the rollout it hides under —
                 # such configurations keep the full-width interleaved launches
                 and self._critic_blocks() >= self.MIN_OVERLAP_BLOCKS
-                and getattr(self, '_collector', None) is not None
+                and self._rollout.collector is not None
                 # only behind a rollout that came through the collector (it binds the Segment's
                 # buffers anew every rollout; anybody else — rollout.DeviceRollout's captured graph —
                 # may hold their addresses, and the overlap swaps the observation buffer)
-                and getattr(self, '_host_rollout', False))
+                and self._rollout.host_rollout)
+
+    # (what the benchmark and the tests read of the chain: None / 0 before the first one)
+    _critic_stream = property(lambda self: self._chain and self._chain.stream)
+    _gate_ticket = property(lambda self: self._chain.gate_ticket if self._chain else 0)
+    critic_chain_ms = property(lambda self: self._chain and self._chain.chain_ms)
+
+    @property
+    def _critic_pending(self):
+        """The chain in flight as the tests read it: None, or its `done` event."""
+        chain = self._chain
+        return None if chain is None or chain.done is None else dict(done=chain.done)
 
     @property
     def last_infos(self):
@@ -997,16 +816,14 @@ class PPO(A2C):
     def last_infos(self, value):
         self._last_infos = value
 
+    def _open_gates(self):
+        CriticChain.open_gates()
+
     def settle(self):
         """Waits for the critic iterations a previous update left running and logs their rows."""
-        self._open_gate()
-        pending = getattr(self, '_critic_pending', None)
-        if pending is None:
+        rows = self._chain.settle() if self._chain is not None else CriticChain.open_gates()
+        if rows is None:
             return
-        self._critic_pending = None
-        torch.cuda.current_stream().wait_event(pending['done'])   # whoever reads the critic next is behind it
-        rows = pending['infos'][1].cpu().numpy()
-        self.critic_chain_ms = pending['clock'].elapsed_time(pending['done'])    # (bench.py reports it)
         log_ppo_critic_rows(rows)
         logger.store('critic/iterations', len(rows))
         log_learning_rate('critic', self.critic_updater, self)
@@ -1026,9 +843,9 @@ class PPO(A2C):
         super().close()
 
     def _update(self):
+        self.settle()
+        self._range_rewards()
         if not self._overlap():
-            self.settle()
-            self._range_rewards()
             infos = self.enqueue_update().cpu().numpy()          # the only sync of the update
             parallel.check_one_shot()
             log_ppo_update(infos)
@@ -1038,15 +855,9 @@ class PPO(A2C):
             self._record_rewards()
             self._update_normalizers()
             return
-        self.settle()
-        self._range_rewards()
-        replay, actor, critic = self.replay, self.actor_updater, self.critic_updater
-        critic.max_workgroups = self._critic_width()
-        values, next_values = self._evaluate()
-        replay.compute_returns(values, next_values)
-        updates = replay.updates_per_get()
-        infos = torch.zeros(2, updates, updaters.INFO_WIDTH, device=self.device)
-        actor.reset_stop()
+        replay, actor, chain = self.replay, self.actor_updater, self._chain
+        infos = self._begin_update(fresh=True)
+        updates = infos.shape[1]
         buffers = replay.buffers
         obs, act, raw_adv, log_probs, returns = (
             replays.flatten_batch(buffers[k]) for k in replays.segments.LEARNER_KEYS)
@@ -1058,134 +869,26 @@ class PPO(A2C):
             actor.enqueue_grad(obs, act, raw_adv, replay.adv_stats, log_probs)
             actor.enqueue_step(n, replay.adv_stats, infos[0, it])
         last.record()
-        # the critic's iterations: same inputs, the normalisers as they are NOW, their own stream
-        snapshot = tuple(t.clone() for t in critic.norm_tensors())
-        value_range = critic.range_tensors()
-        if value_range is not None:       # (the Return normaliser is refreshed below, under the chain)
-            value_range = tuple(t.clone() for t in value_range)
-        normaliser_done = False
-        if parallel.exchanging() and self.model.observation_normalizer:
-            # Several ranks: the normaliser's update is a collective + a read-back on THIS stream; issued
-            # after the critic's chain it would queue behind the chain's 80 all-reduces on the
-            # communicator (one rank's host blocked for the whole chain).  It depends on neither
-            # network (a2c.py:126-127 merges the rollout's recorded sums), the chain reads the snapshot:
-            # it goes first.
-            self.model.observation_normalizer.update()
-            normaliser_done = True
-        ready = torch.cuda.Event()
-        ready.record()
-        if getattr(self, '_critic_stream', None) is None:
-            self._critic_stream = _side_stream('critic')
+        normalizer = self.model.observation_normalizer
+        ahead = normalizer if parallel.exchanging() and normalizer else None      # (see CriticChain.launch)
+        if chain.launch(obs, returns, infos, normalizer_first=ahead):
+            # Whoever reads the critic through torch — a forward pass of the module, state_dict() — finds it
+            # final: both settle first, and so does the logger's dump (the package's own readers call settle())
             logger.before_dump(self, 'settle')
-            self._guard_critic_readers()
-        side = self._critic_stream
-        side.wait_event(ready)
-        clock, done = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        with torch.cuda.stream(side):
-            self._arm_gate(side)
-            clock.record(side)
-            for it in range(updates):
-                critic.enqueue_grad(obs, returns, norm=snapshot, value_range=value_range)
-                critic.enqueue_step(n, infos[1, it])
-            done.record(side)
-        # (Enqueued HERE, while the GPU is busy with the actor's chain and the host has nothing else
-        #  to do.  Round 4 also tried it late — from agent.update at the Segment row from which the
-        #  chain just finishes before the rollout does, so that the next update's first launches find
-        #  the chip at its working clock (profiles/r04_clock_ramp.md): the 160 enqueues then sit on the
-        #  host-bound collect loop's critical path, 82.3 against 80.9 ms per step.)
-        self._critic_pending = dict(done=done, clock=clock, infos=infos,
-                                    keep=(obs, returns, snapshot, value_range))
+            self.model.critic.register_forward_pre_hook(lambda module, args: self.settle())     # (settle: None)
+            self.model.register_state_dict_pre_hook(lambda module, prefix, keep_vars: self.settle())
         rows = infos[0].cpu().numpy()                    # waits for the actor's iterations only
         self.actor_chain_ms = first.elapsed_time(last)   # (bench.py reports it)
         parallel.check_one_shot()
         logger.store('actor/iterations', log_ppo_actor_rows(rows))
         log_learning_rate('actor', self.actor_updater, self)
         self._last_infos = np.stack([rows, np.zeros_like(rows)])
-        if self.model.observation_normalizer and not normaliser_done:
-            self.model.observation_normalizer.update()
+        if normalizer and ahead is None:
+            normalizer.update()
         self._record_rewards()
         if self.model.return_normalizer:
             self.model.return_normalizer.update()
-        # What the next rollout depends on — the actor, the normaliser — is on the current stream up
-        # to here: a stream of its own carries that point to the collector (step() -> begin_rollout),
-        # which also moves the rollout's observations to the spare buffer.  Everything ELSE that
-        # follows on the current stream waits for the critic's iterations as well, and whoever reads
-        # the critic through torch — state_dict(), a checkpoint, a forward pass of the module — goes
-        # through settle() first (_guard_critic_readers), so the critic is read final, as after the
-        # reference's update.
-        if getattr(self, '_rollout_marker', None) is None:
-            self._rollout_marker = _side_stream('rollout marker')
-        ordered = torch.cuda.Event()
-        ordered.record()
-        self._rollout_marker.wait_event(ordered)
-        self._rollout_behind = self._rollout_marker
-        if self._gate_row is None:
-            torch.cuda.current_stream().wait_event(done)
-        # (A chain parked behind a gate is NOT put in front of the current stream: the gate opens late in
-        #  the next rollout, and user work on this stream — a `current_stream().synchronize()` after
-        #  agent.update — would stall for most of a rollout.  Whoever reads the critic is ordered behind
-        #  the chain by settle(): the package's own readers, a forward pass of the module, state_dict().)
-        self._rollout_started = time.perf_counter()
-
-    # The critic's launches are enqueued above, while the host has nothing else to do, but they need not
-    # START there: behind a phase in which the device is lightly loaded (a rollout keeps a few compute
-    # units polling) the next update's first launches run 10 - 25 % slower until the device's power
-    # management has followed the load (~25 ms: the whole actor chain, profiles/r04_clock_ramp.md).  A gate
-    # (tonic_stream_gate: one polling wave) holds the chain back until the row of the NEXT rollout from
-    # which it just finishes before that rollout does — the host opens it with a plain store from
-    # agent.update — so the update that follows starts on a device at its working point.  Timing only;
-    # whoever needs the critic (settle), the current stream (test_step) or a rollout slower than the
-    # last one (the gate's own limit) opens it as well.  TONIC_AMD_CRITIC_GATE=0: the chain starts at once.
-    GATE_MARGIN_MS = 1.0
-    GATE_ROLLOUT_US = 100e3
-
-    def _arm_gate(self, side):
-        self._gate_row = None
-        chain_ms, step_us = getattr(self, 'critic_chain_ms', None), getattr(self, '_rollout_step_us', None)
-        if os.environ.get('TONIC_AMD_CRITIC_GATE', '1') == '0' or not chain_ms or not step_us:
-            return
-        if parallel.exchanging():
-            # The chain's iterations all-reduce their gradient sums: a collective issued on the main
-            # stream meanwhile (the normaliser's statistics) queues BEHIND them on the communicator,
-            # and with a host-synchronous backend the first of them blocks the host — the only party
-            # that can open a gate.  Ranks that exchange never hold the chain back.
-            return
-        rows = self.replay.max_size
-        row = rows - int(np.ceil((1.1 * chain_ms + self.GATE_MARGIN_MS) * 1e3 / step_us))
-        if row <= 0 or rows * step_us > self.GATE_ROLLOUT_US:
-            # the chain needs the whole rollout / a rollout much longer than the device's ramp: nothing to
-            # gain, and a polling wave must not sit in a hardware queue for long (HIP streams share a
-            # handful of them: whatever another stream launches into that queue waits behind the gate)
-            return
-        if getattr(self, '_gate_word', None) is None:
-            self._gate_word = torch.zeros(1, dtype=torch.int32).pin_memory()
-            self._gate_view = self._gate_word.numpy()
-            self._gate_ticket = 0
-        self._gate_ticket += 1
-        # (its own limit: twice the time the host needs to that row — nobody who synchronises the device
-        #  without asking the agent first waits longer than that)
-        limit = max(0.01, 2.0 * row * step_us * 1e-6 + 0.005)
-        _lib.check(_lib.load().tonic_stream_gate(self._gate_word.data_ptr(), self._gate_ticket, limit,
-                                                 side.cuda_stream), 'stream gate')
-        self._gate_row = row
-        _ARMED_GATES.add(self)
-
-    def _open_gate(self):
-        # The critic stream is shared by the agents of a process (_side_stream): whatever another
-        # agent has parked there holds THIS agent's chain too, so every armed gate is opened.
-        for agent in list(_ARMED_GATES):
-            if agent._gate_row is not None:
-                agent._gate_view[0] = agent._gate_ticket
-                agent._gate_row = None
-        _ARMED_GATES.clear()
-
-    def _guard_critic_readers(self):
-        """Whoever reads the critic through torch — a forward pass of the module, state_dict() —
-        finds it final: both settle first (the package's own readers call settle() themselves)."""
-        def before(*args, **kwargs):
-            self.settle()
-        self.model.critic.register_forward_pre_hook(before)
-        self.model.register_state_dict_pre_hook(lambda module, prefix, keep_vars: self.settle())
+        chain.hand_over(self._rollout)
 
 
 def log_ppo_update(infos):
